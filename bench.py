@@ -3,7 +3,7 @@
 edge mask decoder + MaPLe/Alpha-CLIP ViT-L/14@336, stage 1 + stage 2 classification), batch 8 per GPU,
 synthetic images + deterministic synthetic weights (BASELINE.json configs[2]; configs[3] for N > 1).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1 without RANK in the environment: this process starts N ranks itself (`python -m torch.distributed.run`,
 as a child, before anything here has touched the GPU), relays rank 0's JSON line and exits with the child's
@@ -14,6 +14,10 @@ from step to step (images (r + i) mod 16 and (r + B + i) mod 16 on rank r), so t
 not hide behind identical inputs.  Rank 0 prints ONE JSON line.
 `value`       : whole-job images/s over the K timed steps (wall clock, barrier + synchronize on both sides, max over ranks);
                 `step_ms` holds the median / p10 / p90 of the per-step HIP-event durations of the same K steps.
+
+A plain run does only that (set-up, W warm-up steps, K timed steps, the line; `parity` then holds the finiteness of the last two
+timed steps' outputs and the hand-off error count).  `--full` adds what follows, each part still switched off by its --no-* option.
+`--dump-outputs DIR` writes the last timed step's outputs (what the caller of the timed path receives) to DIR/<name>.npy.
 `parity`      : the outputs of the LAST TWO TIMED steps (one per batch) are checked: all finite; EVERY image against the reference
                 digest (tests/golden/demo_digest.npz: 16 images, each a B = 1 forward of the reference itself): IoU >= 0.999,
                 |mask| and |class logits| <= 1e-3, same prediction -- on EVERY rank (rank r's batches are the digest's images
@@ -24,6 +28,7 @@ not hide behind identical inputs.  Rank 0 prints ONE JSON line.
                 kernels measured the same way (algorithmic 4*S^2*hd per head).
 `cpu_baseline`: the CPU oracle (oracle/cvlm_oracle.py, a port of the reference forward) timed on the host cores on a
                 bounded sample (rank 0, N = 1 only).
+`exact_mode`  : the same loop in precision `exact` for 5 steps behind the timed loop; `power`: socket power during the timed steps.
 
 Other lines (same JSON shape, `config.workload` says which):
   --workload encoder                                  BASELINE configs[1]: SAM ViT-H image encoder only, batch 8
@@ -215,11 +220,52 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + --single-device: rehearse the N-rank path on a box with ONE GPU (all ranks on cuda:0)")
     ap.add_argument("--single-device", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity against the reference digests, the text-bank check of N > 1, socket power, the "
+                         "roofline repeat, the `exact` leg and the CPU baseline (each still switched off by its --no-* option below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32 / float64, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-leg", action="store_true", help="cascade workload: skip the 5-step run of the same loop in precision `exact` behind the timed loop")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-power", action="store_true", help="do not sample socket power / clock during the timed steps")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                                   # a plain run sets up, warms up, times the steps and prints the line: nothing else
+        args.no_cpu_baseline = args.no_exact_leg = args.no_roofline = args.no_power = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 60_000_000                 # under 64 MB with the .npy headers
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """`--dump-outputs`: one DIR/<name>.npy per array, float32 (float64 for float64 and integer outputs), so that two builds can be
+    compared output for output.  Should the arrays exceed DUMP_LIMIT_BYTES in all, every array above 1 MB keeps a sample of its
+    flattened elements at positions drawn from a generator seeded by its name (the same positions in every run)."""
+    import zlib
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu()
+            t = t.double() if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) else t.float()
+            out[name] = t.numpy()
+        else:
+            a = np.asarray(t)
+            out[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iu" else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = {k for k, a in out.items() if a.nbytes > 1 << 20}
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in out.items() if k not in big)
+        share = room / sum(out[k].nbytes for k in big)
+        for k in big:
+            a = out[k].reshape(-1)
+            idx = np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, int(a.size * share), replace=False)
+            out[k] = a[np.sort(idx)]
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -470,15 +516,16 @@ def evalloop_line(args, torch, np, g, c, dev, B, make_model, sampler, t0, percen
         loop.step(*batch(k))
         preds += loop.last[1].cpu().tolist()
     items = [(im, gt, int(preds[i]) if i % 3 else (int(preds[i]) + 1) % len(names)) for i, (im, gt, _) in enumerate(items)]
-    # ---- first pass over the whole synthetic split, untimed: the run the parity check below reads (logits kept)
-    loop = DeviceEvalLoop(model, names)
-    kept = []
-    for k in range(nb):
-        loop.step(*batch(k))
-        kept.append((loop.last[0].clone(), loop.last[1].clone(), loop.last[2].clone(), [m.clone() for m in loop.last[3]]))
-    torch.cuda.synchronize()
-    dev_metrics, dev_cls = loop.results()
-    dev_cod = loop.cod_results()
+    # ---- --full: first pass over the whole synthetic split, untimed: the run the parity check below reads (logits kept)
+    if args.full:
+        loop = DeviceEvalLoop(model, names)
+        kept = []
+        for k in range(nb):
+            loop.step(*batch(k))
+            kept.append((loop.last[0].clone(), loop.last[1].clone(), loop.last[2].clone(), [m.clone() for m in loop.last[3]]))
+        torch.cuda.synchronize()
+        dev_metrics, dev_cls = loop.results()
+        dev_cod = loop.cod_results()
     setup_s = time.time() - t0
 
     # ---- the timed loop: W warm-up steps, K timed steps, the final read-back of the metric dict INSIDE the timed region
@@ -502,6 +549,10 @@ def evalloop_line(args, torch, np, g, c, dev, B, make_model, sampler, t0, percen
     finally:
         power = sampler.stop(wall0 + 0.3, time.time())
     value = B * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"metrics": [timed_metrics[k] for k in sorted(timed_metrics)],
+                                         "classification": [timed_cls[k] for k in sorted(timed_cls)],
+                                         "calc_cod": [v for _, v in sorted(loop.cod_results().items())]})
     sec = loop.section_ms()
     tot = sum(sec.values())
     shares = {k: round(v / tot, 4) for k, v in sec.items()}
@@ -510,20 +561,24 @@ def evalloop_line(args, torch, np, g, c, dev, B, make_model, sampler, t0, percen
 
     # ---- what needs no CPU restatement: finite outputs, no abandoned hand-offs, the timed loop's dict equals the first pass's
     n_all = nb * B
-    finite = all(bool(torch.isfinite(kp[0]).all()) and bool(torch.isfinite(kp[2]).all()) for kp in kept)
     cas = model.cascade()
     handoff = sum(e.ws.gemm_errors() for e in (cas, cas.encoder, cas.decoder, cas.clip))
-    same_run = max(abs(timed_metrics[k] - dev_metrics[k]) for k in dev_metrics) if args.steps % nb == 0 and args.steps >= nb else None
-    parity = {"outputs_finite": finite, "parity_checked": False, "images": n_all, "gemm_handoff_errors": handoff,
-              "timed_loop_dict_equals_first_pass": same_run,
-              "device_metrics": {k: round(float(v), 6) for k, v in dev_metrics.items()}, "device_classification": dev_cls,
-              "device_calc_cod": {k: round(float(v), 6) for k, v in dev_cod.items()}}
-    # pipelined: stage 2 shares one CLIP forward with the next batch's pass 1 -- other K-splits, other fp32 summation order: a mask level
-    # may move on a handful of pixels
-    parity["ok"] = bool(finite and handoff == 0 and (same_run is None or same_run < (1e-4 if args.pipelined else 1e-12)))
-    # with --no-cpu-baseline nothing below compares against the oracle; `ok` is then self-consistency only and says so
-    parity["ok_means"] = "self-consistency only (finite outputs, no hand-off errors, the timed loop's dict equals the first pass): nothing was " \
-                         "compared with the oracle / reference in this run"
+    if not args.full:
+        parity = {"parity_checked": False, "images": n_all, "gemm_handoff_errors": handoff, "ok": handoff == 0,
+                  "ok_means": "no hand-off errors: nothing was checked beyond that in this run (see --full)"}
+    else:
+        finite = all(bool(torch.isfinite(kp[0]).all()) and bool(torch.isfinite(kp[2]).all()) for kp in kept)
+        same_run = max(abs(timed_metrics[k] - dev_metrics[k]) for k in dev_metrics) if args.steps % nb == 0 and args.steps >= nb else None
+        parity = {"outputs_finite": finite, "parity_checked": False, "images": n_all, "gemm_handoff_errors": handoff,
+                  "timed_loop_dict_equals_first_pass": same_run,
+                  "device_metrics": {k: round(float(v), 6) for k, v in dev_metrics.items()}, "device_classification": dev_cls,
+                  "device_calc_cod": {k: round(float(v), 6) for k, v in dev_cod.items()}}
+        # pipelined: stage 2 shares one CLIP forward with the next batch's pass 1 -- other K-splits, other fp32 summation order: a mask
+        # level may move on a handful of pixels
+        parity["ok"] = bool(finite and handoff == 0 and (same_run is None or same_run < (1e-4 if args.pipelined else 1e-12)))
+        # with --no-cpu-baseline nothing below compares against the oracle; `ok` is then self-consistency only and says so
+        parity["ok_means"] = "self-consistency only (finite outputs, no hand-off errors, the timed loop's dict equals the first pass): nothing " \
+                             "was compared with the oracle / reference in this run"
 
     # ---- cpu_baseline leg: the same loop's two tails as the reference runs them, on the host -- Pillow + numpy preprocessing (what
     # torchvision's transforms call, datasets/wrappers.py:22-62) and D2H + cv2-style resize + the six numpy metric classes
@@ -788,9 +843,11 @@ def main():
             return enc.forward(batches[k][0], out_name=names[k])
         mine, elapsed, step_ms, outs, power = timed_loop(step)
         value = world * B * args.steps / elapsed
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"features": outs[-1][1]})
         finite = all(bool(torch.isfinite(o).all()) for _, o in outs)
         parity = {"outputs_finite": finite, "parity_checked": False, "ok": finite}
-        dname = {"demo": "demo_digest.npz", "hires1536": "hires1536_digest.npz"}.get(args.geometry)
+        dname = {"demo": "demo_digest.npz", "hires1536": "hires1536_digest.npz"}.get(args.geometry) if args.full else None
         if dname and os.path.exists(digest.golden_path(dname)):
             dg = digest.load(digest.golden_path(dname))
             chk = digest.check_demo_features if args.geometry == "demo" else digest.check_hires_features
@@ -923,9 +980,11 @@ def main():
             finally:
                 power = sampler.stop(wall0 + 0.3, time.time())
         value = B * args.steps / elapsed
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(zip(("pred_mask", "pred", "score"), seen[(args.steps - 1) % nb])))
         finite = all(bool(torch.isfinite(o[0]).all()) and bool(torch.isfinite(o[2]).all()) for o in seen.values())
         parity = {"outputs_finite": finite, "parity_checked": False, "ok": finite}
-        if args.geometry == "demo" and os.path.exists(digest.golden_path("demo_digest.npz")):
+        if args.full and args.geometry == "demo" and os.path.exists(digest.golden_path("demo_digest.npz")):
             dg = digest.load(digest.golden_path("demo_digest.npz"))
             res = [digest.check_cascade(o[0], o[1], o[2], dg, list(range(k * B, (k + 1) * B))) for k, o in sorted(seen.items())]
             checked = sorted(set(i for r in res for i in r["checked_images"]))
@@ -992,7 +1051,7 @@ def main():
     torch.cuda.synchronize()
     text_bank_s = time.time() - tt
     bank_check = None
-    if world > 1:
+    if world > 1 and args.full:
         # the gathered banks are bit-identical on every rank and equal to the single-GPU banks
         alone, alone_tr = cas.clip.text_features(eot, "test"), cas.clip.text_features(eot_tr, "train")
         same = torch.tensor([int(torch.equal(alone, tf) and torch.equal(alone_tr, tf_tr))], device=dev)
@@ -1015,13 +1074,15 @@ def main():
 
     mine, elapsed, step_ms, outs, power = timed_loop(step, flush=cas.flush)
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("masks", "pred", "logits"), outs[-1][1])))
 
     # ---- parity of the timed outputs (last two timed steps = both batches): finite everywhere, and every image against the
-    # reference digest -- on EVERY rank (the ranks' batches are rotations of the digest's images)
+    # reference digest (--full) -- on EVERY rank (the ranks' batches are rotations of the digest's images)
     finite = all(bool(torch.isfinite(o[0]).all()) and bool(torch.isfinite(o[2]).all()) for _, o in outs)
     parity = {"outputs_finite": finite, "parity_checked": False, "ok": finite}
     dpath = digest.golden_path("demo_digest.npz")
-    if args.geometry == "demo" and os.path.exists(dpath):
+    if args.full and args.geometry == "demo" and os.path.exists(dpath):
         dg = digest.load(dpath)
         res = [digest.check_cascade(o[0], o[1], o[2], dg, ids[k]) for k, o in outs]
         res = [r for r in res if r["checked_images"]]
@@ -1039,7 +1100,7 @@ def main():
     parity["mx_self_check"] = cas.mx_self_check_result
     parity["gemm_handoff_errors"] = sum(e.ws.gemm_errors() for e in (cas, cas.encoder, cas.decoder, cas.clip))
     parity["ok"] = bool(parity["ok"] and parity["gemm_handoff_errors"] == 0)
-    if n_dig and os.path.exists(dpath) and not parity["parity_checked"]:
+    if args.full and n_dig and os.path.exists(dpath) and not parity["parity_checked"]:
         parity["ok"] = False                                 # a digest exists and this rank verified nothing: not a pass
     parity["all_ranks_ok"] = all_ranks(parity["ok"])
     parity["min_images_checked_against_reference_per_rank"] = min_over_ranks(len(parity.get("checked_images", [])))

@@ -334,7 +334,7 @@ def test_openai_archive_loads_like_the_reference(golden_dir=os.path.join(REPO, "
         assert abs(float(t.sum()) - s1) <= 1e-9 * max(1.0, abs(s1)) and abs(float(t.pow(2).sum()) - s2) <= 1e-9 * max(1.0, s2), k
     pl = "prompt_learner."
     for name in ("token_prefix", "token_suffix", "token_prefix_test", "token_suffix_test"):
-        assert np.array_equal(sd[pl + name].numpy(), gd[name]), name
+        assert np.array_equal(sd[pl + name].cpu().numpy(), gd[name]), name          # (on the GPU when there is one)
     assert float(sd["image_encoder.conv1_alpha.weight"].abs().max()) == 0.0        # zero-initialised alpha branch
     assert clip._eot("test") == gd["eot_test"].tolist() and clip._eot("train") == gd["eot_train"].tolist()
     # the matrix tensors carry fp16-rounded values (convert_weights), the others do not
@@ -378,7 +378,8 @@ def test_dassl_checkpoint_drops_the_fixed_token_vectors(tmp_path):
     after = clip.state_dict()
     assert torch.equal(after["prompt_learner.token_prefix"], before["prompt_learner.token_prefix"])
     assert torch.equal(after["prompt_learner.token_suffix"], before["prompt_learner.token_suffix"])
-    assert float(after["prompt_learner.ctx"].mean()) == 0.25 and float(after["prompt_learner.token_prefix_test"].mean()) == 3.0
+    # every element (the model sits on the GPU when there is one, where a mean of 3.0s need not come out as exactly 3.0)
+    assert bool((after["prompt_learner.ctx"] == 0.25).all()) and bool((after["prompt_learner.token_prefix_test"] == 3.0).all())
     assert torch.equal(after["image_encoder.proj"], before["image_encoder.proj"])
     assert clip._engine is None and clip._engine_text_dirty
 

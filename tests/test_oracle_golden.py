@@ -67,14 +67,19 @@ def test_cascade_outputs_match_reference(run, gold):
     assert O.mask_iou(run["m"].numpy(), gold["mask_logits"]) >= 0.9999
 
 
-def test_batch_equals_per_image(run):
-    """The reference only runs B=1; the batched oracle must equal per-image calls."""
-    g, c, sd = run["g"], run["c"], run["sd"]
-    inp, ci, cm = (torch.from_numpy(t) for t in synth.make_inputs(g, c, 2))
+def test_batch_equals_per_image(run, gold):
+    """The reference only runs B=1; the batched oracle must equal per-image calls.  Both run in float64: in float32 the batched
+    and the single-image GEMMs round differently by ~1e-5, by an amount that depends on the host's BLAS kernels and thread count."""
+    g, c = run["g"], run["c"]
+    sd = O.to_torch_sd(synth.make_full_state_dict(g, c), torch.float64)
+    inp, ci, cm = (torch.from_numpy(t).double() for t in synth.make_inputs(g, c, 2))
+    bank = torch.from_numpy(gold["bank_test"]).double()
     with torch.no_grad():
-        m1, _, l1 = O.cascade(inp[1:], ci[1:], cm[1:], sd, g, c, run["tf"], torch.from_numpy(
-            np.load(os.path.join(os.path.dirname(__file__), "golden", "tiny_cascade.npz"))["bank_test"]))
-    assert d(m1, run["m"][1:]) < 1e-5 and d(l1, run["logits"][1:]) < 1e-5
+        tf = O.clip_text_features(sd, c, gold["eot_test"].tolist())
+        m, _, l = O.cascade(inp, ci, cm, sd, g, c, tf, bank)
+        m1, _, l1 = O.cascade(inp[1:], ci[1:], cm[1:], sd, g, c, tf, bank)
+    assert m.dtype == l.dtype == torch.float64
+    assert d(m1, m[1:]) < 1e-10 and d(l1, l[1:]) < 1e-10
 
 
 def test_tokens_fixture(golden_dir):

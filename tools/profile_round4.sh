@@ -5,13 +5,13 @@ set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_r4
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 4 --warmup 2 --no-overlap --no-cpu-baseline --no-power > $O/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 4 --warmup 2 --no-overlap --no-cpu-baseline --no-power > $O/bench_stats.log 2>&1
 python tools/summarize_profiles.py stats $O/stats $O/r04_bench_exact_b8_kernel_stats.csv
 python tools/kernel_gaps.py $O/stats > $O/r04_kernel_gaps.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 bench.py --steps 4 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 bench.py --steps 4 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_write.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 bench.py --full --steps 4 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 bench.py --full --steps 4 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_write.log 2>&1
 python tools/summarize_profiles.py traffic $O/fetch $O/write $O/r04_gemm_traffic.json "gemm_nt_kernel<3" 0.5
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/sq -- python3 bench.py --steps 2 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_sq.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/sq -- python3 bench.py --full --steps 2 --warmup 1 --no-overlap --no-cpu-baseline --no-roofline --no-power > $O/bench_sq.log 2>&1
 python - <<'PY'
 import csv, glob, collections, json
 f = sorted(glob.glob("gpurun_out/prof_r4/sq/**/*_counter_collection.csv", recursive=True))[-1]
@@ -35,10 +35,10 @@ json.dump(out, open("gpurun_out/prof_r4/r04_sq_counters.json", "w"), indent=1); 
 PY
 rm -rf $O/stats $O/fetch $O/write $O/sq
 python tools/gemm_shapes.py --batch 8 --reps 2 --pipelined > $O/r04_per_shape_times.log 2>&1
-python bench.py --workload encoder --steps 8 --warmup 2 > $O/r04_bench_encoder_b8.json 2> $O/enc.err; tail -c 600 $O/r04_bench_encoder_b8.json
-python bench.py --geometry hires1536 --batch 4 --workload encoder --steps 6 --warmup 2 > $O/r04_bench_hires1536_b4.json 2> $O/hires.err; tail -c 600 $O/r04_bench_hires1536_b4.json
-python bench.py --surface dropin --batch 1 --steps 32 --no-cpu-baseline > $O/r04_bench_dropin_b1.json 2> $O/dropin_b1.err; tail -c 300 $O/r04_bench_dropin_b1.json
-python bench.py --surface dropin --batch 8 --steps 10 --no-cpu-baseline > $O/r04_bench_dropin_b8.json 2> $O/dropin_b8.err; tail -c 300 $O/r04_bench_dropin_b8.json
+python bench.py --full --workload encoder --steps 8 --warmup 2 > $O/r04_bench_encoder_b8.json 2> $O/enc.err; tail -c 600 $O/r04_bench_encoder_b8.json
+python bench.py --full --geometry hires1536 --batch 4 --workload encoder --steps 6 --warmup 2 > $O/r04_bench_hires1536_b4.json 2> $O/hires.err; tail -c 600 $O/r04_bench_hires1536_b4.json
+python bench.py --full --surface dropin --batch 1 --steps 32 --no-cpu-baseline > $O/r04_bench_dropin_b1.json 2> $O/dropin_b1.err; tail -c 300 $O/r04_bench_dropin_b1.json
+python bench.py --full --surface dropin --batch 8 --steps 10 --no-cpu-baseline > $O/r04_bench_dropin_b8.json 2> $O/dropin_b8.err; tail -c 300 $O/r04_bench_dropin_b8.json
 python tools/gemm_shapes.py --batch 1 --reps 4 > $O/r04_per_shape_times_b1.log 2>&1
 BATCH=1 python tools/graph_step.py > $O/r04_hipgraph_b1.log 2>&1
 ls -la $O
