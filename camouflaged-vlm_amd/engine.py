@@ -178,8 +178,11 @@ class _Base:
         self.ws = Workspace(device)
         self.ksplit = True          # False: GEMMs get no workspace, i.e. no K-split of any kind: the summation order is independent of M
         self.class_token_tail = True    # CLIP vision tower: the last block behind its qkv projection runs for the class tokens only
+        self.record: Optional[dict] = None   # {"attn_splits": set, "mx_operands": bool} while Cascade._mx_self_check runs a leg
 
     def gemm(self, a: H2, lin: Linear, M: int, **kw) -> None:
+        if self.record is not None:
+            self.record["mx_operands"] |= bool(getattr(a, "mx", False) or getattr(kw.get("out_h2"), "mx", False))
         kw.setdefault("split", self.prec.gemm)
         alpha = kw.pop("alpha", 1.0)
         if "bias" not in kw:
@@ -189,6 +192,8 @@ class _Base:
                  workspace=self.ws.gemm_ws() if self.ksplit else None, w_il=w_il, w_mx=lin.w_mx if getattr(a, "mx", False) else None, **kw)
 
     def attention(self, qkv: H2, out: H2, B: int, S: int, heads: int, hd: int, **kw) -> None:
+        if self.record is not None and kw.get("mode", 0) in (1, 2):
+            self.record["attn_splits"].add((kw.get("split_qk", 3), kw.get("split_pv", 3)))
         hip.attention(qkv, out, B, S, heads, hd,
                       workspace=self.ws.scratch("attn_ws", hip.attention_workspace_bytes(B, S, heads, hd, **kw)), **kw)
 
@@ -472,8 +477,10 @@ class SamEncoder(_Base):
         sq, sp = self.attn_split(M)
         for i, blk in enumerate(self.blocks):
             hip.ln_stats_merge(pcs, M, D, 1e-6, mrg, gws)
-            # split_qk == 1: the attention kernels read K's hi plane only -- the projection does not write the other (a sixth of its stores)
-            self.gemm(xh, blk["qkv_f"], M, out_h2=qkv, head_major=(T, g.num_heads, g.head_dim), head_major_nolo=2 if sq == 1 else 0, alpha=inv,
+            # where this block's attention kernel reads K's hi plane only (split (1, 2) on the ViT-H kernels, (1, 1)) the projection does not
+            # write the other (a sixth of its stores); every other shape runs (1, 2) as (3, 3) and needs it -- the workspace holds stale data
+            k_lo = hip.attention_reads_k_lo(2 if blk["window"] > 0 else 1, G, blk["window"], g.head_dim, sq, sp)
+            self.gemm(xh, blk["qkv_f"], M, out_h2=qkv, head_major=(T, g.num_heads, g.head_dim), head_major_nolo=0 if k_lo else 2, alpha=inv,
                       ln_fold=(mrg, blk["qkv_f"].colsum))
             if blk["window"] > 0:
                 self.attention(qkv, att, B, T, g.num_heads, g.head_dim, mode=2, grid=G, window=blk["window"],
@@ -1182,32 +1189,59 @@ class Cascade(_Base):
 
     # ---- precision `mx` self-check -----------------------------------------------------------------------
     # The mx arithmetic (e4m3 correction products, one-term q.k^T, P as one f16) was adopted on the evidence of synthetic weights.  A
-    # checkpoint nobody has measured gets a measurement of its own: before the first batch of two or more images (the forwards that take
-    # the mx path; one image per call runs the `exact` arithmetic anyway, SamEncoder.attn_split) the engine runs the first two images as a
-    # batch (mx) and image 0 alone (exact) and compares every mask logit and the prediction of image 0.  Beyond MX_SELF_CHECK_TOL -- 3/4 of
-    # the 1e-3 gate, the exact arithmetic itself sitting 5e-5 from the reference -- or with another prediction, it says so and serves
-    # every later forward in `exact`.  Cost: one B = 2 and one B = 1 forward (~60 ms) and one host synchronisation per weight load.
+    # checkpoint nobody has measured gets a measurement of its own: before the first forward that takes the mx path -- more than 4096 token
+    # rows in the ViT-H encoder (SamEncoder.attn_split, _blocks_folded) -- the engine runs that forward's batch (or its shortest prefix of
+    # more than 4096 rows: mx) and image 0 alone with `exact` forced on every engine, and compares every mask logit and the prediction of
+    # image 0.  Beyond MX_SELF_CHECK_TOL -- 3/4 of the 1e-3 gate, the exact arithmetic itself sitting 5e-5 from the reference -- or with
+    # another prediction, it says so and serves every later forward in `exact`.  `mx_self_check_result` records what each leg executed
+    # (the ViT-H attention splits launched, whether any GEMM took an mx operand), from the engines' own bookkeeping.
+    # Cost: one forward of the mx leg and one B = 1 forward, and one host synchronisation per weight load.
     MX_SELF_CHECK_TOL = 7.5e-4
 
+    def _engines(self):
+        return (self, self.encoder, self.decoder, self.clip)
+
+    def _recorded(self, fn):
+        """fn() with every engine's bookkeeping on: -> (fn's result, {"attn_splits": sorted list, "mx_operands": bool})."""
+        rec = {"attn_splits": set(), "mx_operands": False}
+        for eng in self._engines():
+            eng.record = rec
+        try:
+            out = fn()
+        finally:
+            for eng in self._engines():
+                eng.record = None
+        return out, {"attn_splits": sorted(rec["attn_splits"]), "mx_operands": rec["mx_operands"]}
+
     def _mx_self_check(self, inp, clip_image, clip_mask) -> None:
-        if (not self.prec.mx or not self.mx_self_check or self.mx_self_check_result is not None or inp.shape[0] < 2 or
-                inp.shape[0] * self.g.grid * self.g.grid <= 4096 or torch.cuda.is_current_stream_capturing()):
+        T = self.g.grid * self.g.grid
+        if (not self.prec.mx or not self.mx_self_check or self.mx_self_check_result is not None or inp.shape[0] * T <= 4096 or
+                torch.cuda.is_current_stream_capturing()):
             return
         self.mx_self_check_result = {"running": True}                  # (the forwards below come back through here)
-        m2, p2, l2 = (t.clone() for t in self.cascade(inp[:2], clip_image[:2], clip_mask[:2]))
-        m1, p1, l1 = self.cascade(inp[:1], clip_image[:1], clip_mask[:1])
+        n = 4096 // T + 1                                                # the shortest prefix that takes the mx path
+        (m2, p2, l2), mx_leg = self._recorded(lambda: tuple(t.clone() for t in self.cascade(inp[:n], clip_image[:n], clip_mask[:n])))
+        prev = [eng.prec for eng in self._engines()]
+        exact = Precision.named("exact")
+        for eng in self._engines():
+            eng.prec = exact
+        try:
+            (m1, p1, l1), ref_leg = self._recorded(lambda: self.cascade(inp[:1], clip_image[:1], clip_mask[:1]))
+        finally:
+            for eng, pr in zip(self._engines(), prev):
+                eng.prec = pr
         dm, dl = float((m2[:1] - m1).abs().max()), float((l2[:1] - l1).abs().max())
         same = bool(torch.equal(p2[:1], p1))
         bad = not (dm <= self.MX_SELF_CHECK_TOL and dl <= self.MX_SELF_CHECK_TOL and same) or not math.isfinite(dm)
         self.mx_self_check_result = {"max_abs_mask_diff": dm, "max_abs_class_logit_diff": dl, "pred_equal": same, "tolerance": self.MX_SELF_CHECK_TOL,
-                                     "demoted_to_exact": bad}
+                                     "demoted_to_exact": bad, "mx_leg": dict(mx_leg, images=n), "exact_leg": dict(ref_leg, images=1)}
         if bad:
             import warnings
             warnings.warn(f"camouflaged_vlm_amd: precision `mx` differs from `exact` on these weights by {dm:.2e} (mask logits) / {dl:.2e} (class "
                           f"logits), prediction {'equal' if same else 'DIFFERENT'} on the first image (tolerance {self.MX_SELF_CHECK_TOL:.1e}): "
                           "serving in precision `exact` from here on", RuntimeWarning)
             exact = dataclasses.replace(self.prec, mx=False, qk=3, pv=3)
-            for eng in (self, self.encoder, self.decoder, self.clip):
+            for eng in self._engines():
                 eng.prec = exact
 
     # ---- LayerNorm-fold refusal guard (ADVICE r3) ---------------------------------------------------------------------------

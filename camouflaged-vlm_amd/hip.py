@@ -497,6 +497,22 @@ def attention(qkv: H2, out: H2, B: int, S: int, heads: int, hd: int, *, mode: in
     _check(load().cvlm_attention(C.byref(a), C.c_void_p(_stream())), "cvlm_attention")
 
 
+def attention_reads_k_lo(mode: int, grid: int, window: int, hd: int, split_qk: int, split_pv: int, out_lo: bool = True) -> bool:
+    """Whether cvlm_attention (csrc/attention.hip) reads K's lo plane for these arguments -- its dispatch restated.  False only where
+    the kernel that runs takes no lo plane of K: split (1, 2) on the ViT-H kernels (64 x 64 / 96 x 96 global maps; 14 x 14 windows with
+    an h2 output) and split (1, 1) everywhere.  (1, 2) on every other shape runs as (3, 3) and reads it; so does (3, 1).  A qkv
+    projection may skip K's lo plane (cvlm_gemm_args.hm_nolo bit 1) only where this says False."""
+    if (split_qk, split_pv) == (1, 1):
+        return False
+    if (split_qk, split_pv) != (1, 2):
+        return True
+    if mode == 1 and hd == 80:
+        return grid not in (64, 96)
+    if mode == 2 and hd == 80:
+        return not (window == 14 and out_lo)
+    return True
+
+
 def attention_workspace_bytes(B: int, S: int, heads: int, hd: int, *, mode: int = 0, grid: int = 0, split_qk: int = 3,
                               split_pv: int = 3, **_unused) -> int:
     """Bytes of caller-owned scratch cvlm_attention wants for these arguments (0 for most modes)."""

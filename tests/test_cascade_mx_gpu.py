@@ -4,7 +4,8 @@ products without the lo planes of Q and P (split 2), against the digests of the 
 
 Adoption gate of the mode: mask logits <= 5e-4, class logits <= 2.5e-4, IoU >= 0.9999, equal predictions on EVERY one of
 the 16 reference images -- twice inside the north-star gate (1e-3 / 0.999) that digest.check_* applies.
-The tiny test geometry (D = 160) has no mx launches (K % 64 != 0); the operator-level tests are tests/test_gemm_mx_gpu.py.
+The tiny test geometry (D = 160) has no mx GEMM launches (K % 64 != 0), but above 4096 token rows it runs the (1, 2) attention split (on the
+generic kernel, as (3, 3)); the operator-level tests are tests/test_gemm_mx_gpu.py and tests/test_attention_peaked_gpu.py.
 """
 import dataclasses
 import os
@@ -305,3 +306,91 @@ def test_mx_encoder_hires_1536_batch4(golden_dir):
     print(f"mx, 1536^2 ViT-H encoder B=4 vs reference digest: {r}")
     assert r["ok"] and r["checked_images"] == [0, 1, 2, 3] and r["max_abs_feature_err"] <= 5e-4
     assert enc.ws.gemm_errors() == 0
+
+
+def _tiny_cascade(g, precision, sd_np=None):
+    from camouflaged_vlm_amd import spec, synth
+    from camouflaged_vlm_amd.engine import Cascade, Precision
+    c = spec.TINY_CLIP
+    sd_np = synth.make_full_state_dict(g, c) if sd_np is None else sd_np
+    cas = Cascade({k: torch.from_numpy(v) for k, v in sd_np.items()}, g, c, torch.device("cuda:0"), Precision.named(precision))
+    cas.clip.set_text_bank(cas.clip.text_features(spec.default_eot(c, "test"), "test"),
+                           torch.from_numpy(synth.make_text_bank(c.n_cls_test, c.embed_dim, "test")), "test")
+    return cas, sd_np
+
+
+@pytest.mark.parametrize("inp_size,B", [(320, 12), (512, 5)])
+def test_mx_attention_reads_a_written_k_lo_plane(monkeypatch, inp_size, B):
+    """Precision `mx` on token maps the ViT-H attention kernels do not serve (20 x 20 and 32 x 32 global maps: the generic kernel runs
+    split (1, 2) as (3, 3) and reads K's lo plane) with more than 4096 token rows, so that the path itself -- not the self-check -- is
+    under test.  The qkv workspace starts as NaN: a projection that skips K's lo plane there (hm_nolo) leaves NaN for the attention to
+    read.  Masks and class logits finite, within Cascade.MX_SELF_CHECK_TOL of `exact` on the same batch, the same predictions."""
+    from camouflaged_vlm_amd import spec, synth
+    monkeypatch.setenv("CVLM_MX_SELF_CHECK", "0")
+    g = dataclasses.replace(spec.TINY_SAM, inp_size=inp_size)
+    cas, sd_np = _tiny_cascade(g, "mx")
+    ref, _ = _tiny_cascade(g, "exact", sd_np)
+    dev = torch.device("cuda:0")
+    inp, ci, cm = (torch.from_numpy(t).to(dev) for t in synth.make_inputs(g, spec.TINY_CLIP, batch=B))
+    M, D = B * g.grid * g.grid, g.embed_dim
+    assert M > 4096
+    cas.encoder.ws._flat[("h2", "qkv")] = torch.full((2 * M * 3 * D,), float("nan"), dtype=torch.float16, device=dev)
+    rec = {"attn_splits": set(), "mx_operands": False}
+    cas.encoder.record = rec
+    m, p, l = (t.clone() for t in cas.cascade(inp, ci, cm))
+    cas.encoder.record = None
+    m0, p0, l0 = ref.cascade(inp, ci, cm)
+    torch.cuda.synchronize()
+    dm, dl = float((m - m0).abs().max()), float((l - l0).abs().max())
+    print(f"mx at {inp_size} px, B = {B}: vs exact mask {dm:.2e} class logits {dl:.2e}")
+    assert bool(torch.isfinite(m).all()) and bool(torch.isfinite(l).all())
+    assert dm <= cas.MX_SELF_CHECK_TOL and dl <= cas.MX_SELF_CHECK_TOL and torch.equal(p, p0)
+    assert rec["attn_splits"] == {(1, 2)}, rec                       # the (1, 2) path ran: generic kernel for the global blocks
+
+
+def test_mx_self_check_legs_differ_on_the_tiny_geometry():
+    """Cascade._mx_self_check compares what it claims to compare: on the tiny geometry (400 tokens per image) the mx leg is the shortest
+    prefix of more than 4096 token rows (11 images: split (1, 2) attention), the reference leg image 0 in `exact` ((3, 3), no mx
+    operand).  (Before: images 0-1 as a batch against image 0 alone -- both legs `exact` at this size.)"""
+    from camouflaged_vlm_amd import spec, synth
+    g = spec.TINY_SAM
+    cas, _ = _tiny_cascade(g, "mx")
+    dev = torch.device("cuda:0")
+    inp, ci, cm = (torch.from_numpy(t).to(dev) for t in synth.make_inputs(g, spec.TINY_CLIP, batch=12))
+    cas.cascade(inp[:10], ci[:10], cm[:10])                          # 4000 token rows: no mx path, no check
+    assert cas.mx_self_check_result is None
+    cas.cascade(inp, ci, cm)
+    r = cas.mx_self_check_result
+    print("mx self-check, tiny geometry B = 12:", r)
+    assert r["mx_leg"]["images"] == 11 and r["mx_leg"]["attn_splits"] == [(1, 2)]
+    assert r["exact_leg"]["images"] == 1 and r["exact_leg"]["attn_splits"] == [(3, 3)] and not r["exact_leg"]["mx_operands"]
+    assert cas.prec.mx == (not r["demoted_to_exact"]) and cas.encoder.prec.qk == (1 if cas.prec.mx else 3)
+
+
+def test_mx_self_check_legs_differ_on_the_demo_geometry(demo_mx):
+    """Demo geometry, B = 2: the mx leg takes the mx GEMMs and (1, 2) attention, the reference leg neither."""
+    from camouflaged_vlm_amd import synth
+    cas, dg, g, c, dev = demo_mx
+    if cas.mx_self_check_result is None:
+        inp, ci, cm = (torch.from_numpy(t).to(dev) for t in synth.make_inputs(g, c, batch=2))
+        cas.cascade(inp, ci, cm)
+    r = cas.mx_self_check_result
+    assert r["mx_leg"] == {"images": 2, "attn_splits": [(1, 2)], "mx_operands": True}, r
+    assert r["exact_leg"] == {"images": 1, "attn_splits": [(3, 3)], "mx_operands": False}, r
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_mx_self_check_fires_on_one_image_at_1536(B):
+    """A whole Cascade built at 1536^2 (reduced width: embed_dim 160, hd 80, 96 x 96 map -- the global block takes the g64pp (1, 2)
+    kernel): 9216 token rows per image take the mx path, so ONE image is checked -- the mx leg is that image, the reference leg the same
+    image in `exact`.  (Before: a B = 1 call ran `mx` and never triggered the check.)"""
+    from camouflaged_vlm_amd import spec, synth
+    g = spec.SamGeometry(inp_size=1536, embed_dim=160, depth=2, num_heads=2, global_attn_indexes=(1,))
+    cas, _ = _tiny_cascade(g, "mx")
+    dev = torch.device("cuda:0")
+    inp, ci, cm = (torch.from_numpy(t).to(dev) for t in synth.make_inputs(g, spec.TINY_CLIP, batch=B))
+    cas.cascade(inp, ci, cm)
+    r = cas.mx_self_check_result
+    print(f"mx self-check, 1536^2 reduced width, B = {B}:", r)
+    assert r["mx_leg"]["images"] == 1 and r["mx_leg"]["attn_splits"] == [(1, 2)]
+    assert r["exact_leg"] == {"images": 1, "attn_splits": [(3, 3)], "mx_operands": False}, r
