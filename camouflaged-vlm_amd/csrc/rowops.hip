@@ -381,9 +381,11 @@ __global__ __launch_bounds__(256) void dense_pe_kernel(const float* __restrict__
     }
 }
 
+// EDGE_OUT: also write the edge probability sigmoid(g) of every pixel (cvlm_mask_head_edge); the mask arithmetic is the same code
+template <bool EDGE_OUT>
 __global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict__ up, const float* __restrict__ edge,
                                                         const float* __restrict__ hyper, int HW, int C,
-                                                        float* __restrict__ low) {
+                                                        float* __restrict__ low, float* __restrict__ edge_prob) {
     const int b = blockIdx.y;
     const float* h0 = hyper + (int64_t)b * 5 * C;
     const float* h4 = h0 + 4 * C;
@@ -407,6 +409,7 @@ __global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict_
         }
         const float s = 1.0f / (1.0f + expf(-g));
         low[(int64_t)b * HW + pix] = m * s + m;
+        if constexpr (EDGE_OUT) edge_prob[(int64_t)b * HW + pix] = s;
     }
 }
 
@@ -552,6 +555,56 @@ __global__ __launch_bounds__(1024) void clip_head_kernel(const float* __restrict
     __syncthreads();
     const int best = __float_as_int(red[0]);
     for (int d = tid; d < D; d += 1024) txt_sel[(int64_t)b * D + d] = txt[(int64_t)best * D + d];
+}
+
+// Hypothesis selection: one 256-thread block per row.  The row sits in LDS; the rank of class c is the number of classes j with
+// v[j] > v[c], or v[j] == v[c] and j < c -- descending order, ties to the lower index, so rank 0 is the first maximum that
+// clip_head_kernel's strict-`>` scan keeps.  A row holding a NaN has no order: every slot gets -1 and its sel rows NaN.  With idx_in
+// no ranks are formed: the given indices are gathered (any K; an index outside [0, C) gets the NaN row's treatment).
+constexpr int TOPK_MAXC = 1024;
+
+__global__ __launch_bounds__(256) void topk_select_kernel(const float* __restrict__ logits, int C, int K,
+                                                          const float* __restrict__ txt, int D,
+                                                          const int64_t* __restrict__ idx_in, int64_t* __restrict__ idx_out,
+                                                          float* __restrict__ sel) {
+    __shared__ float v[TOPK_MAXC];
+    __shared__ int slot[TOPK_MAXC];
+    __shared__ int has_nan;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (!idx_in) {
+        if (tid == 0) has_nan = 0;
+        __syncthreads();
+        const float* row = logits + (int64_t)b * C;
+        for (int c = tid; c < C; c += 256) {
+            v[c] = row[c];
+            if (__builtin_isnan(v[c])) has_nan = 1;
+        }
+        __syncthreads();
+        if (has_nan) {
+            for (int k = tid; k < K; k += 256) slot[k] = -1;
+        } else {
+            for (int c = tid; c < C; c += 256) {
+                const float x = v[c];
+                int r = 0;
+                for (int j = 0; j < C; ++j) r += (v[j] > x) || (v[j] == x && j < c);
+                if (r < K) slot[r] = c;
+            }
+        }
+        __syncthreads();
+    }
+    auto pick = [&](int k) -> int {
+        if (!idx_in) return slot[k];
+        const int64_t c = idx_in[(int64_t)b * K + k];
+        return (c >= 0 && c < C) ? (int)c : -1;
+    };
+    for (int k = tid; k < K; k += 256) idx_out[(int64_t)b * K + k] = pick(k);
+    const int wv = D >> 2;
+    const float nan = __builtin_nanf("");
+    for (int64_t i = tid; i < (int64_t)K * wv; i += 256) {
+        const int k = (int)(i / wv), d = (int)(i - (int64_t)k * wv);
+        const int c = pick(k);
+        ((float4*)sel)[((int64_t)b * K + k) * wv + d] = c >= 0 ? ((const float4*)txt)[(int64_t)c * wv + d] : make_float4(nan, nan, nan, nan);
+    }
 }
 
 __global__ __launch_bounds__(64) void normalize_add_kernel(const float* __restrict__ x, const float* __restrict__ add,
@@ -835,8 +888,17 @@ int cvlm_dense_pe(const float* gauss, int32_t size, int32_t C, float* out, void*
 int cvlm_mask_head(const float* up, const float* edge_emb, const float* hyper, int32_t B, int32_t HW, int32_t C,
                    float* low, void* stream) {
     if (!up || !hyper || !low || (C & 3)) return CVLM_E_BADARG;
-    hipLaunchKernelGGL(mask_head_kernel, dim3(grid_for(HW, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, up,
-                       edge_emb, hyper, HW, C, low);
+    hipLaunchKernelGGL(mask_head_kernel<false>, dim3(grid_for(HW, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, up,
+                       edge_emb, hyper, HW, C, low, nullptr);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_mask_head_edge(const float* up, const float* edge_emb, const float* hyper, int32_t P, int32_t HW, int32_t C,
+                        float* low, float* edge_prob, void* stream) {
+    if (!up || !edge_emb || !hyper || !low || !edge_prob || P <= 0 || P > 65535 || HW <= 0 || C <= 0 || (C & 3)) return CVLM_E_BADARG;
+    hipLaunchKernelGGL(mask_head_kernel<true>, dim3(grid_for(HW, 256, 1024), P), dim3(256), 0, (hipStream_t)stream, up,
+                       edge_emb, hyper, HW, C, low, edge_prob);
     CVLM_CHECK_LAUNCH();
     return 0;
 }
@@ -896,6 +958,15 @@ int cvlm_clip_head(const float* img, const float* txt, float logit_scale_exp, in
     if (!img || !txt || !img_n || !logits || !pred || !txt_sel || C <= 0 || C > 1024) return CVLM_E_BADARG;
     hipLaunchKernelGGL(clip_head_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, img, txt, logit_scale_exp, C, D,
                        img_n, logits, pred, txt_sel);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
+                     int64_t* idx_out, float* sel, void* stream) {
+    if ((!logits && !idx_in) || !txt || !idx_out || !sel || B <= 0 || C <= 0 || K <= 0 || D <= 0 || (D & 3)) return CVLM_E_BADARG;
+    if (!idx_in && (C > TOPK_MAXC || K > C)) return CVLM_E_BADARG;                 // ranking: the row in LDS, K of its C classes
+    hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, C, K, txt, D, idx_in, idx_out, sel);
     CVLM_CHECK_LAUNCH();
     return 0;
 }

@@ -8,7 +8,8 @@ Differences that are deliberate and documented:
   * batched inputs are supported and are defined as B independent B=1 forwards (the reference's
     decoder only works for B=1, mask_decoder_edge.py:156-158);
   * the image-independent MaPLe text encoder is evaluated once per weight load, not per call;
-  * training methods (forward/backward_G/optimize_parameters) are out of scope and raise.
+  * training methods (forward/backward_G/optimize_parameters) are out of scope and raise;
+  * ``infer_classes`` is an extension (K class hypotheses per image), not a method of the reference.
 """
 from __future__ import annotations
 
@@ -109,6 +110,17 @@ class SAM(nn.Module):
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().infer_test(input.float().contiguous(), clip_image.float().contiguous(),
                                          clip_zero_mask.float().contiguous())
+
+    def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None):
+        """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
+        the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
+        decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
+        pass-1 logits) and `classes` (int64 (B, K)).  -> engine.ClassHypotheses ("K class hypotheses per image")."""
+        H, W = input.shape[-2:]
+        assert H == self.inp_size and W == self.inp_size, \
+            f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
+        return self.cascade().infer_classes(input.float().contiguous(), clip_image.float().contiguous(),
+                                            clip_zero_mask.float().contiguous(), classes=classes, topk=topk)
 
     def infer(self, input, clip_image, clip_zero_mask):
         """:305-329 (bs = 1 variant of infer_test)."""

@@ -663,9 +663,12 @@ class MaskDecoder(_Base):
             self.gemm(a, lin, rows, out_f32=out, residual=const, batch=B, stride_a=rows * lin.K, stride_r=0, stride_o=rows * lin.N, **kw)
 
     def forward(self, feats: torch.Tensor, sparse: torch.Tensor, no_mask: torch.Tensor, gauss: torch.Tensor,
-                B: int, taps: Optional[dict] = None) -> torch.Tensor:
+                B: int, taps: Optional[dict] = None, edge_out: bool = False):
         """feats f32 [B*T][C]; sparse f32 [B][2][C] -> low-res mask logits f32 [B][4G][4G] (mask 0, :133-135).
-        mask_decoder_edge.py:96-190, transformer_maskdecoder_edge.py:62-214."""
+        mask_decoder_edge.py:96-190, transformer_maskdecoder_edge.py:62-214.  B counts prompts: one row of `sparse` and one
+        copy of the image's features each (the reference expands to sparse_prompt_embeddings.size(0), :150-158).
+        edge_out=True: -> (mask logits, edge probabilities f32 [B][4G][4G] = sigmoid(hyper_edge . edge_embedding), :182-184)
+        from cvlm_mask_head_edge in place of cvlm_mask_head; every other launch is the same."""
         g, ws = self.g, self.ws
         G, C, T, H = g.grid, g.prompt_embed_dim, g.grid * g.grid, g.dec_heads
         NT = self.tokens.shape[0]
@@ -777,11 +780,15 @@ class MaskDecoder(_Base):
             self.gemm(t1, self.lin[mlp + ".layers.1"], B, out_h2=t2, act=ACT_RELU)
             self.gemm(t2, self.lin[mlp + ".layers.2"], B, out_f32=hyper[:, slot], ldo=5 * (C // 8))
         low = ws.f32("low", B, HW)
-        hip.mask_head(up, edge_emb, hyper, B, HW, C // 8, low)
+        if edge_out:
+            edge = ws.f32("low_edge", B, HW)
+            hip.mask_head_edge(up, edge_emb, hyper, B, HW, C // 8, low, edge)
+        else:
+            hip.mask_head(up, edge_emb, hyper, B, HW, C // 8, low)
         if taps is not None:
             taps.update(hs=hs.clone(), src=keys.clone(), upscaled=up.clone(), edge_emb=edge_emb.clone(),
                         hyper=hyper.clone(), low_res_masks=low.clone())
-        return low
+        return (low, edge) if edge_out else low
 
 
 class VanillaMaskDecoder(MaskDecoder):
@@ -1147,6 +1154,19 @@ class ClipModel(_Base):
         return img_n.unsqueeze(1), sel.unsqueeze(1), pred, logits
 
 
+@dataclass
+class ClassHypotheses:
+    """K class hypotheses per image from one encoder pass (Cascade.infer_classes).  Hypothesis k of image b is what `infer_test` /
+    `cascade` return for that image had CLIP pass 1 predicted classes[b, k]; the prompts run in the order p = b * K + k of the
+    reference's repeat_interleave (models/mmseg/models/sam/mask_decoder_edge.py:150-158)."""
+    classes: torch.Tensor           # (B, K) int64; with topk= the K largest pass-1 logits, descending: classes[:, 0] = pass 1's prediction
+    pass1_logits: torch.Tensor      # (B, n_cls) CLIP pass 1 (mapleAlphaCLIP.py:285-294), as in `cascade`
+    masks: torch.Tensor             # (B, K, S, S) f32 mask logits (models/sam_maskdecoder_edge.py:354)
+    edges: torch.Tensor             # (B, K, S, S) f32 edge probabilities sigmoid(hyper_edge . edge_embedding), upsampled (:298-302)
+    logits: torch.Tensor            # (B, K, n_cls) stage 2 of each hypothesis (demo.py:117-122)
+    pred: torch.Tensor              # (B, K) int64 stage-2 prediction
+
+
 # ================================================================================================
 # The cascade  (models/sam_maskdecoder_edge.py:331-357 + demo.py:116-122)
 # ================================================================================================
@@ -1355,6 +1375,180 @@ class Cascade(_Base):
             taps.update(features=feats.clone(), sparse=sparse.clone(), pass1_logits=score.clone())
         self._fold_guard_arm(torch.cuda.current_stream())
         return masks
+
+    # ---- K class hypotheses per image ---------------------------------------------------------------------------
+    # Prompts per decoder pass of infer_classes.  From above, the 32-bit limits of the launchers: row counts are int32 and some row
+    # kernels form element offsets in 32 bits, so no decoder buffer may reach 2^31 bytes -- the widest, the first 3x3 convolution's
+    # output (16 T rows of C / 4 floats per prompt, 16 MiB at 64 x 64 tokens), allows 127 prompts at the demo geometry.  Below that,
+    # the workspace: the decoder keeps its buffers for the engine's life, sized by the largest pass it has run.
+    CLASS_CHUNK = 64
+
+    def class_chunk(self) -> int:
+        g = self.g
+        T, C = g.grid * g.grid, g.prompt_embed_dim
+        limit = (2 ** 31 - 1) // (16 * T * (C // 4) * 4)
+        return max(1, min(self.CLASS_CHUNK, limit))
+
+    def _class_request(self, B: int, classes, topk):
+        """Host-side validation of infer_classes' hypotheses before any launch -> (K, host int64 (B, K) tensor or None)."""
+        n_cls = self.clip.txt["test"].shape[0]
+        if (classes is None) == (topk is None):
+            raise ValueError("infer_classes: give exactly one of classes= and topk=")
+        if topk is not None:
+            if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)):
+                raise ValueError(f"infer_classes: topk must be an int, got {type(topk).__name__}")
+            K = int(topk)
+            if not 1 <= K <= n_cls:
+                raise ValueError(f"infer_classes: topk={K} outside [1, n_cls = {n_cls}]")
+            if n_cls > 1024:
+                raise ValueError(f"infer_classes: topk ranks up to 1024 classes (cvlm_topk_select), the bank has {n_cls}")
+            return K, None
+        if not isinstance(classes, torch.Tensor):
+            raise ValueError(f"infer_classes: classes must be an int64 tensor (B, K), got {type(classes).__name__}")
+        if classes.dtype != torch.int64 or classes.dim() != 2 or int(classes.shape[0]) != B:
+            raise ValueError(f"infer_classes: classes must be int64 of shape ({B}, K), got {classes.dtype} {tuple(classes.shape)}")
+        K = int(classes.shape[1])
+        if K < 1:
+            raise ValueError("infer_classes: classes has K = 0 hypotheses")
+        host = classes.detach().to("cpu").contiguous()              # a device tensor: one synchronisation, for this check
+        if bool(((host < 0) | (host >= n_cls)).any()):
+            raise ValueError(f"infer_classes: a class index outside [0, {n_cls})")
+        return K, host
+
+    @staticmethod
+    def _per_prompt(src: torch.Tensor, K: int, p0: int, p1: int, dst: torch.Tensor) -> None:
+        """dst[p - p0] = src[p // K] for the prompts p0 <= p < p1 (device copies of per-image rows, one per image)."""
+        for b in range(p0 // K, (p1 - 1) // K + 1):
+            lo, hi = max(p0, b * K), min(p1, (b + 1) * K)
+            dst[lo - p0:hi - p0].copy_(src[b:b + 1].expand(hi - lo, *src.shape[1:]))
+
+    def _class_prompts(self, img_f: torch.Tensor, sel: torch.Tensor, B: int, P: int):
+        """sparse_prompts for P = B * K prompts: sam_visual_proj once per image, sam_text_proj of the P text rows
+        (models/sam_maskdecoder_edge.py:342-344) -> (vis f32 [B][C], txt f32 [P][C])."""
+        ws, C, D = self.ws, self.g.prompt_embed_dim, sel.shape[-1]
+        hv, ht = ws.h2("cp_hv", B, D), ws.h2("cp_ht", P, D)
+        vis, txt = ws.f32("cp_vis", B, C), ws.f32("cp_txt", P, C)
+        hip.layernorm(img_f.reshape(B, D), self.vproj[0], self.vproj[1], 1e-5, B, D, out_h2=hv)
+        self.gemm(hv, self.vproj[2], B, out_f32=vis)
+        hip.layernorm(vis, self.vproj[3], self.vproj[4], 1e-5, B, C, out_f32=vis)
+        hip.layernorm(sel.reshape(P, D), self.tproj[0], self.tproj[1], 1e-5, P, D, out_h2=ht)
+        self.gemm(ht, self.tproj[2], P, out_f32=txt)
+        return vis, txt
+
+    def _class_stage2(self, masks: torch.Tensor, clip_image: torch.Tensor, B: int, K: int, p0: int, p1: int,
+                      logits: torch.Tensor, pred: torch.Tensor) -> None:
+        """demo.py:117-122 for the prompts p0 <= p < p1 as ONE CLIP forward: its images are the groups clip_image[b_lo:b_hi] of
+        one hypothesis slot k each (ClipModel.image_features stacks groups without copying them), the alphas follow in that
+        order; results go back to the prompt order p = b * K + k."""
+        S, R, n = self.g.inp_size, self.c.image_resolution, p1 - p0
+        alpha = self.ws.f32("cls_alpha", n, 1, R, R)
+        hip.bilinear(masks[p0:p1], n, S, S, alpha, R, R, sigmoid_in=True)
+        groups = []                                                  # (k, b_lo, b_hi): prompts b * K + k of this range
+        for k in range(K):
+            b_lo, b_hi = max(0, -(-(p0 - k) // K)), min(B, -(-(p1 - k) // K))
+            if b_lo < b_hi:
+                groups.append((k, b_lo, b_hi))
+        if len(groups) == 1:
+            images, alphas = [clip_image[groups[0][1]:groups[0][2]]], [alpha]
+        else:
+            alpha_q = self.ws.f32("cls_alpha_q", n, 1, R, R)
+            images, alphas, q = [], [], 0
+            for k, b_lo, b_hi in groups:
+                m = b_hi - b_lo
+                alpha_q[q:q + m].copy_(alpha[b_lo * K + k - p0:(b_hi - 1) * K + k - p0 + 1:K])
+                images.append(clip_image[b_lo:b_hi])
+                alphas.append(alpha_q[q:q + m])
+                q += m
+        _, _, pr, lg = self.clip.forward(images, alphas)
+        q = 0
+        for k, b_lo, b_hi in groups:
+            m = b_hi - b_lo
+            logits[b_lo * K + k:(b_hi - 1) * K + k + 1:K].copy_(lg[q:q + m])
+            pred[b_lo * K + k:(b_hi - 1) * K + k + 1:K].copy_(pr[q:q + m])
+            q += m
+
+    def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
+                      topk: Optional[int] = None) -> ClassHypotheses:
+        """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
+        topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
+        pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
+        the two; both are validated on the host before anything is launched (ValueError) -- a `classes` tensor on the device
+        costs one synchronisation for that check.  Same machinery as cascade(pipelined=False): mx self-check, flush() of an owed
+        pipelined stage 2, the LayerNorm-fold guard, CLIP pass 1 on the side stream under the encoder; the current stream waits
+        for the results before the call returns.  Prompts p = b * K + k run through the decoder `class_chunk()` at a time; stage 2
+        is one CLIP forward per chunk.  Hypothesis k is bit for bit what `cascade(pipelined=False)` gives for class classes[b, k]
+        when the GEMM row counts match -- K = 1 with B <= class_chunk() -- and otherwise within the batch tolerance of the GEMM
+        K-splits.  A pass-1 row holding a NaN has no order: with topk= its classes are -1 and its masks, edges and
+        stage-2 logits NaN; its stage-2 `pred` is what cvlm_clip_head answers for NaN logits, class 0 -- read `classes`, not `pred`,
+        to tell such a hypothesis."""
+        B = int(inp.shape[0])
+        K, host_classes = self._class_request(B, classes, topk)
+        self._mx_self_check(inp, clip_image, clip_mask)
+        self.flush()
+        self._fold_guard_check()
+        g, dev = self.g, self.device
+        P, S, T, C, G = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim, g.grid
+        txt_bank = self.clip.txt["test"]
+        n_cls, D = txt_bank.shape
+        idx_in = None if host_classes is None else host_classes.to(dev)
+        main = torch.cuda.current_stream()
+        if self.overlap_clip:                                        # encoder's first blocks, then the CLIP pass: see infer_test
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.device)
+            side = self._side
+            ready = torch.cuda.Event()
+            ready.record(main)
+            res = []
+
+            def issue_clip():
+                side.wait_event(ready)
+                with torch.cuda.stream(side):
+                    res.append(self.clip.forward(clip_image, clip_mask))
+
+            feats = self.encoder.forward(inp, None, issue_hook=issue_clip)
+            enc_done = torch.cuda.Event()
+            enc_done.record(main)
+            img_f, _, _, score = res[0]
+        else:
+            side = main
+            feats = self.encoder.forward(inp, None)
+            img_f, _, _, score = self.clip.forward(clip_image, clip_mask)
+        with torch.cuda.stream(side):
+            if side is not main:
+                side.wait_event(enc_done)
+            cls = torch.empty(B, K, dtype=torch.int64, device=dev)
+            sel = self.ws.f32("cls_sel", P, D)
+            hip.topk_select(score if idx_in is None else None, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
+            vis, txt = self._class_prompts(img_f, sel, B, P)
+            masks = torch.empty(B, K, S, S, device=dev)
+            edges = torch.empty(B, K, S, S, device=dev)
+            logits = torch.empty(B, K, n_cls, device=dev)
+            pred = torch.empty(B, K, dtype=torch.int64, device=dev)
+            mflat, eflat = masks.view(P, S, S), edges.view(P, S, S)
+            chunk = self.class_chunk()
+            for p0 in range(0, P, chunk):
+                p1 = min(P, p0 + chunk)
+                n = p1 - p0
+                if K == 1:                                           # one prompt per image: the features rows as they are
+                    fr = feats[p0 * T:p1 * T]
+                else:
+                    fr = self.ws.f32("cls_feats", n * T, C)
+                    self._per_prompt(feats.view(B, T * C), K, p0, p1, fr.view(n, T * C))
+                sp = self.ws.f32("cls_sparse", n, 2, C)
+                self._per_prompt(vis, K, p0, p1, sp[:, 0])
+                sp[:, 1].copy_(txt[p0:p1])
+                low, low_e = self.decoder.forward(fr, sp, self.no_mask, self.gauss, n, None, edge_out=True)
+                hip.bilinear(low, n, 4 * G, 4 * G, mflat[p0:p1], S, S)          # :380-387 (2nd resize = identity)
+                hip.bilinear(low_e, n, 4 * G, 4 * G, eflat[p0:p1], S, S)        # postprocess_masks(low_res_edges), :299
+                self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P))
+        self._fold_guard_arm(side)
+        if side is not main:
+            for t in (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)):
+                t.record_stream(side)
+            for t in (cls, score, masks, edges, logits, pred):
+                t.record_stream(main)
+            main.wait_stream(side)
+        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

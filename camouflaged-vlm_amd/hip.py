@@ -25,6 +25,7 @@ EXPORTS = [
     "cvlm_mask_to_u8", "cvlm_mask_joint_hist", "cvlm_mask_wfm", "cvlm_topk_accumulate",
     "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
     "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
+    "cvlm_mask_head_edge", "cvlm_topk_select",
 ]
 ABI_VERSION = 12
 
@@ -544,6 +545,21 @@ def mask_head(up, edge_emb, hyper, B: int, HW: int, Cc: int, low) -> None:
     _check(load().cvlm_mask_head(C.c_void_p(up.data_ptr()), C.c_void_p(_p(edge_emb)),
                                  C.c_void_p(hyper.data_ptr()), C.c_int32(B), C.c_int32(HW), C.c_int32(Cc),
                                  C.c_void_p(low.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_head")
+
+
+def mask_head_edge(up, edge_emb, hyper, P: int, HW: int, Cc: int, low, edge_prob) -> None:
+    """cvlm_mask_head for P prompts, also writing the edge probabilities edge_prob f32 [P][HW]."""
+    _check(load().cvlm_mask_head_edge(C.c_void_p(up.data_ptr()), C.c_void_p(edge_emb.data_ptr()), C.c_void_p(hyper.data_ptr()),
+                                      C.c_int32(P), C.c_int32(HW), C.c_int32(Cc), C.c_void_p(low.data_ptr()),
+                                      C.c_void_p(edge_prob.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_head_edge")
+
+
+def topk_select(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, sel) -> None:
+    """idx_out int64 [B][K] = the K largest logits per row, descending, ties to the lower index (or idx_in when given:
+    gather only); sel f32 [B][K][D] = txt[idx_out] (include/cvlm.h)."""
+    _check(load().cvlm_topk_select(C.c_void_p(_p(logits)), C.c_int32(B), C.c_int32(Cc), C.c_int32(K), C.c_void_p(txt.data_ptr()),
+                                   C.c_int32(D), C.c_void_p(_p(idx_in)), C.c_void_p(idx_out.data_ptr()), C.c_void_p(sel.data_ptr()),
+                                   C.c_void_p(_stream())), "cvlm_topk_select")
 
 
 def bilinear(x, N: int, hin: int, win: int, out, hout: int, wout: int, sigmoid_in: bool = False) -> None:

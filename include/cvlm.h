@@ -284,6 +284,15 @@ int cvlm_dense_pe(const float* gauss, int32_t size, int32_t C, float* out, void*
 int cvlm_mask_head(const float* up, const float* edge_emb, const float* hyper, int32_t B, int32_t HW, int32_t C,
                    float* low, void* stream);
 
+/* The same mask head for P prompts with the edge map as a second output (K class hypotheses per image,
+ * mask_decoder_edge.py:150-186: the decoder expands to sparse_prompt_embeddings.size(0) prompts; `edge` at :182-184 is
+ * the low-res edge map that models/sam_maskdecoder_edge.py:298-302 upsamples into pred_edge).
+ * up, edge_emb f32 [P][HW][C]; hyper f32 [P][5][C].  low: what cvlm_mask_head writes -- same kernel, same per-pixel arithmetic, same bits;
+ * edge_prob[p][pix] = sigmoid(hyper[p][4].edge_emb).  CVLM_E_BADARG: a NULL pointer, P outside [1, 65535], HW or C <= 0,
+ * C % 4 != 0. */
+int cvlm_mask_head_edge(const float* up, const float* edge_emb, const float* hyper, int32_t P, int32_t HW, int32_t C,
+                        float* low, float* edge_prob, void* stream);
+
 /* Bilinear resize, align_corners=False (F.interpolate): in f32 [N][hin][win] -> out [N][hout][wout];
  * sigmoid_in != 0 applies sigmoid to the input first (demo.py:117-120). */
 int cvlm_bilinear(const float* in, int32_t N, int32_t hin, int32_t win, float* out, int32_t hout, int32_t wout,
@@ -314,6 +323,19 @@ int cvlm_gather_rows_h2(const void* x_hi, const void* x_lo, float scale, int32_t
  * logits [B][C], pred int64 [B], txt_sel [B][D] = txt[pred]. */
 int cvlm_clip_head(const float* img, const float* txt, float logit_scale_exp, int32_t B, int32_t C, int32_t D,
                    float* img_n, float* logits, int64_t* pred, float* txt_sel, void* stream);
+
+/* K class hypotheses per image (cocotrainers/mapleAlphaCLIP.py:285-294 keeps the argmax; this keeps the K largest).
+ * logits f32 [B][C]; txt f32 [C][D]; idx_out int64 [B][K]; sel f32 [B][K][D].
+ * idx_in == NULL: idx_out[b] = the K largest logits of row b in descending order, ties to the lower index -- on a finite row
+ *   idx_out[b][0] equals cvlm_clip_head's pred (its strict-`>` first maximum).  A row holding a NaN gets -1 in every slot and
+ *   NaN sel rows (its hypotheses come out NaN, never as a plausible class); cvlm_clip_head keeps returning class 0 for such a
+ *   row, unchanged.  Needs C <= 1024 and 1 <= K <= C.
+ * idx_in != NULL (int64 [B][K], any K >= 1): no ranking, logits may be NULL; idx_out = idx_in, an index outside [0, C) reads
+ *   as -1 with a NaN sel row.
+ * sel[b][k] = txt[idx_out[b][k]], bit for bit.  CVLM_E_BADARG: a NULL pointer, B, C, K or D <= 0, D % 4 != 0, and when ranking
+ *   C > 1024 or K > C. */
+int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
+                     int64_t* idx_out, float* sel, void* stream);
 
 /* Row L2 normalise + add: out[r] = x[r]/||x[r]|| + add[r] (text bank, mapleAlphaCLIP.py:290-291). */
 int cvlm_normalize_add(const float* x, const float* add, int32_t R, int32_t D, float* out, void* stream);
