@@ -13,6 +13,7 @@ from __future__ import annotations
 import dataclasses
 import math
 import os
+import warnings
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -1193,9 +1194,6 @@ class Cascade(_Base):
         # as ONE vision-tower forward over both batches (M = 9296 at B = 8: 36 row tiles instead of twice 18.2; out_proj 148
         # tiles on 256 CUs instead of twice 76).  `fuse_clip = False` keeps the two forwards apart (tests).
         self.fuse_clip = True
-        # Host issue order inside a step: the encoder's first blocks BEFORE the side stream's CLIP launches (rounds 1-2 issued the
-        # CLIP pass first).  It decides nothing at B = 8 (the host is far ahead of the GPU); with one image the host IS the pace
-        # of a CLIP pass and the encoder behind it started 4 ms late (profiles/r03_encoder_first_ab.log).
         self._pending = None                                         # (masks, clip_image, pred, logits) of the batch whose stage 2 is still owed
         self._pending_stream = None
         self._clip_done = None                                       # end of the last fused CLIP forward (reader of the owned input copies)
@@ -1256,7 +1254,6 @@ class Cascade(_Base):
         self.mx_self_check_result = {"max_abs_mask_diff": dm, "max_abs_class_logit_diff": dl, "pred_equal": same, "tolerance": self.MX_SELF_CHECK_TOL,
                                      "demoted_to_exact": bad, "mx_leg": dict(mx_leg, images=n), "exact_leg": dict(ref_leg, images=1)}
         if bad:
-            import warnings
             warnings.warn(f"camouflaged_vlm_amd: precision `mx` differs from `exact` on these weights by {dm:.2e} (mask logits) / {dl:.2e} (class "
                           f"logits), prediction {'equal' if same else 'DIFFERENT'} on the first image (tolerance {self.MX_SELF_CHECK_TOL:.1e}): "
                           "serving in precision `exact` from here on", RuntimeWarning)
@@ -1268,16 +1265,13 @@ class Cascade(_Base):
     # A row with |mu| / sigma > 128 cannot be served by the folded LayerNorm within the error budget:
     # cvlm_ln_stats_merge writes NaN for it and counts it in word 513 of the GEMM workspace -- a NaN mask, never a finite wrong
     # one.  The reference's nn.LayerNorm serves such rows, so the product must not keep returning NaN: after every forward the
-    # two counters (encoder, CLIP tower) are copied to pinned host memory asynchronously (no synchronisation on the path); the
-    # next call that finds the copy complete and a counter raised switches BOTH towers to the separate two-pass LayerNorm
+    # two counters (encoder, CLIP tower; cumulative) are copied to pinned host memory asynchronously (no synchronisation on the
+    # path); a later call that finds a copy complete and a counter raised switches BOTH towers to the separate two-pass LayerNorm
     # schedule for the rest of the model's life and says so.  The batch that met the rows has NaN outputs (loud); every later
-    # batch is served.
-    # The refusal guard: after every forward the two refusal counters (word 513 of the encoder's and the CLIP
-    # tower's GEMM workspaces; cumulative) are copied to pinned host memory asynchronously; a later call that finds a copy complete and a
-    # counter raised switches both towers to the separate LayerNorm passes.  The copies in flight form a FIFO over a small pool of pinned
-    # slots and the check polls the OLDEST (one slot re-armed on every call is never complete when the next call looks at it
-    # in a loop that runs ahead of the GPU -- the pipelined loops -- and the switch never fired there).  With every slot in flight a
-    # call arms nothing: the counters are cumulative, a later copy carries the same news.
+    # batch is served.  The copies in flight form a FIFO over a small pool of pinned slots and the check polls the OLDEST (ADVICE
+    # r4: one slot re-armed on every call is never complete when the next call looks at it in a loop that runs ahead of the GPU
+    # -- the pipelined loops -- and the switch never fired there).  With every slot in flight a call arms nothing: the counters
+    # are cumulative, a later copy carries the same news.
     _GUARD_SLOTS = 4
 
     def _fold_guard_check(self) -> None:
@@ -1293,10 +1287,9 @@ class Cascade(_Base):
                 self.fold_refusals = refused
                 self.encoder.fold_disabled = True
                 self.clip.fold_disabled = True
-                import warnings
                 warnings.warn(f"camouflaged_vlm_amd: {refused} token row(s) with |mean| / std > 128 were refused by the folded LayerNorm "
                               "(their images came out NaN); switching to the separate LayerNorm passes from this batch on "
-                              "(set CVLM_LN_FOLD=0 to start that way)", RuntimeWarning, stacklevel=3)
+                              "(set CVLM_LN_FOLD=0 to start that way)", RuntimeWarning, stacklevel=4)
 
     def _fold_guard_arm(self, stream) -> None:
         if not ((self.encoder.ln_fold and not self.encoder.fold_disabled) or (self.clip.ln_fold and not self.clip.fold_disabled)):
@@ -1320,60 +1313,144 @@ class Cascade(_Base):
             ev.record(stream)
         self._guard.append((slot, ev))
 
+    # ---- the step every entry point shares: prologue, stage 1 on two streams, prompts, decoder, alpha, epilogue ---------------
+    def _begin(self, inp, clip_image, clip_mask, flush: bool = True, alternate: bool = False) -> str:
+        """Prologue of an entry point -> name of the features buffer its encoder writes.  The mx self-check (its two forwards come
+        back through here and find its marker), `flush()` of an owed pipelined stage 2 (not for the call that takes the debt over),
+        the poll of the fold-refusal guard.  alternate: the two `cascade` forms may leave a batch on the side stream, so two
+        features buffers alternate and the caller's stream first waits until the batch before the previous one has left the side
+        stream -- its decoder read the buffer this encoder run is about to overwrite."""
+        self._mx_self_check(inp, clip_image, clip_mask)
+        if flush:
+            self.flush()
+        self._fold_guard_check()
+        if not alternate:
+            return "features"
+        if self._done[self._parity] is not None:
+            torch.cuda.current_stream().wait_event(self._done[self._parity])
+        return "features%d" % self._parity
+
+    def _stage1(self, inp, clip_fn, out_name: str, taps: Optional[dict] = None, tail_on_side: bool = True, clip_first: bool = False):
+        """The SAM encoder on the caller's stream with `clip_fn()` -- CLIP pass 1, or the fused [stage 2 | pass 1] forward -- on the
+        side stream underneath it -> (features in workspace buffer `out_name`, what clip_fn returned, tail stream).  The tail stream
+        is where the caller puts the work that needs both; it is already ordered behind them: the side stream behind the encoder's
+        end (the decoder's hundreds of small launches then leave the caller's stream free for the next encoder), or with
+        tail_on_side = False the caller's stream behind the side stream.
+        The CLIP forward only needs (clip_image, clip_mask): under the encoder its small grids (228..1184 workgroups) fill CUs the
+        big encoder GEMMs leave idle at tile boundaries.  The side stream waits for the inputs, not for the encoder.
+        Host issue order: the ENCODER's first blocks before the CLIP launches (SamEncoder.HOOK_AFTER_BLOCKS; rounds 1-2 issued the
+        CLIP pass first).  It decides nothing at B = 8 (the host is far ahead of the GPU); one image's pass is ~190 launches of a
+        few workgroups each, the GPU runs them as fast as the host can issue them -- the host IS the pace of the pass -- and an
+        encoder issued behind them started 4 ms late with the chip nearly idle until then (tools/step_timeline.py,
+        profiles/r03_encoder_first_ab.log).  Five blocks (3 ms of GPU work for one image) are queued first, then the pass, then
+        the rest: a slow host (a profiler, a loaded node) does not push the pass behind ALL of the encoder's launches either.
+        overlap_clip = False: the same launches on the caller's stream alone, which is then the tail stream; encoder then clip_fn,
+        or with clip_first the other way round (the fused loop's order; profiles of both exist)."""
+        main = torch.cuda.current_stream()
+        if not self.overlap_clip:
+            if clip_first:
+                res = clip_fn()
+            feats = self.encoder.forward(inp, taps, out_name=out_name)
+            if not clip_first:
+                res = clip_fn()
+            return feats, res, main
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        side = self._side
+        ready = torch.cuda.Event()
+        ready.record(main)
+        res = []
+
+        def issue_clip():
+            side.wait_event(ready)
+            with torch.cuda.stream(side):
+                res.append(clip_fn())
+
+        feats = self.encoder.forward(inp, taps, out_name=out_name, issue_hook=issue_clip)
+        if not tail_on_side:
+            main.wait_stream(side)
+            return feats, res[0], main
+        enc_done = torch.cuda.Event()
+        enc_done.record(main)
+        side.wait_event(enc_done)
+        return feats, res[0], side
+
+    def _end(self, tail, ins=(), outs=(), alternate: bool = False, wait: bool = True) -> None:
+        """Epilogue of an entry point whose last launches went to `tail`: the completion event of an alternating batch, the
+        fold-refusal guard armed behind it, and -- where the tail is the side stream -- the caching allocator told which stream
+        reads the caller's inputs and which the outputs, and (wait) the caller's stream ordered behind the side stream.
+        (`tail` is `_stage1`'s: the object `self._side` or the caller's stream.  torch.cuda.current_stream() builds a new Stream
+        object per call, so identity says nothing about the caller's stream; it does about the one side stream.)"""
+        if alternate:
+            done = torch.cuda.Event()
+            done.record(tail)
+            self._done[self._parity] = done
+            self._parity ^= 1
+        self._fold_guard_arm(tail)
+        if tail is not self._side:
+            return
+        main = torch.cuda.current_stream()
+        for t in ins:
+            t.record_stream(tail)
+        for t in outs:
+            t.record_stream(main)
+        if wait:
+            main.wait_stream(tail)
+
+    def _project_prompts(self, img_f: torch.Tensor, txt_f: torch.Tensor, B: int, P: int, sparse: Optional[torch.Tensor] = None):
+        """models/sam_maskdecoder_edge.py:342-344: sam_visual_proj of the B image rows, sam_text_proj of the P text rows
+        -> (vis f32 [B][C], txt f32 [P][C]); with `sparse` f32 [B][2][C] (P = B) each is also copied to its prompt slot."""
+        ws, C, D = self.ws, self.g.prompt_embed_dim, txt_f.shape[-1]
+        hv, ht = ws.h2("pp_hv", B, D), ws.h2("pp_ht", P, D)
+        vis, txt = ws.f32("pp_vis", B, C), ws.f32("pp_txt", P, C)
+        hip.layernorm(img_f.reshape(B, D), self.vproj[0], self.vproj[1], 1e-5, B, D, out_h2=hv)
+        self.gemm(hv, self.vproj[2], B, out_f32=vis)
+        hip.layernorm(vis, self.vproj[3], self.vproj[4], 1e-5, B, C, out_f32=vis)
+        if sparse is not None:
+            sparse[:, 0].copy_(vis)
+        hip.layernorm(txt_f.reshape(P, D), self.tproj[0], self.tproj[1], 1e-5, P, D, out_h2=ht)
+        self.gemm(ht, self.tproj[2], P, out_f32=txt)
+        if sparse is not None:
+            sparse[:, 1].copy_(txt)
+        return vis, txt
+
     def sparse_prompts(self, img_f: torch.Tensor, txt_f: torch.Tensor, B: int) -> torch.Tensor:
-        """models/sam_maskdecoder_edge.py:342-344."""
-        ws, C = self.ws, self.g.prompt_embed_dim
-        h = ws.h2("sp_h", B, 768)
-        sparse = ws.f32("sparse", B, 2, C)
-        tmp = ws.f32("sp_tmp", B, C)
-        hip.layernorm(img_f.reshape(B, 768), self.vproj[0], self.vproj[1], 1e-5, B, 768, out_h2=h)
-        self.gemm(h, self.vproj[2], B, out_f32=tmp)
-        hip.layernorm(tmp, self.vproj[3], self.vproj[4], 1e-5, B, C, out_f32=tmp)
-        sparse[:, 0].copy_(tmp)
-        hip.layernorm(txt_f.reshape(B, 768), self.tproj[0], self.tproj[1], 1e-5, B, 768, out_h2=h)
-        self.gemm(h, self.tproj[2], B, out_f32=tmp)
-        sparse[:, 1].copy_(tmp)
+        sparse = self.ws.f32("sparse", B, 2, self.g.prompt_embed_dim)
+        self._project_prompts(img_f, txt_f, B, B, sparse)
         return sparse
 
-    def infer_test(self, inp, clip_image, clip_mask, taps: Optional[dict] = None) -> torch.Tensor:
-        self._mx_self_check(inp, clip_image, clip_mask)
-        self.flush()
-        self._fold_guard_check()
+    def _mask_logits(self, feats: torch.Tensor, sparse: torch.Tensor, n: int, out: Optional[torch.Tensor] = None,
+                     edge_out: Optional[torch.Tensor] = None, taps: Optional[dict] = None) -> torch.Tensor:
+        """Features rows + n prompts -> mask logits at the input size, f32 [n][1][S][S] or into `out` (n maps of S x S); with
+        `edge_out` the edge probabilities beside them (MaskDecoder.forward(edge_out=True))."""
         g = self.g
+        low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, edge_out=edge_out is not None)
+        if edge_out is not None:
+            low, low_e = low
+        if out is None:
+            out = torch.empty(n, 1, g.inp_size, g.inp_size, device=self.device)
+        hip.bilinear(low, n, 4 * g.grid, 4 * g.grid, out, g.inp_size, g.inp_size)   # :380-387 (2nd resize = identity)
+        if edge_out is not None:
+            hip.bilinear(low_e, n, 4 * g.grid, 4 * g.grid, edge_out, g.inp_size, g.inp_size)   # postprocess_masks(low_res_edges), :299
+        return out
+
+    def _alpha(self, mask_logits: torch.Tensor, name: str) -> torch.Tensor:
+        """demo.py:117-119: alpha = resize(sigmoid(mask)) at the CLIP resolution, in workspace buffer `name`."""
+        n, R = mask_logits.shape[0], self.c.image_resolution
+        alpha = self.ws.f32(name, n, 1, R, R)
+        hip.bilinear(mask_logits, n, self.g.inp_size, self.g.inp_size, alpha, R, R, sigmoid_in=True)
+        return alpha
+
+    def infer_test(self, inp, clip_image, clip_mask, taps: Optional[dict] = None) -> torch.Tensor:
+        """models/sam_maskdecoder_edge.py:331-357.  Prompts, decoder and resize run on the caller's stream."""
+        out_name = self._begin(inp, clip_image, clip_mask)
         B = inp.shape[0]
-        # CLIP pass 1 only needs (clip_image, clip_mask): it runs on a side stream underneath the SAM encoder so
-        # its small grids (228..1184 workgroups) fill CUs the big encoder GEMMs leave idle at tile boundaries
-        if self.overlap_clip:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-            main = torch.cuda.current_stream()
-            # the host issues the ENCODER's first blocks before the CLIP pass: one image's pass is ~190 launches of a few
-            # workgroups each, the GPU runs them as fast as the host can issue them, and an encoder issued behind them started
-            # 4 ms late with the chip nearly idle until then (tools/step_timeline.py).  Five blocks (3 ms of GPU work for one
-            # image) are queued first, then the pass, then the rest: a slow host (a profiler, a loaded node) does not push the
-            # pass behind ALL of the encoder's launches either.  The side stream waits for the inputs, not for the encoder.
-            ready = torch.cuda.Event()
-            ready.record(main)
-            res = []
-
-            def issue_clip():
-                self._side.wait_event(ready)
-                with torch.cuda.stream(self._side):
-                    res.append(self.clip.forward(clip_image, clip_mask))
-
-            feats = self.encoder.forward(inp, taps, issue_hook=issue_clip)
-            img_f, txt_f, pred, score = res[0]
-            main.wait_stream(self._side)
-        else:
-            feats = self.encoder.forward(inp, taps)
-            img_f, txt_f, pred, score = self.clip.forward(clip_image, clip_mask)
+        feats, (img_f, txt_f, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name, taps, tail_on_side=False)
         sparse = self.sparse_prompts(img_f, txt_f, B)
-        low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, B, taps)
-        masks = torch.empty(B, 1, g.inp_size, g.inp_size, device=self.device)
-        hip.bilinear(low, B, 4 * g.grid, 4 * g.grid, masks, g.inp_size, g.inp_size)   # :380-387 (2nd resize = identity)
+        masks = self._mask_logits(feats, sparse, B, taps=taps)
         if taps is not None:
             taps.update(features=feats.clone(), sparse=sparse.clone(), pass1_logits=score.clone())
-        self._fold_guard_arm(torch.cuda.current_stream())
+        self._end(tail)
         return masks
 
     # ---- K class hypotheses per image (DESIGN.md §9) ---------------------------------------------------------------------------
@@ -1422,27 +1499,13 @@ class Cascade(_Base):
             lo, hi = max(p0, b * K), min(p1, (b + 1) * K)
             dst[lo - p0:hi - p0].copy_(src[b:b + 1].expand(hi - lo, *src.shape[1:]))
 
-    def _class_prompts(self, img_f: torch.Tensor, sel: torch.Tensor, B: int, P: int):
-        """sparse_prompts for P = B * K prompts: sam_visual_proj once per image, sam_text_proj of the P text rows
-        (models/sam_maskdecoder_edge.py:342-344) -> (vis f32 [B][C], txt f32 [P][C])."""
-        ws, C, D = self.ws, self.g.prompt_embed_dim, sel.shape[-1]
-        hv, ht = ws.h2("cp_hv", B, D), ws.h2("cp_ht", P, D)
-        vis, txt = ws.f32("cp_vis", B, C), ws.f32("cp_txt", P, C)
-        hip.layernorm(img_f.reshape(B, D), self.vproj[0], self.vproj[1], 1e-5, B, D, out_h2=hv)
-        self.gemm(hv, self.vproj[2], B, out_f32=vis)
-        hip.layernorm(vis, self.vproj[3], self.vproj[4], 1e-5, B, C, out_f32=vis)
-        hip.layernorm(sel.reshape(P, D), self.tproj[0], self.tproj[1], 1e-5, P, D, out_h2=ht)
-        self.gemm(ht, self.tproj[2], P, out_f32=txt)
-        return vis, txt
-
     def _class_stage2(self, masks: torch.Tensor, clip_image: torch.Tensor, B: int, K: int, p0: int, p1: int,
                       logits: torch.Tensor, pred: torch.Tensor) -> None:
         """demo.py:117-122 for the prompts p0 <= p < p1 as ONE CLIP forward: its images are the groups clip_image[b_lo:b_hi] of
         one hypothesis slot k each (ClipModel.image_features stacks groups without copying them), the alphas follow in that
         order; results go back to the prompt order p = b * K + k."""
-        S, R, n = self.g.inp_size, self.c.image_resolution, p1 - p0
-        alpha = self.ws.f32("cls_alpha", n, 1, R, R)
-        hip.bilinear(masks[p0:p1], n, S, S, alpha, R, R, sigmoid_in=True)
+        R, n = self.c.image_resolution, p1 - p0
+        alpha = self._alpha(masks[p0:p1], "cls_alpha")
         groups = []                                                  # (k, b_lo, b_hi): prompts b * K + k of this range
         for k in range(K):
             b_lo, b_hi = max(0, -(-(p0 - k) // K)), min(B, -(-(p1 - k) // K))
@@ -1473,53 +1536,28 @@ class Cascade(_Base):
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
         the two; both are validated on the host before anything is launched (ValueError) -- a `classes` tensor on the device
-        costs one synchronisation for that check.  Same machinery as cascade(pipelined=False): mx self-check, flush() of an owed
-        pipelined stage 2, the LayerNorm-fold guard, CLIP pass 1 on the side stream under the encoder; the current stream waits
-        for the results before the call returns.  Prompts p = b * K + k run through the decoder `class_chunk()` at a time; stage 2
-        is one CLIP forward per chunk.  Hypothesis k is bit for bit what `cascade(pipelined=False)` gives for class classes[b, k]
-        when the GEMM row counts match -- K = 1 with B <= class_chunk() -- and otherwise within the batch tolerance of the GEMM
-        K-splits.  A pass-1 row holding a NaN has no order: with topk= its classes are -1 and its masks, edges and
-        stage-2 logits NaN; its stage-2 `pred` is what cvlm_clip_head answers for NaN logits, class 0 -- read `classes`, not `pred`,
-        to tell such a hypothesis."""
+        costs one synchronisation for that check.  The step of cascade(pipelined=False) with K prompts per image in place of one:
+        `_begin`, `_stage1` (CLIP pass 1 under the encoder, everything else on the side stream), `_project_prompts`, then per
+        `class_chunk()` prompts p = b * K + k `_mask_logits` and one CLIP forward over `_alpha` of the chunk's masks, `_end` (the
+        current stream waits for the results before the call returns).  Hypothesis k is bit for bit what `cascade(pipelined=False)`
+        gives for class classes[b, k] when the GEMM row counts match -- K = 1 with B <= class_chunk() -- and otherwise within the
+        batch tolerance of the GEMM K-splits.  A pass-1 row holding a NaN has no order: with topk= its classes are -1
+        and its masks, edges and stage-2 logits NaN; its stage-2 `pred` is what cvlm_clip_head answers for NaN logits, class 0 --
+        read `classes`, not `pred`, to tell such a hypothesis."""
         B = int(inp.shape[0])
         K, host_classes = self._class_request(B, classes, topk)
-        self._mx_self_check(inp, clip_image, clip_mask)
-        self.flush()
-        self._fold_guard_check()
+        out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
-        P, S, T, C, G = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim, g.grid
+        P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
         txt_bank = self.clip.txt["test"]
         n_cls, D = txt_bank.shape
         idx_in = None if host_classes is None else host_classes.to(dev)
-        main = torch.cuda.current_stream()
-        if self.overlap_clip:                                        # encoder's first blocks, then the CLIP pass: see infer_test
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-            side = self._side
-            ready = torch.cuda.Event()
-            ready.record(main)
-            res = []
-
-            def issue_clip():
-                side.wait_event(ready)
-                with torch.cuda.stream(side):
-                    res.append(self.clip.forward(clip_image, clip_mask))
-
-            feats = self.encoder.forward(inp, None, issue_hook=issue_clip)
-            enc_done = torch.cuda.Event()
-            enc_done.record(main)
-            img_f, _, _, score = res[0]
-        else:
-            side = main
-            feats = self.encoder.forward(inp, None)
-            img_f, _, _, score = self.clip.forward(clip_image, clip_mask)
-        with torch.cuda.stream(side):
-            if side is not main:
-                side.wait_event(enc_done)
+        feats, (img_f, _, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        with torch.cuda.stream(tail):
             cls = torch.empty(B, K, dtype=torch.int64, device=dev)
             sel = self.ws.f32("cls_sel", P, D)
             hip.topk_select(score if idx_in is None else None, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
-            vis, txt = self._class_prompts(img_f, sel, B, P)
+            vis, txt = self._project_prompts(img_f, sel, B, P)
             masks = torch.empty(B, K, S, S, device=dev)
             edges = torch.empty(B, K, S, S, device=dev)
             logits = torch.empty(B, K, n_cls, device=dev)
@@ -1537,25 +1575,14 @@ class Cascade(_Base):
                 sp = self.ws.f32("cls_sparse", n, 2, C)
                 self._per_prompt(vis, K, p0, p1, sp[:, 0])
                 sp[:, 1].copy_(txt[p0:p1])
-                low, low_e = self.decoder.forward(fr, sp, self.no_mask, self.gauss, n, None, edge_out=True)
-                hip.bilinear(low, n, 4 * G, 4 * G, mflat[p0:p1], S, S)          # :380-387 (2nd resize = identity)
-                hip.bilinear(low_e, n, 4 * G, 4 * G, eflat[p0:p1], S, S)        # postprocess_masks(low_res_edges), :299
+                self._mask_logits(fr, sp, n, out=mflat[p0:p1], edge_out=eflat[p0:p1])
                 self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P))
-        self._fold_guard_arm(side)
-        if side is not main:
-            for t in (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)):
-                t.record_stream(side)
-            for t in (cls, score, masks, edges, logits, pred):
-                t.record_stream(main)
-            main.wait_stream(side)
+        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)), (cls, score, masks, edges, logits, pred))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""
-        B, R = mask_logits.shape[0], self.c.image_resolution
-        alpha = self.ws.f32("alpha2", B, 1, R, R)
-        hip.bilinear(mask_logits, B, self.g.inp_size, self.g.inp_size, alpha, R, R, sigmoid_in=True)
-        return self.clip.forward(clip_image, alpha)
+        return self.clip.forward(clip_image, self._alpha(mask_logits, "alpha2"))
 
     def cascade(self, inp, clip_image, clip_mask, pipelined: bool = False):
         """Stage 1 + stage 2.  With the side stream enabled only the SAM encoder runs on the caller's stream; CLIP pass
@@ -1570,54 +1597,15 @@ class Cascade(_Base):
         feeding batches MUST call `flush()`; until then `pred` holds -1 and `logits` NaN (sentinels, never stale data).
         The inputs may be refilled in place as soon as the call has returned: `clip_image` / `clip_mask` are copied (on the
         caller's stream) into buffers the engine owns before anything reads them later."""
-        self._mx_self_check(inp, clip_image, clip_mask)
         if pipelined and self.fuse_clip:
             return self._cascade_fused(inp, clip_image, clip_mask)
-        self.flush()
-        self._fold_guard_check()
-        if not self.overlap_clip:
-            masks = self.infer_test(inp, clip_image, clip_mask)
+        out_name = self._begin(inp, clip_image, clip_mask, alternate=True)
+        B = inp.shape[0]
+        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        with torch.cuda.stream(tail):
+            masks = self._mask_logits(feats, self.sparse_prompts(img_f, txt_f, B), B)
             _, _, pred, logits = self.stage2(masks, clip_image)
-            return masks, pred, logits
-        g, B = self.g, inp.shape[0]
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        main, side = torch.cuda.current_stream(), self._side
-        # the batch before the previous one has left the side stream: its decoder read the features buffer this encoder
-        # run is about to overwrite (two buffers alternate)
-        if self._done[self._parity] is not None:
-            main.wait_event(self._done[self._parity])
-        ready = torch.cuda.Event()                                   # encoder's first blocks, then the CLIP pass: see infer_test
-        ready.record(main)
-        res = []
-
-        def issue_clip():
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                res.append(self.clip.forward(clip_image, clip_mask))
-
-        feats = self.encoder.forward(inp, None, out_name="features%d" % self._parity, issue_hook=issue_clip)
-        enc_done = torch.cuda.Event()
-        enc_done.record(main)
-        img_f, txt_f, _, _ = res[0]
-        with torch.cuda.stream(side):
-            side.wait_event(enc_done)
-            sparse = self.sparse_prompts(img_f, txt_f, B)
-            low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, B, None)
-            masks = torch.empty(B, 1, g.inp_size, g.inp_size, device=self.device)
-            hip.bilinear(low, B, 4 * g.grid, 4 * g.grid, masks, g.inp_size, g.inp_size)
-            _, _, pred, logits = self.stage2(masks, clip_image)
-            done = torch.cuda.Event()
-            done.record(side)
-        self._fold_guard_arm(side)
-        self._done[self._parity] = done
-        self._parity ^= 1
-        for t in (inp, clip_image, clip_mask):
-            t.record_stream(side)
-        for t in (masks, pred, logits):
-            t.record_stream(main)
-        if not pipelined:
-            main.wait_stream(side)
+        self._end(tail, (inp, clip_image, clip_mask), (masks, pred, logits), alternate=True, wait=not pipelined)
         return masks, pred, logits
 
     def _cascade_fused(self, inp, clip_image, clip_mask):
@@ -1627,38 +1615,27 @@ class Cascade(_Base):
         issue (bench.py does, inside the timed region).  The returned `pred` / `logits` tensors hold sentinels (-1 / NaN) until
         that later launch fills them; `masks` is filled by this one.  cocotrainers/mapleAlphaCLIP.py:281-294 twice,
         demo.py:117-122."""
-        g, B = self.g, inp.shape[0]
-        self._fold_guard_check()
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        main = torch.cuda.current_stream()
-        side = self._side if self.overlap_clip else main             # overlap_clip = False: same launches, one stream (profiling)
-        self._pending_stream = side
-        if self._done[self._parity] is not None:                     # the batch before the previous one has left the side stream
-            main.wait_event(self._done[self._parity])
+        out_name = self._begin(inp, clip_image, clip_mask, flush=False, alternate=True)
+        B, R = inp.shape[0], self.c.image_resolution
         prev = self._pending
         # The side stream reads clip_image / clip_mask now (pass 1) and clip_image again one call later (the owed stage 2): keep
         # copies the engine owns, made on the caller's stream, so that a serving loop may refill its input buffers in place
         # (ADVICE r3).  3.6 MB at B = 8; two buffers alternate with the batches in flight.
-        R = self.c.image_resolution
         if self._clip_done is not None:                              # the forward that read these buffers two batches ago
-            main.wait_event(self._clip_done)                         # (it ran under the previous encoder: long finished)
+            torch.cuda.current_stream().wait_event(self._clip_done)  # (it ran under the previous encoder: long finished)
         own_image = self.ws.f32("own_clip_image%d" % self._parity, B, 3, R, R)
         own_mask = self.ws.f32("own_clip_mask%d" % self._parity, B, 1, R, R)
         own_image.copy_(clip_image)
         own_mask.copy_(clip_mask)
-        clip_image, clip_mask = own_image, own_mask
 
         def clip_forwards():
             try:
                 if prev is None:
-                    i_f, t_f, _, _ = self.clip.forward(clip_image, clip_mask)
+                    i_f, t_f, _, _ = self.clip.forward(own_image, own_mask)
                     return i_f, t_f
                 p_masks, p_image, p_pred, p_logits = prev
                 Bp = p_masks.shape[0]
-                alpha = self.ws.f32("alpha2", Bp, 1, R, R)
-                hip.bilinear(p_masks, Bp, g.inp_size, g.inp_size, alpha, R, R, sigmoid_in=True)
-                img_n, sel, pred_all, logits_all = self.clip.forward([p_image, clip_image], [alpha, clip_mask])
+                img_n, sel, pred_all, logits_all = self.clip.forward([p_image, own_image], [self._alpha(p_masks, "alpha2"), own_mask])
                 p_pred.copy_(pred_all[:Bp])                          # results of the previous batch land in the tensors it returned
                 p_logits.copy_(logits_all[:Bp])
                 return img_n[Bp:], sel[Bp:]
@@ -1666,47 +1643,14 @@ class Cascade(_Base):
                 self._clip_done = torch.cuda.Event()
                 self._clip_done.record(torch.cuda.current_stream())
 
-        if side is not main:                                         # encoder's first blocks, then the CLIP pass: see infer_test
-            ready = torch.cuda.Event()
-            ready.record(main)
-            res = []
-
-            def issue_clip():
-                side.wait_event(ready)
-                with torch.cuda.stream(side):
-                    res.append(clip_forwards())
-
-            feats = self.encoder.forward(inp, None, out_name="features%d" % self._parity, issue_hook=issue_clip)
-            enc_done = torch.cuda.Event()
-            enc_done.record(main)
-            img_f, txt_f = res[0]
-        else:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                img_f, txt_f = clip_forwards()
-            feats = self.encoder.forward(inp, None, out_name="features%d" % self._parity)
-            enc_done = torch.cuda.Event()
-            enc_done.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(enc_done)
-            sparse = self.sparse_prompts(img_f, txt_f, B)
-            low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, B, None)
-            masks = torch.empty(B, 1, g.inp_size, g.inp_size, device=self.device)
-            hip.bilinear(low, B, 4 * g.grid, 4 * g.grid, masks, g.inp_size, g.inp_size)
-            n_cls = self.clip.txt["test"].shape[0]
+        feats, (img_f, txt_f), tail = self._stage1(inp, clip_forwards, out_name, clip_first=True)
+        with torch.cuda.stream(tail):
+            masks = self._mask_logits(feats, self.sparse_prompts(img_f, txt_f, B), B)
             # owed until the next call / flush(): sentinels, so that a missing flush() reads as "not computed", never as data
             pred = torch.full((B,), -1, dtype=torch.int64, device=self.device)
-            logits = torch.full((B, n_cls), float("nan"), device=self.device)
-            done = torch.cuda.Event()
-            done.record(side)
-        self._fold_guard_arm(side)
-        self._done[self._parity] = done
-        self._parity ^= 1
-        self._pending = (masks, clip_image, pred, logits)
-        for t in (inp,):
-            t.record_stream(side)
-        for t in (masks, pred, logits):
-            t.record_stream(main)
+            logits = torch.full((B, self.clip.txt["test"].shape[0]), float("nan"), device=self.device)
+        self._pending, self._pending_stream = (masks, own_image, pred, logits), tail
+        self._end(tail, (inp,), (masks, pred, logits), alternate=True, wait=False)
         return masks, pred, logits
 
     def batch_done_event(self) -> "torch.cuda.Event":
