@@ -7,6 +7,7 @@ C ABI together with the current HIP stream).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional, Tuple
 
@@ -25,7 +26,7 @@ EXPORTS = [
     "cvlm_mask_to_u8", "cvlm_mask_joint_hist", "cvlm_mask_wfm", "cvlm_topk_accumulate",
     "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
     "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
-    "cvlm_mask_head_edge", "cvlm_topk_select",
+    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan",
 ]
 ABI_VERSION = 12
 
@@ -55,6 +56,16 @@ class GemmArgs(C.Structure):
         ("out_mxs", C.c_void_p), ("ldo_s", C.c_int64), ("ldol", C.c_int64), ("ldrl", C.c_int64),
         ("hm_nolo", C.c_int32),
     ]
+
+
+class GemmLaunchInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n0", "N", "nbx", "nby", "grid_x", "grid_y", "block", "lds_bytes", "group_m", "tail_rem",
+                                         "tail_split", "total_blocks", "sk_parts", "uses_workspace")] + [("kernel", C.c_char * 128)]
+
+
+class GemmPlanInfo(C.Structure):
+    """cvlm_gemm_plan_info (include/cvlm.h): what cvlm_debug_gemm_plan fills."""
+    _fields_ = [("launches", C.c_int32), ("launch", GemmLaunchInfo * 2)]
 
 
 class AttnArgs(C.Structure):
@@ -301,18 +312,18 @@ class H2:
         return H2(self.t.view((2,) + tuple(shape)))
 
 
-def gemm(a: H2, w: H2, M: int, N: int, K: int, *, lda: Optional[int] = None, ldw: Optional[int] = None,
-         bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, ldr: Optional[int] = None,
-         out_f32: Optional[torch.Tensor] = None, ldo: Optional[int] = None, out_h2: Optional[H2] = None,
-         ldoh: Optional[int] = None, alpha: float = 1.0, act: int = ACT_NONE, split: int = 3, batch: int = 1,
-         stride_a: int = 0, stride_w: int = 0, stride_r: int = 0, stride_o: int = 0, stride_oh: int = 0,
-         pixel_shuffle: Optional[Tuple[int, int, int]] = None,
-         head_major: Optional[Tuple[int, int, int]] = None, head_major_nolo: int = 0, out_scale: float = 1.0,
-         workspace: Optional[torch.Tensor] = None,
-         ln_fold: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-         residual_h2: Optional[Tuple["H2", float]] = None, ldrh: Optional[int] = None,
-         row_stats: Optional[torch.Tensor] = None, conv3x3: Optional[Tuple[int, int, int]] = None,
-         w_il: Optional[torch.Tensor] = None, w_mx: Optional["H2MX"] = None) -> None:
+def gemm_args(a: H2, w: H2, M: int, N: int, K: int, *, lda: Optional[int] = None, ldw: Optional[int] = None,
+              bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, ldr: Optional[int] = None,
+              out_f32: Optional[torch.Tensor] = None, ldo: Optional[int] = None, out_h2: Optional[H2] = None,
+              ldoh: Optional[int] = None, alpha: float = 1.0, act: int = ACT_NONE, split: int = 3, batch: int = 1,
+              stride_a: int = 0, stride_w: int = 0, stride_r: int = 0, stride_o: int = 0, stride_oh: int = 0,
+              pixel_shuffle: Optional[Tuple[int, int, int]] = None,
+              head_major: Optional[Tuple[int, int, int]] = None, head_major_nolo: int = 0, out_scale: float = 1.0,
+              workspace: Optional[torch.Tensor] = None,
+              ln_fold: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+              residual_h2: Optional[Tuple["H2", float]] = None, ldrh: Optional[int] = None,
+              row_stats: Optional[torch.Tensor] = None, conv3x3: Optional[Tuple[int, int, int]] = None,
+              w_il: Optional[torch.Tensor] = None, w_mx: Optional["H2MX"] = None) -> GemmArgs:
     """w_mx: the weight as an mx operand (`H2MX.from_planes(w)`, ABI 10) -- used when `a` is an H2MX: hi.hi on fp16, the two correction
     products on the block-scaled e4m3 matrix instruction.  An H2MX `out_h2` / `residual_h2` selects out_mx / res_mx.
     w_il: the same weight with its planes interleaved per 32 k-elements (`interleave_planes(w)`, ABI 6): the big-tile kernels stage
@@ -323,7 +334,6 @@ def gemm(a: H2, w: H2, M: int, N: int, K: int, *, lda: Optional[int] = None, ldw
     GEMM (include/cvlm.h);
     residual_h2 = (x h2, scale): residual given as h2 planes; row_stats [ceil(N/64)][M][2] f32: piece statistics of the result rows
     (plain stores, bit-reproducible: nothing to zero)."""
-    _on_current_device(a.t)
     g = GemmArgs()
     if getattr(a, "mx", False):
         assert w_mx is not None and w_mx.C >= K and a.C >= K, "an mx activation needs the mx image of the weight"
@@ -382,7 +392,23 @@ def gemm(a: H2, w: H2, M: int, N: int, K: int, *, lda: Optional[int] = None, ldw
         g.lda = conv3x3[2]
     if workspace is not None:
         g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    _check(load().cvlm_gemm(C.byref(g), C.c_void_p(_stream())), "cvlm_gemm")
+    return g
+
+
+@functools.wraps(gemm_args, assigned=("__doc__",))                 # help(), inspect.signature and editors show the parameter list above
+def gemm(a: H2, w: H2, M: int, N: int, K: int, **kw) -> None:
+    _on_current_device(a.t)
+    _check(load().cvlm_gemm(C.byref(gemm_args(a, w, M, N, K, **kw)), C.c_void_p(_stream())), "cvlm_gemm")
+
+
+def gemm_plan(a: H2, w: H2, M: int, N: int, K: int, *, cus: int = 256, **kw) -> list:
+    """Dry run of `gemm` with the same arguments on a device of `cus` compute units (cvlm_debug_gemm_plan: nothing is launched, no device
+    is needed): one dict per launch -- kernel instantiation, grid, LDS bytes and the GemmParams fields csrc/gemm_plan.h chose."""
+    g, info = gemm_args(a, w, M, N, K, **kw), GemmPlanInfo()
+    have_ws = bool(g.workspace) and g.workspace_bytes >= gemm_workspace_bytes()
+    _check(load().cvlm_debug_gemm_plan(C.byref(g), int(have_ws), cus, C.byref(info)), "cvlm_debug_gemm_plan")
+    return [dict({n: getattr(l, n) for n, _ in GemmLaunchInfo._fields_[:-1]}, kernel=l.kernel.decode())
+            for l in info.launch[:info.launches]]
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, M: int, D: int, *,

@@ -139,6 +139,20 @@ typedef struct cvlm_gemm_args {
 } cvlm_gemm_args;
 int cvlm_gemm(const cvlm_gemm_args* args, void* stream);
 int64_t cvlm_gemm_workspace_bytes(void);
+/* Debug entry, outside the ABI contract (its struct may change without a new CVLM_ABI_VERSION): the launches cvlm_gemm would make for
+ * `args` with (have_ws != 0) or without a sufficient workspace on a device of `cus` compute units, under the CVLM_GEMM_* knobs of this
+ * process -- the decision of csrc/gemm_plan.h.  Launches nothing, dereferences no device pointer, needs no device.  Returns 0 or the
+ * negative CVLM_E_* code cvlm_gemm would return before its first launch. */
+typedef struct cvlm_gemm_plan_info {
+    int32_t launches;                                  /* 1, or 2 for a column split */
+    struct {
+        int32_t n0, N;                                 /* the launch computes columns [n0, n0 + N) */
+        int32_t nbx, nby, grid_x, grid_y, block, lds_bytes;
+        int32_t group_m, tail_rem, tail_split, total_blocks, sk_parts, uses_workspace;
+        char kernel[128];                              /* "gemm_nt_kernel<template arguments>" */
+    } launch[2];
+} cvlm_gemm_plan_info;
+int cvlm_debug_gemm_plan(const cvlm_gemm_args* args, int have_ws, int cus, cvlm_gemm_plan_info* out);
 
 /* Row LayerNorm over the last axis: y = LN(x + add) * gamma + beta, biased variance, then act.
  * Replaces nn.LayerNorm (image_encoder.py:432,444; alpha_clip_rw/model.py:162-168;

@@ -272,9 +272,10 @@ def test_gemm_interleaved_activations_same_bits(hip, monkeypatch, M, N, K, varia
 
 
 def test_gemm_column_split_partial_round_h2res(hip, monkeypatch):
-    """CVLM_GEMM_COLSPLIT=2: a grid of several rounds with a partial last one (32 x 10 tiles of 256^2 = 1.25 rounds) as whole rounds
-    + the remaining columns, h2-residual form: outputs, in-place residual and the statistics pieces carry the bits of the
-    single launch."""
+    """A grid of several rounds with a partial last one (32 x 10 tiles of 256^2 = 1.25 rounds), h2-residual form.  The column split of
+    such grids (once CVLM_GEMM_COLSPLIT=2) is gone: any non-zero value now means the one-round split of csrc/gemm_plan.h, which this
+    launch (M > 4096, h2 residual) does not take.  Under both values outputs, in-place residual and the statistics pieces carry the
+    same bits, and they are right."""
     M, N, K, XS = 8192, 2560, 256, 0.25
     a, w, bias, res = rnd(M, K, seed=61), rnd(N, K, seed=62, scale=K ** -0.5), rnd(N, seed=63), rnd(M, N, seed=64)
     A, W = dev_h2(hip, a), dev_h2(hip, w)
