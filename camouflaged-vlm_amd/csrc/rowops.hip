@@ -381,6 +381,19 @@ __global__ __launch_bounds__(256) void dense_pe_kernel(const float* __restrict__
     }
 }
 
+// The per-pixel arithmetic of the mask head (mask_decoder_edge.py:181-186), stated once for mask_head_kernel and
+// mask_head_multi_kernel, with the choice between a product-and-add and a fused multiply-add taken from the compiler: what it forms
+// depends on the code around (in mask_head_kernel it multiplies in pairs and adds; the gate is one fma).  Four rounded products
+// added left to right onto the running sum, and fma(m, s, m), are what mask_head_kernel has always computed; equal inputs give
+// equal bits in both kernels.
+__device__ __forceinline__ float mh_dot4(float acc, const float4 a, const float4 w) {
+#pragma clang fp contract(off)
+    acc += a.x * w.x + a.y * w.y + a.z * w.z + a.w * w.w;
+    return acc;
+}
+__device__ __forceinline__ float mh_sigmoid(float g) { return 1.0f / (1.0f + expf(-g)); }
+__device__ __forceinline__ float mh_gate(float m, float s) { return __builtin_fmaf(m, s, m); }
+
 // EDGE_OUT: also write the edge probability sigmoid(g) of every pixel (cvlm_mask_head_edge); the mask arithmetic is the same code
 template <bool EDGE_OUT>
 __global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict__ up, const float* __restrict__ edge,
@@ -392,25 +405,84 @@ __global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict_
     for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < HW; pix += gridDim.x * blockDim.x) {
         const float4* u = (const float4*)(up + ((int64_t)b * HW + pix) * C);
         float m = 0.f, g = 0.f;
-        for (int c = 0; c < (C >> 2); ++c) {
-            const float4 a = u[c];
-            const float4 w0 = ((const float4*)h0)[c];
-            m += a.x * w0.x + a.y * w0.y + a.z * w0.z + a.w * w0.w;
-        }
+        for (int c = 0; c < (C >> 2); ++c) m = mh_dot4(m, u[c], ((const float4*)h0)[c]);
         if (!edge) {                                             // vanilla decoder: plain hypernetwork product
             low[(int64_t)b * HW + pix] = m;
             continue;
         }
         const float4* e = (const float4*)(edge + ((int64_t)b * HW + pix) * C);
-        for (int c = 0; c < (C >> 2); ++c) {
-            const float4 d = e[c];
-            const float4 w4 = ((const float4*)h4)[c];
-            g += d.x * w4.x + d.y * w4.y + d.z * w4.z + d.w * w4.w;
-        }
-        const float s = 1.0f / (1.0f + expf(-g));
-        low[(int64_t)b * HW + pix] = m * s + m;
+        for (int c = 0; c < (C >> 2); ++c) g = mh_dot4(g, e[c], ((const float4*)h4)[c]);
+        const float s = mh_sigmoid(g);
+        low[(int64_t)b * HW + pix] = mh_gate(m, s);
         if constexpr (EDGE_OUT) edge_prob[(int64_t)b * HW + pix] = s;
     }
+}
+
+// NM masks of one prompt from ONE pass over its rows (cvlm_mask_head_multi).  mask_head_kernel lets every lane walk its own
+// 128-byte row, so one load instruction touches 64 cache lines; here a block fetches its MH_TILE pixels' rows -- one contiguous
+// piece of `up`, then of `edge` -- with coalesced 16-byte loads into LDS and each lane reads its pixel's row from there, in the
+// same order of c.  LDS row pitch C | 4 floats: pitch / 4 is odd, so the 16 lanes of a 16-byte LDS read group land on 16
+// different 4-bank slots (C = 32: pitch 36, conflict free).  `edge` reuses the tile of `up`: 36 KiB per block at C = 32, four
+// blocks per CU, whose load and compute phases overlap one another.
+constexpr int MH_TILE = 256;
+__host__ __device__ inline int mh_pitch(int C) { return C | 4; }
+
+__device__ __forceinline__ void mh_stage(const float4* __restrict__ src, int nvec, int CV, int pitch, float* tile) {
+    constexpr int U = 8;                                         // loads in flight per lane before the first LDS write
+    const int dr = MH_TILE / CV, dc = MH_TILE % CV;              // a step of MH_TILE vectors in (row, column of the row)
+    int r = threadIdx.x / CV, c = threadIdx.x % CV;
+    for (int i0 = threadIdx.x; i0 < nvec; i0 += U * MH_TILE) {
+        float4 v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) v[k] = src[min(i0 + k * MH_TILE, nvec - 1)];       // past the tile's end: its last vector, not stored
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (i0 + k * MH_TILE < nvec) *(float4*)(tile + r * pitch + 4 * c) = v[k];
+            r += dr;
+            c += dc;
+            if (c >= CV) { c -= CV; ++r; }
+        }
+    }
+}
+
+template <int NM>
+__global__ __launch_bounds__(MH_TILE) void mask_head_multi_kernel(const float* __restrict__ up, const float* __restrict__ edge,
+                                                                  const float* __restrict__ hyper, int HW, int C,
+                                                                  float* __restrict__ low, float* __restrict__ edge_prob) {
+    extern __shared__ __attribute__((aligned(16))) float mh_tile[];
+    const int p = blockIdx.y, pix0 = blockIdx.x * MH_TILE, tid = threadIdx.x;
+    const int rows = min(MH_TILE, HW - pix0), CV = C >> 2, pitch = mh_pitch(C);
+    const float4* h = (const float4*)(hyper + (int64_t)p * 5 * C);
+    const int64_t first = ((int64_t)p * HW + pix0) * C;          // the tile's rows are contiguous in up / edge
+    const float4* row = (const float4*)(mh_tile + tid * pitch);
+    float* out = low + (int64_t)p * NM * HW + pix0 + tid;
+    float m[NM];
+#pragma unroll
+    for (int k = 0; k < NM; ++k) m[k] = 0.f;
+    mh_stage((const float4*)(up + first), rows * CV, CV, pitch, mh_tile);
+    __syncthreads();
+    if (tid < rows)
+        for (int c = 0; c < CV; ++c) {
+            const float4 a = row[c];
+#pragma unroll
+            for (int k = 0; k < NM; ++k) m[k] = mh_dot4(m[k], a, h[k * CV + c]);
+        }
+    if (!edge) {                                                 // vanilla decoder: plain hypernetwork products
+        if (tid < rows)
+#pragma unroll
+            for (int k = 0; k < NM; ++k) out[(int64_t)k * HW] = m[k];
+        return;
+    }
+    __syncthreads();                                             // every lane has read its row of `up`
+    mh_stage((const float4*)(edge + first), rows * CV, CV, pitch, mh_tile);
+    __syncthreads();
+    if (tid >= rows) return;
+    float g = 0.f;
+    for (int c = 0; c < CV; ++c) g = mh_dot4(g, row[c], h[4 * CV + c]);
+    const float s = mh_sigmoid(g);
+#pragma unroll
+    for (int k = 0; k < NM; ++k) out[(int64_t)k * HW] = mh_gate(m[k], s);
+    if (edge_prob) edge_prob[(int64_t)p * HW + pix0 + tid] = s;
 }
 
 __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ in, int hin, int win,
@@ -899,6 +971,25 @@ int cvlm_mask_head_edge(const float* up, const float* edge_emb, const float* hyp
     if (!up || !edge_emb || !hyper || !low || !edge_prob || P <= 0 || P > 65535 || HW <= 0 || C <= 0 || (C & 3)) return CVLM_E_BADARG;
     hipLaunchKernelGGL(mask_head_kernel<true>, dim3(grid_for(HW, 256, 1024), P), dim3(256), 0, (hipStream_t)stream, up,
                        edge_emb, hyper, HW, C, low, edge_prob);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_mask_head_multi(const float* up, const float* edge_emb, const float* hyper, int32_t P, int32_t HW, int32_t C,
+                         int32_t n_masks, float* low, float* edge_prob, void* stream) {
+    if (!up || !hyper || !low || (edge_prob && !edge_emb) || P <= 0 || P > 65535 || HW <= 0 || C <= 0 || (C & 3) || n_masks < 1 ||
+        n_masks > 4)
+        return CVLM_E_BADARG;
+    const size_t lds = (size_t)MH_TILE * mh_pitch(C) * sizeof(float);
+    if (lds > 65536) return CVLM_E_UNSUPPORTED;                  // rows of more than 60 floats: the tile of 256 would not fit
+    const dim3 grid((HW + MH_TILE - 1) / MH_TILE, P);
+    hipStream_t s = (hipStream_t)stream;
+    switch (n_masks) {
+        case 1: hipLaunchKernelGGL(mask_head_multi_kernel<1>, grid, dim3(MH_TILE), lds, s, up, edge_emb, hyper, HW, C, low, edge_prob); break;
+        case 2: hipLaunchKernelGGL(mask_head_multi_kernel<2>, grid, dim3(MH_TILE), lds, s, up, edge_emb, hyper, HW, C, low, edge_prob); break;
+        case 3: hipLaunchKernelGGL(mask_head_multi_kernel<3>, grid, dim3(MH_TILE), lds, s, up, edge_emb, hyper, HW, C, low, edge_prob); break;
+        default: hipLaunchKernelGGL(mask_head_multi_kernel<4>, grid, dim3(MH_TILE), lds, s, up, edge_emb, hyper, HW, C, low, edge_prob); break;
+    }
     CVLM_CHECK_LAUNCH();
     return 0;
 }

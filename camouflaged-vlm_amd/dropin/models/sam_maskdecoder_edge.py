@@ -111,7 +111,7 @@ class SAM(nn.Module):
         return self.cascade().infer_test(input.float().contiguous(), clip_image.float().contiguous(),
                                          clip_zero_mask.float().contiguous())
 
-    def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None):
+    def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False):
         """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
         the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
         decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
@@ -120,7 +120,18 @@ class SAM(nn.Module):
         assert H == self.inp_size and W == self.inp_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().infer_classes(input.float().contiguous(), clip_image.float().contiguous(),
-                                            clip_zero_mask.float().contiguous(), classes=classes, topk=topk)
+                                            clip_zero_mask.float().contiguous(), classes=classes, topk=topk, quality=quality)
+
+    def infer_test_multimask(self, input, clip_image, clip_zero_mask, multimask_output=True, all_masks=False):
+        """EXTENSION, not a reference method: `infer_test` with the decoder's multimask output -- the candidate masks and the
+        quality `iou_pred` the reference's `mask_decoder(..., multimask_output=...)` returns and `infer_test` drops
+        (mask_decoder_edge.py:130-135, 163-190).  -> engine.MaskSet (INTEGRATION.md, "Multimask output")."""
+        H, W = input.shape[-2:]
+        assert H == self.inp_size and W == self.inp_size, \
+            f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
+        return self.cascade().infer_test_multimask(input.float().contiguous(), clip_image.float().contiguous(),
+                                                   clip_zero_mask.float().contiguous(), multimask_output=multimask_output,
+                                                   all_masks=all_masks)
 
     def infer(self, input, clip_image, clip_zero_mask):
         """:305-329 (bs = 1 variant of infer_test)."""

@@ -14,7 +14,7 @@ import dataclasses
 import math
 import os
 import warnings
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -565,6 +565,10 @@ class MaskDecoder(_Base):
 
         self.up = {n: (convT2(n + ".0"), convT2(n + ".3")) for n in ("output_upscaling", "embedding_encoder")}
         self.mf = (convT3("embedding_maskfeature.0"), convT3("embedding_maskfeature.3"))
+        # the IoU head's last Linear (N = 4, mask_decoder_edge.py:67-69) padded with zero rows to the hypernetwork tails' N = C / 8:
+        # forward(multi=) runs it as the GEMM shape those launch
+        self.iou_tail = Linear(sd[P + "iou_prediction_head.layers.2.weight"], sd[P + "iou_prediction_head.layers.2.bias"], device,
+                               n_pad=C // 8)
         self.pe: Optional[torch.Tensor] = None
         self._merged(sd, P)
 
@@ -664,12 +668,18 @@ class MaskDecoder(_Base):
             self.gemm(a, lin, rows, out_f32=out, residual=const, batch=B, stride_a=rows * lin.K, stride_r=0, stride_o=rows * lin.N, **kw)
 
     def forward(self, feats: torch.Tensor, sparse: torch.Tensor, no_mask: torch.Tensor, gauss: torch.Tensor,
-                B: int, taps: Optional[dict] = None, edge_out: bool = False):
+                B: int, taps: Optional[dict] = None, edge_out: bool = False, multi: int = 0):
         """feats f32 [B*T][C]; sparse f32 [B][2][C] -> low-res mask logits f32 [B][4G][4G] (mask 0, :133-135).
         mask_decoder_edge.py:96-190, transformer_maskdecoder_edge.py:62-214.  B counts prompts: one row of `sparse` and one
         copy of the image's features each (the reference expands to sparse_prompt_embeddings.size(0), :150-158).
         edge_out=True: -> (mask logits, edge probabilities f32 [B][4G][4G] = sigmoid(hyper_edge . edge_embedding), :182-184)
-        from cvlm_mask_head_edge in place of cvlm_mask_head; every other launch is the same."""
+        from cvlm_mask_head_edge in place of cvlm_mask_head; every other launch is the same.
+        multi=n (1..4): the decoder's multimask outputs (predict_masks, :163-190) -> (masks 0..n-1 f32 [B][n][4G][4G], edge
+        probabilities f32 [B][4G][4G], iou_pred f32 [B][4] -- a view of padded rows).  Behind today's launches: the hypernetwork
+        MLPs of mask tokens 1..n-1 (hs rows 2..n, :172-178) into slots 1..n-1 of `hyper`, iou_prediction_head on hs row 0 (:188),
+        and cvlm_mask_head_multi -- one pass over the rows for all n planes and the edge map -- in place of cvlm_mask_head.  Plane
+        0 and the edge map hold the bits of the edge_out=True call."""
+        assert 0 <= multi <= 4, multi
         g, ws = self.g, self.ws
         G, C, T, H = g.grid, g.prompt_embed_dim, g.grid * g.grid, g.dec_heads
         NT = self.tokens.shape[0]
@@ -775,11 +785,26 @@ class MaskDecoder(_Base):
         # planes of hs (row b * NT + token: pointer offset + row pitch NT * C)
         hyper = ws.f32("hyper", B, 5, C // 8)
         t1, t2 = ws.h2("h_t1", B, C), ws.h2("h_t2", B, C)
-        for tok_row, mlp, slot in ((1, "output_hypernetworks_mlps.0", 0), (NT - 1, "edge_mlp", 4)):
+        rows = [(1, "output_hypernetworks_mlps.0", 0), (NT - 1, "edge_mlp", 4)]
+        rows += [(1 + i, "output_hypernetworks_mlps.%d" % i, i) for i in range(1, multi)]
+        for tok_row, mlp, slot in rows:
             rowh = H2(hs_h.t[:, tok_row:])
             self.gemm(rowh, self.lin[mlp + ".layers.0"], B, lda=NT * C, out_h2=t1, act=ACT_RELU)
             self.gemm(t1, self.lin[mlp + ".layers.1"], B, out_h2=t2, act=ACT_RELU)
             self.gemm(t2, self.lin[mlp + ".layers.2"], B, out_f32=hyper[:, slot], ldo=5 * (C // 8))
+        if multi:
+            head = "iou_prediction_head.layers."
+            NH = self.lin[head + "0"].N
+            i1, i2, iou = ws.h2("iou_t1", B, NH), ws.h2("iou_t2", B, NH), ws.f32("iou_pred", B, self.iou_tail.N)
+            self.gemm(hs_h, self.lin[head + "0"], B, lda=NT * C, out_h2=i1, act=ACT_RELU)          # hs row 0: the IoU token
+            self.gemm(i1, self.lin[head + "1"], B, out_h2=i2, act=ACT_RELU)
+            self.gemm(i2, self.iou_tail, B, out_f32=iou)
+            low, edge = ws.f32("low_multi", B, multi, HW), ws.f32("low_edge", B, HW)
+            hip.mask_head_multi(up, edge_emb, hyper, B, HW, C // 8, multi, low, edge)
+            if taps is not None:
+                taps.update(hs=hs.clone(), src=keys.clone(), upscaled=up.clone(), edge_emb=edge_emb.clone(),
+                            hyper=hyper.clone(), low_res_masks=low.clone(), low_res_edges=edge.clone(), iou_pred=iou[:, :4].clone())
+            return low, edge, iou[:, :4]
         low = ws.f32("low", B, HW)
         if edge_out:
             edge = ws.f32("low_edge", B, HW)
@@ -1166,6 +1191,23 @@ class ClassHypotheses:
     edges: torch.Tensor             # (B, K, S, S) f32 edge probabilities sigmoid(hyper_edge . edge_embedding), upsampled (:298-302)
     logits: torch.Tensor            # (B, K, n_cls) stage 2 of each hypothesis (demo.py:117-122)
     pred: torch.Tensor              # (B, K) int64 stage-2 prediction
+    # quality=True: (B, K) f32, the decoder's predicted quality iou_pred[:, 0] of each hypothesis's mask (mask_decoder_edge.py:188), NaN
+    # where classes is -1; otherwise None.  An init-only pseudo-field: dataclasses.fields() keeps listing the tensors every call returns
+    iou: InitVar[Optional[torch.Tensor]] = None
+
+    def __post_init__(self, iou):
+        self.iou = iou
+
+
+@dataclass
+class MaskSet:
+    """The edge decoder's multimask output for a batch (Cascade.infer_test_multimask; models/mmseg/models/sam/mask_decoder_edge.py:
+    130-135, 163-190): M candidate masks per image with the quality the decoder predicts for each.  M = 3 (masks 1..3,
+    multimask_output=True), 1 (mask 0, what `infer_test` returns) or 4 (all_masks=True).  Nothing is ranked: the caller chooses."""
+    masks: torch.Tensor             # (B, M, S, S) f32 mask logits at the input size (postprocess_masks, models/sam_maskdecoder_edge.py:355)
+    iou: torch.Tensor               # (B, M) f32 predicted mask quality, iou_pred of the same slice
+    edges: torch.Tensor             # (B, S, S) f32 edge probabilities, upsampled (one edge map gates every mask, :182-186)
+    low_res_masks: torch.Tensor     # (B, M, 4G, 4G) f32 the decoder's own output
 
 
 # ================================================================================================
@@ -1420,13 +1462,19 @@ class Cascade(_Base):
         return sparse
 
     def _mask_logits(self, feats: torch.Tensor, sparse: torch.Tensor, n: int, out: Optional[torch.Tensor] = None,
-                     edge_out: Optional[torch.Tensor] = None, taps: Optional[dict] = None) -> torch.Tensor:
+                     edge_out: Optional[torch.Tensor] = None, taps: Optional[dict] = None,
+                     iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Features rows + n prompts -> mask logits at the input size, f32 [n][1][S][S] or into `out` (n maps of S x S); with
-        `edge_out` the edge probabilities beside them (MaskDecoder.forward(edge_out=True))."""
+        `edge_out` the edge probabilities beside them (MaskDecoder.forward(edge_out=True)); with `iou_out` f32 [n] (needs
+        edge_out) also the predicted quality of each mask, from MaskDecoder.forward(multi=1): same mask and edge bits."""
         g = self.g
-        low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, edge_out=edge_out is not None)
-        if edge_out is not None:
-            low, low_e = low
+        if iou_out is not None:
+            low, low_e, iou = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, multi=1)
+            iou_out.copy_(iou[:, 0])
+        else:
+            low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, edge_out=edge_out is not None)
+            if edge_out is not None:
+                low, low_e = low
         if out is None:
             out = torch.empty(n, 1, g.inp_size, g.inp_size, device=self.device)
         hip.bilinear(low, n, 4 * g.grid, 4 * g.grid, out, g.inp_size, g.inp_size)   # :380-387 (2nd resize = identity)
@@ -1452,6 +1500,31 @@ class Cascade(_Base):
             taps.update(features=feats.clone(), sparse=sparse.clone(), pass1_logits=score.clone())
         self._end(tail)
         return masks
+
+    def infer_test_multimask(self, inp, clip_image, clip_mask, multimask_output: bool = True, all_masks: bool = False) -> MaskSet:
+        """`infer_test` with the decoder's multimask output: the same steps -- `_begin`, `_stage1`,
+        `sparse_prompts`, decoder, resize, `_end`, all on the caller's stream -- with MaskDecoder.forward(multi=) in place of the
+        one-mask decoder call.  The slice is the reference's (mask_decoder_edge.py:130-135): multimask_output=True -> masks 1..3
+        and their three qualities, False -> mask 0 (bit for bit `infer_test`'s mask) and its quality; all_masks=True -> all four."""
+        out_name = self._begin(inp, clip_image, clip_mask)
+        g, dev, B = self.g, self.device, int(inp.shape[0])
+        S, L = g.inp_size, 4 * g.grid
+        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name, tail_on_side=False)
+        sparse = self.sparse_prompts(img_f, txt_f, B)
+        m0, M = (0, 4) if all_masks else (1, 3) if multimask_output else (0, 1)
+        n = m0 + M                                                   # planes the mask head forms: 0..n-1
+        low, low_e, iou = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, B, multi=n)
+        low = low.view(B, n, L, L)
+        masks, edges = torch.empty(B, M, S, S, device=dev), torch.empty(B, S, S, device=dev)
+        if m0 == 0:
+            hip.bilinear(low, B * M, L, L, masks, S, S)             # :380-387 (2nd resize = identity)
+        else:
+            for b in range(B):                                       # planes 1..3 of an image lie together
+                hip.bilinear(low[b, m0:], M, L, L, masks[b], S, S)
+        hip.bilinear(low_e, B, L, L, edges, S, S)                    # postprocess_masks(low_res_edges), :299
+        out = MaskSet(masks=masks, iou=iou[:, m0:n].clone(), edges=edges, low_res_masks=low[:, m0:].clone())
+        self._end(tail)
+        return out
 
     # ---- K class hypotheses per image (DESIGN.md §9) ---------------------------------------------------------------------------
     # Prompts per decoder pass of infer_classes.  From above, the 32-bit limits of the launchers: row counts are int32 and some row
@@ -1531,7 +1604,7 @@ class Cascade(_Base):
             q += m
 
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
-                      topk: Optional[int] = None) -> ClassHypotheses:
+                      topk: Optional[int] = None, quality: bool = False) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -1543,7 +1616,12 @@ class Cascade(_Base):
         gives for class classes[b, k] when the GEMM row counts match -- K = 1 with B <= class_chunk() -- and otherwise within the
         batch tolerance of the GEMM K-splits.  A pass-1 row holding a NaN has no order: with topk= its classes are -1
         and its masks, edges and stage-2 logits NaN; its stage-2 `pred` is what cvlm_clip_head answers for NaN logits, class 0 --
-        read `classes`, not `pred`, to tell such a hypothesis."""
+        read `classes`, not `pred`, to tell such a hypothesis.
+        quality=True: `iou` (B, K), the quality the decoder itself predicts for each hypothesis's mask (iou_pred[:, 0],
+        mask_decoder_edge.py:188), from the same decoder pass of each chunk -- MaskDecoder.forward(multi=1): three more one-row-per-
+        prompt GEMMs and cvlm_mask_head_multi with one plane, so masks, edges and stage 2 keep their bits and the decoder buffers
+        their sizes (`class_chunk()` holds as it is); NaN for a hypothesis whose class is -1.  Nothing is chosen here: the caller
+        ranks.  quality=False makes exactly the launches it made before."""
         B = int(inp.shape[0])
         K, host_classes = self._class_request(B, classes, topk)
         out_name = self._begin(inp, clip_image, clip_mask)
@@ -1562,6 +1640,7 @@ class Cascade(_Base):
             edges = torch.empty(B, K, S, S, device=dev)
             logits = torch.empty(B, K, n_cls, device=dev)
             pred = torch.empty(B, K, dtype=torch.int64, device=dev)
+            iou = torch.empty(B, K, device=dev) if quality else None
             mflat, eflat = masks.view(P, S, S), edges.view(P, S, S)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
@@ -1575,10 +1654,13 @@ class Cascade(_Base):
                 sp = self.ws.f32("cls_sparse", n, 2, C)
                 self._per_prompt(vis, K, p0, p1, sp[:, 0])
                 sp[:, 1].copy_(txt[p0:p1])
-                self._mask_logits(fr, sp, n, out=mflat[p0:p1], edge_out=eflat[p0:p1])
+                self._mask_logits(fr, sp, n, out=mflat[p0:p1], edge_out=eflat[p0:p1], iou_out=iou.view(P)[p0:p1] if quality else None)
                 self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P))
-        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)), (cls, score, masks, edges, logits, pred))
-        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred)
+            if quality:
+                iou.masked_fill_(cls < 0, float("nan"))
+        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
+                  (cls, score, masks, edges, logits, pred) + ((iou,) if quality else ()))
+        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

@@ -26,7 +26,7 @@ EXPORTS = [
     "cvlm_mask_to_u8", "cvlm_mask_joint_hist", "cvlm_mask_wfm", "cvlm_topk_accumulate",
     "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
     "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
-    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan",
+    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan", "cvlm_mask_head_multi",
 ]
 ABI_VERSION = 12
 
@@ -578,6 +578,14 @@ def mask_head_edge(up, edge_emb, hyper, P: int, HW: int, Cc: int, low, edge_prob
     _check(load().cvlm_mask_head_edge(C.c_void_p(up.data_ptr()), C.c_void_p(edge_emb.data_ptr()), C.c_void_p(hyper.data_ptr()),
                                       C.c_int32(P), C.c_int32(HW), C.c_int32(Cc), C.c_void_p(low.data_ptr()),
                                       C.c_void_p(edge_prob.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_head_edge")
+
+
+def mask_head_multi(up, edge_emb, hyper, P: int, HW: int, Cc: int, n_masks: int, low, edge_prob=None) -> None:
+    """low f32 [P][n_masks][HW] = masks 0..n_masks-1 of P prompts from one pass over up / edge_emb; edge_prob f32 [P][HW] (optional);
+    edge_emb None: the plain hypernetwork products (include/cvlm.h)."""
+    _check(load().cvlm_mask_head_multi(C.c_void_p(up.data_ptr()), C.c_void_p(_p(edge_emb)), C.c_void_p(hyper.data_ptr()),
+                                       C.c_int32(P), C.c_int32(HW), C.c_int32(Cc), C.c_int32(n_masks), C.c_void_p(low.data_ptr()),
+                                       C.c_void_p(_p(edge_prob)), C.c_void_p(_stream())), "cvlm_mask_head_multi")
 
 
 def topk_select(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, sel) -> None:

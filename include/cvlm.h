@@ -307,6 +307,19 @@ int cvlm_mask_head(const float* up, const float* edge_emb, const float* hyper, i
 int cvlm_mask_head_edge(const float* up, const float* edge_emb, const float* hyper, int32_t P, int32_t HW, int32_t C,
                         float* low, float* edge_prob, void* stream);
 
+/* All the decoder's masks of a prompt from one pass over its rows (multimask output, mask_decoder_edge.py:163-190: `predict_masks`
+ * forms four masks (:181), gates every one by the one edge map (:182-186); `forward` hands out masks 1..3 or mask 0, :130-135).
+ * up, edge_emb f32 [P][HW][C]; hyper f32 [P][5][C]; n_masks in 1..4.  low f32 [P][n_masks][HW]:
+ * low[p][m][pix] = x*sigmoid(e) + x with x = hyper[p][m].up[p][pix], e = hyper[p][4].edge_emb[p][pix]; edge_prob (optional, may be
+ * NULL) f32 [P][HW] = sigmoid(e).  edge_emb == NULL (then edge_prob must be NULL too): low = x, the vanilla decoder's products
+ * (models/mmseg/models/sam/mask_decoder.py:139).  Plane m = 0 and edge_prob hold the bits cvlm_mask_head / cvlm_mask_head_edge
+ * write for the same inputs: the per-pixel arithmetic is the same code, summed over c in the same order.  Every row of up /
+ * edge_emb is fetched once, a tile of 256 pixels at a time through LDS by coalesced 16-byte loads.
+ * CVLM_E_BADARG: up, hyper or low NULL, edge_prob without edge_emb, P outside [1, 65535], HW or C <= 0, C % 4 != 0, n_masks
+ * outside [1, 4].  CVLM_E_UNSUPPORTED: C > 60 (the tile would not fit 64 KiB of LDS). */
+int cvlm_mask_head_multi(const float* up, const float* edge_emb, const float* hyper, int32_t P, int32_t HW, int32_t C,
+                         int32_t n_masks, float* low, float* edge_prob, void* stream);
+
 /* Bilinear resize, align_corners=False (F.interpolate): in f32 [N][hin][win] -> out [N][hout][wout];
  * sigmoid_in != 0 applies sigmoid to the input first (demo.py:117-120). */
 int cvlm_bilinear(const float* in, int32_t N, int32_t hin, int32_t win, float* out, int32_t hout, int32_t wout,
