@@ -679,6 +679,49 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
     }
 }
 
+// Block expansion dst[p] = src[image_of[p]]: grid (chunk, p), a chunk = XB_CHUNK elements of every tensor the launch carries, so one
+// prompt's block still spreads over the chip.  Pure data movement (integer lanes: no float op ever sees the bits).  VEC: 16-byte
+// loads and stores, all of a lane's loads issued before its first store (four in flight for the f32 tensor, two per h2 plane);
+// otherwise -- a base or a block size that is no multiple of 16 bytes -- element by element.  Offsets are 64-bit.
+constexpr int XB_CHUNK = 4096;
+
+template <typename T, int U>
+__device__ __forceinline__ void xb_copy(const T* __restrict__ s, T* __restrict__ d, int n) {
+    int i = threadIdx.x;
+    for (; i + (U - 1) * 256 < n; i += 256 * U) {                   // all U of this lane in range: no branch between the loads
+        T v[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) v[j] = s[i + j * 256];
+#pragma unroll
+        for (int j = 0; j < U; ++j) d[i + j * 256] = v[j];
+    }
+    for (; i < n; i += 256) d[i] = s[i];                            // the rest of a short chunk
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void expand_blocks_kernel(const int32_t* __restrict__ image_of, int64_t block_elems,
+                                                            const uint32_t* __restrict__ sf, uint32_t* __restrict__ df,
+                                                            const uint16_t* __restrict__ shi, const uint16_t* __restrict__ slo,
+                                                            uint16_t* __restrict__ dhi, uint16_t* __restrict__ dlo) {
+    const int64_t e0 = (int64_t)blockIdx.x * XB_CHUNK;
+    const int64_t left = block_elems - e0;
+    const int n = left < XB_CHUNK ? (int)left : XB_CHUNK;           // elements of this chunk (VEC: a multiple of 8)
+    const int64_t so = (int64_t)image_of[blockIdx.y] * block_elems + e0, dn = (int64_t)blockIdx.y * block_elems + e0;
+    if (VEC) {
+        if (df) xb_copy<uint4, 4>((const uint4*)(sf + so), (uint4*)(df + dn), n >> 2);
+        if (dhi) {
+            xb_copy<uint4, 2>((const uint4*)(shi + so), (uint4*)(dhi + dn), n >> 3);
+            xb_copy<uint4, 2>((const uint4*)(slo + so), (uint4*)(dlo + dn), n >> 3);
+        }
+    } else {
+        if (df) xb_copy<uint32_t, 4>(sf + so, df + dn, n);
+        if (dhi) {
+            xb_copy<uint16_t, 4>(shi + so, dhi + dn, n);
+            xb_copy<uint16_t, 4>(slo + so, dlo + dn, n);
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void normalize_add_kernel(const float* __restrict__ x, const float* __restrict__ add,
                                                            int D, float* __restrict__ out) {
     const int r = blockIdx.x, lane = threadIdx.x;
@@ -1058,6 +1101,28 @@ int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const
     if ((!logits && !idx_in) || !txt || !idx_out || !sel || B <= 0 || C <= 0 || K <= 0 || D <= 0 || (D & 3)) return CVLM_E_BADARG;
     if (!idx_in && (C > TOPK_MAXC || K > C)) return CVLM_E_BADARG;                 // ranking: the row in LDS, K of its C classes
     hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, C, K, txt, D, idx_in, idx_out, sel);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_expand_blocks(const int32_t* image_of, int32_t P, int32_t B, int64_t block_elems, const float* src_f32, float* dst_f32,
+                       const void* src_hi, const void* src_lo, void* dst_hi, void* dst_lo, void* stream) {
+    if (!image_of || P <= 0 || P > 65535 || B <= 0 || block_elems <= 0) return CVLM_E_BADARG;
+    const bool f32 = src_f32 || dst_f32, h2 = src_hi || src_lo || dst_hi || dst_lo;
+    if (!f32 && !h2) return CVLM_E_BADARG;                                         // no output set
+    if (f32 && (!src_f32 || !dst_f32)) return CVLM_E_BADARG;
+    if (h2 && (!src_hi || !src_lo || !dst_hi || !dst_lo)) return CVLM_E_BADARG;    // one plane without the other
+    // no output of 2^31 bytes or more -- 4 bytes per element: the f32 tensor, or the two planes of the h2 pair, which the engine keeps in
+    // one buffer (block_elems < 2^31 first: the product below cannot overflow)
+    if (block_elems >= (int64_t)1 << 31 || (int64_t)P * block_elems * 4 >= (int64_t)1 << 31) return CVLM_E_BADARG;
+    const uintptr_t bases = (uintptr_t)src_f32 | (uintptr_t)dst_f32 | (uintptr_t)src_hi | (uintptr_t)src_lo | (uintptr_t)dst_hi | (uintptr_t)dst_lo;
+    const bool vec = !(bases & 15) && !(block_elems & (h2 ? 7 : 3));
+    const dim3 grid((unsigned)((block_elems + XB_CHUNK - 1) / XB_CHUNK), P);
+    hipStream_t s = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(expand_blocks_kernel<true>, grid, dim3(256), 0, s, image_of, block_elems, (const uint32_t*)src_f32, (uint32_t*)dst_f32,
+                                (const uint16_t*)src_hi, (const uint16_t*)src_lo, (uint16_t*)dst_hi, (uint16_t*)dst_lo);
+    else hipLaunchKernelGGL(expand_blocks_kernel<false>, grid, dim3(256), 0, s, image_of, block_elems, (const uint32_t*)src_f32, (uint32_t*)dst_f32,
+                            (const uint16_t*)src_hi, (const uint16_t*)src_lo, (uint16_t*)dst_hi, (uint16_t*)dst_lo);
     CVLM_CHECK_LAUNCH();
     return 0;
 }

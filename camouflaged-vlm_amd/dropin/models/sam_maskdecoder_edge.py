@@ -133,6 +133,22 @@ class SAM(nn.Module):
                                                    clip_zero_mask.float().contiguous(), multimask_output=multimask_output,
                                                    all_masks=all_masks)
 
+    def encode_images(self, input, clip_image, clip_zero_mask):
+        """EXTENSION, not a reference method: the SAM encoder, CLIP pass 1 and the decoder's prompt-independent part, once, for
+        any number of `decode_classes` calls on the same images.  -> engine.EncodedImages ("Encode once, decode
+        many times")."""
+        H, W = input.shape[-2:]
+        assert H == self.inp_size and W == self.inp_size, \
+            f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
+        return self.cascade().encode(input.float().contiguous(), clip_image.float().contiguous(),
+                                     clip_zero_mask.float().contiguous())
+
+    def decode_classes(self, enc, **kw):
+        """EXTENSION, not a reference method: K prompts per encoded image -- `classes=`, `topk=` or caller-supplied text rows
+        `text=` (what sam_text_proj takes at :342-344), optionally for a subset `images=`, with `quality=` / `stage2=` as
+        engine.Cascade.decode documents them.  No encoder launch.  -> engine.ClassHypotheses."""
+        return self.cascade().decode(enc, **kw)
+
     def infer(self, input, clip_image, clip_zero_mask):
         """:305-329 (bs = 1 variant of infer_test)."""
         return self.infer_test(input, clip_image, clip_zero_mask)

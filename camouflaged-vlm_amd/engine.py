@@ -667,11 +667,84 @@ class MaskDecoder(_Base):
         else:
             self.gemm(a, lin, rows, out_f32=out, residual=const, batch=B, stride_a=rows * lin.K, stride_r=0, stride_o=rows * lin.N, **kw)
 
+    # ---- one decoder, two steps: the part that reads no prompt, over B images, and the part that does, over P prompts ----
+    def image_state(self, B: int, owned: bool = False) -> "DecoderImageState":
+        """The buffers `image_part` writes for B images: the workspace buffers the prompt part works in (owned=False), or tensors of
+        their own that no later call touches (Cascade.encode)."""
+        g, ws = self.g, self.ws
+        C, T, NT = g.prompt_embed_dim, g.grid * g.grid, self.tokens.shape[0]
+        if owned:
+            f32 = lambda *shape: torch.empty(*shape, device=self.device)
+            return DecoderImageState(f32(B * 16 * T, C // 8), f32(B * T, C), H2.empty(B * T, C, device=self.device),
+                                     f32(B * NT, C), H2.empty(B * NT, C, device=self.device))
+        return DecoderImageState(ws.f32("edge_feat", B * 16 * T, C // 8), ws.f32("keys", B * T, C), ws.h2("d_keys_h", B * T, C),
+                                 ws.f32("queries", B * NT, C), ws.h2("d_queries_h", B * NT, C))
+
+    def _token_attn(self, st: "DecoderImageState", B: int, name: str, qp, k, v, nk: int, norm) -> None:
+        """softmax(q k^T) v -> out_proj + queries -> LayerNorm -> queries (f32 + h2); q / k / v already projected"""
+        ws, C, NT = self.ws, self.g.prompt_embed_dim, self.tokens.shape[0]
+        I = self.lin[name + ".out_proj"].K
+        oh, ao_q = ws.h2("t_o%d" % I, B * NT, I), ws.f32("ao_q", B * NT, C)
+        hip.small_attention(qp, k, v, None, B, NT, nk, self.g.dec_heads, I // self.g.dec_heads, out_h2=oh)
+        self.gemm(oh, self.lin[name + ".out_proj"], B * NT, residual=st.queries, out_f32=ao_q)
+        hip.layernorm(ao_q, *norm, 1e-5, B * NT, C, out_f32=st.queries, out_h2=st.queries_h)
+
+    def _image_attn(self, st: "DecoderImageState", B: int, name: str, qconst, k, v, nk: int, norm) -> None:
+        ws, C, T = self.ws, self.g.prompt_embed_dim, self.g.grid * self.g.grid
+        I = self.lin[name + ".out_proj"].K
+        iq, ioh, ao_k = ws.f32("i_q", B * T, I), ws.h2("i_o", B * T, I), ws.f32("ao_k", B * T, C)
+        self._bgemm(st.keys_h, self.lin[name + ".q_proj"], B, T, iq, qconst)
+        hip.small_attention(iq, k, v, None, B, T, nk, self.g.dec_heads, I // self.g.dec_heads, out_h2=ioh)
+        self.gemm(ioh, self.lin[name + ".out_proj"], B * T, residual=st.keys, out_f32=ao_k)
+        hip.layernorm(ao_k, *norm, 1e-5, B * T, C, out_f32=st.keys, out_h2=st.keys_h)
+
+    def _tokens_to_image(self, st: "DecoderImageState", B: int, name: str, qconst, kvlin: Linear, kvconst, norm) -> None:
+        ws, T, NT = self.ws, self.g.grid * self.g.grid, self.tokens.shape[0]
+        I = self.lin[name + ".q_proj"].N
+        qp, kv = ws.f32("t_q", B * NT, I), ws.f32("i_kv", B * T, 2 * I)
+        self._bgemm(st.queries_h, self.lin[name + ".q_proj"], B, NT, qp, qconst)
+        self._bgemm(st.keys_h, kvlin, B, T, kv, kvconst)
+        self._token_attn(st, B, name, qp, kv[:, :I], kv[:, I:], T, norm)
+
+    def image_part(self, feats: torch.Tensor, no_mask: torch.Tensor, gauss: torch.Tensor, B: int, st: "DecoderImageState") -> None:
+        """What the decoder computes from an image alone, for B images, into the buffers of `st`: the `embedding_encoder` upscale of
+        the features (edge_feat, mask_decoder_edge.py:82-87), src = features + no_mask (:150-158), layer 0's queries (image
+        independent: consts q0) and layer 0's token -> image attention through norm2 (transformer_maskdecoder_edge.py:183-187),
+        whose queries no prompt has touched yet.  feats f32 [B*T][C]."""
+        g, ws = self.g, self.ws
+        G, C, T, NT = g.grid, g.prompt_embed_dim, g.grid * g.grid, self.tokens.shape[0]
+        if self.consts is None:
+            self._build_consts(gauss)
+        cst = self.consts
+        fh = ws.h2("feats_h", B * T, C)
+        hip.split_f32(feats, fh)
+        self._upscale(fh, B, G, "embedding_encoder", False, st.edge_feat)
+        # :150-158 tokens / src; every stream lives as f32 rows + the h2 planes of the same values
+        hip.add_rows(feats, no_mask, 1, B * T, C, out_f32=st.keys, out_h2=st.keys_h)
+        zeros = ws._get("f32", "d_zeros", B * NT * C, torch.float32, True).view(B * NT, C)    # zero-filled once, never written
+        hip.add_rows(zeros, cst["q0"], NT, B * NT, C, out_f32=st.queries, out_h2=st.queries_h)  # layer 0's queries for every image
+        L = "transformer.layers.0."
+        self._tokens_to_image(st, B, L + "cross_attn_token_to_image", cst[L + "t2i_q"], self.m[L + "t2i_kv"], cst[L + "t2i_kv"],
+                              self.ln[L + "norm2"])
+
     def forward(self, feats: torch.Tensor, sparse: torch.Tensor, no_mask: torch.Tensor, gauss: torch.Tensor,
                 B: int, taps: Optional[dict] = None, edge_out: bool = False, multi: int = 0):
         """feats f32 [B*T][C]; sparse f32 [B][2][C] -> low-res mask logits f32 [B][4G][4G] (mask 0, :133-135).
         mask_decoder_edge.py:96-190, transformer_maskdecoder_edge.py:62-214.  B counts prompts: one row of `sparse` and one
         copy of the image's features each (the reference expands to sparse_prompt_embeddings.size(0), :150-158).
+        `image_part` over the B copies, then `prompt_part` on its outputs where they lie; the options are `prompt_part`'s."""
+        st = self.image_state(B)
+        self.image_part(feats, no_mask, gauss, B, st)
+        return self.prompt_part(st, sparse, B, taps=taps, edge_out=edge_out, multi=multi)
+
+    def prompt_part(self, st: "DecoderImageState", sparse: torch.Tensor, B: int, image_of: Optional[torch.Tensor] = None, n_images: int = 0,
+                    taps: Optional[dict] = None, edge_out: bool = False, multi: int = 0):
+        """Everything of the decoder from the condition-token projections on, for B prompts; sparse f32 [B][2][C] -> low-res mask
+        logits f32 [B][4G][4G] (mask 0, :133-135).
+        image_of None: prompt p is image p of `st`, whose buffers are worked on in place (they are the workspace's: `forward`).
+        image_of int32 [B] on the device, entries in [0, n_images): `st` holds n_images images and is only read -- one
+        cvlm_expand_blocks launch each for keys (f32 + planes), queries (f32 + planes) and edge_feat copies image image_of[p]'s
+        blocks to prompt p's place in the workspace buffers, and the work goes on there.
         edge_out=True: -> (mask logits, edge probabilities f32 [B][4G][4G] = sigmoid(hyper_edge . edge_embedding), :182-184)
         from cvlm_mask_head_edge in place of cvlm_mask_head; every other launch is the same.
         multi=n (1..4): the decoder's multimask outputs (predict_masks, :163-190) -> (masks 0..n-1 f32 [B][n][4G][4G], edge
@@ -683,18 +756,13 @@ class MaskDecoder(_Base):
         g, ws = self.g, self.ws
         G, C, T, H = g.grid, g.prompt_embed_dim, g.grid * g.grid, g.dec_heads
         NT = self.tokens.shape[0]
-        if self.consts is None:
-            self._build_consts(gauss)
         cst = self.consts
-        fh = ws.h2("feats_h", B * T, C)
-        hip.split_f32(feats, fh)
-        edge_feat = self._upscale(fh, B, G, "embedding_encoder", False, ws.f32("edge_feat", B * 16 * T, C // 8))
-        # :150-158 tokens / src; every stream lives as f32 rows + the h2 planes of the same values
-        keys, keys_h = ws.f32("keys", B * T, C), ws.h2("d_keys_h", B * T, C)
-        hip.add_rows(feats, no_mask, 1, B * T, C, out_f32=keys, out_h2=keys_h)
-        queries, queries_h = ws.f32("queries", B * NT, C), ws.h2("d_queries_h", B * NT, C)
-        zeros = ws._get("f32", "d_zeros", B * NT * C, torch.float32, True).view(B * NT, C)    # zero-filled once, never written
-        hip.add_rows(zeros, cst["q0"], NT, B * NT, C, out_f32=queries, out_h2=queries_h)        # layer 0's queries for every image
+        if image_of is not None:
+            src, st = st, self.image_state(B)
+            hip.expand_blocks(image_of, B, n_images, T * C, src_f32=src.keys, dst_f32=st.keys, src_h2=src.keys_h, dst_h2=st.keys_h)
+            hip.expand_blocks(image_of, B, n_images, NT * C, src_f32=src.queries, dst_f32=st.queries, src_h2=src.queries_h, dst_h2=st.queries_h)
+            hip.expand_blocks(image_of, B, n_images, 16 * T * (C // 8), src_f32=src.edge_feat, dst_f32=st.edge_feat)
+        edge_feat, keys, keys_h, queries, queries_h = st.edge_feat, st.keys, st.keys_h, st.queries, st.queries_h
         # condition tokens: k = (cond + cond_pe) W_k = 2 cond W_k (:98-99), v = cond W_v, for the four condition attentions at once
         cond_h = ws.h2("cond_h", B * 2, C)
         hip.split_f32(sparse, cond_h)
@@ -702,31 +770,11 @@ class MaskDecoder(_Base):
         ck, cv = ws.f32("cond_kp", B * 2, NC), ws.f32("cond_vp", B * 2, NC)
         self.gemm(cond_h, self.m["cond_k"], B * 2, out_f32=ck, alpha=2.0)
         self.gemm(cond_h, self.m["cond_v"], B * 2, out_f32=cv)
-        ao_q, ao_k = ws.f32("ao_q", B * NT, C), ws.f32("ao_k", B * T, C)
+        ao_q = ws.f32("ao_q", B * NT, C)
         hidh = ws.h2("d_hid", B * NT, g.dec_mlp)
-
-        def token_attn(name: str, qp, k, v, nk: int, norm) -> None:
-            """softmax(q k^T) v -> out_proj + queries -> LayerNorm -> queries (f32 + h2); q / k / v already projected"""
-            I = self.lin[name + ".out_proj"].K
-            oh = ws.h2("t_o%d" % I, B * NT, I)
-            hip.small_attention(qp, k, v, None, B, NT, nk, H, I // H, out_h2=oh)
-            self.gemm(oh, self.lin[name + ".out_proj"], B * NT, residual=queries, out_f32=ao_q)
-            hip.layernorm(ao_q, *norm, 1e-5, B * NT, C, out_f32=queries, out_h2=queries_h)
-
-        def image_attn(name: str, qconst, k, v, nk: int, norm) -> None:
-            I = self.lin[name + ".out_proj"].K
-            iq, ioh = ws.f32("i_q", B * T, I), ws.h2("i_o", B * T, I)
-            self._bgemm(keys_h, self.lin[name + ".q_proj"], B, T, iq, qconst)
-            hip.small_attention(iq, k, v, None, B, T, nk, H, I // H, out_h2=ioh)
-            self.gemm(ioh, self.lin[name + ".out_proj"], B * T, residual=keys, out_f32=ao_k)
-            hip.layernorm(ao_k, *norm, 1e-5, B * T, C, out_f32=keys, out_h2=keys_h)
-
-        def tokens_to_image(name: str, qconst, kvlin: Linear, kvconst, norm) -> None:
-            I = self.lin[name + ".q_proj"].N
-            qp, kv = ws.f32("t_q", B * NT, I), ws.f32("i_kv", B * T, 2 * I)
-            self._bgemm(queries_h, self.lin[name + ".q_proj"], B, NT, qp, qconst)
-            self._bgemm(keys_h, kvlin, B, T, kv, kvconst)
-            token_attn(name, qp, kv[:, :I], kv[:, I:], T, norm)
+        token_attn = lambda *a: self._token_attn(st, B, *a)
+        image_attn = lambda *a: self._image_attn(st, B, *a)
+        tokens_to_image = lambda *a: self._tokens_to_image(st, B, *a)
 
         for i in range(g.dec_depth):
             L = f"transformer.layers.{i}."
@@ -735,8 +783,8 @@ class MaskDecoder(_Base):
                 qkv = ws.f32("sa_qkv", B * NT, 3 * C)
                 self._bgemm(queries_h, self.m[L + "self_qkv"], B, NT, qkv, cst[L + "self_qkv"])
                 token_attn(L + "self_attn", qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], NT, ln("norm1"))
-            # tokens -> image (:183-187)
-            tokens_to_image(L + "cross_attn_token_to_image", cst[L + "t2i_q"], self.m[L + "t2i_kv"], cst[L + "t2i_kv"], ln("norm2"))
+                # tokens -> image (:183-187); layer 0's is `image_part`'s
+                tokens_to_image(L + "cross_attn_token_to_image", cst[L + "t2i_q"], self.m[L + "t2i_kv"], cst[L + "t2i_kv"], ln("norm2"))
             # tokens -> cond (:189-193)
             name = L + "cross_attn_token_to_cond"
             I = self.lin[name + ".q_proj"].N
@@ -815,6 +863,19 @@ class MaskDecoder(_Base):
             taps.update(hs=hs.clone(), src=keys.clone(), upscaled=up.clone(), edge_emb=edge_emb.clone(),
                         hyper=hyper.clone(), low_res_masks=low.clone())
         return (low, edge) if edge_out else low
+
+
+@dataclass
+class DecoderImageState:
+    """What MaskDecoder.image_part leaves for the prompt part, for B images (T = G * G tokens, NT = 6 decoder tokens)."""
+    edge_feat: torch.Tensor         # f32 [B*16T][C/8] the embedding_encoder upscale of the features
+    keys: torch.Tensor              # f32 [B*T][C] src = features + no_mask
+    keys_h: H2                      # the same values as h2 planes
+    queries: torch.Tensor           # f32 [B*NT][C] the tokens behind layer 0's token -> image attention and norm2
+    queries_h: H2
+
+    def tensors(self):
+        return (self.edge_feat, self.keys, self.keys_h.t, self.queries, self.queries_h.t)
 
 
 class VanillaMaskDecoder(MaskDecoder):
@@ -1185,18 +1246,83 @@ class ClassHypotheses:
     """K class hypotheses per image from one encoder pass (Cascade.infer_classes).  Hypothesis k of image b is what `infer_test` /
     `cascade` return for that image had CLIP pass 1 predicted classes[b, k]; the prompts run in the order p = b * K + k of the
     reference's repeat_interleave (models/mmseg/models/sam/mask_decoder_edge.py:150-158)."""
-    classes: torch.Tensor           # (B, K) int64; with topk= the K largest pass-1 logits, descending: classes[:, 0] = pass 1's prediction
+    # (B, K) int64; with topk= the K largest pass-1 logits, descending: classes[:, 0] = pass 1's prediction; None from Cascade.decode(text=)
+    classes: Optional[torch.Tensor]
     pass1_logits: torch.Tensor      # (B, n_cls) CLIP pass 1 (mapleAlphaCLIP.py:285-294), as in `cascade`
     masks: torch.Tensor             # (B, K, S, S) f32 mask logits (models/sam_maskdecoder_edge.py:354)
     edges: torch.Tensor             # (B, K, S, S) f32 edge probabilities sigmoid(hyper_edge . edge_embedding), upsampled (:298-302)
-    logits: torch.Tensor            # (B, K, n_cls) stage 2 of each hypothesis (demo.py:117-122)
-    pred: torch.Tensor              # (B, K) int64 stage-2 prediction
+    logits: Optional[torch.Tensor]  # (B, K, n_cls) stage 2 of each hypothesis (demo.py:117-122); None from Cascade.decode(stage2=False)
+    pred: Optional[torch.Tensor]    # (B, K) int64 stage-2 prediction; None from Cascade.decode(stage2=False)
     # quality=True: (B, K) f32, the decoder's predicted quality iou_pred[:, 0] of each hypothesis's mask (mask_decoder_edge.py:188), NaN
     # where classes is -1; otherwise None.  An init-only pseudo-field: dataclasses.fields() keeps listing the tensors every call returns
     iou: InitVar[Optional[torch.Tensor]] = None
 
     def __post_init__(self, iou):
         self.iou = iou
+
+
+@dataclass
+class EncodedImages:
+    """B images encoded once (Cascade.encode), for any number of Cascade.decode calls.  Every tensor is the object's
+    own -- none is a workspace view --, so it stays valid across any later call on the engine.  The SAM features themselves are not
+    kept: the decoder's image part has consumed them."""
+    state: DecoderImageState        # MaskDecoder.image_part's outputs for the B images
+    vis: torch.Tensor               # (B, C) f32 sam_visual_proj of the CLIP image rows (models/sam_maskdecoder_edge.py:342-343)
+    clip_image: torch.Tensor        # (B, 3, R, R) f32 a copy of the caller's: stage 2 reads it
+    pass1_logits: torch.Tensor      # (B, n_cls) CLIP pass 1 (mapleAlphaCLIP.py:285-294)
+    pass1_pred: torch.Tensor        # (B,) int64
+    B: int
+    engine: "Cascade"               # the engine that made it: only that one decodes it
+
+
+def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=None, topk=None, text=None, images=None):
+    """Every check of a Cascade.decode request, on the host, before anything is launched (ValueError) -> (images: list of n ints,
+    K, host int64 (n, K) classes or None).  B images in the session, n_cls rows of width D in the text bank.  A `classes` tensor on
+    the device costs one synchronisation for this check; `text` is checked by dtype and shape only."""
+    if not same_engine:
+        raise ValueError("decode: these images were encoded by another engine")
+    if images is None:
+        images = list(range(B))
+    else:
+        if isinstance(images, (torch.Tensor, np.ndarray, str, bytes)) or not isinstance(images, Sequence):
+            raise ValueError(f"decode: images must be a host sequence of ints, got {type(images).__name__}")
+        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in images):
+            raise ValueError("decode: images must hold ints")
+        images = [int(i) for i in images]
+        if not images:
+            raise ValueError("decode: images is empty")
+        if any(i < 0 or i >= B for i in images):
+            raise ValueError(f"decode: an image index outside [0, {B})")
+    n = len(images)
+    if sum(x is not None for x in (classes, topk, text)) != 1:
+        raise ValueError("decode: give exactly one of classes=, topk= and text=")
+    if topk is not None:
+        if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)):
+            raise ValueError(f"decode: topk must be an int, got {type(topk).__name__}")
+        K = int(topk)
+        if not 1 <= K <= n_cls:
+            raise ValueError(f"decode: topk={K} outside [1, n_cls = {n_cls}]")
+        if n_cls > 1024:
+            raise ValueError(f"decode: topk ranks up to 1024 classes (cvlm_topk_select), the bank has {n_cls}")
+        return images, K, None
+    if text is not None:
+        if not isinstance(text, torch.Tensor):
+            raise ValueError(f"decode: text must be an f32 tensor (n, K, D), got {type(text).__name__}")
+        if text.dtype != torch.float32 or text.dim() != 3 or int(text.shape[0]) != n or int(text.shape[2]) != D:
+            raise ValueError(f"decode: text must be float32 of shape ({n}, K, {D}), got {text.dtype} {tuple(text.shape)}")
+        if int(text.shape[1]) < 1:
+            raise ValueError("decode: text has K = 0 hypotheses")
+        return images, int(text.shape[1]), None
+    if not isinstance(classes, torch.Tensor):
+        raise ValueError(f"decode: classes must be an int64 tensor (n, K), got {type(classes).__name__}")
+    if classes.dtype != torch.int64 or classes.dim() != 2 or int(classes.shape[0]) != n:
+        raise ValueError(f"decode: classes must be int64 of shape ({n}, K), got {classes.dtype} {tuple(classes.shape)}")
+    if int(classes.shape[1]) < 1:
+        raise ValueError("decode: classes has K = 0 hypotheses")
+    host = classes.detach().to("cpu").contiguous()
+    if bool(((host < 0) | (host >= n_cls)).any()):
+        raise ValueError(f"decode: a class index outside [0, {n_cls})")
+    return images, int(classes.shape[1]), host
 
 
 @dataclass
@@ -1439,19 +1565,30 @@ class Cascade(_Base):
         if wait:
             main.wait_stream(tail)
 
-    def _project_prompts(self, img_f: torch.Tensor, txt_f: torch.Tensor, B: int, P: int, sparse: Optional[torch.Tensor] = None):
-        """models/sam_maskdecoder_edge.py:342-344: sam_visual_proj of the B image rows, sam_text_proj of the P text rows
-        -> (vis f32 [B][C], txt f32 [P][C]); with `sparse` f32 [B][2][C] (P = B) each is also copied to its prompt slot."""
-        ws, C, D = self.ws, self.g.prompt_embed_dim, txt_f.shape[-1]
-        hv, ht = ws.h2("pp_hv", B, D), ws.h2("pp_ht", P, D)
-        vis, txt = ws.f32("pp_vis", B, C), ws.f32("pp_txt", P, C)
+    def _project_vis(self, img_f: torch.Tensor, B: int) -> torch.Tensor:
+        """models/sam_maskdecoder_edge.py:342-343: sam_visual_proj of the B image rows -> f32 [B][C] (workspace)."""
+        ws, C, D = self.ws, self.g.prompt_embed_dim, img_f.shape[-1]
+        hv, vis = ws.h2("pp_hv", B, D), ws.f32("pp_vis", B, C)
         hip.layernorm(img_f.reshape(B, D), self.vproj[0], self.vproj[1], 1e-5, B, D, out_h2=hv)
         self.gemm(hv, self.vproj[2], B, out_f32=vis)
         hip.layernorm(vis, self.vproj[3], self.vproj[4], 1e-5, B, C, out_f32=vis)
-        if sparse is not None:
-            sparse[:, 0].copy_(vis)
+        return vis
+
+    def _project_txt(self, txt_f: torch.Tensor, P: int) -> torch.Tensor:
+        """models/sam_maskdecoder_edge.py:344: sam_text_proj of P text rows of any origin -> f32 [P][C] (workspace)."""
+        ws, C, D = self.ws, self.g.prompt_embed_dim, txt_f.shape[-1]
+        ht, txt = ws.h2("pp_ht", P, D), ws.f32("pp_txt", P, C)
         hip.layernorm(txt_f.reshape(P, D), self.tproj[0], self.tproj[1], 1e-5, P, D, out_h2=ht)
         self.gemm(ht, self.tproj[2], P, out_f32=txt)
+        return txt
+
+    def _project_prompts(self, img_f: torch.Tensor, txt_f: torch.Tensor, B: int, P: int, sparse: Optional[torch.Tensor] = None):
+        """models/sam_maskdecoder_edge.py:342-344: sam_visual_proj of the B image rows, sam_text_proj of the P text rows
+        -> (vis f32 [B][C], txt f32 [P][C]); with `sparse` f32 [B][2][C] (P = B) each is also copied to its prompt slot."""
+        vis = self._project_vis(img_f, B)
+        if sparse is not None:
+            sparse[:, 0].copy_(vis)
+        txt = self._project_txt(txt_f, P)
         if sparse is not None:
             sparse[:, 1].copy_(txt)
         return vis, txt
@@ -1461,18 +1598,25 @@ class Cascade(_Base):
         self._project_prompts(img_f, txt_f, B, B, sparse)
         return sparse
 
-    def _mask_logits(self, feats: torch.Tensor, sparse: torch.Tensor, n: int, out: Optional[torch.Tensor] = None,
+    def _mask_logits(self, feats, sparse: torch.Tensor, n: int, out: Optional[torch.Tensor] = None,
                      edge_out: Optional[torch.Tensor] = None, taps: Optional[dict] = None,
                      iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Features rows + n prompts -> mask logits at the input size, f32 [n][1][S][S] or into `out` (n maps of S x S); with
         `edge_out` the edge probabilities beside them (MaskDecoder.forward(edge_out=True)); with `iou_out` f32 [n] (needs
-        edge_out) also the predicted quality of each mask, from MaskDecoder.forward(multi=1): same mask and edge bits."""
+        edge_out) also the predicted quality of each mask, from MaskDecoder.forward(multi=1): same mask and edge bits.
+        `feats` may be (image state, image_of, n_images) in place of features rows: the decoder's image part has run already
+        (Cascade.encode) and only MaskDecoder.prompt_part does."""
         g = self.g
+        if isinstance(feats, tuple):
+            st, image_of, n_images = feats
+            dec = lambda **kw: self.decoder.prompt_part(st, sparse, n, image_of, n_images, taps=taps, **kw)
+        else:
+            dec = lambda **kw: self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, **kw)
         if iou_out is not None:
-            low, low_e, iou = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, multi=1)
+            low, low_e, iou = dec(multi=1)
             iou_out.copy_(iou[:, 0])
         else:
-            low = self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, edge_out=edge_out is not None)
+            low = dec(edge_out=edge_out is not None)
             if edge_out is not None:
                 low, low_e = low
         if out is None:
@@ -1660,6 +1804,96 @@ class Cascade(_Base):
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
                   (cls, score, masks, edges, logits, pred) + ((iou,) if quality else ()))
+        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
+
+    # ---- encode once, decode many times -------------------------------------------------------------------------
+    def encode(self, inp, clip_image, clip_mask) -> EncodedImages:
+        """Everything `infer_classes` computes before it knows a prompt, kept: `_begin` (mx self-check, `flush()`, fold guard),
+        `_stage1` (the SAM encoder with CLIP pass 1 on the side stream under it), then on the tail stream the decoder's image part
+        (MaskDecoder.image_part) into tensors of the result's own, `sam_visual_proj` of the B image rows and a copy of
+        `clip_image`, then `_end` (the current stream waits for the results before the call returns).  The result owns all its
+        tensors and stays valid across any later call on this engine -- other batches, more prompts, pipelined batches.
+        Size per image at the demo geometry (T = 4096 tokens, C = 256): edge_feat 16 T (C / 8) f32 = 8 MiB, keys f32 4 MiB, keys'
+        h2 planes 4 MiB, the CLIP image 1.3 MiB and a few rows: about 17.3 MiB."""
+        out_name = self._begin(inp, clip_image, clip_mask)
+        B = int(inp.shape[0])
+        feats, (img_f, _, pred, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        with torch.cuda.stream(tail):
+            st = self.decoder.image_state(B, owned=True)
+            self.decoder.image_part(feats, self.no_mask, self.gauss, B, st)
+            vis = self._project_vis(img_f, B).clone()
+            own_image = clip_image.clone()
+        self._end(tail, (inp, clip_image, clip_mask), st.tensors() + (vis, own_image, score, pred))
+        return EncodedImages(state=st, vis=vis, clip_image=own_image, pass1_logits=score, pass1_pred=pred, B=B, engine=self)
+
+    def _gather_blocks(self, name: str, src: torch.Tensor, idx: torch.Tensor, n: int, B: int) -> torch.Tensor:
+        """src f32 [B][...] -> workspace buffer `name` f32 [n][...] = src[idx] (one cvlm_expand_blocks launch)."""
+        dst = self.ws.f32(name, n, *src.shape[1:])
+        hip.expand_blocks(idx, n, B, int(np.prod(src.shape[1:])), src_f32=src, dst_f32=dst)
+        return dst
+
+    def decode(self, enc: EncodedImages, *, classes: Optional[torch.Tensor] = None, topk: Optional[int] = None,
+               text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
+               stage2: bool = True) -> ClassHypotheses:
+        """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
+        of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
+        (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
+        open-vocabulary hook of models/sam_maskdecoder_edge.py:342-344; the result's `classes` is None).  images: a host sequence
+        of ints in [0, enc.B), repeats allowed, default all B in order; n = len(images); prompt order p = i * K + k for i over
+        `images`.  stage2=False: no CLIP launch, `logits` and `pred` are None.  quality=True: as in `infer_classes`.
+        Every check is `decode_request`, on the host, before anything is launched (ValueError).  Then `flush()` of an owed pipelined
+        stage 2, the fold-guard poll, and per `class_chunk()` prompts MaskDecoder.prompt_part with the prompt -> image map,
+        the resize and `_class_stage2` -- all on the caller's stream; `enc` is only read.  No encoder launch, and of CLIP only
+        stage 2's.  Bits: those of `infer_classes` on the same inputs when the GEMM row counts match or the K-splits are off,
+        otherwise within the batch tolerance -- the image part ran over B images here and over B * K copies there."""
+        if not isinstance(enc, EncodedImages):
+            raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
+        txt_bank = self.clip.txt["test"]
+        n_cls, D = (int(v) for v in txt_bank.shape)
+        images, K, host_classes = decode_request(same_engine=enc.engine is self, B=enc.B, n_cls=n_cls, D=D, classes=classes, topk=topk,
+                                                 text=text, images=images)
+        self.flush()
+        self._fold_guard_check()
+        g, dev, B = self.g, self.device, enc.B
+        n = len(images)
+        P, S, C = n * K, g.inp_size, g.prompt_embed_dim
+        image_of = torch.tensor([i for i in images for _ in range(K)], dtype=torch.int32).to(dev)
+        if images == list(range(B)):
+            clip_image, score = enc.clip_image, enc.pass1_logits
+        else:                                                        # the subset's rows first, then as n images
+            idx = torch.tensor(images, dtype=torch.int32).to(dev)
+            clip_image = self._gather_blocks("dec_clip_image", enc.clip_image, idx, n, B)
+            score = torch.empty(n, n_cls, device=dev)
+            hip.expand_blocks(idx, n, B, n_cls, src_f32=enc.pass1_logits, dst_f32=score)
+        if text is not None:
+            cls, sel = None, text.detach().to(dev).contiguous().view(P, D)
+        else:
+            cls = torch.empty(n, K, dtype=torch.int64, device=dev)
+            sel = self.ws.f32("cls_sel", P, D)
+            idx_in = None if host_classes is None else host_classes.to(dev)
+            hip.topk_select(score if idx_in is None else None, n, n_cls, K, txt_bank, D, idx_in, cls, sel)
+        txt = self._project_txt(sel, P)
+        masks = torch.empty(n, K, S, S, device=dev)
+        edges = torch.empty(n, K, S, S, device=dev)
+        logits = torch.empty(n, K, n_cls, device=dev) if stage2 else None
+        pred = torch.empty(n, K, dtype=torch.int64, device=dev) if stage2 else None
+        iou = torch.empty(n, K, device=dev) if quality else None
+        mflat, eflat = masks.view(P, S, S), edges.view(P, S, S)
+        chunk = self.class_chunk()
+        for p0 in range(0, P, chunk):
+            p1 = min(P, p0 + chunk)
+            m = p1 - p0
+            of = image_of[p0:p1]
+            sp = self.ws.f32("cls_sparse", m, 2, C)
+            sp[:, 0].copy_(self._gather_blocks("dec_vis", enc.vis, of, m, B))
+            sp[:, 1].copy_(txt[p0:p1])
+            self._mask_logits((enc.state, of, B), sp, m, out=mflat[p0:p1], edge_out=eflat[p0:p1],
+                              iou_out=iou.view(P)[p0:p1] if quality else None)
+            if stage2:
+                self._class_stage2(mflat, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P))
+        if quality and cls is not None:
+            iou.masked_fill_(cls < 0, float("nan"))
+        self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor):

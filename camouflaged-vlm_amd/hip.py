@@ -26,7 +26,7 @@ EXPORTS = [
     "cvlm_mask_to_u8", "cvlm_mask_joint_hist", "cvlm_mask_wfm", "cvlm_topk_accumulate",
     "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
     "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
-    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan", "cvlm_mask_head_multi",
+    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan", "cvlm_mask_head_multi", "cvlm_expand_blocks",
 ]
 ABI_VERSION = 12
 
@@ -594,6 +594,19 @@ def topk_select(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, s
     _check(load().cvlm_topk_select(C.c_void_p(_p(logits)), C.c_int32(B), C.c_int32(Cc), C.c_int32(K), C.c_void_p(txt.data_ptr()),
                                    C.c_int32(D), C.c_void_p(_p(idx_in)), C.c_void_p(idx_out.data_ptr()), C.c_void_p(sel.data_ptr()),
                                    C.c_void_p(_stream())), "cvlm_topk_select")
+
+
+def expand_blocks(image_of: torch.Tensor, P: int, B: int, block_elems: int, *, src_f32: Optional[torch.Tensor] = None,
+                  dst_f32: Optional[torch.Tensor] = None, src_h2: Optional[H2] = None, dst_h2: Optional[H2] = None) -> None:
+    """dst[p] = src[image_of[p]] for P blocks of block_elems contiguous elements out of B source blocks: an f32 pair, an h2 pair (both
+    planes) or both in one launch, bit for bit (include/cvlm.h).  image_of int32 [P] on the device, entries in [0, B): the caller's
+    contract."""
+    assert image_of.dtype == torch.int32 and image_of.is_contiguous() and image_of.numel() >= P
+    _check(load().cvlm_expand_blocks(
+        C.c_void_p(image_of.data_ptr()), C.c_int32(P), C.c_int32(B), C.c_int64(block_elems), C.c_void_p(_p(src_f32)), C.c_void_p(_p(dst_f32)),
+        C.c_void_p(src_h2.hi.data_ptr() if src_h2 is not None else None), C.c_void_p(src_h2.lo.data_ptr() if src_h2 is not None else None),
+        C.c_void_p(dst_h2.hi.data_ptr() if dst_h2 is not None else None), C.c_void_p(dst_h2.lo.data_ptr() if dst_h2 is not None else None),
+        C.c_void_p(_stream())), "cvlm_expand_blocks")
 
 
 def bilinear(x, N: int, hin: int, win: int, out, hout: int, wout: int, sigmoid_in: bool = False) -> None:

@@ -364,6 +364,19 @@ int cvlm_clip_head(const float* img, const float* txt, float logit_scale_exp, in
 int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
                      int64_t* idx_out, float* sel, void* stream);
 
+/* Per-image blocks expanded to per-prompt blocks (the reference's repeat_interleave of the image embedding over the prompts,
+ * mask_decoder_edge.py:150-158, for any prompt -> image map): dst[p] = src[image_of[p]] for p in [0, P), blocks of block_elems
+ * contiguous elements drawn from B source blocks.  image_of int32 [P] on the device, every entry in [0, B): the caller's contract
+ * (Cascade.decode validates its request on the host), nothing on the device checks it.  One launch moves an f32 pair (src_f32 ->
+ * dst_f32), an h2 pair (src_hi / src_lo -> dst_hi / dst_lo, both planes) or both; the bits are copied, no arithmetic.  16-byte
+ * loads and stores when every base is 16-byte aligned and block_elems is a multiple of 4 (f32 only) or 8 (with planes),
+ * element-wise otherwise; grid (chunk of 4096 elements, p), 64-bit offsets, no LDS, no atomics, no workspace.
+ * CVLM_E_BADARG, before anything touches the device: image_of NULL, P outside [1, 65535], B or block_elems <= 0, no output set, a
+ * source without its destination or the reverse, one h2 plane without the other, P * block_elems * 4 >= 2^31 (no output of
+ * 2^31 bytes or more -- the f32 tensor, or the two planes of an h2 pair together; the rule every decoder buffer obeys). */
+int cvlm_expand_blocks(const int32_t* image_of, int32_t P, int32_t B, int64_t block_elems, const float* src_f32, float* dst_f32,
+                       const void* src_hi, const void* src_lo, void* dst_hi, void* dst_lo, void* stream);
+
 /* Row L2 normalise + add: out[r] = x[r]/||x[r]|| + add[r] (text bank, mapleAlphaCLIP.py:290-291). */
 int cvlm_normalize_add(const float* x, const float* add, int32_t R, int32_t D, float* out, void* stream);
 
