@@ -679,6 +679,195 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* __restric
     }
 }
 
+// ---- class vocabularies at run time ------------------------------------------------------------------------------
+// Prompt assembly: out[i][t] = (1 <= t <= n_ctx ? ctx[t - 1] : table[ids[i][t]] or emb[i][t]) + pos[t], t < L.  One float4 per lane
+// and step, whole rows gathered, the add of add_rows_kernel (a + b, then * 1 there).
+__global__ __launch_bounds__(256) void text_assemble_kernel(const int32_t* __restrict__ ids, const float* __restrict__ table,
+                                                            const float* __restrict__ emb, const float* __restrict__ ctx, int n_ctx,
+                                                            const float* __restrict__ pos, int ctx_len, int L, int wv,
+                                                            float* __restrict__ out, int64_t nvec) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / wv;
+        const int c = (int)(i - row * wv);
+        const int64_t p = row / L;
+        const int t = (int)(row - p * L);
+        const float4* src;
+        if (t >= 1 && t <= n_ctx) src = (const float4*)ctx + (int64_t)(t - 1) * wv;
+        else if (ids) src = (const float4*)table + (int64_t)ids[p * ctx_len + t] * wv;
+        else src = (const float4*)emb + (p * ctx_len + t) * wv;
+        float4 v = src[c];
+        const float4 u = ((const float4*)pos)[(int64_t)t * wv + c];
+        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+        ((float4*)out)[i] = v;
+    }
+}
+
+// clip_head_kernel tiled over classes.  Grid (class tile, group of CHW_IMGS images), 4 waves.  A wave first prepares four of the group's
+// images: the norm with clip_head_kernel's additions (its 256 threads' strided partial sums are the four 64-lane passes here, each
+// closed by wave_sum, the four results added in order), then pr = lscale * (x / nrm) into LDS, laid out [image][d].  After one
+// barrier a wave owns `cpw` classes of the tile: the class row goes to registers once (the lane-strided d = lane + 64 k of
+// clip_head_kernel) and meets every image of the group from LDS -- same products, same order of additions, same wave_sum.  The
+// tile's logits wait in LDS for CHW_IMGS lanes that scan them per image, skipping NaNs, and leave (value, index or -1) in the
+// workspace; clip_head_wide_combine_kernel closes the scan.
+constexpr int CHW_IMGS = 16;           // images per group: a text row is fetched once per group
+constexpr int CHW_MAXCPW = 8;          // classes per wave, at most
+constexpr int CHW_KMAX = 16;           // D <= 1024, as clip_head_kernel's register path
+constexpr int CHW_MAXC = 65536;
+
+__host__ __device__ inline int chw_cpw(int C) { const int q = C / 1024; return q < 1 ? 1 : q > CHW_MAXCPW ? CHW_MAXCPW : q; }
+__host__ __device__ inline int chw_tiles(int C) { const int ct = 4 * chw_cpw(C); return (C + ct - 1) / ct; }
+
+__global__ __launch_bounds__(256) void clip_head_wide_kernel(const float* __restrict__ img, const float* __restrict__ txt, float lscale,
+                                                             int P, int C, int D, int cpw, float* __restrict__ img_n,
+                                                             float* __restrict__ logits, float* __restrict__ cand_v,
+                                                             int* __restrict__ cand_i) {
+    extern __shared__ float chw_lds[];
+    float* prs = chw_lds;                                             // [CHW_IMGS][D]
+    float* slog = chw_lds + CHW_IMGS * D;                             // [CHW_IMGS][4 * CHW_MAXCPW]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x, p0 = blockIdx.y * CHW_IMGS;
+    const int ni = P - p0 < CHW_IMGS ? P - p0 : CHW_IMGS;
+    for (int i = wave * 4; i < wave * 4 + 4 && i < ni; ++i) {
+        const float* x = img + (int64_t)(p0 + i) * D;
+        float r[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            float s = 0.f;
+            for (int d = v * 64 + lane; d < D; d += 256) s += x[d] * x[d];
+            r[v] = wave_sum(s);
+        }
+        const float nrm = sqrtf(r[0] + r[1] + r[2] + r[3]);
+        for (int d = lane; d < D; d += 64) {
+            const float q = x[d] / nrm;
+            prs[i * D + d] = lscale * q;
+            if (tile == 0) img_n[(int64_t)(p0 + i) * D + d] = q;
+        }
+    }
+    __syncthreads();
+    const int ct = 4 * cpw, c0 = tile * ct;
+    for (int j = 0; j < cpw; ++j) {
+        const int c = c0 + wave * cpw + j;
+        if (c >= C) break;
+        const float* t = txt + (int64_t)c * D;
+        float tv[CHW_KMAX];
+#pragma unroll
+        for (int k = 0; k < CHW_KMAX; ++k) { const int d = lane + 64 * k; tv[k] = d < D ? t[d] : 0.f; }
+        for (int i = 0; i < ni; ++i) {
+            const float* pr = prs + i * D;
+            float a = 0.f;
+#pragma unroll
+            for (int k = 0; k < CHW_KMAX; ++k) if (lane + 64 * k < D) a += pr[lane + 64 * k] * tv[k];
+            a = wave_sum(a);
+            if (lane == 0) { slog[i * (4 * CHW_MAXCPW) + wave * cpw + j] = a; logits[(int64_t)(p0 + i) * C + c] = a; }
+        }
+    }
+    __syncthreads();
+    if (tid < ni) {
+        const int nc = C - c0 < ct ? C - c0 : ct;
+        const float* v = slog + tid * (4 * CHW_MAXCPW);
+        int best = -1; float bv = 0.f;
+        for (int c = 0; c < nc; ++c) {
+            const float x = v[c];
+            if (!__builtin_isnan(x) && (best < 0 || x > bv)) { bv = x; best = c; }
+        }
+        const int64_t o = (int64_t)(p0 + tid) * gridDim.x + tile;
+        cand_v[o] = bv;
+        cand_i[o] = best < 0 ? -1 : c0 + best;
+    }
+}
+
+// (value, index) order of the scans: larger value first, equal values to the lower index; index -1 = nothing yet
+__device__ __forceinline__ bool cand_better(float ov, int oi, float v, int i) {
+    return oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i));
+}
+
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (cand_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+}
+
+// block-wide (value, index) maximum of 256 threads' candidates, returned to every thread; sv / si: 4 slots of LDS each
+__device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* si) {
+    wave_argmax(v, i);
+    __syncthreads();                                                  // the slots' previous readers are done
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    v = sv[0]; i = si[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) if (cand_better(sv[w], si[w], v, i)) { v = sv[w]; i = si[w]; }
+}
+
+// One block per image: the tiles' candidates in ascending order per thread, then across the block.  The sequential strict-`>` scan from
+// class 0 answers 0 when class 0 is a NaN (nothing compares greater) and otherwise the first maximum of the non-NaN classes.
+__global__ __launch_bounds__(256) void clip_head_wide_combine_kernel(const float* __restrict__ logits, const float* __restrict__ cand_v,
+                                                                     const int* __restrict__ cand_i, int tiles, int C, int D,
+                                                                     const float* __restrict__ txt, int64_t* __restrict__ pred,
+                                                                     float* __restrict__ txt_sel) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    float bv = 0.f; int bi = -1;
+    for (int t = tid; t < tiles; t += 256) {
+        const float v = cand_v[(int64_t)p * tiles + t];
+        const int i = cand_i[(int64_t)p * tiles + t];
+        if (cand_better(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+    block_argmax(bv, bi, sv, si);
+    const int best = (bi < 0 || __builtin_isnan(logits[(int64_t)p * C])) ? 0 : bi;
+    if (tid == 0) pred[p] = best;
+    const int wv = D >> 2;
+    for (int d = tid; d < wv; d += 256) ((float4*)txt_sel)[(int64_t)p * wv + d] = ((const float4*)txt)[(int64_t)best * wv + d];
+}
+
+// topk_select_kernel's ranking without the row in LDS: K rounds, each the block-wide maximum of the classes that stand behind the
+// previous winner in the order (value descending, index ascending).  The row is re-read from L2 every round.
+constexpr int TOPKW_MAXK = 64;
+
+__global__ __launch_bounds__(256) void topk_select_wide_kernel(const float* __restrict__ logits, int C, int K, const float* __restrict__ txt,
+                                                               int D, int64_t* __restrict__ idx_out, float* __restrict__ sel) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int slot[TOPKW_MAXK];
+    __shared__ int has_nan;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (int64_t)b * C;
+    if (tid == 0) has_nan = 0;
+    __syncthreads();
+    bool nan_here = false;
+    for (int c = tid; c < C; c += 256) nan_here |= __builtin_isnan(row[c]);
+    if (nan_here) has_nan = 1;
+    __syncthreads();
+    if (has_nan) {
+        for (int k = tid; k < K; k += 256) slot[k] = -1;
+    } else {
+        float pv = 0.f; int pi = -1;                                  // the previous round's winner
+        for (int k = 0; k < K; ++k) {
+            float bv = 0.f; int bi = -1;
+            for (int c = tid; c < C; c += 256) {
+                const float v = row[c];
+                const bool behind = pi < 0 || v < pv || (v == pv && c > pi);
+                if (behind && (bi < 0 || v > bv)) { bv = v; bi = c; }
+            }
+            block_argmax(bv, bi, sv, si);
+            if (tid == 0) slot[k] = bi;
+            pv = bv; pi = bi;
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += 256) idx_out[(int64_t)b * K + k] = slot[k];
+    const int wv = D >> 2;
+    const float nan = __builtin_nanf("");
+    for (int64_t i = tid; i < (int64_t)K * wv; i += 256) {
+        const int k = (int)(i / wv), d = (int)(i - (int64_t)k * wv);
+        const int c = slot[k];
+        ((float4*)sel)[((int64_t)b * K + k) * wv + d] = c >= 0 ? ((const float4*)txt)[(int64_t)c * wv + d] : make_float4(nan, nan, nan, nan);
+    }
+}
+
 // Block expansion dst[p] = src[image_of[p]]: grid (chunk, p), a chunk = XB_CHUNK elements of every tensor the launch carries, so one
 // prompt's block still spreads over the chip.  Pure data movement (integer lanes: no float op ever sees the bits).  VEC: 16-byte
 // loads and stores, all of a lane's loads issued before its first store (four in flight for the f32 tensor, two per h2 plane);
@@ -1101,6 +1290,54 @@ int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const
     if ((!logits && !idx_in) || !txt || !idx_out || !sel || B <= 0 || C <= 0 || K <= 0 || D <= 0 || (D & 3)) return CVLM_E_BADARG;
     if (!idx_in && (C > TOPK_MAXC || K > C)) return CVLM_E_BADARG;                 // ranking: the row in LDS, K of its C classes
     hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, C, K, txt, D, idx_in, idx_out, sel);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_text_assemble(const int32_t* ids, const float* table, int32_t V, const float* emb, const float* ctx, int32_t n_ctx,
+                       const float* pos, int32_t n, int32_t ctx_len, int32_t L, int32_t W, float* out, void* stream) {
+    if ((ids != nullptr) == (emb != nullptr) || (ids && (!table || V <= 0)) || !ctx || !pos || !out) return CVLM_E_BADARG;
+    if (n <= 0 || ctx_len <= 0 || L <= 0 || W <= 0 || (W & 3) || L > ctx_len || n_ctx < 0 || n_ctx >= ctx_len) return CVLM_E_BADARG;
+    if ((int64_t)n * L * W * 4 >= (int64_t)1 << 31) return CVLM_E_BADARG;
+    const int64_t nvec = (int64_t)n * L * (W >> 2);
+    hipLaunchKernelGGL(text_assemble_kernel, dim3(grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, ids, table, emb, ctx, n_ctx, pos,
+                       ctx_len, L, W >> 2, out, nvec);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int64_t cvlm_clip_head_wide_workspace_bytes(int32_t P, int32_t C) {
+    if (P <= 0 || P > 65535 || C <= 0 || C > CHW_MAXC) return -1;
+    return (int64_t)P * chw_tiles(C) * 8;                            // per (image, class tile): value f32, index int32
+}
+
+int cvlm_clip_head_wide(const float* img, const float* txt, float logit_scale_exp, int32_t P, int32_t C, int32_t D, float* img_n,
+                        float* logits, int64_t* pred, float* txt_sel, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!img || !txt || !img_n || !logits || !pred || !txt_sel || !workspace) return CVLM_E_BADARG;
+    if (P <= 0 || P > 65535 || C <= 0 || C > CHW_MAXC || D <= 0 || (D & 3) || D > 64 * CHW_KMAX) return CVLM_E_BADARG;
+    if (((uintptr_t)workspace & 15) || workspace_bytes < cvlm_clip_head_wide_workspace_bytes(P, C)) return CVLM_E_BADARG;
+    const int tiles = chw_tiles(C);
+    float* cand_v = (float*)workspace;
+    int* cand_i = (int*)(cand_v + (int64_t)P * tiles);
+    const size_t lds = (size_t)(CHW_IMGS * D + CHW_IMGS * 4 * CHW_MAXCPW) * sizeof(float);
+    if (lds > 65536) {                                                // D > 992: above the default dynamic LDS limit
+        hipError_t e = hipFuncSetAttribute((const void*)clip_head_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(clip_head_wide_kernel, dim3(tiles, (P + CHW_IMGS - 1) / CHW_IMGS), dim3(256), lds, s, img, txt, logit_scale_exp,
+                       P, C, D, chw_cpw(C), img_n, logits, cand_v, cand_i);
+    CVLM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(clip_head_wide_combine_kernel, dim3(P), dim3(256), 0, s, logits, cand_v, cand_i, tiles, C, D, txt, pred, txt_sel);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_topk_select_wide(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
+                          int64_t* idx_out, float* sel, void* stream) {
+    if (!logits || idx_in || !txt || !idx_out || !sel || B <= 0 || K <= 0 || D <= 0 || (D & 3)) return CVLM_E_BADARG;
+    if (C <= 0 || C > CHW_MAXC || K > TOPKW_MAXK || K > C) return CVLM_E_BADARG;
+    hipLaunchKernelGGL(topk_select_wide_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, C, K, txt, D, idx_out, sel);
     CVLM_CHECK_LAUNCH();
     return 0;
 }

@@ -82,6 +82,10 @@ class CustomCLIP(nn.Module):
         self.eot = {"train": list(eot_train) if eot_train is not None else None,
                     "test": list(eot_test) if eot_test is not None else None}
         host.populate(self, spec.clip_entries(geometry, prefix=""), seed=seed)
+        # CLIP's token_embedding.weight, kept for vocabularies made at run time (make_vocabulary): a plain attribute on the host,
+        # never a parameter or buffer -- the module's state_dict keys stay the reference's
+        self.token_embedding_table: Optional[torch.Tensor] = None
+        self._table_on_device = None
         if clip_model is not None:
             self._load_from_clip(clip_model)
         self.dtype = torch.float32
@@ -135,6 +139,7 @@ class CustomCLIP(nn.Module):
             loaded.add(nk)
         if "token_embedding.weight" in sd:
             table = sd["token_embedding.weight"].detach().float()
+            self.set_token_embedding(table)
             n_ctx = self.geometry.n_ctx
             for split, names, toks, sfx in (("train", self.classnames, tokens_train, ""),
                                             ("test", self.classnames_test, tokens_test, "_test")):
@@ -152,6 +157,34 @@ class CustomCLIP(nn.Module):
         self._engine_text_dirty = True
         self._engine_train_dirty = True
         self.loaded_from_clip = sorted(loaded)
+
+    def set_token_embedding(self, table: torch.Tensor) -> None:
+        """Keep CLIP's token-embedding table f32 (V, text_width) for `make_vocabulary(tokens=...)`; `_load_from_clip` does this when
+        its source has one.  Not part of the state_dict."""
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or int(table.shape[1]) != self.geometry.text_width:
+            raise ValueError(f"set_token_embedding: table must be a tensor (V, {self.geometry.text_width})")
+        self.token_embedding_table = table.detach().float().contiguous()
+        self._table_on_device = None
+
+    def make_vocabulary(self, *, tokens=None, table=None, embeddings=None, eot=None, bank=None, name=None, **kw):
+        """EXTENSION, not a reference method: a class vocabulary at run time (engine.ClipModel.make_vocabulary) from token ids --
+        against `table`, or the kept token-embedding table when none is passed -- or from embedded prompts.  -> engine.Vocabulary,
+        valid until the engine is rebuilt (load_state_dict, .cuda())."""
+        eng = self.engine()
+        if tokens is not None and table is None:
+            if self.token_embedding_table is None:
+                raise RuntimeError("make_vocabulary(tokens=...): no token-embedding table kept: pass table= or call "
+                                   "set_token_embedding(table) first")
+            if self._table_on_device is None or self._table_on_device.device != eng.device:
+                self._table_on_device = self.token_embedding_table.to(eng.device)
+            table = self._table_on_device
+        return eng.make_vocabulary(tokens=tokens, table=table, embeddings=embeddings, eot=eot, bank=bank, name=name, **kw)
+
+    def check_vocabulary(self, vocab) -> None:
+        """A vocabulary is bound to the engine that made it; load_state_dict / .cuda() build a new one."""
+        if vocab is not None and getattr(vocab, "engine", None) is not self.engine():
+            raise RuntimeError("this vocabulary was made before the engine was rebuilt (load_state_dict / .cuda()) or by another "
+                               "model: make it again with make_vocabulary")
 
     def load_text_features(self, train_text_features, test_text_features):
         self.train_text_features = train_text_features
@@ -197,13 +230,17 @@ class CustomCLIP(nn.Module):
             self._engine_text_dirty = False
         return self._engine
 
-    def forward(self, image, mask, label=None, train=False):
+    def forward(self, image, mask, label=None, train=False, vocab=None):
         """cocotrainers/mapleAlphaCLIP.py:264-294.  train=True (:267-280) is the same forward-only arithmetic on the TRAIN prompts
         (`prompt_learner()` instead of `forward_test()`) and the train bank -> logits [B][n_cls_train]; nothing on this path takes
         gradients (the training loop itself, losses and optimizer, is out of scope)."""
         eng = self.engine()
+        if vocab is not None:                                    # EXTENSION: the test branch against a run-time vocabulary
+            if train:
+                raise ValueError("vocab= goes with the test branch (train=False)")
+            self.check_vocabulary(vocab)
         if not train:
-            return eng.forward(image.float().contiguous(), mask.float().contiguous(), "test")
+            return eng.forward(image.float().contiguous(), mask.float().contiguous(), "test", vocab=vocab)
         if getattr(self, "_engine_train_dirty", True) or "train" not in eng.txt:
             if self.train_text_features is None:
                 raise RuntimeError("text features not loaded: call load_text_features(train, test) first "

@@ -103,15 +103,36 @@ class SAM(nn.Module):
         """:268-270 (``self.training`` lands in ``label``: always the test branch, Appendix B.2)."""
         return self.clip_model(image, alpha, self.training)
 
-    def infer_test(self, input, clip_image, clip_zero_mask):
+    # ---- class vocabularies at run time (EXTENSION; INTEGRATION.md, "Vocabularies at run time") ------------------------------------
+    def make_vocabulary(self, **kw):
+        """EXTENSION, not a reference method: a class vocabulary from token ids (`tokens=`, against `table=` or the CLIP module's
+        kept token-embedding table) or embedded prompts (`embeddings=`, `eot=`), with its `bank=` and a `name=`.  -> engine.Vocabulary
+        for `vocab=` of the inference methods and `use_vocabulary`; valid until the engines are rebuilt (load_state_dict, .cuda())."""
+        if not hasattr(self, "clip_model"):
+            raise RuntimeError("call load_mapleAlphaCLIP(...) first (demo.py:87)")
+        return self.clip_model.make_vocabulary(**kw)
+
+    def use_vocabulary(self, vocab) -> None:
+        """EXTENSION: make `vocab` the default of every inference method (None: the constructor's classes again)."""
+        self._vocab(vocab)
+        self.cascade().use_vocabulary(vocab)
+
+    def _vocab(self, vocab):
+        if vocab is not None:
+            if not hasattr(self, "clip_model"):
+                raise RuntimeError("call load_mapleAlphaCLIP(...) first (demo.py:87)")
+            self.clip_model.check_vocabulary(vocab)
+        return vocab
+
+    def infer_test(self, input, clip_image, clip_zero_mask, vocab=None):
         """:331-357 -> (B,1,inp_size,inp_size) fp32 mask logits."""
         H, W = input.shape[-2:]
         assert H == self.inp_size and W == self.inp_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().infer_test(input.float().contiguous(), clip_image.float().contiguous(),
-                                         clip_zero_mask.float().contiguous())
+                                         clip_zero_mask.float().contiguous(), vocab=self._vocab(vocab))
 
-    def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False):
+    def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False, vocab=None):
         """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
         the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
         decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
@@ -120,9 +141,10 @@ class SAM(nn.Module):
         assert H == self.inp_size and W == self.inp_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().infer_classes(input.float().contiguous(), clip_image.float().contiguous(),
-                                            clip_zero_mask.float().contiguous(), classes=classes, topk=topk, quality=quality)
+                                            clip_zero_mask.float().contiguous(), classes=classes, topk=topk, quality=quality,
+                                            vocab=self._vocab(vocab))
 
-    def infer_test_multimask(self, input, clip_image, clip_zero_mask, multimask_output=True, all_masks=False):
+    def infer_test_multimask(self, input, clip_image, clip_zero_mask, multimask_output=True, all_masks=False, vocab=None):
         """EXTENSION, not a reference method: `infer_test` with the decoder's multimask output -- the candidate masks and the
         quality `iou_pred` the reference's `mask_decoder(..., multimask_output=...)` returns and `infer_test` drops
         (mask_decoder_edge.py:130-135, 163-190).  -> engine.MaskSet (INTEGRATION.md, "Multimask output")."""
@@ -131,9 +153,9 @@ class SAM(nn.Module):
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().infer_test_multimask(input.float().contiguous(), clip_image.float().contiguous(),
                                                    clip_zero_mask.float().contiguous(), multimask_output=multimask_output,
-                                                   all_masks=all_masks)
+                                                   all_masks=all_masks, vocab=self._vocab(vocab))
 
-    def encode_images(self, input, clip_image, clip_zero_mask):
+    def encode_images(self, input, clip_image, clip_zero_mask, vocab=None):
         """EXTENSION, not a reference method: the SAM encoder, CLIP pass 1 and the decoder's prompt-independent part, once, for
         any number of `decode_classes` calls on the same images.  -> engine.EncodedImages ("Encode once, decode
         many times")."""
@@ -141,12 +163,14 @@ class SAM(nn.Module):
         assert H == self.inp_size and W == self.inp_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
         return self.cascade().encode(input.float().contiguous(), clip_image.float().contiguous(),
-                                     clip_zero_mask.float().contiguous())
+                                     clip_zero_mask.float().contiguous(), vocab=self._vocab(vocab))
 
     def decode_classes(self, enc, **kw):
         """EXTENSION, not a reference method: K prompts per encoded image -- `classes=`, `topk=` or caller-supplied text rows
         `text=` (what sam_text_proj takes at :342-344), optionally for a subset `images=`, with `quality=` / `stage2=` as
-        engine.Cascade.decode documents them.  No encoder launch.  -> engine.ClassHypotheses."""
+        engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
+        with.  No encoder launch.  -> engine.ClassHypotheses."""
+        self._vocab(kw.get("vocab"))
         return self.cascade().decode(enc, **kw)
 
     def infer(self, input, clip_image, clip_zero_mask):

@@ -59,6 +59,12 @@ class Precision:
 X_SCALE = 2.0 ** -2
 HID_SCALE = 2.0 ** -2
 
+# Class vocabularies at run time
+VOCAB_CHUNK = 256          # prompts per text-tower pass of ClipModel.make_vocabulary: bounds the grow-only workspace
+RANK_CAP = 1024            # classes cvlm_topk_select ranks
+RANK_CAP_WIDE = 65536      # classes cvlm_clip_head_wide scores and cvlm_topk_select_wide ranks
+RANK_WIDE_MAXK = 64        # hypotheses cvlm_topk_select_wide ranks
+
 
 def _ceil(a: int, b: int) -> int:
     return (a + b - 1) // b * b
@@ -1207,6 +1213,12 @@ class ClipModel(_Base):
         hip.add_rows(full, self.tpos[:L].contiguous(), L, n * L, Wd, out_f32=x)
         # A rank's shard must give the bits of the full bank: no K-split here -- tail chain and split-K pick their
         # number of parts from M = prompts x positions, which differs between a shard and the whole (runs once per weight load)
+        return self._text_tower(x, eot, n, L)
+
+    def _text_tower(self, x: torch.Tensor, eot: List[int], n: int, L: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The text transformer on assembled prompts x f32 [n][L][text_width] (overwritten), the EOT pick, ln_final and the text
+        projection (mapleAlphaCLIP.py:66-78) -> f32 [n][embed_dim], into `out` when given.  No K-split: see text_features."""
+        c, Wd = self.c, self.c.text_width
         self.ksplit = False
         try:
             self._blocks(x, self.tblocks, n, L, Wd, c.text_heads, self.deep_text, 1, causal=True)
@@ -1214,11 +1226,43 @@ class ClipModel(_Base):
             hip.gather_rows(x, n, L, Wd, torch.tensor(eot, dtype=torch.int32, device=self.device), 0, rows_f)
             rh = H2.empty(n, Wd, device=self.device)
             hip.layernorm(rows_f, *self.ln_final, 1e-5, n, Wd, out_h2=rh)
-            out = torch.empty(n, c.embed_dim, device=self.device)
+            if out is None:
+                out = torch.empty(n, c.embed_dim, device=self.device)
             self.gemm(rh, self.tproj, n, out_f32=out)
         finally:
             self.ksplit = True
         return out
+
+    # ---- class vocabularies at run time ------------------------------------------------------------------------
+    def make_vocabulary(self, *, tokens=None, table=None, embeddings=None, eot=None, bank=None, name: Optional[str] = None,
+                        chunk: int = VOCAB_CHUNK) -> "Vocabulary":
+        """A class vocabulary from token ids (`tokens` host int (n, context_length) + `table` f32 (V, text_width), the CLIP
+        token_embedding.weight, host or device) or from embedded prompts (`embeddings` f32 (n, context_length, text_width) + `eot`):
+        the MaPLe prompts [prefix | ctx | suffix] (mapleAlphaCLIP.py:132-168, 210-227; positions 1..n_ctx are the learned ctx
+        whatever the input holds there), `text_features`' launch sequence on them in chunks of `chunk` prompts -- every chunk at
+        L = max(eot) + 1 of the WHOLE vocabulary, so a row's bits do not depend on `chunk` --, then normalise + bank (:289-291; bank
+        None: no add).  Every check is `vocabulary_request`, on the host, before anything is launched (ValueError)."""
+        c, dev = self.c, self.device
+        n, eot, ids = vocabulary_request(context_length=c.context_length, text_width=c.text_width, n_ctx=c.n_ctx, embed_dim=c.embed_dim,
+                                         tokens=tokens, table=table, embeddings=embeddings, eot=eot, bank=bank, chunk=chunk)
+        L, Wd, D = max(eot) + 1, c.text_width, c.embed_dim
+        pos = self.tpos[:L].contiguous()
+        if ids is not None:
+            table = table.detach().contiguous().to(dev)
+            ids = torch.from_numpy(ids).to(dev)
+        tf = torch.empty(n, D, device=dev)
+        for i0 in range(0, n, chunk):
+            i1 = min(n, i0 + chunk)
+            m = i1 - i0
+            x = torch.empty(m, L, Wd, device=dev)
+            if ids is not None:
+                hip.text_assemble(ids[i0:i1], table, None, self.ctx, pos, m, c.context_length, L, Wd, x)
+            else:
+                hip.text_assemble(None, None, embeddings[i0:i1].detach().contiguous().to(dev), self.ctx, pos, m, c.context_length, L, Wd, x)
+            self._text_tower(x, eot[i0:i1], m, L, out=tf[i0:i1])
+        rows = torch.empty(n, D, device=dev)
+        hip.normalize_add(tf, None if bank is None else bank.detach().contiguous().to(dev), n, D, rows)
+        return Vocabulary(rows=rows, text_features=tf, eot=eot, n=n, D=D, name=name, engine=self)
 
     def set_text_bank(self, text_feat: torch.Tensor, bank: torch.Tensor, split: str = "test") -> None:
         """txt = normalise(text_feat) + bank, no re-normalisation (mapleAlphaCLIP.py:290-291)."""
@@ -1227,18 +1271,106 @@ class ClipModel(_Base):
         hip.normalize_add(text_feat, self.dev(bank), n, D, out)
         self.txt[split] = out
 
-    def forward(self, image: torch.Tensor, alpha: torch.Tensor, split: str = "test"):
-        """CustomCLIP.forward test branch (mapleAlphaCLIP.py:281-294)."""
-        txt = self.txt[split]
+    def forward(self, image: torch.Tensor, alpha: torch.Tensor, split: str = "test", vocab: Optional["Vocabulary"] = None):
+        """CustomCLIP.forward test branch (mapleAlphaCLIP.py:281-294); vocab: score against a run-time vocabulary's rows instead of
+        the split's bank."""
+        if vocab is not None and vocab.engine is not self:
+            raise ValueError("this vocabulary was made by another engine")
         feat = self.image_features(image, alpha)              # lists of tensors: one forward over the stacked groups
+        self.last_features = feat                             # raw image features (workspace view): Cascade.encode keeps a copy
+        return self.head(feat, split, vocab)
+
+    def head(self, feat: torch.Tensor, split: str = "test", vocab: Optional["Vocabulary"] = None):
+        """mapleAlphaCLIP.py:289-294 on raw image features f32 [B][D]: one launch of cvlm_clip_head, or above 1024 classes of
+        cvlm_clip_head_wide -> (img_n [B][1][D], txt[pred] [B][1][D], pred, logits)."""
+        if vocab is not None and vocab.engine is not self:
+            raise ValueError("this vocabulary was made by another engine")
+        txt = self.txt[split] if vocab is None else vocab.rows
         B = feat.shape[0]
         n, D = txt.shape
         img_n = torch.empty(B, D, device=self.device)
         logits = torch.empty(B, n, device=self.device)
         pred = torch.empty(B, dtype=torch.int64, device=self.device)
         sel = torch.empty(B, D, device=self.device)
-        hip.clip_head(feat, txt, self.logit_scale_exp, B, n, D, img_n, logits, pred, sel)
+        if n <= 1024:
+            hip.clip_head(feat, txt, self.logit_scale_exp, B, n, D, img_n, logits, pred, sel)
+        else:
+            hip.clip_head_wide(feat, txt, self.logit_scale_exp, B, n, D, img_n, logits, pred, sel,
+                               self.ws.scratch("head_wide_ws", hip.clip_head_wide_workspace_bytes(B, n)))
         return img_n.unsqueeze(1), sel.unsqueeze(1), pred, logits
+
+
+# ================================================================================================
+# Class vocabularies at run time  (DESIGN.md §12; cocotrainers/mapleAlphaCLIP.py:132-168, 210-227, 289-291)
+# ================================================================================================
+
+
+@dataclass
+class Vocabulary:
+    """A class vocabulary made at run time (ClipModel.make_vocabulary).  Owns its tensors: none is a workspace view."""
+    rows: torch.Tensor              # (n, D) f32 on the device: normalise(text_features) + bank (mapleAlphaCLIP.py:289-291)
+    text_features: torch.Tensor     # (n, D) f32 the text tower's output (:64-78)
+    eot: List[int]                  # host: the EOT position of each prompt
+    n: int
+    D: int
+    name: Optional[str]
+    engine: "ClipModel"             # the engine that made it: only that one scores against it
+
+
+def vocabulary_request(*, context_length: int, text_width: int, n_ctx: int, embed_dim: int, tokens=None, table=None, embeddings=None,
+                       eot=None, bank=None, chunk: int = VOCAB_CHUNK):
+    """Every check of a ClipModel.make_vocabulary request, on the host, before anything is launched (ValueError) -> (n, eot as a
+    list of n ints, the token ids as a contiguous host int32 array (n, context_length) or None for the embeddings form).
+    Form 1: tokens (host int array (n, context_length), ids in [0, V)) + table (f32 (V, text_width)); eot defaults to
+    tokens.argmax(-1) (mapleAlphaCLIP.py:76).  Form 2: embeddings (f32 (n, context_length, text_width)) + eot.  bank: f32
+    (n, embed_dim) or None.  n >= 1 and n_ctx < eot[i] < context_length for every prompt."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"make_vocabulary: chunk must be a positive int, got {chunk!r}")
+    if (tokens is None) == (embeddings is None):
+        raise ValueError("make_vocabulary: give exactly one of tokens= (with table=) and embeddings= (with eot=)")
+    ids = None
+    if tokens is not None:
+        if isinstance(tokens, torch.Tensor):
+            if tokens.device.type != "cpu":
+                raise ValueError("make_vocabulary: tokens must be a host array")
+            tokens = tokens.numpy()
+        tokens = np.asarray(tokens)
+        if tokens.dtype == np.bool_ or not np.issubdtype(tokens.dtype, np.integer):
+            raise ValueError(f"make_vocabulary: tokens must hold ints, got {tokens.dtype}")
+        if tokens.ndim != 2 or tokens.shape[1] != context_length:
+            raise ValueError(f"make_vocabulary: tokens must have shape (n, {context_length}), got {tuple(tokens.shape)}")
+        n = int(tokens.shape[0])
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or int(table.shape[1]) != text_width \
+                or int(table.shape[0]) < 1:
+            raise ValueError(f"make_vocabulary: table must be a float32 tensor (V, {text_width})")
+        if n >= 1 and (int(tokens.min()) < 0 or int(tokens.max()) >= int(table.shape[0])):
+            raise ValueError(f"make_vocabulary: a token id outside [0, {int(table.shape[0])})")
+        if eot is None and n >= 1:
+            eot = tokens.argmax(-1)
+        ids = np.ascontiguousarray(tokens, dtype=np.int32)
+    else:
+        if table is not None:
+            raise ValueError("make_vocabulary: table= goes with tokens=, not with embeddings=")
+        if not isinstance(embeddings, torch.Tensor) or embeddings.dtype != torch.float32 or embeddings.dim() != 3 or \
+                tuple(embeddings.shape[1:]) != (context_length, text_width):
+            raise ValueError(f"make_vocabulary: embeddings must be a float32 tensor (n, {context_length}, {text_width})")
+        n = int(embeddings.shape[0])
+        if eot is None:
+            raise ValueError("make_vocabulary: embeddings= needs eot=")
+    if n < 1:
+        raise ValueError("make_vocabulary: an empty vocabulary")
+    if n > RANK_CAP_WIDE:
+        raise ValueError(f"make_vocabulary: {n} classes, the head scores up to {RANK_CAP_WIDE}")
+    if isinstance(eot, torch.Tensor):
+        eot = eot.detach().cpu().numpy()
+    eot = np.asarray(eot)
+    if eot.dtype == np.bool_ or not np.issubdtype(eot.dtype, np.integer) or eot.shape != (n,):
+        raise ValueError(f"make_vocabulary: eot must hold {n} ints")
+    if int(eot.min()) <= n_ctx or int(eot.max()) >= context_length:
+        raise ValueError(f"make_vocabulary: an EOT position outside ({n_ctx}, {context_length})")
+    if bank is not None and (not isinstance(bank, torch.Tensor) or bank.dtype != torch.float32 or tuple(bank.shape) != (n, embed_dim)):
+        raise ValueError(f"make_vocabulary: bank must be a float32 tensor ({n}, {embed_dim}) or None")
+    return n, [int(e) for e in eot], ids
 
 
 @dataclass
@@ -1273,12 +1405,16 @@ class EncodedImages:
     pass1_pred: torch.Tensor        # (B,) int64
     B: int
     engine: "Cascade"               # the engine that made it: only that one decodes it
+    vocab: Optional[Vocabulary] = None              # the vocabulary `encode` scored pass 1 against; None: the constructor's bank
+    pass1_features: Optional[torch.Tensor] = None   # (B, D) f32 raw CLIP image features of pass 1: decode(vocab=) re-scores them
 
 
-def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=None, topk=None, text=None, images=None):
+def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=None, topk=None, text=None, images=None,
+                   rank_cap: int = RANK_CAP):
     """Every check of a Cascade.decode request, on the host, before anything is launched (ValueError) -> (images: list of n ints,
     K, host int64 (n, K) classes or None).  B images in the session, n_cls rows of width D in the text bank.  A `classes` tensor on
-    the device costs one synchronisation for this check; `text` is checked by dtype and shape only."""
+    the device costs one synchronisation for this check; `text` is checked by dtype and shape only.  rank_cap: the classes topk= may
+    rank -- 1024 (cvlm_topk_select), or 65536 on the vocabulary path (cvlm_topk_select_wide, which ranks at most 64 hypotheses)."""
     if not same_engine:
         raise ValueError("decode: these images were encoded by another engine")
     if images is None:
@@ -1302,8 +1438,10 @@ def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=Non
         K = int(topk)
         if not 1 <= K <= n_cls:
             raise ValueError(f"decode: topk={K} outside [1, n_cls = {n_cls}]")
-        if n_cls > 1024:
-            raise ValueError(f"decode: topk ranks up to 1024 classes (cvlm_topk_select), the bank has {n_cls}")
+        if n_cls > rank_cap:
+            raise ValueError(f"decode: topk ranks up to {rank_cap} classes (cvlm_topk_select), the bank has {n_cls}")
+        if n_cls > RANK_CAP and K > RANK_WIDE_MAXK:
+            raise ValueError(f"decode: topk={K}: above {RANK_CAP} classes at most {RANK_WIDE_MAXK} hypotheses are ranked (cvlm_topk_select_wide)")
         return images, K, None
     if text is not None:
         if not isinstance(text, torch.Tensor):
@@ -1362,6 +1500,7 @@ class Cascade(_Base):
         # as ONE vision-tower forward over both batches (M = 9296 at B = 8: 36 row tiles instead of twice 18.2; out_proj 148
         # tiles on 256 CUs instead of twice 76).  `fuse_clip = False` keeps the two forwards apart (tests).
         self.fuse_clip = True
+        self._vocab: Optional[Vocabulary] = None                     # use_vocabulary: the default of every entry point (None: the constructor's bank)
         self._pending = None                                         # (masks, clip_image, pred, logits) of the batch whose stage 2 is still owed
         self._pending_stream = None
         self._clip_done = None                                       # end of the last fused CLIP forward (reader of the owned input copies)
@@ -1633,11 +1772,50 @@ class Cascade(_Base):
         hip.bilinear(mask_logits, n, self.g.inp_size, self.g.inp_size, alpha, R, R, sigmoid_in=True)
         return alpha
 
-    def infer_test(self, inp, clip_image, clip_mask, taps: Optional[dict] = None) -> torch.Tensor:
-        """models/sam_maskdecoder_edge.py:331-357.  Prompts, decoder and resize run on the caller's stream."""
+    # ---- class vocabularies at run time ------------------------------------------------------------------------
+    def use_vocabulary(self, vocab: Optional[Vocabulary]) -> None:
+        """Make `vocab` the default of every entry point -- `cascade(pipelined=True)` included, whose fused CLIP forward scores one
+        vocabulary per step; an owed pipelined stage 2 is flushed first, against the vocabulary its batch ran with.  None restores
+        the constructor's bank."""
+        if vocab is not None:
+            self._check_vocab(vocab)
+        self.flush()
+        self._vocab = vocab
+
+    def _check_vocab(self, vocab) -> None:
+        if not isinstance(vocab, Vocabulary):
+            raise ValueError(f"vocab must come from make_vocabulary, got {type(vocab).__name__}")
+        if vocab.engine is not self.clip:
+            raise ValueError("this vocabulary was made by another engine")
+
+    def _vocab_of(self, vocab: Optional[Vocabulary]) -> Optional[Vocabulary]:
+        """The vocabulary a call runs with: its own, else `use_vocabulary`'s, else None (the constructor's bank)."""
+        if vocab is None:
+            return self._vocab
+        self._check_vocab(vocab)
+        return vocab
+
+    def _bank(self, vocab: Optional[Vocabulary]) -> torch.Tensor:
+        return self.clip.txt["test"] if vocab is None else vocab.rows
+
+    def _select(self, score, B: int, n_cls: int, K: int, bank: torch.Tensor, D: int, idx_in, cls, sel) -> None:
+        """K text rows per image: ranked from `score` (cvlm_topk_select, above 1024 classes cvlm_topk_select_wide) or gathered by idx_in."""
+        if idx_in is None and n_cls > RANK_CAP:
+            hip.topk_select_wide(score, B, n_cls, K, bank, D, None, cls, sel)
+        else:
+            hip.topk_select(score if idx_in is None else None, B, n_cls, K, bank, D, idx_in, cls, sel)
+
+    def make_vocabulary(self, **kw) -> Vocabulary:
+        """ClipModel.make_vocabulary on this cascade's CLIP engine."""
+        return self.clip.make_vocabulary(**kw)
+
+    def infer_test(self, inp, clip_image, clip_mask, taps: Optional[dict] = None, vocab: Optional[Vocabulary] = None) -> torch.Tensor:
+        """models/sam_maskdecoder_edge.py:331-357.  Prompts, decoder and resize run on the caller's stream.  vocab: pass 1 scores
+        against a run-time vocabulary instead of the constructor's bank."""
+        vocab = self._vocab_of(vocab)
         out_name = self._begin(inp, clip_image, clip_mask)
         B = inp.shape[0]
-        feats, (img_f, txt_f, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name, taps, tail_on_side=False)
+        feats, (img_f, txt_f, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask, vocab=vocab), out_name, taps, tail_on_side=False)
         sparse = self.sparse_prompts(img_f, txt_f, B)
         masks = self._mask_logits(feats, sparse, B, taps=taps)
         if taps is not None:
@@ -1645,15 +1823,17 @@ class Cascade(_Base):
         self._end(tail)
         return masks
 
-    def infer_test_multimask(self, inp, clip_image, clip_mask, multimask_output: bool = True, all_masks: bool = False) -> MaskSet:
+    def infer_test_multimask(self, inp, clip_image, clip_mask, multimask_output: bool = True, all_masks: bool = False,
+                             vocab: Optional[Vocabulary] = None) -> MaskSet:
         """`infer_test` with the decoder's multimask output: the same steps -- `_begin`, `_stage1`,
         `sparse_prompts`, decoder, resize, `_end`, all on the caller's stream -- with MaskDecoder.forward(multi=) in place of the
         one-mask decoder call.  The slice is the reference's (mask_decoder_edge.py:130-135): multimask_output=True -> masks 1..3
         and their three qualities, False -> mask 0 (bit for bit `infer_test`'s mask) and its quality; all_masks=True -> all four."""
+        vocab = self._vocab_of(vocab)
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev, B = self.g, self.device, int(inp.shape[0])
         S, L = g.inp_size, 4 * g.grid
-        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name, tail_on_side=False)
+        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask, vocab=vocab), out_name, tail_on_side=False)
         sparse = self.sparse_prompts(img_f, txt_f, B)
         m0, M = (0, 4) if all_masks else (1, 3) if multimask_output else (0, 1)
         n = m0 + M                                                   # planes the mask head forms: 0..n-1
@@ -1683,9 +1863,10 @@ class Cascade(_Base):
         limit = (2 ** 31 - 1) // (16 * T * (C // 4) * 4)
         return max(1, min(self.CLASS_CHUNK, limit))
 
-    def _class_request(self, B: int, classes, topk):
+    def _class_request(self, B: int, classes, topk, vocab: Optional[Vocabulary] = None):
         """Host-side validation of infer_classes' hypotheses before any launch -> (K, host int64 (B, K) tensor or None)."""
-        n_cls = self.clip.txt["test"].shape[0]
+        n_cls = int(self._bank(vocab).shape[0])
+        rank_cap = RANK_CAP if vocab is None else RANK_CAP_WIDE
         if (classes is None) == (topk is None):
             raise ValueError("infer_classes: give exactly one of classes= and topk=")
         if topk is not None:
@@ -1694,8 +1875,11 @@ class Cascade(_Base):
             K = int(topk)
             if not 1 <= K <= n_cls:
                 raise ValueError(f"infer_classes: topk={K} outside [1, n_cls = {n_cls}]")
-            if n_cls > 1024:
+            if n_cls > rank_cap:
                 raise ValueError(f"infer_classes: topk ranks up to 1024 classes (cvlm_topk_select), the bank has {n_cls}")
+            if n_cls > RANK_CAP and K > RANK_WIDE_MAXK:
+                raise ValueError(f"infer_classes: topk={K}: above {RANK_CAP} classes at most {RANK_WIDE_MAXK} hypotheses are ranked "
+                                 "(cvlm_topk_select_wide)")
             return K, None
         if not isinstance(classes, torch.Tensor):
             raise ValueError(f"infer_classes: classes must be an int64 tensor (B, K), got {type(classes).__name__}")
@@ -1717,7 +1901,7 @@ class Cascade(_Base):
             dst[lo - p0:hi - p0].copy_(src[b:b + 1].expand(hi - lo, *src.shape[1:]))
 
     def _class_stage2(self, masks: torch.Tensor, clip_image: torch.Tensor, B: int, K: int, p0: int, p1: int,
-                      logits: torch.Tensor, pred: torch.Tensor) -> None:
+                      logits: torch.Tensor, pred: torch.Tensor, vocab: Optional[Vocabulary] = None) -> None:
         """demo.py:117-122 for the prompts p0 <= p < p1 as ONE CLIP forward: its images are the groups clip_image[b_lo:b_hi] of
         one hypothesis slot k each (ClipModel.image_features stacks groups without copying them), the alphas follow in that
         order; results go back to the prompt order p = b * K + k."""
@@ -1739,7 +1923,7 @@ class Cascade(_Base):
                 images.append(clip_image[b_lo:b_hi])
                 alphas.append(alpha_q[q:q + m])
                 q += m
-        _, _, pr, lg = self.clip.forward(images, alphas)
+        _, _, pr, lg = self.clip.forward(images, alphas, vocab=vocab)
         q = 0
         for k, b_lo, b_hi in groups:
             m = b_hi - b_lo
@@ -1748,7 +1932,7 @@ class Cascade(_Base):
             q += m
 
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
-                      topk: Optional[int] = None, quality: bool = False) -> ClassHypotheses:
+                      topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -1765,20 +1949,23 @@ class Cascade(_Base):
         mask_decoder_edge.py:188), from the same decoder pass of each chunk -- MaskDecoder.forward(multi=1): three more one-row-per-
         prompt GEMMs and cvlm_mask_head_multi with one plane, so masks, edges and stage 2 keep their bits and the decoder buffers
         their sizes (`class_chunk()` holds as it is); NaN for a hypothesis whose class is -1.  Nothing is chosen here: the caller
-        ranks.  quality=False makes exactly the launches it made before."""
+        ranks.  quality=False makes exactly the launches it made before.
+        vocab: a run-time vocabulary in place of the constructor's bank: `classes` / `topk` index it, pass 1 and stage 2
+        score against it -- up to 65536 classes, topk <= 64 above 1024."""
         B = int(inp.shape[0])
-        K, host_classes = self._class_request(B, classes, topk)
+        vocab = self._vocab_of(vocab)
+        K, host_classes = self._class_request(B, classes, topk, vocab)
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
-        txt_bank = self.clip.txt["test"]
+        txt_bank = self._bank(vocab)
         n_cls, D = txt_bank.shape
         idx_in = None if host_classes is None else host_classes.to(dev)
-        feats, (img_f, _, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        feats, (img_f, _, _, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask, vocab=vocab), out_name)
         with torch.cuda.stream(tail):
             cls = torch.empty(B, K, dtype=torch.int64, device=dev)
             sel = self.ws.f32("cls_sel", P, D)
-            hip.topk_select(score if idx_in is None else None, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
+            self._select(score, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
             vis, txt = self._project_prompts(img_f, sel, B, P)
             masks = torch.empty(B, K, S, S, device=dev)
             edges = torch.empty(B, K, S, S, device=dev)
@@ -1799,7 +1986,7 @@ class Cascade(_Base):
                 self._per_prompt(vis, K, p0, p1, sp[:, 0])
                 sp[:, 1].copy_(txt[p0:p1])
                 self._mask_logits(fr, sp, n, out=mflat[p0:p1], edge_out=eflat[p0:p1], iou_out=iou.view(P)[p0:p1] if quality else None)
-                self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P))
+                self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab)
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
@@ -1807,24 +1994,29 @@ class Cascade(_Base):
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
-    def encode(self, inp, clip_image, clip_mask) -> EncodedImages:
+    def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
         """Everything `infer_classes` computes before it knows a prompt, kept: `_begin` (mx self-check, `flush()`, fold guard),
         `_stage1` (the SAM encoder with CLIP pass 1 on the side stream under it), then on the tail stream the decoder's image part
         (MaskDecoder.image_part) into tensors of the result's own, `sam_visual_proj` of the B image rows and a copy of
         `clip_image`, then `_end` (the current stream waits for the results before the call returns).  The result owns all its
         tensors and stays valid across any later call on this engine -- other batches, more prompts, pipelined batches.
         Size per image at the demo geometry (T = 4096 tokens, C = 256): edge_feat 16 T (C / 8) f32 = 8 MiB, keys f32 4 MiB, keys'
-        h2 planes 4 MiB, the CLIP image 1.3 MiB and a few rows: about 17.3 MiB."""
+        h2 planes 4 MiB, the CLIP image 1.3 MiB and a few rows: about 17.3 MiB.
+        vocab: pass 1 scores against a run-time vocabulary; the result remembers it (`vocab`) and keeps pass 1's raw
+        image features (`pass1_features`), from which `decode(vocab=)` re-scores pass 1 against any other."""
+        vocab = self._vocab_of(vocab)
         out_name = self._begin(inp, clip_image, clip_mask)
         B = int(inp.shape[0])
-        feats, (img_f, _, pred, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        feats, (img_f, _, pred, score), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask, vocab=vocab), out_name)
         with torch.cuda.stream(tail):
             st = self.decoder.image_state(B, owned=True)
             self.decoder.image_part(feats, self.no_mask, self.gauss, B, st)
             vis = self._project_vis(img_f, B).clone()
             own_image = clip_image.clone()
-        self._end(tail, (inp, clip_image, clip_mask), st.tensors() + (vis, own_image, score, pred))
-        return EncodedImages(state=st, vis=vis, clip_image=own_image, pass1_logits=score, pass1_pred=pred, B=B, engine=self)
+            raw = self.clip.last_features.clone()                    # pass 1's raw image features: decode(vocab=) re-scores them
+        self._end(tail, (inp, clip_image, clip_mask), st.tensors() + (vis, own_image, score, pred, raw))
+        return EncodedImages(state=st, vis=vis, clip_image=own_image, pass1_logits=score, pass1_pred=pred, B=B, engine=self, vocab=vocab,
+                             pass1_features=raw)
 
     def _gather_blocks(self, name: str, src: torch.Tensor, idx: torch.Tensor, n: int, B: int) -> torch.Tensor:
         """src f32 [B][...] -> workspace buffer `name` f32 [n][...] = src[idx] (one cvlm_expand_blocks launch)."""
@@ -1834,7 +2026,7 @@ class Cascade(_Base):
 
     def decode(self, enc: EncodedImages, *, classes: Optional[torch.Tensor] = None, topk: Optional[int] = None,
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
-               stage2: bool = True) -> ClassHypotheses:
+               stage2: bool = True, vocab: Optional[Vocabulary] = None) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -1845,33 +2037,43 @@ class Cascade(_Base):
         stage 2, the fold-guard poll, and per `class_chunk()` prompts MaskDecoder.prompt_part with the prompt -> image map,
         the resize and `_class_stage2` -- all on the caller's stream; `enc` is only read.  No encoder launch, and of CLIP only
         stage 2's.  Bits: those of `infer_classes` on the same inputs when the GEMM row counts match or the K-splits are off,
-        otherwise within the batch tolerance -- the image part ran over B images here and over B * K copies there."""
+        otherwise within the batch tolerance -- the image part ran over B images here and over B * K copies there.
+        vocab: the vocabulary to decode against, default the one `enc` was encoded with (enc.vocab).  Another one first re-scores pass 1
+        from enc.pass1_features against it -- one head launch, no encoder launch, no CLIP forward --; the returned pass1_logits are
+        the re-scored ones."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
-        txt_bank = self.clip.txt["test"]
+        if vocab is None:
+            vocab = enc.vocab
+        if vocab is not None:
+            self._check_vocab(vocab)
+        txt_bank = self._bank(vocab)
         n_cls, D = (int(v) for v in txt_bank.shape)
         images, K, host_classes = decode_request(same_engine=enc.engine is self, B=enc.B, n_cls=n_cls, D=D, classes=classes, topk=topk,
-                                                 text=text, images=images)
+                                                 text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
         n = len(images)
         P, S, C = n * K, g.inp_size, g.prompt_embed_dim
         image_of = torch.tensor([i for i in images for _ in range(K)], dtype=torch.int32).to(dev)
+        pass1 = enc.pass1_logits
+        if vocab is not enc.vocab:                                   # another vocabulary: pass 1 re-scored from the kept features
+            _, _, _, pass1 = self.clip.head(enc.pass1_features, vocab=vocab)
         if images == list(range(B)):
-            clip_image, score = enc.clip_image, enc.pass1_logits
+            clip_image, score = enc.clip_image, pass1
         else:                                                        # the subset's rows first, then as n images
             idx = torch.tensor(images, dtype=torch.int32).to(dev)
             clip_image = self._gather_blocks("dec_clip_image", enc.clip_image, idx, n, B)
             score = torch.empty(n, n_cls, device=dev)
-            hip.expand_blocks(idx, n, B, n_cls, src_f32=enc.pass1_logits, dst_f32=score)
+            hip.expand_blocks(idx, n, B, n_cls, src_f32=pass1, dst_f32=score)
         if text is not None:
             cls, sel = None, text.detach().to(dev).contiguous().view(P, D)
         else:
             cls = torch.empty(n, K, dtype=torch.int64, device=dev)
             sel = self.ws.f32("cls_sel", P, D)
             idx_in = None if host_classes is None else host_classes.to(dev)
-            hip.topk_select(score if idx_in is None else None, n, n_cls, K, txt_bank, D, idx_in, cls, sel)
+            self._select(score, n, n_cls, K, txt_bank, D, idx_in, cls, sel)
         txt = self._project_txt(sel, P)
         masks = torch.empty(n, K, S, S, device=dev)
         edges = torch.empty(n, K, S, S, device=dev)
@@ -1890,17 +2092,17 @@ class Cascade(_Base):
             self._mask_logits((enc.state, of, B), sp, m, out=mflat[p0:p1], edge_out=eflat[p0:p1],
                               iou_out=iou.view(P)[p0:p1] if quality else None)
             if stage2:
-                self._class_stage2(mflat, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P))
+                self._class_stage2(mflat, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab)
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
 
-    def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor):
+    def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""
-        return self.clip.forward(clip_image, self._alpha(mask_logits, "alpha2"))
+        return self.clip.forward(clip_image, self._alpha(mask_logits, "alpha2"), vocab=self._vocab_of(vocab))
 
-    def cascade(self, inp, clip_image, clip_mask, pipelined: bool = False):
+    def cascade(self, inp, clip_image, clip_mask, pipelined: bool = False, vocab: Optional[Vocabulary] = None):
         """Stage 1 + stage 2.  With the side stream enabled only the SAM encoder runs on the caller's stream; CLIP pass
         1, the sparse prompts, the mask decoder (hundreds of launches of a few workgroups each), the resize and stage 2
         run on the side stream.
@@ -1913,14 +2115,17 @@ class Cascade(_Base):
         feeding batches MUST call `flush()`; until then `pred` holds -1 and `logits` NaN (sentinels, never stale data).
         The inputs may be refilled in place as soon as the call has returned: `clip_image` / `clip_mask` are copied (on the
         caller's stream) into buffers the engine owns before anything reads them later."""
+        if pipelined and vocab is not None:                          # a step of the loop scores one vocabulary: the engine's default
+            raise ValueError("cascade(pipelined=True): no per-call vocabulary, set the loop's with use_vocabulary()")
         if pipelined and self.fuse_clip:
             return self._cascade_fused(inp, clip_image, clip_mask)
+        vocab = self._vocab_of(vocab)
         out_name = self._begin(inp, clip_image, clip_mask, alternate=True)
         B = inp.shape[0]
-        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask), out_name)
+        feats, (img_f, txt_f, _, _), tail = self._stage1(inp, lambda: self.clip.forward(clip_image, clip_mask, vocab=vocab), out_name)
         with torch.cuda.stream(tail):
             masks = self._mask_logits(feats, self.sparse_prompts(img_f, txt_f, B), B)
-            _, _, pred, logits = self.stage2(masks, clip_image)
+            _, _, pred, logits = self.stage2(masks, clip_image, vocab)
         self._end(tail, (inp, clip_image, clip_mask), (masks, pred, logits), alternate=True, wait=not pipelined)
         return masks, pred, logits
 
@@ -1933,6 +2138,7 @@ class Cascade(_Base):
         demo.py:117-122."""
         out_name = self._begin(inp, clip_image, clip_mask, flush=False, alternate=True)
         B, R = inp.shape[0], self.c.image_resolution
+        vocab = self._vocab                                          # use_vocabulary's: it flushes, so the owed batch ran with the same one
         prev = self._pending
         # The side stream reads clip_image / clip_mask now (pass 1) and clip_image again one call later (the owed stage 2): keep
         # copies the engine owns, made on the caller's stream, so that a serving loop may refill its input buffers in place
@@ -1947,11 +2153,11 @@ class Cascade(_Base):
         def clip_forwards():
             try:
                 if prev is None:
-                    i_f, t_f, _, _ = self.clip.forward(own_image, own_mask)
+                    i_f, t_f, _, _ = self.clip.forward(own_image, own_mask, vocab=vocab)
                     return i_f, t_f
                 p_masks, p_image, p_pred, p_logits = prev
                 Bp = p_masks.shape[0]
-                img_n, sel, pred_all, logits_all = self.clip.forward([p_image, own_image], [self._alpha(p_masks, "alpha2"), own_mask])
+                img_n, sel, pred_all, logits_all = self.clip.forward([p_image, own_image], [self._alpha(p_masks, "alpha2"), own_mask], vocab=vocab)
                 p_pred.copy_(pred_all[:Bp])                          # results of the previous batch land in the tensors it returned
                 p_logits.copy_(logits_all[:Bp])
                 return img_n[Bp:], sel[Bp:]
@@ -1964,7 +2170,7 @@ class Cascade(_Base):
             masks = self._mask_logits(feats, self.sparse_prompts(img_f, txt_f, B), B)
             # owed until the next call / flush(): sentinels, so that a missing flush() reads as "not computed", never as data
             pred = torch.full((B,), -1, dtype=torch.int64, device=self.device)
-            logits = torch.full((B, self.clip.txt["test"].shape[0]), float("nan"), device=self.device)
+            logits = torch.full((B, self._bank(vocab).shape[0]), float("nan"), device=self.device)
         self._pending, self._pending_stream = (masks, own_image, pred, logits), tail
         self._end(tail, (inp,), (masks, pred, logits), alternate=True, wait=False)
         return masks, pred, logits

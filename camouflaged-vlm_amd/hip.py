@@ -27,6 +27,7 @@ EXPORTS = [
     "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
     "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
     "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan", "cvlm_mask_head_multi", "cvlm_expand_blocks",
+    "cvlm_text_assemble", "cvlm_clip_head_wide_workspace_bytes", "cvlm_clip_head_wide", "cvlm_topk_select_wide",
 ]
 ABI_VERSION = 12
 
@@ -646,6 +647,41 @@ def clip_head(img, txt, logit_scale_exp: float, B: int, Cc: int, D: int, img_n, 
                                  C.c_int32(B), C.c_int32(Cc), C.c_int32(D), C.c_void_p(img_n.data_ptr()),
                                  C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()),
                                  C.c_void_p(txt_sel.data_ptr()), C.c_void_p(_stream())), "cvlm_clip_head")
+
+
+def clip_head_wide_workspace_bytes(P: int, Cc: int) -> int:
+    n = int(load().cvlm_clip_head_wide_workspace_bytes(C.c_int32(P), C.c_int32(Cc)))
+    if n < 0:
+        raise RuntimeError(f"cvlm_clip_head_wide_workspace_bytes: P = {P}, C = {Cc} outside the entry's bounds")
+    return n
+
+
+def clip_head_wide(img, txt, logit_scale_exp: float, P: int, Cc: int, D: int, img_n, logits, pred, txt_sel, workspace: torch.Tensor) -> None:
+    """cvlm_clip_head for up to 65536 classes, tiled over classes (include/cvlm.h); workspace: uint8, at least
+    clip_head_wide_workspace_bytes(P, Cc) bytes."""
+    _check(load().cvlm_clip_head_wide(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), C.c_float(logit_scale_exp),
+                                      C.c_int32(P), C.c_int32(Cc), C.c_int32(D), C.c_void_p(img_n.data_ptr()),
+                                      C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()), C.c_void_p(txt_sel.data_ptr()),
+                                      C.c_void_p(workspace.data_ptr()), C.c_int64(workspace.numel() * workspace.element_size()),
+                                      C.c_void_p(_stream())), "cvlm_clip_head_wide")
+
+
+def topk_select_wide(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, sel) -> None:
+    """topk_select's ranking for up to 65536 classes, K <= 64, under its signature; idx_in must be None (include/cvlm.h)."""
+    _check(load().cvlm_topk_select_wide(C.c_void_p(logits.data_ptr()), C.c_int32(B), C.c_int32(Cc), C.c_int32(K), C.c_void_p(txt.data_ptr()),
+                                        C.c_int32(D), C.c_void_p(_p(idx_in)), C.c_void_p(idx_out.data_ptr()), C.c_void_p(sel.data_ptr()),
+                                        C.c_void_p(_stream())), "cvlm_topk_select_wide")
+
+
+def text_assemble(ids: Optional[torch.Tensor], table: Optional[torch.Tensor], emb: Optional[torch.Tensor], ctx: torch.Tensor,
+                  pos: torch.Tensor, n: int, ctx_len: int, L: int, W: int, out: torch.Tensor) -> None:
+    """out f32 [n][L][W] = [prefix | ctx | suffix] + pos of a vocabulary's prompts, from token ids (int32 [n][ctx_len]) and the
+    embedding table or from embedded prompts f32 [n][ctx_len][W] (include/cvlm.h)."""
+    assert ids is None or (ids.dtype == torch.int32 and ids.is_contiguous())
+    _check(load().cvlm_text_assemble(C.c_void_p(_p(ids)), C.c_void_p(_p(table)), C.c_int32(0 if table is None else int(table.shape[0])),
+                                     C.c_void_p(_p(emb)), C.c_void_p(ctx.data_ptr()), C.c_int32(int(ctx.shape[0])), C.c_void_p(pos.data_ptr()),
+                                     C.c_int32(n), C.c_int32(ctx_len), C.c_int32(L), C.c_int32(W), C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(_stream())), "cvlm_text_assemble")
 
 
 def normalize_add(x, add, R: int, D: int, out) -> None:

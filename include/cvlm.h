@@ -364,6 +364,49 @@ int cvlm_clip_head(const float* img, const float* txt, float logit_scale_exp, in
 int cvlm_topk_select(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
                      int64_t* idx_out, float* sel, void* stream);
 
+/* ---- Class vocabularies at run time.  Three entries beside the ones above; none of those changes (ABI 12 stays). ----
+ *
+ * Prompt assembly of a vocabulary (cocotrainers/mapleAlphaCLIP.py:132-168, 210-227: prompts = [prefix | ctx | suffix] with prefix /
+ * suffix cut from token_embedding(tokenized_prompts), then `prompts + positional_embedding`, :66):
+ *   out[i][t] = (1 <= t <= n_ctx ? ctx[t - 1] : src(i, t)) + pos[t]     for i in [0, n), t in [0, L),
+ * src(i, t) = table[ids[i * ctx_len + t]] (ids int32 [n][ctx_len], table f32 [V][W]) or emb[i][t] (emb f32 [n][ctx_len][W]); exactly
+ * one of ids / emb is given.  ctx f32 [n_ctx][W], pos f32 [>= L][W], out f32 [n][L][W].  One f32 add per element -- the add
+ * cvlm_add_rows performs in ClipModel.text_features: the same bits as concatenating the rows and adding the positions.  Whole rows
+ * are gathered with 16-byte loads, offsets are 64-bit.  The ids are the caller's contract (engine.vocabulary_request validates them on
+ * the host): nothing on the device checks them.
+ * CVLM_E_BADARG, before anything touches the device: both or neither of ids / emb, ids without table or V <= 0, a NULL ctx / pos /
+ * out, n, ctx_len, L or W <= 0, W % 4 != 0, L > ctx_len, n_ctx < 0 or n_ctx >= ctx_len, n * L * W * 4 >= 2^31. */
+int cvlm_text_assemble(const int32_t* ids, const float* table, int32_t V, const float* emb, const float* ctx, int32_t n_ctx,
+                       const float* pos, int32_t n, int32_t ctx_len, int32_t L, int32_t W, float* out, void* stream);
+
+/* cvlm_clip_head (cocotrainers/mapleAlphaCLIP.py:289-294) for up to 65536 classes.  Same inputs and outputs, P image rows.
+ * The grid is tiled over CLASSES (4 to 32 per workgroup, one to eight per wave: C / 1024, so that C = 1024 already gives 256
+ * workgroups) and image groups (16 per workgroup): a text row is fetched once per group of 16 images and held in registers while
+ * the group's image rows -- scaled once, in LDS -- pass it.  Each logit is formed with
+ * cvlm_clip_head's arithmetic (pr = logit_scale_exp * (x[d] / nrm); the lane-strided products d = lane + 64 k added in ascending
+ * k; the butterfly wave sum; nrm from the same 256-thread reduction): logits and img_n carry cvlm_clip_head's bits wherever that
+ * entry runs its register path (D <= 1024).  pred is what the sequential strict-`>` scan from class 0 gives -- the lowest index
+ * among equal maxima; a NaN is selected only where it stands at class 0; an all-NaN row gives 0 -- in two steps without atomics:
+ * every class tile leaves (value, index, whether a non-NaN exists) of its own scan in `workspace`, a second kernel combines the
+ * tiles in ascending order and copies txt_sel = txt[pred].
+ * workspace: cvlm_clip_head_wide_workspace_bytes(P, C) bytes, 16-byte aligned; contents need no initialisation.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer, P <= 0 or P > 65535, C outside [1, 65536], D <= 0,
+ * D % 4 != 0 or D > 1024, workspace_bytes too small.  cvlm_clip_head_wide_workspace_bytes: -1 for sizes outside those bounds. */
+int64_t cvlm_clip_head_wide_workspace_bytes(int32_t P, int32_t C);
+int cvlm_clip_head_wide(const float* img, const float* txt, float logit_scale_exp, int32_t P, int32_t C, int32_t D, float* img_n,
+                        float* logits, int64_t* pred, float* txt_sel, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cvlm_topk_select's ranking for 1024 < C <= 65536 classes, 1 <= K <= 64, under cvlm_topk_select's signature (idx_in must be NULL:
+ * gather-only calls keep using that entry, which takes any C): idx_out[b] = the K largest logits of
+ * row b, descending, ties to the lower index; a row holding a NaN gets -1 in every slot and NaN sel rows; on a finite row
+ * idx_out[b][0] equals cvlm_clip_head_wide's pred; sel[b][k] = txt[idx_out[b][k]] bit for bit.  One 256-thread block per row, K
+ * rounds of a block-wide (value, index) argmax over the classes below the previous winner in that order -- the row stays in
+ * memory (L2), no LDS row.
+ * CVLM_E_BADARG: a NULL logits / txt / idx_out / sel, a non-NULL idx_in, B, K or D <= 0, D % 4 != 0, C outside [1, 65536], K > 64
+ * or K > C. */
+int cvlm_topk_select_wide(const float* logits, int32_t B, int32_t C, int32_t K, const float* txt, int32_t D, const int64_t* idx_in,
+                          int64_t* idx_out, float* sel, void* stream);
+
 /* Per-image blocks expanded to per-prompt blocks (the reference's repeat_interleave of the image embedding over the prompts,
  * mask_decoder_edge.py:150-158, for any prompt -> image map): dst[p] = src[image_of[p]] for p in [0, P), blocks of block_elems
  * contiguous elements drawn from B source blocks.  image_of int32 [P] on the device, every entry in [0, B): the caller's contract
