@@ -18,17 +18,52 @@ LIB_PATH = os.path.join(_PKG, "lib", "libcvlm_hip.so")
 
 ACT_NONE, ACT_GELU, ACT_QUICKGELU, ACT_RELU, ACT_ABS_POST = 0, 1, 2, 3, 4
 
-EXPORTS = [
-    "cvlm_abi_version", "cvlm_target_arch", "cvlm_gemm", "cvlm_layernorm", "cvlm_add_rows", "cvlm_split_f32",
-    "cvlm_patchify", "cvlm_im2col3x3", "cvlm_reinterpret_transpose", "cvlm_attention", "cvlm_small_attention",
-    "cvlm_dense_pe", "cvlm_mask_head", "cvlm_bilinear", "cvlm_clip_assemble", "cvlm_overwrite_rows",
-    "cvlm_gather_rows", "cvlm_clip_head", "cvlm_normalize_add", "cvlm_resample_u8", "cvlm_u8_to_tensor",
-    "cvlm_mask_to_u8", "cvlm_mask_joint_hist", "cvlm_mask_wfm", "cvlm_topk_accumulate",
-    "cvlm_gemm_workspace_bytes", "cvlm_attention_workspace_bytes", "cvlm_row_stats_split", "cvlm_row_stats_split_mx", "cvlm_gather_rows_h2",
-    "cvlm_ln_stats_merge", "cvlm_small_attention_h2", "cvlm_prob_quantise", "cvlm_prob_moments", "cvlm_prob_wfm",
-    "cvlm_mask_head_edge", "cvlm_topk_select", "cvlm_debug_gemm_plan", "cvlm_mask_head_multi", "cvlm_expand_blocks",
-    "cvlm_text_assemble", "cvlm_clip_head_wide_workspace_bytes", "cvlm_clip_head_wide", "cvlm_topk_select_wide",
-]
+# The C ABI of include/cvlm.h, one line per function: "<return>:<parameters>", one letter per type -- i int / int32_t, l int64_t, f float,
+# p a data pointer, G / A / I a pointer to GemmArgs / AttnArgs / GemmPlanInfo, z const char* -- and a final s for `void* stream`, which
+# `_call` supplies.  tests/test_host_cpu.py holds every line against the header's prototype.
+_SIGNATURES = {
+    "cvlm_abi_version": "i:", "cvlm_target_arch": "z:",
+    "cvlm_gemm": "i:Gs", "cvlm_gemm_workspace_bytes": "l:", "cvlm_debug_gemm_plan": "i:GiiI",
+    "cvlm_layernorm": "i:plpipppfipppiis",
+    "cvlm_add_rows": "i:ppifpppiis",
+    "cvlm_ln_stats_merge": "i:pliifpps",
+    "cvlm_row_stats_split": "i:pfpppliiils",
+    "cvlm_row_stats_split_mx": "i:pfplplplpliiils",
+    "cvlm_split_f32": "i:pppls",
+    "cvlm_patchify": "i:pipiiiiippis",
+    "cvlm_im2col3x3": "i:piiiipps",
+    "cvlm_reinterpret_transpose": "i:piiifpps",
+    "cvlm_attention": "i:As", "cvlm_attention_workspace_bytes": "l:A",
+    "cvlm_small_attention": "i:plplplpliiiiis",
+    "cvlm_small_attention_h2": "i:plplplplppliiiiis",
+    "cvlm_dense_pe": "i:piips",
+    "cvlm_mask_head": "i:pppiiips",
+    "cvlm_mask_head_edge": "i:pppiiipps",
+    "cvlm_mask_head_multi": "i:pppiiiipps",
+    "cvlm_bilinear": "i:piiipiiis",
+    "cvlm_clip_assemble": "i:ppppiiiips",
+    "cvlm_overwrite_rows": "i:piiiiips",
+    "cvlm_gather_rows": "i:piiipips",
+    "cvlm_gather_rows_h2": "i:ppfiiipips",
+    "cvlm_clip_head": "i:ppfiiipppps",
+    "cvlm_topk_select": "i:piiipippps",
+    "cvlm_text_assemble": "i:ppippipiiiips",
+    "cvlm_clip_head_wide_workspace_bytes": "l:ii",
+    "cvlm_clip_head_wide": "i:ppfiiipppppls",
+    "cvlm_topk_select_wide": "i:piiipippps",
+    "cvlm_expand_blocks": "i:piilpppppps",
+    "cvlm_normalize_add": "i:ppiips",
+    "cvlm_resample_u8": "i:piiiippiiips",
+    "cvlm_u8_to_tensor": "i:piiiiiiiippps",
+    "cvlm_mask_to_u8": "i:piiiiips",
+    "cvlm_mask_joint_hist": "i:ppiiipps",
+    "cvlm_mask_wfm": "i:ppiiipppps",
+    "cvlm_prob_quantise": "i:piiippps",
+    "cvlm_prob_moments": "i:ppiiipppps",
+    "cvlm_prob_wfm": "i:ppiiipppps",
+    "cvlm_topk_accumulate": "i:ppiipps",
+}
+EXPORTS = list(_SIGNATURES)
 ABI_VERSION = 12
 
 
@@ -81,6 +116,11 @@ class AttnArgs(C.Structure):
     ]
 
 
+_CTYPES = {"i": C.c_int32, "l": C.c_int64, "f": C.c_float, "p": C.c_void_p, "s": C.c_void_p, "z": C.c_char_p,
+           "G": C.POINTER(GemmArgs), "A": C.POINTER(AttnArgs), "I": C.POINTER(GemmPlanInfo)}
+ABI = {name: (_CTYPES[sig[0]], [_CTYPES[c] for c in sig[2:]]) for name, sig in _SIGNATURES.items()}    # name -> (restype, argtypes)
+_STREAMED = frozenset(name for name, sig in _SIGNATURES.items() if sig.endswith("s"))
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -95,10 +135,9 @@ def load() -> C.CDLL:
             f"{path} is missing: the HIP kernels are the only compute path of this package. "
             "Build them with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
     lib = C.CDLL(path)
-    lib.cvlm_abi_version.restype = C.c_int
-    lib.cvlm_target_arch.restype = C.c_char_p
-    for name in EXPORTS[2:]:
-        getattr(lib, name).restype = C.c_int64 if name.endswith("_workspace_bytes") else C.c_int
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.cvlm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI {lib.cvlm_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -114,8 +153,19 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _planes(x: Optional["H2"]) -> Tuple[Optional[int], Optional[int]]:
+    return (None, None) if x is None else (x.hi.data_ptr(), x.lo.data_ptr())
+
+
 def _stream() -> Optional[int]:
     return torch.cuda.current_stream().cuda_stream or None
+
+
+def _call(name: str, *args) -> None:
+    """One call of the entry `name` with plain Python values (ints, floats, None for NULL, a struct for a struct pointer: `ABI` holds
+    the C types); the current stream is appended where the entry takes one.  Raises on a non-zero return code."""
+    fn = getattr(load(), name)
+    _check(fn(*args, _stream()) if name in _STREAMED else fn(*args), name)
 
 
 def _on_current_device(t: torch.Tensor) -> None:
@@ -127,7 +177,7 @@ def _on_current_device(t: torch.Tensor) -> None:
 
 
 def gemm_workspace_bytes() -> int:
-    return int(load().cvlm_gemm_workspace_bytes())
+    return load().cvlm_gemm_workspace_bytes()
 
 
 def new_gemm_workspace(device) -> torch.Tensor:
@@ -399,7 +449,7 @@ def gemm_args(a: H2, w: H2, M: int, N: int, K: int, *, lda: Optional[int] = None
 @functools.wraps(gemm_args, assigned=("__doc__",))                 # help(), inspect.signature and editors show the parameter list above
 def gemm(a: H2, w: H2, M: int, N: int, K: int, **kw) -> None:
     _on_current_device(a.t)
-    _check(load().cvlm_gemm(C.byref(gemm_args(a, w, M, N, K, **kw)), C.c_void_p(_stream())), "cvlm_gemm")
+    _call("cvlm_gemm", gemm_args(a, w, M, N, K, **kw))
 
 
 def gemm_plan(a: H2, w: H2, M: int, N: int, K: int, *, cus: int = 256, **kw) -> list:
@@ -407,7 +457,7 @@ def gemm_plan(a: H2, w: H2, M: int, N: int, K: int, *, cus: int = 256, **kw) -> 
     is needed): one dict per launch -- kernel instantiation, grid, LDS bytes and the GemmParams fields csrc/gemm_plan.h chose."""
     g, info = gemm_args(a, w, M, N, K, **kw), GemmPlanInfo()
     have_ws = bool(g.workspace) and g.workspace_bytes >= gemm_workspace_bytes()
-    _check(load().cvlm_debug_gemm_plan(C.byref(g), int(have_ws), cus, C.byref(info)), "cvlm_debug_gemm_plan")
+    _call("cvlm_debug_gemm_plan", g, int(have_ws), cus, info)
     return [dict({n: getattr(l, n) for n, _ in GemmLaunchInfo._fields_[:-1]}, kernel=l.kernel.decode())
             for l in info.launch[:info.launches]]
 
@@ -416,20 +466,13 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
               ldx: Optional[int] = None, add: Optional[torch.Tensor] = None, add_rows: int = 0,
               sum_out: Optional[torch.Tensor] = None, act: int = ACT_NONE, out_f32: Optional[torch.Tensor] = None,
               out_h2: Optional[H2] = None) -> None:
-    _check(load().cvlm_layernorm(
-        C.c_void_p(x.data_ptr()), C.c_int64(ldx if ldx is not None else D), C.c_void_p(_p(add)), C.c_int32(add_rows),
-        C.c_void_p(_p(sum_out)), C.c_void_p(gamma.data_ptr()), C.c_void_p(beta.data_ptr()), C.c_float(eps),
-        C.c_int32(act), C.c_void_p(_p(out_f32)), C.c_void_p(out_h2.hi.data_ptr() if out_h2 else None),
-        C.c_void_p(out_h2.lo.data_ptr() if out_h2 else None), C.c_int32(M), C.c_int32(D), C.c_void_p(_stream())),
-        "cvlm_layernorm")
+    _call("cvlm_layernorm", x.data_ptr(), ldx if ldx is not None else D, _p(add), add_rows, _p(sum_out), gamma.data_ptr(),
+          beta.data_ptr(), eps, act, _p(out_f32), *_planes(out_h2), M, D)
 
 
 def add_rows(a: torch.Tensor, b: Optional[torch.Tensor], b_rows: int, M: int, D: int, *, scale: float = 1.0,
              out_f32: Optional[torch.Tensor] = None, out_h2: Optional[H2] = None) -> None:
-    _check(load().cvlm_add_rows(
-        C.c_void_p(a.data_ptr()), C.c_void_p(_p(b)), C.c_int32(b_rows), C.c_float(scale), C.c_void_p(_p(out_f32)),
-        C.c_void_p(out_h2.hi.data_ptr() if out_h2 else None), C.c_void_p(out_h2.lo.data_ptr() if out_h2 else None),
-        C.c_int32(M), C.c_int32(D), C.c_void_p(_stream())), "cvlm_add_rows")
+    _call("cvlm_add_rows", a.data_ptr(), _p(b), b_rows, scale, _p(out_f32), *_planes(out_h2), M, D)
 
 
 def stats_pieces(D: int) -> int:
@@ -443,9 +486,7 @@ def ln_stats_merge(pieces: torch.Tensor, M: int, D: int, eps: float, merged: tor
     what `gemm(ln_fold=...)` reads.  workspace: a cvlm_gemm workspace whose error word counts refused rows."""
     assert pieces.dim() == 3 and pieces.shape[0] == stats_pieces(D) and pieces.shape[1] >= M and pieces.is_contiguous()
     assert tuple(merged.shape) == (M, 2) and merged.is_contiguous()
-    _check(load().cvlm_ln_stats_merge(C.c_void_p(pieces.data_ptr()), C.c_int64(pieces.shape[1]), C.c_int32(M), C.c_int32(D),
-                                      C.c_float(eps), C.c_void_p(merged.data_ptr()), C.c_void_p(_p(workspace)),
-                                      C.c_void_p(_stream())), "cvlm_ln_stats_merge")
+    _call("cvlm_ln_stats_merge", pieces.data_ptr(), pieces.shape[1], M, D, eps, merged.data_ptr(), _p(workspace))
 
 
 def row_stats_split(x: torch.Tensor, scale: float, out: H2, stats: torch.Tensor, M: int, D: int, *, row0: int = 0,
@@ -455,44 +496,30 @@ def row_stats_split(x: torch.Tensor, scale: float, out: H2, stats: torch.Tensor,
     assert stats.dim() == 3 and stats.shape[0] == stats_pieces(D) and stats.shape[2] == 2 and stats.is_contiguous()
     if getattr(out, "mx", False):                                     # the rows as an mx operand (image + block exponents + lo plane), ABI 10
         assert out.lo is not None and out.c0 == 0 and out.C == D
-        _check(load().cvlm_row_stats_split_mx(
-            C.c_void_p(x.data_ptr()), C.c_float(scale), C.c_void_p(out.t.data_ptr() + row0 * out.t.stride(0)), C.c_int64(out.t.stride(0) // 2),
-            C.c_void_p(out.s.data_ptr() + row0 * out.s.stride(0)), C.c_int64(out.s.stride(1)),
-            C.c_void_p(out.lo.data_ptr() + 2 * row0 * out.lo.stride(0)), C.c_int64(out.lo.stride(0)), C.c_void_p(stats.data_ptr() + 8 * row0),
-            C.c_int64(stats.shape[1]), C.c_int32(M), C.c_int32(D), C.c_int32(copies), C.c_int64(dst_row_stride), C.c_void_p(_stream())),
-            "cvlm_row_stats_split_mx")
+        _call("cvlm_row_stats_split_mx", x.data_ptr(), scale, out.t.data_ptr() + row0 * out.t.stride(0), out.t.stride(0) // 2,
+              out.s.data_ptr() + row0 * out.s.stride(0), out.s.stride(1), out.lo.data_ptr() + 2 * row0 * out.lo.stride(0),
+              out.lo.stride(0), stats.data_ptr() + 8 * row0, stats.shape[1], M, D, copies, dst_row_stride)
         return
-    _check(load().cvlm_row_stats_split(C.c_void_p(x.data_ptr()), C.c_float(scale), C.c_void_p(out.hi.data_ptr() + 2 * row0 * D),
-                                       C.c_void_p(out.lo.data_ptr() + 2 * row0 * D), C.c_void_p(stats.data_ptr() + 8 * row0),
-                                       C.c_int64(stats.shape[1]), C.c_int32(M), C.c_int32(D), C.c_int32(copies),
-                                       C.c_int64(dst_row_stride), C.c_void_p(_stream())), "cvlm_row_stats_split")
+    _call("cvlm_row_stats_split", x.data_ptr(), scale, out.hi.data_ptr() + 2 * row0 * D, out.lo.data_ptr() + 2 * row0 * D,
+          stats.data_ptr() + 8 * row0, stats.shape[1], M, D, copies, dst_row_stride)
 
 
 def split_f32(x: torch.Tensor, out: H2) -> None:
-    _check(load().cvlm_split_f32(C.c_void_p(x.data_ptr()), C.c_void_p(out.hi.data_ptr()),
-                                 C.c_void_p(out.lo.data_ptr()), C.c_int64(x.numel()), C.c_void_p(_stream())),
-           "cvlm_split_f32")
+    _call("cvlm_split_f32", x.data_ptr(), *_planes(out), x.numel())
 
 
 def patchify(src0: torch.Tensor, src1: Optional[torch.Tensor], p: int, out: H2, ldk: int) -> None:
     B, C0, H, W = src0.shape
     C1 = 0 if src1 is None else src1.shape[1]
-    _check(load().cvlm_patchify(
-        C.c_void_p(src0.data_ptr()), C.c_int32(C0), C.c_void_p(_p(src1)), C.c_int32(C1), C.c_int32(B), C.c_int32(H),
-        C.c_int32(W), C.c_int32(p), C.c_void_p(out.hi.data_ptr()), C.c_void_p(out.lo.data_ptr()), C.c_int32(ldk),
-        C.c_void_p(_stream())), "cvlm_patchify")
+    _call("cvlm_patchify", src0.data_ptr(), C0, _p(src1), C1, B, H, W, p, *_planes(out), ldk)
 
 
 def im2col3x3(x: torch.Tensor, B: int, H: int, W: int, Cc: int, out: H2) -> None:
-    _check(load().cvlm_im2col3x3(C.c_void_p(x.data_ptr()), C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cc),
-                                 C.c_void_p(out.hi.data_ptr()), C.c_void_p(out.lo.data_ptr()), C.c_void_p(_stream())),
-           "cvlm_im2col3x3")
+    _call("cvlm_im2col3x3", x.data_ptr(), B, H, W, Cc, *_planes(out))
 
 
 def reinterpret_transpose(x: torch.Tensor, B: int, T: int, D: int, out: H2, scale: float = 1.0) -> None:
-    _check(load().cvlm_reinterpret_transpose(C.c_void_p(x.data_ptr()), C.c_int32(B), C.c_int32(T), C.c_int32(D),
-                                             C.c_float(scale), C.c_void_p(out.hi.data_ptr()), C.c_void_p(out.lo.data_ptr()),
-                                             C.c_void_p(_stream())), "cvlm_reinterpret_transpose")
+    _call("cvlm_reinterpret_transpose", x.data_ptr(), B, T, D, scale, *_planes(out))
 
 
 def attention(qkv: H2, out: H2, B: int, S: int, heads: int, hd: int, *, mode: int = 0, grid: int = 0, window: int = 0,
@@ -517,12 +544,12 @@ def attention(qkv: H2, out: H2, B: int, S: int, heads: int, hd: int, *, mode: in
     a.scale = float(hd) ** -0.5 if scale is None else scale
     a.qkv_layout = int(head_major)
     a.q_rows = q_rows
-    need = int(load().cvlm_attention_workspace_bytes(C.byref(a)))
+    need = load().cvlm_attention_workspace_bytes(a)
     if need > 0:
         if workspace is None or workspace.numel() * workspace.element_size() < need:
             workspace = torch.empty(need, dtype=torch.uint8, device=qkv.t.device)
         a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    _check(load().cvlm_attention(C.byref(a), C.c_void_p(_stream())), "cvlm_attention")
+    _call("cvlm_attention", a)
 
 
 def attention_reads_k_lo(mode: int, grid: int, window: int, hd: int, split_qk: int, split_pv: int, out_lo: bool = True) -> bool:
@@ -546,7 +573,7 @@ def attention_workspace_bytes(B: int, S: int, heads: int, hd: int, *, mode: int 
     """Bytes of caller-owned scratch cvlm_attention wants for these arguments (0 for most modes)."""
     a = AttnArgs()
     a.B, a.S, a.heads, a.hd, a.mode, a.grid, a.split_qk, a.split_pv = B, S, heads, hd, mode, grid, split_qk, split_pv
-    return int(load().cvlm_attention_workspace_bytes(C.byref(a)))
+    return load().cvlm_attention_workspace_bytes(a)
 
 
 def small_attention(q, k, v, out, B: int, nq: int, nk: int, heads: int, hd: int, out_h2: Optional[H2] = None) -> None:
@@ -556,45 +583,33 @@ def small_attention(q, k, v, out, B: int, nq: int, nk: int, heads: int, hd: int,
     pitch = lambda t: t.stride(-2) if t.dim() >= 2 else ld
     for t in (q, k, v):
         assert t.dtype == torch.float32 and t.stride(-1) == 1
-    _check(load().cvlm_small_attention_h2(
-        C.c_void_p(q.data_ptr()), C.c_int64(pitch(q)), C.c_void_p(k.data_ptr()), C.c_int64(pitch(k)), C.c_void_p(v.data_ptr()),
-        C.c_int64(pitch(v)), C.c_void_p(_p(out)), C.c_int64(ld), C.c_void_p(out_h2.hi.data_ptr() if out_h2 is not None else None),
-        C.c_void_p(out_h2.lo.data_ptr() if out_h2 is not None else None), C.c_int64(ld), C.c_int32(B), C.c_int32(nq), C.c_int32(nk),
-        C.c_int32(heads), C.c_int32(hd), C.c_void_p(_stream())), "cvlm_small_attention_h2")
+    _call("cvlm_small_attention_h2", q.data_ptr(), pitch(q), k.data_ptr(), pitch(k), v.data_ptr(), pitch(v), _p(out), ld,
+          *_planes(out_h2), ld, B, nq, nk, heads, hd)
 
 
 def dense_pe(gauss: torch.Tensor, size: int, Cc: int, out: torch.Tensor) -> None:
-    _check(load().cvlm_dense_pe(C.c_void_p(gauss.data_ptr()), C.c_int32(size), C.c_int32(Cc),
-                                C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), "cvlm_dense_pe")
+    _call("cvlm_dense_pe", gauss.data_ptr(), size, Cc, out.data_ptr())
 
 
 def mask_head(up, edge_emb, hyper, B: int, HW: int, Cc: int, low) -> None:
-    _check(load().cvlm_mask_head(C.c_void_p(up.data_ptr()), C.c_void_p(_p(edge_emb)),
-                                 C.c_void_p(hyper.data_ptr()), C.c_int32(B), C.c_int32(HW), C.c_int32(Cc),
-                                 C.c_void_p(low.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_head")
+    _call("cvlm_mask_head", up.data_ptr(), _p(edge_emb), hyper.data_ptr(), B, HW, Cc, low.data_ptr())
 
 
 def mask_head_edge(up, edge_emb, hyper, P: int, HW: int, Cc: int, low, edge_prob) -> None:
     """cvlm_mask_head for P prompts, also writing the edge probabilities edge_prob f32 [P][HW]."""
-    _check(load().cvlm_mask_head_edge(C.c_void_p(up.data_ptr()), C.c_void_p(edge_emb.data_ptr()), C.c_void_p(hyper.data_ptr()),
-                                      C.c_int32(P), C.c_int32(HW), C.c_int32(Cc), C.c_void_p(low.data_ptr()),
-                                      C.c_void_p(edge_prob.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_head_edge")
+    _call("cvlm_mask_head_edge", up.data_ptr(), edge_emb.data_ptr(), hyper.data_ptr(), P, HW, Cc, low.data_ptr(), edge_prob.data_ptr())
 
 
 def mask_head_multi(up, edge_emb, hyper, P: int, HW: int, Cc: int, n_masks: int, low, edge_prob=None) -> None:
     """low f32 [P][n_masks][HW] = masks 0..n_masks-1 of P prompts from one pass over up / edge_emb; edge_prob f32 [P][HW] (optional);
     edge_emb None: the plain hypernetwork products (include/cvlm.h)."""
-    _check(load().cvlm_mask_head_multi(C.c_void_p(up.data_ptr()), C.c_void_p(_p(edge_emb)), C.c_void_p(hyper.data_ptr()),
-                                       C.c_int32(P), C.c_int32(HW), C.c_int32(Cc), C.c_int32(n_masks), C.c_void_p(low.data_ptr()),
-                                       C.c_void_p(_p(edge_prob)), C.c_void_p(_stream())), "cvlm_mask_head_multi")
+    _call("cvlm_mask_head_multi", up.data_ptr(), _p(edge_emb), hyper.data_ptr(), P, HW, Cc, n_masks, low.data_ptr(), _p(edge_prob))
 
 
 def topk_select(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, sel) -> None:
     """idx_out int64 [B][K] = the K largest logits per row, descending, ties to the lower index (or idx_in when given:
     gather only); sel f32 [B][K][D] = txt[idx_out] (include/cvlm.h)."""
-    _check(load().cvlm_topk_select(C.c_void_p(_p(logits)), C.c_int32(B), C.c_int32(Cc), C.c_int32(K), C.c_void_p(txt.data_ptr()),
-                                   C.c_int32(D), C.c_void_p(_p(idx_in)), C.c_void_p(idx_out.data_ptr()), C.c_void_p(sel.data_ptr()),
-                                   C.c_void_p(_stream())), "cvlm_topk_select")
+    _call("cvlm_topk_select", _p(logits), B, Cc, K, txt.data_ptr(), D, _p(idx_in), idx_out.data_ptr(), sel.data_ptr())
 
 
 def expand_blocks(image_of: torch.Tensor, P: int, B: int, block_elems: int, *, src_f32: Optional[torch.Tensor] = None,
@@ -603,54 +618,37 @@ def expand_blocks(image_of: torch.Tensor, P: int, B: int, block_elems: int, *, s
     planes) or both in one launch, bit for bit (include/cvlm.h).  image_of int32 [P] on the device, entries in [0, B): the caller's
     contract."""
     assert image_of.dtype == torch.int32 and image_of.is_contiguous() and image_of.numel() >= P
-    _check(load().cvlm_expand_blocks(
-        C.c_void_p(image_of.data_ptr()), C.c_int32(P), C.c_int32(B), C.c_int64(block_elems), C.c_void_p(_p(src_f32)), C.c_void_p(_p(dst_f32)),
-        C.c_void_p(src_h2.hi.data_ptr() if src_h2 is not None else None), C.c_void_p(src_h2.lo.data_ptr() if src_h2 is not None else None),
-        C.c_void_p(dst_h2.hi.data_ptr() if dst_h2 is not None else None), C.c_void_p(dst_h2.lo.data_ptr() if dst_h2 is not None else None),
-        C.c_void_p(_stream())), "cvlm_expand_blocks")
+    _call("cvlm_expand_blocks", image_of.data_ptr(), P, B, block_elems, _p(src_f32), _p(dst_f32), *_planes(src_h2), *_planes(dst_h2))
 
 
 def bilinear(x, N: int, hin: int, win: int, out, hout: int, wout: int, sigmoid_in: bool = False) -> None:
-    _check(load().cvlm_bilinear(C.c_void_p(x.data_ptr()), C.c_int32(N), C.c_int32(hin), C.c_int32(win),
-                                C.c_void_p(out.data_ptr()), C.c_int32(hout), C.c_int32(wout),
-                                C.c_int32(int(sigmoid_in)), C.c_void_p(_stream())), "cvlm_bilinear")
+    _call("cvlm_bilinear", x.data_ptr(), N, hin, win, out.data_ptr(), hout, wout, int(sigmoid_in))
 
 
 def clip_assemble(patches, cls, pos, ctx, B: int, P: int, W: int, nctx: int, out) -> None:
-    _check(load().cvlm_clip_assemble(C.c_void_p(patches.data_ptr()), C.c_void_p(cls.data_ptr()),
-                                     C.c_void_p(pos.data_ptr()), C.c_void_p(ctx.data_ptr()), C.c_int32(B),
-                                     C.c_int32(P), C.c_int32(W), C.c_int32(nctx), C.c_void_p(out.data_ptr()),
-                                     C.c_void_p(_stream())), "cvlm_clip_assemble")
+    _call("cvlm_clip_assemble", patches.data_ptr(), cls.data_ptr(), pos.data_ptr(), ctx.data_ptr(), B, P, W, nctx, out.data_ptr())
 
 
 def overwrite_rows(x, B: int, L: int, W: int, first: int, n: int, src) -> None:
-    _check(load().cvlm_overwrite_rows(C.c_void_p(x.data_ptr()), C.c_int32(B), C.c_int32(L), C.c_int32(W),
-                                      C.c_int32(first), C.c_int32(n), C.c_void_p(src.data_ptr()),
-                                      C.c_void_p(_stream())), "cvlm_overwrite_rows")
+    _call("cvlm_overwrite_rows", x.data_ptr(), B, L, W, first, n, src.data_ptr())
 
 
 def gather_rows_h2(x: H2, scale: float, B: int, L: int, W: int, idx, fixed: int, out) -> None:
     """out[b] = (hi + lo)[b][idx[b] or fixed] * scale: one row per sequence of an h2 stream [B][L][W] as f32."""
-    _check(load().cvlm_gather_rows_h2(C.c_void_p(x.hi.data_ptr()), C.c_void_p(x.lo.data_ptr()), C.c_float(scale), C.c_int32(B),
-                                      C.c_int32(L), C.c_int32(W), C.c_void_p(_p(idx)), C.c_int32(fixed),
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), "cvlm_gather_rows_h2")
+    _call("cvlm_gather_rows_h2", *_planes(x), scale, B, L, W, _p(idx), fixed, out.data_ptr())
 
 
 def gather_rows(x, B: int, L: int, W: int, idx, fixed: int, out) -> None:
-    _check(load().cvlm_gather_rows(C.c_void_p(x.data_ptr()), C.c_int32(B), C.c_int32(L), C.c_int32(W),
-                                   C.c_void_p(_p(idx)), C.c_int32(fixed), C.c_void_p(out.data_ptr()),
-                                   C.c_void_p(_stream())), "cvlm_gather_rows")
+    _call("cvlm_gather_rows", x.data_ptr(), B, L, W, _p(idx), fixed, out.data_ptr())
 
 
 def clip_head(img, txt, logit_scale_exp: float, B: int, Cc: int, D: int, img_n, logits, pred, txt_sel) -> None:
-    _check(load().cvlm_clip_head(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), C.c_float(logit_scale_exp),
-                                 C.c_int32(B), C.c_int32(Cc), C.c_int32(D), C.c_void_p(img_n.data_ptr()),
-                                 C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()),
-                                 C.c_void_p(txt_sel.data_ptr()), C.c_void_p(_stream())), "cvlm_clip_head")
+    _call("cvlm_clip_head", img.data_ptr(), txt.data_ptr(), logit_scale_exp, B, Cc, D, img_n.data_ptr(), logits.data_ptr(),
+          pred.data_ptr(), txt_sel.data_ptr())
 
 
 def clip_head_wide_workspace_bytes(P: int, Cc: int) -> int:
-    n = int(load().cvlm_clip_head_wide_workspace_bytes(C.c_int32(P), C.c_int32(Cc)))
+    n = load().cvlm_clip_head_wide_workspace_bytes(P, Cc)
     if n < 0:
         raise RuntimeError(f"cvlm_clip_head_wide_workspace_bytes: P = {P}, C = {Cc} outside the entry's bounds")
     return n
@@ -659,18 +657,13 @@ def clip_head_wide_workspace_bytes(P: int, Cc: int) -> int:
 def clip_head_wide(img, txt, logit_scale_exp: float, P: int, Cc: int, D: int, img_n, logits, pred, txt_sel, workspace: torch.Tensor) -> None:
     """cvlm_clip_head for up to 65536 classes, tiled over classes (include/cvlm.h); workspace: uint8, at least
     clip_head_wide_workspace_bytes(P, Cc) bytes."""
-    _check(load().cvlm_clip_head_wide(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), C.c_float(logit_scale_exp),
-                                      C.c_int32(P), C.c_int32(Cc), C.c_int32(D), C.c_void_p(img_n.data_ptr()),
-                                      C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()), C.c_void_p(txt_sel.data_ptr()),
-                                      C.c_void_p(workspace.data_ptr()), C.c_int64(workspace.numel() * workspace.element_size()),
-                                      C.c_void_p(_stream())), "cvlm_clip_head_wide")
+    _call("cvlm_clip_head_wide", img.data_ptr(), txt.data_ptr(), logit_scale_exp, P, Cc, D, img_n.data_ptr(), logits.data_ptr(),
+          pred.data_ptr(), txt_sel.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size())
 
 
 def topk_select_wide(logits, B: int, Cc: int, K: int, txt, D: int, idx_in, idx_out, sel) -> None:
     """topk_select's ranking for up to 65536 classes, K <= 64, under its signature; idx_in must be None (include/cvlm.h)."""
-    _check(load().cvlm_topk_select_wide(C.c_void_p(logits.data_ptr()), C.c_int32(B), C.c_int32(Cc), C.c_int32(K), C.c_void_p(txt.data_ptr()),
-                                        C.c_int32(D), C.c_void_p(_p(idx_in)), C.c_void_p(idx_out.data_ptr()), C.c_void_p(sel.data_ptr()),
-                                        C.c_void_p(_stream())), "cvlm_topk_select_wide")
+    _call("cvlm_topk_select_wide", logits.data_ptr(), B, Cc, K, txt.data_ptr(), D, _p(idx_in), idx_out.data_ptr(), sel.data_ptr())
 
 
 def text_assemble(ids: Optional[torch.Tensor], table: Optional[torch.Tensor], emb: Optional[torch.Tensor], ctx: torch.Tensor,
@@ -678,33 +671,24 @@ def text_assemble(ids: Optional[torch.Tensor], table: Optional[torch.Tensor], em
     """out f32 [n][L][W] = [prefix | ctx | suffix] + pos of a vocabulary's prompts, from token ids (int32 [n][ctx_len]) and the
     embedding table or from embedded prompts f32 [n][ctx_len][W] (include/cvlm.h)."""
     assert ids is None or (ids.dtype == torch.int32 and ids.is_contiguous())
-    _check(load().cvlm_text_assemble(C.c_void_p(_p(ids)), C.c_void_p(_p(table)), C.c_int32(0 if table is None else int(table.shape[0])),
-                                     C.c_void_p(_p(emb)), C.c_void_p(ctx.data_ptr()), C.c_int32(int(ctx.shape[0])), C.c_void_p(pos.data_ptr()),
-                                     C.c_int32(n), C.c_int32(ctx_len), C.c_int32(L), C.c_int32(W), C.c_void_p(out.data_ptr()),
-                                     C.c_void_p(_stream())), "cvlm_text_assemble")
+    _call("cvlm_text_assemble", _p(ids), _p(table), 0 if table is None else int(table.shape[0]), _p(emb), ctx.data_ptr(),
+          int(ctx.shape[0]), pos.data_ptr(), n, ctx_len, L, W, out.data_ptr())
 
 
 def normalize_add(x, add, R: int, D: int, out) -> None:
-    _check(load().cvlm_normalize_add(C.c_void_p(x.data_ptr()), C.c_void_p(_p(add)), C.c_int32(R), C.c_int32(D),
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), "cvlm_normalize_add")
+    _call("cvlm_normalize_add", x.data_ptr(), _p(add), R, D, out.data_ptr())
 
 
 def resample_u8(src: torch.Tensor, bounds: torch.Tensor, kk: torch.Tensor, n_out: int, axis: int, dst: torch.Tensor) -> None:
     """src/dst uint8 [N][H][W][C]; bounds int32 [n_out][2]; kk int32 [n_out][ksize] (device tensors)."""
     N, H, W, Cc = src.shape
-    _check(load().cvlm_resample_u8(C.c_void_p(src.data_ptr()), C.c_int32(N), C.c_int32(H), C.c_int32(W), C.c_int32(Cc),
-                                   C.c_void_p(bounds.data_ptr()), C.c_void_p(kk.data_ptr()), C.c_int32(kk.shape[1]),
-                                   C.c_int32(n_out), C.c_int32(axis), C.c_void_p(dst.data_ptr()), C.c_void_p(_stream())),
-           "cvlm_resample_u8")
+    _call("cvlm_resample_u8", src.data_ptr(), N, H, W, Cc, bounds.data_ptr(), kk.data_ptr(), kk.shape[1], n_out, axis, dst.data_ptr())
 
 
 def u8_to_tensor(src: torch.Tensor, top: int, left: int, ch: int, cw: int, mean: torch.Tensor, std: torch.Tensor,
                  dst: torch.Tensor) -> None:
     N, H, W, Cc = src.shape
-    _check(load().cvlm_u8_to_tensor(C.c_void_p(src.data_ptr()), C.c_int32(N), C.c_int32(H), C.c_int32(W), C.c_int32(Cc),
-                                    C.c_int32(top), C.c_int32(left), C.c_int32(ch), C.c_int32(cw),
-                                    C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                    C.c_void_p(_stream())), "cvlm_u8_to_tensor")
+    _call("cvlm_u8_to_tensor", src.data_ptr(), N, H, W, Cc, top, left, ch, cw, mean.data_ptr(), std.data_ptr(), dst.data_ptr())
 
 
 def mask_to_u8(logits: torch.Tensor, h: int, w: int, dst: torch.Tensor) -> None:
@@ -712,8 +696,7 @@ def mask_to_u8(logits: torch.Tensor, h: int, w: int, dst: torch.Tensor) -> None:
     N, Hs, Ws = logits.shape
     assert logits.dtype == torch.float32 and dst.dtype == torch.uint8 and tuple(dst.shape) == (N, h, w)
     assert logits.is_contiguous() and dst.is_contiguous()
-    _check(load().cvlm_mask_to_u8(C.c_void_p(logits.data_ptr()), C.c_int32(N), C.c_int32(Hs), C.c_int32(Ws), C.c_int32(h),
-                                  C.c_int32(w), C.c_void_p(dst.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_to_u8")
+    _call("cvlm_mask_to_u8", logits.data_ptr(), N, Hs, Ws, h, w, dst.data_ptr())
 
 
 def mask_joint_hist(pre: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, hist: torch.Tensor) -> None:
@@ -722,9 +705,7 @@ def mask_joint_hist(pre: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, hi
     assert pre.dtype == torch.uint8 and gt.dtype == torch.uint8 and tuple(gt.shape) == (N, h, w)
     assert stats.dtype == torch.int64 and tuple(stats.shape) == (N, 3) and hist.dtype == torch.int32
     assert tuple(hist.shape) == (N, 4, 2, 256) and pre.is_contiguous() and gt.is_contiguous()
-    _check(load().cvlm_mask_joint_hist(C.c_void_p(pre.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_int32(N), C.c_int32(h),
-                                       C.c_int32(w), C.c_void_p(stats.data_ptr()), C.c_void_p(hist.data_ptr()),
-                                       C.c_void_p(_stream())), "cvlm_mask_joint_hist")
+    _call("cvlm_mask_joint_hist", pre.data_ptr(), gt.data_ptr(), N, h, w, stats.data_ptr(), hist.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:
@@ -732,9 +713,7 @@ def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[t
     B, Cc = scores.shape
     assert scores.dtype == torch.float32 and labels.dtype == torch.int32 and counters.dtype == torch.int32
     assert scores.is_contiguous() and labels.numel() == B and counters.numel() == 3
-    _check(load().cvlm_topk_accumulate(C.c_void_p(scores.data_ptr()), C.c_void_p(labels.data_ptr()), C.c_int32(B),
-                                       C.c_int32(Cc), C.c_void_p(_p(pred)), C.c_void_p(counters.data_ptr()),
-                                       C.c_void_p(_stream())), "cvlm_topk_accumulate")
+    _call("cvlm_topk_accumulate", scores.data_ptr(), labels.data_ptr(), B, Cc, _p(pred), counters.data_ptr())
 
 
 def mask_wfm_workspace_bytes(N: int, h: int, w: int) -> int:
@@ -750,9 +729,7 @@ def mask_wfm(pre: torch.Tensor, gt: torch.Tensor, hist: torch.Tensor, gauss49: t
     assert hist.dtype == torch.int32 and gauss49.dtype == torch.float64 and gauss49.numel() == 49
     assert out3.dtype == torch.float64 and tuple(out3.shape) == (N, 3) and workspace.numel() * workspace.element_size() >= mask_wfm_workspace_bytes(N, h, w)
     assert pre.is_contiguous() and gt.is_contiguous() and hist.is_contiguous()
-    _check(load().cvlm_mask_wfm(C.c_void_p(pre.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_int32(N), C.c_int32(h), C.c_int32(w),
-                                C.c_void_p(hist.data_ptr()), C.c_void_p(gauss49.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                C.c_void_p(out3.data_ptr()), C.c_void_p(_stream())), "cvlm_mask_wfm")
+    _call("cvlm_mask_wfm", pre.data_ptr(), gt.data_ptr(), N, h, w, hist.data_ptr(), gauss49.data_ptr(), workspace.data_ptr(), out3.data_ptr())
 
 
 def prob_workspace_bytes(N: int, h: int, w: int) -> int:
@@ -765,8 +742,7 @@ def prob_quantise(prob: torch.Tensor, minmax: torch.Tensor, q: torch.Tensor, wor
     N, h, w = prob.shape
     assert prob.dtype == torch.float32 and prob.is_contiguous() and minmax.dtype == torch.float32 and tuple(minmax.shape) == (N, 2)
     assert q.dtype == torch.uint8 and tuple(q.shape) == (N, h, w) and q.is_contiguous() and workspace.numel() >= prob_workspace_bytes(N, h, w)
-    _check(load().cvlm_prob_quantise(C.c_void_p(prob.data_ptr()), C.c_int32(N), C.c_int32(h), C.c_int32(w), C.c_void_p(minmax.data_ptr()),
-                                     C.c_void_p(q.data_ptr()), C.c_void_p(workspace.data_ptr()), C.c_void_p(_stream())), "cvlm_prob_quantise")
+    _call("cvlm_prob_quantise", prob.data_ptr(), N, h, w, minmax.data_ptr(), q.data_ptr(), workspace.data_ptr())
 
 
 def prob_moments(prob: torch.Tensor, gt: torch.Tensor, minmax: torch.Tensor, stats: torch.Tensor, workspace: torch.Tensor,
@@ -775,9 +751,7 @@ def prob_moments(prob: torch.Tensor, gt: torch.Tensor, minmax: torch.Tensor, sta
     N, h, w = prob.shape
     assert gt.dtype == torch.uint8 and tuple(gt.shape) == (N, h, w) and gt.is_contiguous() and stats.dtype == torch.int64
     assert out.dtype == torch.float64 and tuple(out.shape) == (N, 4, 2, 2) and workspace.numel() >= prob_workspace_bytes(N, h, w)
-    _check(load().cvlm_prob_moments(C.c_void_p(prob.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_int32(N), C.c_int32(h), C.c_int32(w),
-                                    C.c_void_p(minmax.data_ptr()), C.c_void_p(stats.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                    C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), "cvlm_prob_moments")
+    _call("cvlm_prob_moments", prob.data_ptr(), gt.data_ptr(), N, h, w, minmax.data_ptr(), stats.data_ptr(), workspace.data_ptr(), out.data_ptr())
 
 
 def prob_wfm(prob: torch.Tensor, gt: torch.Tensor, minmax: torch.Tensor, gauss49: torch.Tensor, workspace: torch.Tensor,
@@ -785,6 +759,4 @@ def prob_wfm(prob: torch.Tensor, gt: torch.Tensor, minmax: torch.Tensor, gauss49
     N, h, w = prob.shape
     assert out3.dtype == torch.float64 and tuple(out3.shape) == (N, 3) and gauss49.dtype == torch.float64 and gauss49.numel() == 49
     assert workspace.numel() >= prob_workspace_bytes(N, h, w)
-    _check(load().cvlm_prob_wfm(C.c_void_p(prob.data_ptr()), C.c_void_p(gt.data_ptr()), C.c_int32(N), C.c_int32(h), C.c_int32(w),
-                                C.c_void_p(minmax.data_ptr()), C.c_void_p(gauss49.data_ptr()), C.c_void_p(workspace.data_ptr()),
-                                C.c_void_p(out3.data_ptr()), C.c_void_p(_stream())), "cvlm_prob_wfm")
+    _call("cvlm_prob_wfm", prob.data_ptr(), gt.data_ptr(), N, h, w, minmax.data_ptr(), gauss49.data_ptr(), workspace.data_ptr(), out3.data_ptr())

@@ -1,7 +1,6 @@
 """CPU: the K-hypotheses oracle (tests/classes_oracle.py) against the reference's own K-prompt decoder call
 (tests/golden/tiny_classes.npz, tools/make_classes_golden.py), and the argument checks of the two C-ABI entries behind
 Cascade.infer_classes (no GPU needed: they refuse before launching)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -70,12 +69,12 @@ def _lib():
 
 def test_mask_head_edge_refuses_bad_arguments_without_gpu():
     lib = _lib()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(up=p, edge=p, hyper=p, P=2, HW=64, Cc=32, low=p, ep=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_mask_head_edge(a["up"], a["edge"], a["hyper"], C.c_int32(a["P"]), C.c_int32(a["HW"]), C.c_int32(a["Cc"]),
+        return lib.cvlm_mask_head_edge(a["up"], a["edge"], a["hyper"], a["P"], a["HW"], a["Cc"],
                                        a["low"], a["ep"], None)
     for kw in (dict(up=None), dict(edge=None), dict(hyper=None), dict(low=None), dict(ep=None), dict(P=0), dict(P=65536),
                dict(HW=0), dict(Cc=0), dict(Cc=30)):
@@ -84,12 +83,12 @@ def test_mask_head_edge_refuses_bad_arguments_without_gpu():
 
 def test_topk_select_refuses_bad_arguments_without_gpu():
     lib = _lib()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(logits=p, B=2, Cc=5, K=3, txt=p, D=8, idx_in=None, idx_out=p, sel=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_topk_select(a["logits"], C.c_int32(a["B"]), C.c_int32(a["Cc"]), C.c_int32(a["K"]), a["txt"], C.c_int32(a["D"]),
+        return lib.cvlm_topk_select(a["logits"], a["B"], a["Cc"], a["K"], a["txt"], a["D"],
                                     a["idx_in"], a["idx_out"], a["sel"], None)
     for kw in (dict(logits=None), dict(txt=None), dict(idx_out=None), dict(sel=None), dict(B=0), dict(Cc=0), dict(K=0),
                dict(K=6), dict(D=0), dict(D=6), dict(Cc=1025, K=3)):

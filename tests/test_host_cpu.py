@@ -11,8 +11,21 @@ import torch
 
 import camouflaged_vlm_amd as cv
 from camouflaged_vlm_amd import spec, synth
+import abi_header
 
 REPO = cv.REPO_DIR
+
+
+def _ctype(hip, ctype: str, returned: bool = False):
+    """The ctypes type the binding must use for a C type of include/cvlm.h (a parameter, a return value or a struct field)."""
+    import ctypes as C
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "char[128]": C.c_char * 128}
+    struct_pointers = {"const cvlm_gemm_args*": C.POINTER(hip.GemmArgs), "const cvlm_attn_args*": C.POINTER(hip.AttnArgs),
+                       "cvlm_gemm_plan_info*": C.POINTER(hip.GemmPlanInfo)}
+    if ctype in scalars or ctype in struct_pointers:
+        return scalars.get(ctype) or struct_pointers[ctype]
+    assert ctype.endswith("*") and "[" not in ctype, ctype
+    return C.c_char_p if returned and ctype == "const char*" else C.c_void_p
 
 
 def test_library_exports_every_declared_symbol():
@@ -26,6 +39,17 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/cvlm.h but not exported"
     assert set(hip.EXPORTS) == declared
     assert lib.cvlm_abi_version() == hip.ABI_VERSION == 12 and lib.cvlm_target_arch() == b"gfx950"
+    # and the binding's table states every prototype of the header: return type, every parameter type, and which entries take the stream
+    protos = abi_header.prototypes()
+    assert set(protos) == declared == set(hip.ABI)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = hip.ABI[name]
+        assert restype is _ctype(hip, ret, returned=True), name
+        assert argtypes == [_ctype(hip, t) for t, _ in params], name
+        assert (name in hip._STREAMED) == (params[-1:] == [("void*", "stream")]), name
+        assert "stream" not in [n for _, n in params[:-1]], name
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
 
 
 def test_integration_doc_struct_matches_binding():
@@ -42,20 +66,16 @@ def test_integration_doc_struct_matches_binding():
     assert ctypes.sizeof(doc_struct) == ctypes.sizeof(hip.AttnArgs)
     assert [(n, getattr(doc_struct, n).offset) for n, _ in doc_struct._fields_] == \
            [(n, getattr(hip.AttnArgs, n).offset) for n, _ in hip.AttnArgs._fields_]
-    # and the binding mirrors the header: every field name of the C struct, in order
-    hdr = open(os.path.join(REPO, "include", "cvlm.h")).read()
-    for cname, cls in (("cvlm_attn_args", hip.AttnArgs), ("cvlm_gemm_args", hip.GemmArgs)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            first, *rest = decl.split(",")
-            names.append(re.findall(r"[A-Za-z_0-9]+", first)[-1])
-            names += [re.findall(r"[A-Za-z_0-9]+", r)[-1] for r in rest]
-        assert names == [n for n, _ in cls._fields_], cname
+    # and the binding mirrors the header: every field of the C structs, name and type, in order (naturally aligned scalars, pointers
+    # and one char array under the platform's C layout: equal (name, type) sequences are equal layouts)
+    hdr = abi_header.structs()
+    assert set(hdr) == {"cvlm_gemm_args", "cvlm_attn_args", "cvlm_gemm_plan_info"}
+    plan = hdr["cvlm_gemm_plan_info"]
+    assert plan[1][:2] == ("struct[2]", "launch")                   # the nested anonymous struct array: GemmLaunchInfo * 2 in the binding
+    mirror = lambda fields: [(f[1], hip.GemmLaunchInfo * 2 if f[0] == "struct[2]" else _ctype(hip, f[0])) for f in fields]
+    for fields, cls in ((hdr["cvlm_attn_args"], hip.AttnArgs), (hdr["cvlm_gemm_args"], hip.GemmArgs), (plan, hip.GemmPlanInfo),
+                        (plan[1][2], hip.GemmLaunchInfo)):
+        assert mirror(fields) == list(cls._fields_), cls.__name__
 
 
 def test_clip_engine_dropped_when_parent_loads_weights():

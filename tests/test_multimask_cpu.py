@@ -1,7 +1,6 @@
 """CPU: the multimask oracle (tests/multimask_oracle.py) against the reference's own `predict_masks` call
 (tests/golden/tiny_multimask.npz, tools/make_multimask_golden.py), and the argument checks of cvlm_mask_head_multi (no GPU needed:
 it refuses before launching)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -69,13 +68,13 @@ def test_oracle_slice_zero_is_the_one_mask_oracle(oracle_run, gold):
 
 def test_mask_head_multi_refuses_bad_arguments_without_gpu():
     lib = hip.load()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(up=p, edge=p, hyper=p, P=2, HW=64, Cc=32, n=4, low=p, ep=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_mask_head_multi(a["up"], a["edge"], a["hyper"], C.c_int32(a["P"]), C.c_int32(a["HW"]), C.c_int32(a["Cc"]),
-                                        C.c_int32(a["n"]), a["low"], a["ep"], None)
+        return lib.cvlm_mask_head_multi(a["up"], a["edge"], a["hyper"], a["P"], a["HW"], a["Cc"],
+                                        a["n"], a["low"], a["ep"], None)
     for kw in (dict(up=None), dict(hyper=None), dict(low=None), dict(edge=None), dict(n=0), dict(n=5), dict(n=-1), dict(P=0),
                dict(P=65536), dict(HW=0), dict(Cc=0), dict(Cc=30), dict(Cc=-4)):
         assert call(**kw) == -1, kw                          # edge=None with an edge_prob pointer: nothing to write it from

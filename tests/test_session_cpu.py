@@ -1,7 +1,6 @@
 """CPU: what Cascade.encode / Cascade.decode rest on that needs no GPU -- the export and the argument checks of
 cvlm_expand_blocks (the launcher refuses before it touches a device), the pure request check of `decode`, and the text-row
 oracle (tests/session_oracle.py) against the class oracle it generalises (tests/classes_oracle.py)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -23,12 +22,12 @@ def test_expand_blocks_is_exported_and_the_abi_stays():
 
 def test_expand_blocks_refuses_bad_arguments_without_gpu():
     lib = hip.load()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(image_of=p, P=7, B=3, n=4096, sf=p, df=p, shi=p, slo=p, dhi=p, dlo=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_expand_blocks(a["image_of"], C.c_int32(a["P"]), C.c_int32(a["B"]), C.c_int64(a["n"]), a["sf"], a["df"],
+        return lib.cvlm_expand_blocks(a["image_of"], a["P"], a["B"], a["n"], a["sf"], a["df"],
                                       a["shi"], a["slo"], a["dhi"], a["dlo"], None)
     none_h2 = dict(shi=None, slo=None, dhi=None, dlo=None)
     bad = [dict(image_of=None),

@@ -2,7 +2,6 @@
 (`vocabulary_request`, `decode_request(rank_cap=)`), the argument checks of the three C-ABI entries (they refuse before they touch a
 device), and the vocabulary oracle (tests/vocab_oracle.py) against the reference's own run over 1100 classes
 (tests/golden/tiny_vocab.npz, tools/make_vocab_golden.py)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -102,13 +101,13 @@ def test_new_entries_are_exported_and_the_abi_stays():
 
 def test_text_assemble_refuses_bad_arguments_without_gpu():
     lib = hip.load()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(ids=p, table=p, V=11, emb=None, ctx=p, n_ctx=4, pos=p, n=3, cl=77, L=9, W=64, out=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_text_assemble(a["ids"], a["table"], C.c_int32(a["V"]), a["emb"], a["ctx"], C.c_int32(a["n_ctx"]), a["pos"],
-                                      C.c_int32(a["n"]), C.c_int32(a["cl"]), C.c_int32(a["L"]), C.c_int32(a["W"]), a["out"], None)
+        return lib.cvlm_text_assemble(a["ids"], a["table"], a["V"], a["emb"], a["ctx"], a["n_ctx"], a["pos"],
+                                      a["n"], a["cl"], a["L"], a["W"], a["out"], None)
     bad = [dict(ids=None), dict(emb=p), dict(table=None), dict(V=0), dict(V=-3), dict(ctx=None), dict(pos=None), dict(out=None),
            dict(n=0), dict(n=-1), dict(cl=0), dict(L=0), dict(L=78), dict(W=0), dict(W=66), dict(W=-4), dict(n_ctx=-1), dict(n_ctx=77),
            dict(ids=None, table=None, emb=p, n=0), dict(n=1 << 20, L=77, W=768)]                      # an output of 2^31 bytes or more
@@ -118,34 +117,34 @@ def test_text_assemble_refuses_bad_arguments_without_gpu():
 
 def test_clip_head_wide_refuses_bad_arguments_without_gpu():
     lib = hip.load()
-    p = C.c_void_p(4096)
-    need = lib.cvlm_clip_head_wide_workspace_bytes(C.c_int32(17), C.c_int32(2500))
+    p = 4096
+    need = lib.cvlm_clip_head_wide_workspace_bytes(17, 2500)
     assert need > 0
     ok = dict(img=p, txt=p, P=17, Cc=2500, D=768, img_n=p, logits=p, pred=p, sel=p, ws=p, nbytes=need)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_clip_head_wide(a["img"], a["txt"], C.c_float(100.0), C.c_int32(a["P"]), C.c_int32(a["Cc"]), C.c_int32(a["D"]),
-                                       a["img_n"], a["logits"], a["pred"], a["sel"], a["ws"], C.c_int64(a["nbytes"]), None)
+        return lib.cvlm_clip_head_wide(a["img"], a["txt"], 100.0, a["P"], a["Cc"], a["D"],
+                                       a["img_n"], a["logits"], a["pred"], a["sel"], a["ws"], a["nbytes"], None)
     bad = [dict(img=None), dict(txt=None), dict(img_n=None), dict(logits=None), dict(pred=None), dict(sel=None), dict(ws=None),
            dict(P=0), dict(P=-1), dict(P=65536), dict(Cc=0), dict(Cc=-5), dict(Cc=65537), dict(D=0), dict(D=770), dict(D=1028),
-           dict(nbytes=need - 1), dict(nbytes=0), dict(ws=C.c_void_p(4100))]
+           dict(nbytes=need - 1), dict(nbytes=0), dict(ws=4100)]
     for kw in bad:
         assert call(**kw) == -1, kw
     for P, Cc in ((0, 5), (5, 0), (65536, 5), (5, 65537), (-1, -1)):
-        assert lib.cvlm_clip_head_wide_workspace_bytes(C.c_int32(P), C.c_int32(Cc)) == -1
-    assert lib.cvlm_clip_head_wide_workspace_bytes(C.c_int32(1), C.c_int32(1)) > 0
-    assert lib.cvlm_clip_head_wide_workspace_bytes(C.c_int32(65535), C.c_int32(65536)) > 0
+        assert lib.cvlm_clip_head_wide_workspace_bytes(P, Cc) == -1
+    assert lib.cvlm_clip_head_wide_workspace_bytes(1, 1) > 0
+    assert lib.cvlm_clip_head_wide_workspace_bytes(65535, 65536) > 0
 
 
 def test_topk_select_wide_refuses_bad_arguments_without_gpu():
     lib = hip.load()
-    p = C.c_void_p(4096)
+    p = 4096
     ok = dict(logits=p, B=2, Cc=2500, K=5, txt=p, D=8, idx_in=None, idx_out=p, sel=p)
 
     def call(**kw):
         a = dict(ok, **kw)
-        return lib.cvlm_topk_select_wide(a["logits"], C.c_int32(a["B"]), C.c_int32(a["Cc"]), C.c_int32(a["K"]), a["txt"], C.c_int32(a["D"]),
+        return lib.cvlm_topk_select_wide(a["logits"], a["B"], a["Cc"], a["K"], a["txt"], a["D"],
                                          a["idx_in"], a["idx_out"], a["sel"], None)
     for kw in (dict(logits=None), dict(idx_in=p), dict(txt=None), dict(idx_out=None), dict(sel=None), dict(B=0), dict(B=-1), dict(Cc=0), dict(Cc=65537),
                dict(K=0), dict(K=65), dict(Cc=3, K=4), dict(D=0), dict(D=6)):
