@@ -6,6 +6,8 @@
 //   class scores -> top-1 / top-5 counters                                             (recorder/new_evaluator.py:47-59)
 // Byte/integer work, HBM-bound: one read of the 4 B/px logits, one write + one read of the 1 B/px mask and ground truth;
 // 8 KB of counters leave the device instead of a 4 MB float mask per image.
+#include <algorithm>
+
 #include "common.h"
 #include "../../include/cvlm.h"
 
@@ -539,6 +541,145 @@ __global__ __launch_bounds__(64) void topk_kernel(const float* __restrict__ scor
     atomicAdd(&counters[2], 1u);
 }
 
+// ---- packed masks, areas, boxes and overlaps of class hypotheses ------------------------------------------------------
+// area = 0, box = (-1, -1, -1, -1): the corners x0 / y0 are then lowered by UNSIGNED minima (0xffffffff is the largest unsigned and -1
+// as the int32 the caller reads: an empty plane needs no second pass), x1 / y1 raised by signed maxima.
+__global__ __launch_bounds__(256) void mask_pack_init_kernel(int* __restrict__ area, int* __restrict__ box, int P) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    area[p] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
+}
+
+// logit > 0.0f on the bit pattern: sign clear, not zero, not above +inf's pattern (NaN) -- a denormal counts whatever the denormal mode
+__device__ __forceinline__ unsigned mask_positive(float v) { return (__float_as_uint(v) - 1u) < 0x7f800000u ? 1u : 0u; }
+
+// Plane blockIdx.y, 4 pixels per lane and round: lanes 8g .. 8g + 7 of a wave hold the 32 pixels of one word (HW % 32 == 0, and every
+// term of the group index but the lane is a multiple of 64).  Each lane places its nibble at bit 4 * (lane & 7) -- bit i of the word =
+// pixel i --, three xor-shuffles OR the eight nibbles together, and bit reversal + byte swap turn that into packbits' order
+// (pixel i -> bit 7 - (i & 7) of byte i >> 3, bytes in memory order); lane 8g stores the word.  Every lane runs every round, so the
+// shuffles always see their whole group.
+template <bool STATS>
+__global__ __launch_bounds__(256) void mask_pack_kernel(const float* __restrict__ logits, int64_t HW, int W, uint32_t* __restrict__ bits,
+                                                        int* __restrict__ area, int* __restrict__ box) {
+    const int64_t p = blockIdx.y;
+    const float* src = logits + p * HW;
+    uint32_t* dst = bits + p * (HW >> 5);
+    const bool vec = (((uintptr_t)logits) & 15) == 0;                 // planes are 128-byte multiples apart
+    const unsigned groups = (unsigned)(HW >> 2);                      // < 2^29
+    const unsigned span = gridDim.x * 256u;
+    const unsigned rounds = (groups + span - 1) / span;
+    unsigned cnt = 0, x0 = 0xffffffffu, y0 = 0xffffffffu;
+    int x1 = -1, y1 = -1;
+    for (unsigned rd = 0; rd < rounds; ++rd) {
+        const unsigned q = rd * span + blockIdx.x * 256u + threadIdx.x;
+        const bool ok = q < groups;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) {
+            if (vec) v = *(const float4*)(src + 4 * (int64_t)q);
+            else { const float* s = src + 4 * (int64_t)q; v = make_float4(s[0], s[1], s[2], s[3]); }
+        }
+        const unsigned nib = mask_positive(v.x) | mask_positive(v.y) << 1 | mask_positive(v.z) << 2 | mask_positive(v.w) << 3;
+        unsigned word = nib << (4 * (threadIdx.x & 7));
+        word |= __shfl_xor(word, 1, 64);
+        word |= __shfl_xor(word, 2, 64);
+        word |= __shfl_xor(word, 4, 64);
+        if (ok && (threadIdx.x & 7) == 0) dst[q >> 3] = __builtin_bswap32(__brev(word));
+        if (STATS && nib) {
+            const unsigned i0 = 4u * q;                                // < 2^31
+            unsigned y = i0 / (unsigned)W, x = i0 - y * (unsigned)W;
+            cnt += __popc(nib);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (nib >> j & 1) {
+                    x0 = min(x0, x); y0 = min(y0, y);
+                    x1 = max(x1, (int)x); y1 = max(y1, (int)y);
+                }
+                if (++x == (unsigned)W) { x = 0; ++y; }
+            }
+        }
+    }
+    if (!STATS) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
+        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
+    }
+    __shared__ unsigned red[4][5];
+    if ((threadIdx.x & 63) == 0) {
+        unsigned* r = red[threadIdx.x >> 6];
+        r[0] = cnt; r[1] = x0; r[2] = y0; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned c = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+        if (c) {                                                      // a workgroup that found nothing leaves the plane's results alone
+            atomicAdd(&area[p], (int)c);
+            atomicMin((unsigned*)&box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
+            atomicMin((unsigned*)&box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
+            atomicMax(&box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
+            atomicMax(&box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
+        }
+    }
+}
+
+// inter[img][a][b] += popcount(row a AND row b) over the words [blockIdx.x * span, + span) for the 32 x 32 pairs of tile (ta, tb),
+// ta <= tb, of image blockIdx.z.  The tile's 32 + 32 rows are staged OV_WT words at a time (rows past K and words past `words` as
+// zeros); thread (ty, tx) owns the pairs (ty | ty + 16) x (tx | tx + 16): four 16-byte LDS reads per 16 word pairs.  Rows are OV_LD
+// words apart in LDS: 16-byte aligned, and the 16 rows a wave's lanes read start 4 banks apart.
+constexpr int OV_T = 32, OV_WT = 128, OV_LD = OV_WT + 4;
+__global__ __launch_bounds__(256) void mask_overlap_kernel(const uint32_t* __restrict__ bits, int K, int64_t words, int64_t span,
+                                                           int* __restrict__ inter) {
+    __shared__ __attribute__((aligned(16))) uint32_t rows[2 * OV_T][OV_LD];
+    int ta = 0, tb = blockIdx.y;                                      // blockIdx.y counts the tiles (ta, tb >= ta) row by row
+    for (int len = (K + OV_T - 1) / OV_T; tb >= len; tb -= len, --len) ++ta;
+    tb += ta;
+    const int64_t img = blockIdx.z;
+    const uint32_t* base = bits + img * K * words;
+    const int64_t w_begin = (int64_t)blockIdx.x * span, w_end = min(words, w_begin + span);
+    const bool vec = ((((uintptr_t)bits) & 15) == 0) && ((words & 3) == 0);
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    unsigned c00 = 0, c01 = 0, c10 = 0, c11 = 0;
+    for (int64_t w0 = w_begin; w0 < w_end; w0 += OV_WT) {
+        for (int i = threadIdx.x; i < 2 * OV_T * (OV_WT / 4); i += 256) {
+            const int r = i / (OV_WT / 4), c = (i % (OV_WT / 4)) * 4;
+            const int row = (r < OV_T ? ta * OV_T : tb * OV_T - OV_T) + r;
+            const int64_t w = w0 + c;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (row < K && w < w_end) {
+                const uint32_t* s = base + (int64_t)row * words + w;
+                if (vec && w + 4 <= w_end) v = *(const uint4*)s;
+                else { v.x = s[0]; if (w + 1 < w_end) v.y = s[1]; if (w + 2 < w_end) v.z = s[2]; if (w + 3 < w_end) v.w = s[3]; }
+            }
+            *(uint4*)&rows[r][c] = v;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int c = 0; c < OV_WT; c += 4) {
+            const uint4 a0 = *(const uint4*)&rows[ty][c], a1 = *(const uint4*)&rows[ty + 16][c];
+            const uint4 b0 = *(const uint4*)&rows[OV_T + tx][c], b1 = *(const uint4*)&rows[OV_T + tx + 16][c];
+            c00 += __popc(a0.x & b0.x) + __popc(a0.y & b0.y) + __popc(a0.z & b0.z) + __popc(a0.w & b0.w);
+            c01 += __popc(a0.x & b1.x) + __popc(a0.y & b1.y) + __popc(a0.z & b1.z) + __popc(a0.w & b1.w);
+            c10 += __popc(a1.x & b0.x) + __popc(a1.y & b0.y) + __popc(a1.z & b0.z) + __popc(a1.w & b0.w);
+            c11 += __popc(a1.x & b1.x) + __popc(a1.y & b1.y) + __popc(a1.z & b1.z) + __popc(a1.w & b1.w);
+        }
+        __syncthreads();
+    }
+    int* out = inter + img * K * K;
+    const unsigned cs[2][2] = {{c00, c01}, {c10, c11}};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int a = ta * OV_T + ty + 16 * i, b = tb * OV_T + tx + 16 * j;
+            if (cs[i][j] == 0 || a >= K || b >= K) continue;
+            atomicAdd(&out[(int64_t)a * K + b], (int)cs[i][j]);
+            if (ta != tb) atomicAdd(&out[(int64_t)b * K + a], (int)cs[i][j]);   // the diagonal tile computes both orders itself
+        }
+}
+
 inline int grid_for(int64_t n, int cap) {
     int64_t g = (n + 255) / 256;
     return (int)(g > cap ? cap : (g < 1 ? 1 : g));
@@ -591,6 +732,45 @@ int cvlm_mask_joint_hist(const uint8_t* pre, const uint8_t* gt, int32_t N, int32
     hipLaunchKernelGGL(centroid_finalize_kernel, dim3(N), dim3(256), 0, st, partial, gx, (unsigned long long*)stats, hist);
     CVLM_CHECK_LAUNCH();
     hipLaunchKernelGGL(joint_hist_kernel, dim3(gx, N), dim3(256), 0, st, pre, gt, h, w, (const unsigned long long*)stats, hist);
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_mask_pack(const float* logits, int32_t P, int64_t HW, int32_t W, uint8_t* bits, int32_t* area, int32_t* box, void* stream) {
+    if (!logits || !bits || (((uintptr_t)bits) & 3) != 0 || (area == nullptr) != (box == nullptr) || P < 1 || P > 65535 || HW <= 0 ||
+        HW >= ((int64_t)1 << 31) || HW % 32 != 0 || W <= 0 || HW % W != 0)
+        return CVLM_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    // workgroups per plane: about 2048 in all, at most one per 256 lanes' worth of pixels, and at most 128 -- every workgroup that finds
+    // a set pixel ends in five atomics on its plane's results
+    const int64_t by_work = (HW / 4 + 255) / 256;
+    const int64_t want = (2048 + P - 1) / P;
+    const int gx = (int)std::min<int64_t>(std::min<int64_t>(by_work, want), 128);
+    if (area) {
+        hipLaunchKernelGGL(mask_pack_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)area, (int*)box, (int)P);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(mask_pack_kernel<true>, dim3(gx, P), dim3(256), 0, st, logits, HW, (int)W, (uint32_t*)bits, (int*)area, (int*)box);
+    } else {
+        hipLaunchKernelGGL(mask_pack_kernel<false>, dim3(gx, P), dim3(256), 0, st, logits, HW, (int)W, (uint32_t*)bits, (int*)nullptr,
+                           (int*)nullptr);
+    }
+    CVLM_CHECK_LAUNCH();
+    return 0;
+}
+
+int cvlm_mask_overlap(const uint32_t* bits, int32_t n, int32_t K, int64_t words, int32_t* inter, void* stream) {
+    if (!bits || !inter || n < 1 || K < 1 || K > 1024 || (int64_t)n * K > 65535 || words < 1 || words * 32 >= ((int64_t)1 << 31))
+        return CVLM_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(inter, 0, (size_t)n * K * K * sizeof(int32_t), st) != hipSuccess) return (int)hipGetLastError();
+    // spans of words per workgroup: about 1024 workgroups in all, every span a whole number of staged tiles -- a workgroup ends in
+    // up to 2048 atomics, so long rows are walked by few workgroups each
+    const int T = (K + OV_T - 1) / OV_T, tiles = T * (T + 1) / 2;
+    const int64_t wt = (words + OV_WT - 1) / OV_WT;
+    const int64_t gx_want = std::max<int64_t>(1, 1024 / ((int64_t)tiles * n));
+    const int64_t per = (wt + std::min(wt, gx_want) - 1) / std::min(wt, gx_want);   // staged tiles per workgroup
+    const int gx = (int)((wt + per - 1) / per);
+    hipLaunchKernelGGL(mask_overlap_kernel, dim3(gx, tiles, n), dim3(256), 0, st, bits, (int)K, words, per * OV_WT, (int*)inter);
     CVLM_CHECK_LAUNCH();
     return 0;
 }

@@ -1381,16 +1381,24 @@ class ClassHypotheses:
     # (B, K) int64; with topk= the K largest pass-1 logits, descending: classes[:, 0] = pass 1's prediction; None from Cascade.decode(text=)
     classes: Optional[torch.Tensor]
     pass1_logits: torch.Tensor      # (B, n_cls) CLIP pass 1 (mapleAlphaCLIP.py:285-294), as in `cascade`
-    masks: torch.Tensor             # (B, K, S, S) f32 mask logits (models/sam_maskdecoder_edge.py:354)
-    edges: torch.Tensor             # (B, K, S, S) f32 edge probabilities sigmoid(hyper_edge . edge_embedding), upsampled (:298-302)
+    masks: Optional[torch.Tensor]   # (B, K, S, S) f32 mask logits (models/sam_maskdecoder_edge.py:354); None with masks="bits"
+    # (B, K, S, S) f32 edge probabilities sigmoid(hyper_edge . edge_embedding), upsampled (:298-302); None with masks="bits"
+    edges: Optional[torch.Tensor]
     logits: Optional[torch.Tensor]  # (B, K, n_cls) stage 2 of each hypothesis (demo.py:117-122); None from Cascade.decode(stage2=False)
     pred: Optional[torch.Tensor]    # (B, K) int64 stage-2 prediction; None from Cascade.decode(stage2=False)
     # quality=True: (B, K) f32, the decoder's predicted quality iou_pred[:, 0] of each hypothesis's mask (mask_decoder_edge.py:188), NaN
     # where classes is -1; otherwise None.  An init-only pseudo-field: dataclasses.fields() keeps listing the tensors every call returns
     iou: InitVar[Optional[torch.Tensor]] = None
+    # masks="bits" / "both" (DESIGN.md §13), otherwise None; pseudo-fields like `iou`.  mask_bits (B, K, S * S / 8) uint8: masks > 0 in
+    # numpy.packbits' order; area (B, K) int32: set bits; box (B, K, 4) int32: inclusive (x0, y0, x1, y1), -1 for an empty mask.  A
+    # hypothesis whose class is -1 has zero bits, area 0, box -1 and a zero row and column in `inter`.
+    mask_bits: InitVar[Optional[torch.Tensor]] = None
+    area: InitVar[Optional[torch.Tensor]] = None
+    box: InitVar[Optional[torch.Tensor]] = None
+    inter: InitVar[Optional[torch.Tensor]] = None   # overlaps=True: (B, K, K) int32 |mask a AND mask b| per image, diagonal = area
 
-    def __post_init__(self, iou):
-        self.iou = iou
+    def __post_init__(self, iou, mask_bits, area, box, inter):
+        self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
 
 
 @dataclass
@@ -1461,6 +1469,27 @@ def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=Non
     if bool(((host < 0) | (host >= n_cls)).any()):
         raise ValueError(f"decode: a class index outside [0, {n_cls})")
     return images, int(classes.shape[1]), host
+
+
+MASK_MODES = ("logits", "bits", "both")
+OVERLAP_MAXK = 1024        # hypotheses per image cvlm_mask_overlap takes
+OVERLAP_MAXP = 65535       # planes in all it takes
+
+
+def compact_request(*, masks="logits", overlaps=False, n: int, K: int, who: str = "decode"):
+    """Every check of the masks= / overlaps= arguments of Cascade.infer_classes / decode, on the host, before anything
+    is launched (ValueError) -> (want_logits, want_bits, want_inter).  n images with K hypotheses each."""
+    if not isinstance(masks, str) or masks not in MASK_MODES:
+        raise ValueError(f"{who}: masks must be one of {MASK_MODES}, got {masks!r}")
+    if not isinstance(overlaps, (bool, np.bool_)):
+        raise ValueError(f"{who}: overlaps must be a bool, got {type(overlaps).__name__}")
+    if overlaps and masks == "logits":
+        raise ValueError(f"{who}: overlaps=True counts packed masks: ask for masks='bits' or 'both'")
+    if overlaps and K > OVERLAP_MAXK:
+        raise ValueError(f"{who}: overlaps=True takes at most {OVERLAP_MAXK} hypotheses per image (cvlm_mask_overlap), got K = {K}")
+    if overlaps and n * K > OVERLAP_MAXP:
+        raise ValueError(f"{who}: overlaps=True takes at most {OVERLAP_MAXP} hypotheses in all (cvlm_mask_overlap), got {n} x {K}")
+    return masks != "bits", masks != "logits", bool(overlaps)
 
 
 @dataclass
@@ -1739,10 +1768,12 @@ class Cascade(_Base):
 
     def _mask_logits(self, feats, sparse: torch.Tensor, n: int, out: Optional[torch.Tensor] = None,
                      edge_out: Optional[torch.Tensor] = None, taps: Optional[dict] = None,
-                     iou_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     iou_out: Optional[torch.Tensor] = None, edge_low: bool = False) -> torch.Tensor:
         """Features rows + n prompts -> mask logits at the input size, f32 [n][1][S][S] or into `out` (n maps of S x S); with
         `edge_out` the edge probabilities beside them (MaskDecoder.forward(edge_out=True)); with `iou_out` f32 [n] (needs
         edge_out) also the predicted quality of each mask, from MaskDecoder.forward(multi=1): same mask and edge bits.
+        edge_low: the decoder call of `edge_out` without its resize -- the low-resolution edge map stays in the decoder's workspace
+        (masks="bits", DESIGN.md §13: the decoder's launches, and so the mask bits, are those of the call that returns edges).
         `feats` may be (image state, image_of, n_images) in place of features rows: the decoder's image part has run already
         (Cascade.encode) and only MaskDecoder.prompt_part does."""
         g = self.g
@@ -1751,12 +1782,13 @@ class Cascade(_Base):
             dec = lambda **kw: self.decoder.prompt_part(st, sparse, n, image_of, n_images, taps=taps, **kw)
         else:
             dec = lambda **kw: self.decoder.forward(feats, sparse, self.no_mask, self.gauss, n, taps, **kw)
+        with_edge = edge_out is not None or edge_low
         if iou_out is not None:
             low, low_e, iou = dec(multi=1)
             iou_out.copy_(iou[:, 0])
         else:
-            low = dec(edge_out=edge_out is not None)
-            if edge_out is not None:
+            low = dec(edge_out=with_edge)
+            if with_edge:
                 low, low_e = low
         if out is None:
             out = torch.empty(n, 1, g.inp_size, g.inp_size, device=self.device)
@@ -1901,12 +1933,13 @@ class Cascade(_Base):
             dst[lo - p0:hi - p0].copy_(src[b:b + 1].expand(hi - lo, *src.shape[1:]))
 
     def _class_stage2(self, masks: torch.Tensor, clip_image: torch.Tensor, B: int, K: int, p0: int, p1: int,
-                      logits: torch.Tensor, pred: torch.Tensor, vocab: Optional[Vocabulary] = None) -> None:
+                      logits: torch.Tensor, pred: torch.Tensor, vocab: Optional[Vocabulary] = None, base: int = 0) -> None:
         """demo.py:117-122 for the prompts p0 <= p < p1 as ONE CLIP forward: its images are the groups clip_image[b_lo:b_hi] of
         one hypothesis slot k each (ClipModel.image_features stacks groups without copying them), the alphas follow in that
-        order; results go back to the prompt order p = b * K + k."""
+        order; results go back to the prompt order p = b * K + k.  masks[0] is the plane of prompt `base` (the chunk's own buffer
+        with masks="bits")."""
         R, n = self.c.image_resolution, p1 - p0
-        alpha = self._alpha(masks[p0:p1], "cls_alpha")
+        alpha = self._alpha(masks[p0 - base:p1 - base], "cls_alpha")
         groups = []                                                  # (k, b_lo, b_hi): prompts b * K + k of this range
         for k in range(K):
             b_lo, b_hi = max(0, -(-(p0 - k) // K)), min(B, -(-(p1 - k) // K))
@@ -1931,8 +1964,53 @@ class Cascade(_Base):
             pred[b_lo * K + k:(b_hi - 1) * K + k + 1:K].copy_(pr[q:q + m])
             q += m
 
+    # ---- packed masks, areas, boxes and overlaps -----------------------------------------------------------------
+    def _compact_outputs(self, n: int, K: int, want_bits: bool, want_inter: bool):
+        """The result's own (mask_bits, area, box, inter) for n x K hypotheses, None where not asked for."""
+        if not want_bits:
+            return None, None, None, None
+        dev, S = self.device, self.g.inp_size
+        return (torch.empty(n, K, S * S // 8, dtype=torch.uint8, device=dev), torch.empty(n, K, dtype=torch.int32, device=dev),
+                torch.empty(n, K, 4, dtype=torch.int32, device=dev),
+                torch.empty(n, K, K, dtype=torch.int32, device=dev) if want_inter else None)
+
+    def _chunk_planes(self, mflat: Optional[torch.Tensor], eflat: Optional[torch.Tensor], p0: int, p1: int):
+        """Where the full-resolution planes of the prompts p0 <= p < p1 go: the result's tensors, or with masks="bits" the workspace
+        buffer "cls_planes" of at most class_chunk() planes and no edge map -> (mask planes, edge planes or None)."""
+        if mflat is not None:
+            return mflat[p0:p1], eflat[p0:p1]
+        S = self.g.inp_size
+        return self.ws.f32("cls_planes", p1 - p0, S, S), None
+
+    @staticmethod
+    def _pack_chunk(planes: torch.Tensor, compact, p0: int, p1: int) -> None:
+        """cvlm_mask_pack of a chunk's planes into rows p0 .. p1 - 1 of the result's mask_bits / area / box."""
+        bits, area, box, _ = compact
+        if bits is not None:
+            hip.mask_pack(planes, bits.view(-1, bits.shape[-1])[p0:p1], area.view(-1)[p0:p1], box.view(-1, 4)[p0:p1])
+
+    def pack_masks(self, logits: torch.Tensor):
+        """(bits, area, box) of any (N, S, S) or (N, 1, S, S) f32 mask logits on this engine's device, e.g. `infer_test`'s: bits uint8
+        (N, S * S / 8) = logits > 0 in numpy.packbits' order, area int32 (N,), box int32 (N, 4) inclusive (x0, y0, x1, y1), -1 for an
+        empty mask (cvlm_mask_pack).  One launch pair on the caller's stream; ValueError before it for anything else."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (3, 4) or \
+                (logits.dim() == 4 and logits.shape[1] != 1):
+            raise ValueError("pack_masks: logits must be a float32 tensor (N, H, W) or (N, 1, H, W)")
+        N, (H, W) = int(logits.shape[0]), (int(v) for v in logits.shape[-2:])
+        if not 1 <= N <= 65535 or H * W < 1 or (H * W) % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"pack_masks: {N} planes of {H} x {W}: 1 .. 65535 planes of a multiple of 32 pixels below 2^31")
+        if not logits.is_cuda:
+            raise ValueError("pack_masks: logits must be on the device")
+        planes = logits.detach().contiguous().view(N, H, W)
+        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=logits.device)
+        area = torch.empty(N, dtype=torch.int32, device=logits.device)
+        box = torch.empty(N, 4, dtype=torch.int32, device=logits.device)
+        hip.mask_pack(planes, bits, area, box)
+        return bits, area, box
+
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
-                      topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None) -> ClassHypotheses:
+                      topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
+                      masks: str = "logits", overlaps: bool = False) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -1951,10 +2029,17 @@ class Cascade(_Base):
         their sizes (`class_chunk()` holds as it is); NaN for a hypothesis whose class is -1.  Nothing is chosen here: the caller
         ranks.  quality=False makes exactly the launches it made before.
         vocab: a run-time vocabulary in place of the constructor's bank: `classes` / `topk` index it, pass 1 and stage 2
-        score against it -- up to 65536 classes, topk <= 64 above 1024."""
+        score against it -- up to 65536 classes, topk <= 64 above 1024.
+        masks= / overlaps= (`compact_request`, checked with the rest before any launch): "bits" or "both" add
+        `mask_bits`, `area` and `box` -- cvlm_mask_pack on each chunk's full-resolution planes --, overlaps=True `inter`, one
+        cvlm_mask_overlap launch behind the last chunk.  "bits" returns no `masks` and no `edges`: the planes of a chunk live in a
+        workspace buffer of class_chunk() planes, from which `_alpha` reads them, the edge maps are not resized, and no (B, K, S, S)
+        tensor exists; the decoder's launches are those of the default call, so every other field keeps its bits.  The default,
+        masks="logits", overlaps=False, makes exactly the launches and allocations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
+        want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=B, K=K, who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -1967,12 +2052,13 @@ class Cascade(_Base):
             sel = self.ws.f32("cls_sel", P, D)
             self._select(score, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
             vis, txt = self._project_prompts(img_f, sel, B, P)
-            masks = torch.empty(B, K, S, S, device=dev)
-            edges = torch.empty(B, K, S, S, device=dev)
+            m_out = torch.empty(B, K, S, S, device=dev) if want_logits else None
+            e_out = torch.empty(B, K, S, S, device=dev) if want_logits else None
             logits = torch.empty(B, K, n_cls, device=dev)
             pred = torch.empty(B, K, dtype=torch.int64, device=dev)
             iou = torch.empty(B, K, device=dev) if quality else None
-            mflat, eflat = masks.view(P, S, S), edges.view(P, S, S)
+            compact = self._compact_outputs(B, K, want_bits, want_inter)
+            mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
                 p1 = min(P, p0 + chunk)
@@ -1985,13 +2071,19 @@ class Cascade(_Base):
                 sp = self.ws.f32("cls_sparse", n, 2, C)
                 self._per_prompt(vis, K, p0, p1, sp[:, 0])
                 sp[:, 1].copy_(txt[p0:p1])
-                self._mask_logits(fr, sp, n, out=mflat[p0:p1], edge_out=eflat[p0:p1], iou_out=iou.view(P)[p0:p1] if quality else None)
-                self._class_stage2(mflat, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab)
+                planes, eplanes = self._chunk_planes(mflat, eflat, p0, p1)
+                self._mask_logits(fr, sp, n, out=planes, edge_out=eplanes, iou_out=iou.view(P)[p0:p1] if quality else None,
+                                  edge_low=not want_logits)
+                self._pack_chunk(planes, compact, p0, p1)
+                self._class_stage2(planes, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
+            if want_inter:
+                hip.mask_overlap(compact[0], compact[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  (cls, score, masks, edges, logits, pred) + ((iou,) if quality else ()))
-        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact if t is not None))
+        return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
+                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3])
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2026,7 +2118,8 @@ class Cascade(_Base):
 
     def decode(self, enc: EncodedImages, *, classes: Optional[torch.Tensor] = None, topk: Optional[int] = None,
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
-               stage2: bool = True, vocab: Optional[Vocabulary] = None) -> ClassHypotheses:
+               stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
+               overlaps: bool = False) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2040,7 +2133,9 @@ class Cascade(_Base):
         otherwise within the batch tolerance -- the image part ran over B images here and over B * K copies there.
         vocab: the vocabulary to decode against, default the one `enc` was encoded with (enc.vocab).  Another one first re-scores pass 1
         from enc.pass1_features against it -- one head launch, no encoder launch, no CLIP forward --; the returned pass1_logits are
-        the re-scored ones."""
+        the re-scored ones.
+        masks= / overlaps=: as in `infer_classes`, checked by `compact_request` with the rest; with stage2=False and
+        masks="bits" the chunk's planes are only packed."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2051,6 +2146,7 @@ class Cascade(_Base):
         n_cls, D = (int(v) for v in txt_bank.shape)
         images, K, host_classes = decode_request(same_engine=enc.engine is self, B=enc.B, n_cls=n_cls, D=D, classes=classes, topk=topk,
                                                  text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
+        want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=len(images), K=K)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2075,12 +2171,13 @@ class Cascade(_Base):
             idx_in = None if host_classes is None else host_classes.to(dev)
             self._select(score, n, n_cls, K, txt_bank, D, idx_in, cls, sel)
         txt = self._project_txt(sel, P)
-        masks = torch.empty(n, K, S, S, device=dev)
-        edges = torch.empty(n, K, S, S, device=dev)
+        m_out = torch.empty(n, K, S, S, device=dev) if want_logits else None
+        e_out = torch.empty(n, K, S, S, device=dev) if want_logits else None
         logits = torch.empty(n, K, n_cls, device=dev) if stage2 else None
         pred = torch.empty(n, K, dtype=torch.int64, device=dev) if stage2 else None
         iou = torch.empty(n, K, device=dev) if quality else None
-        mflat, eflat = masks.view(P, S, S), edges.view(P, S, S)
+        compact = self._compact_outputs(n, K, want_bits, want_inter)
+        mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
         for p0 in range(0, P, chunk):
             p1 = min(P, p0 + chunk)
@@ -2089,14 +2186,19 @@ class Cascade(_Base):
             sp = self.ws.f32("cls_sparse", m, 2, C)
             sp[:, 0].copy_(self._gather_blocks("dec_vis", enc.vis, of, m, B))
             sp[:, 1].copy_(txt[p0:p1])
-            self._mask_logits((enc.state, of, B), sp, m, out=mflat[p0:p1], edge_out=eflat[p0:p1],
-                              iou_out=iou.view(P)[p0:p1] if quality else None)
+            planes, eplanes = self._chunk_planes(mflat, eflat, p0, p1)
+            self._mask_logits((enc.state, of, B), sp, m, out=planes, edge_out=eplanes,
+                              iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not want_logits)
+            self._pack_chunk(planes, compact, p0, p1)
             if stage2:
-                self._class_stage2(mflat, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab)
+                self._class_stage2(planes, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
+        if want_inter:
+            hip.mask_overlap(compact[0], compact[3])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
         self._fold_guard_arm(torch.cuda.current_stream())
-        return ClassHypotheses(classes=cls, pass1_logits=score, masks=masks, edges=edges, logits=logits, pred=pred, iou=iou)
+        return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
+                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3])
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

@@ -57,6 +57,8 @@ _SIGNATURES = {
     "cvlm_u8_to_tensor": "i:piiiiiiiippps",
     "cvlm_mask_to_u8": "i:piiiiips",
     "cvlm_mask_joint_hist": "i:ppiiipps",
+    "cvlm_mask_pack": "i:pilippps",
+    "cvlm_mask_overlap": "i:piilps",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -706,6 +708,30 @@ def mask_joint_hist(pre: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, hi
     assert stats.dtype == torch.int64 and tuple(stats.shape) == (N, 3) and hist.dtype == torch.int32
     assert tuple(hist.shape) == (N, 4, 2, 256) and pre.is_contiguous() and gt.is_contiguous()
     _call("cvlm_mask_joint_hist", pre.data_ptr(), gt.data_ptr(), N, h, w, stats.data_ptr(), hist.data_ptr())
+
+
+def mask_pack(logits: torch.Tensor, bits: torch.Tensor, area: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None) -> None:
+    """logits f32 [P][H][W] -> bits uint8 [P][H * W / 8] in numpy.packbits' order (bit set iff logit > 0), area int32 [P], box int32
+    [P][4] = inclusive (x0, y0, x1, y1), -1 for an empty plane; area and box together or not at all (include/cvlm.h)."""
+    P, H, W = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and (H * W) % 32 == 0
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous()
+    assert (area is None) == (box is None)
+    if area is not None:
+        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
+    _on_current_device(logits)
+    _call("cvlm_mask_pack", logits.data_ptr(), P, H * W, W, bits.data_ptr(), _p(area), _p(box))
+
+
+def mask_overlap(bits: torch.Tensor, inter: torch.Tensor) -> None:
+    """bits uint8 [n][K][bytes] (mask_pack's planes, bytes % 4 == 0) -> inter int32 [n][K][K] = popcount(plane a AND plane b) per
+    image, the full symmetric matrix (overwritten; include/cvlm.h)."""
+    n, K, nbytes = bits.shape
+    assert bits.dtype == torch.uint8 and bits.is_contiguous() and nbytes % 4 == 0 and bits.data_ptr() % 4 == 0
+    assert inter.dtype == torch.int32 and tuple(inter.shape) == (n, K, K) and inter.is_contiguous()
+    _on_current_device(bits)
+    _call("cvlm_mask_overlap", bits.data_ptr(), n, K, nbytes // 4, inter.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

@@ -449,6 +449,33 @@ int cvlm_mask_to_u8(const float* logits, int32_t N, int32_t Hs, int32_t Ws, int3
 int cvlm_mask_joint_hist(const uint8_t* pre, const uint8_t* gt, int32_t N, int32_t h, int32_t w, uint64_t* stats, uint32_t* hist,
                          void* stream);
 
+/* Packed binary masks with their areas and boxes: what a caller of a class sweep reads in place of the f32 planes.
+ * logits f32 [P][HW] -> bits u8 [P][HW / 8], area i32 [P], box i32 [P][4] = (x0, y0, x1, y1).  Pixel i of a plane is bit
+ * 7 - (i & 7) of byte i >> 3 -- numpy.packbits' default order, the order of `mask_bits` in tests/golden/ -- and is set iff
+ * logit > 0.0f (probability above one half), the binarisation of every digest in tests/golden/, giving the boolean masks whose
+ * counts the reference's IoU is made of (recorder/ovcos_metricer.py:145-156: count_nonzero of AND over count_nonzero of OR):
+ * -0.0, NaN and -inf give 0, the smallest positive denormal gives 1 (the test is made on the bit pattern, whatever the denormal mode).
+ * area = the number of set bits; box is inclusive with x = i % W, y = i / W, and (-1, -1, -1, -1) for an empty plane.  area and box
+ * may be NULL together.  Both are initialised by the call (one small launch ahead of the pass), so a launch sequence replays.  One
+ * pass over the logits: a 16-byte load per lane (element loads when `logits` is not 16-byte aligned), eight lanes combine their
+ * nibbles by shuffles into one 32-bit word that one of them stores whole; counts and box corners are reduced per workgroup and
+ * reach memory as at most five integer atomics per workgroup that found a set pixel -- integer sums and minima, exact in any
+ * order.  64-bit offsets throughout (P * HW * 4 passes 2^31 at 513 planes of 1024^2).  No workspace, no allocation, no
+ * synchronisation.  CVLM_E_BADARG, before anything touches the device: logits or bits NULL, bits not 4-byte aligned, one of area /
+ * box without the other, P outside [1, 65535], HW <= 0, HW >= 2^31, HW % 32 != 0, W <= 0, HW % W != 0. */
+int cvlm_mask_pack(const float* logits, int32_t P, int64_t HW, int32_t W, uint8_t* bits, int32_t* area, int32_t* box, void* stream);
+
+/* Pairwise intersections of the K packed masks of each of n images: bits u32 [n][K][words] (the planes of cvlm_mask_pack read as
+ * words: the popcount of an AND does not depend on the byte order) -> inter i32 [n][K][K], inter[i][a][b] = popcount(plane a AND
+ * plane b) of image i.  The full symmetric matrix is written, its diagonal is the area; IoU = |A & B| / |A | B|, the reference's
+ * definition (recorder/ovcos_metricer.py:145-156), is inter / (area_a + area_b - inter).  inter is zeroed by the call.  Grid (span
+ * of words, tile of 32 x 32 pairs on or above the diagonal, image): the tile's 64 rows are staged in LDS 128 words at a time (16-byte
+ * loads when rows are 16-byte aligned), each thread owns 2 x 2 pairs, and a workgroup adds each non-zero count once, by an integer
+ * atomic, to inter[a][b] and, off the diagonal tile, inter[b][a]: exact and reproducible whatever the schedule.  64-bit offsets.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer, n < 1, K outside [1, 1024], n * K > 65535, words < 1,
+ * words * 32 >= 2^31. */
+int cvlm_mask_overlap(const uint32_t* bits, int32_t n, int32_t K, int64_t words, int32_t* inter, void* stream);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
