@@ -1,0 +1,335 @@
+// Connected components of packed masks (include/cvlm.h: cvlm_mask_components): label equivalence with union-find
+// (Komura 2015; Playne & Hawick 2018), seeded from the horizontal runs of 32-pixel words instead of from pixels.  The per-thread
+// logic -- runs of a word, neighbour rule, find, union, kept-word filter -- is components_logic.h, shared with the sequential host
+// entry at the end of this file.  One thread per word in every pass but the selection; no thread ever waits for another workgroup:
+// every find / union loop lowers a label on each iteration.  All results are integer sums, minima, maxima and counts.
+#include <algorithm>
+#include <vector>
+
+#include "../../include/cvlm.h"
+#include "common.h"
+#include "components_logic.h"
+
+namespace {
+
+constexpr int CC_MAXM = 64;
+
+// Workspace of one plane: four arrays of HW / 2 entries, one entry per possible run start (components_logic.h) -- 14 bytes per pixel.
+struct PlaneWs { int* parent; int* list; int* area; cc_box* box; };
+__host__ __device__ inline int64_t plane_ws_bytes(int64_t HW) { return 14 * HW; }
+__host__ __device__ inline PlaneWs plane_ws(void* workspace, int64_t slot, int64_t HW) {
+    char* b = (char*)workspace + slot * plane_ws_bytes(HW);         // HW % 32 == 0: every array starts on a 64-byte multiple
+    return PlaneWs{(int*)b, (int*)(b + 2 * HW), (int*)(b + 4 * HW), (cc_box*)(b + 6 * HW)};
+}
+
+// n_comp = 0 (it is the counter of the root lists), kept_area = 0, kept_box = -1 for all P planes
+__global__ __launch_bounds__(256) void cc_init_kernel(int* __restrict__ n_comp, int* __restrict__ kept_area, int* __restrict__ kept_box, int P) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    n_comp[p] = 0;
+    if (kept_area) {
+        kept_area[p] = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) kept_box[4 * p + k] = -1;
+    }
+}
+
+// pass 1: plane blockIdx.y of the round, one word per thread
+__global__ __launch_bounds__(256) void cc_seed_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    if (wi >= words) return;
+    const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
+    cc_seed_word(bits + (int64_t)blockIdx.y * words, wi, wpr, ws.parent, ws.area, ws.box);
+}
+
+// pass 2
+__global__ __launch_bounds__(256) void cc_join_kernel(const uint32_t* __restrict__ bits, int words, int wpr, int connectivity, void* workspace) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    if (wi >= words) return;
+    const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
+    cc_join_word(bits + (int64_t)blockIdx.y * words, wi, wpr, connectivity, ws.parent);
+}
+
+// pass 3: every run start is pointed at its root; a root appends itself to the plane's list (one counter add per wave and step), every
+// other run adds its length and box to its root's.  The lanes of a wave hold consecutive words: neighbouring lanes whose runs share a
+// root are summed in registers first (a segmented scan over equal neighbours), and the last lane of each such group issues the five
+// atomics -- a region that fills the plane costs five atomics per wave and step, not per word.  Every lane stays in the loop until
+// the wave has no run left, so ballots and shuffles always see the whole wave.
+__global__ __launch_bounds__(256) void cc_flatten_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace,
+                                                         int* __restrict__ n_comp) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
+    const uint32_t w = wi < words ? cc_unpack(bits[(int64_t)blockIdx.y * words + wi]) : 0u;
+    const int wc = wi < words ? wi : 0;                             // past the plane's end: no run, and no index to overflow
+    const int y = wc / wpr, xw = (wc - y * wpr) * 32, base = wc * 32;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int* counter = n_comp + blockIdx.y;
+    uint32_t rest = w;
+    while (__any(rest != 0u)) {
+        int key = -1, me = -1, len = 0, x0 = 0, x1 = 0;
+        if (rest) {
+            int s, e;
+            cc_next_run(w, rest, s, e);
+            me = base + s;
+            const int root = cc_find(ws.parent, me);
+            if (root != me) { ws.parent[me >> 1] = root; key = root; }
+            len = e - s; x0 = xw + s; x1 = xw + e - 1;
+        }
+        const bool is_root = me >= 0 && key < 0;
+        const unsigned long long roots = __ballot(is_root);
+        if (roots) {
+            int at = 0;
+            if (lane == __builtin_ctzll(roots)) at = atomicAdd(counter, __builtin_popcountll(roots));
+            at = __shfl(at, __builtin_ctzll(roots), 64);
+            if (is_root) ws.list[at + __builtin_popcountll(roots & below)] = me;
+        }
+        // groups of neighbouring lanes with one root: head = the first lane of a group, `first` = my group's head lane
+        const int key_prev = __shfl_up(key, 1, 64);
+        const unsigned long long heads = __ballot(lane == 0 || key != key_prev);
+        const int first = 63 - __builtin_clzll(heads & (below | (1ull << lane)));
+        int y0 = y, y1 = y;
+        for (int d = 1; d < 64 && __any(lane - d >= first); d <<= 1) {
+            const int o_len = __shfl_up(len, d, 64), o_x0 = __shfl_up(x0, d, 64), o_x1 = __shfl_up(x1, d, 64);
+            const int o_y0 = __shfl_up(y0, d, 64), o_y1 = __shfl_up(y1, d, 64);
+            if (lane - d >= first) {
+                len += o_len; x0 = min(x0, o_x0); x1 = max(x1, o_x1); y0 = min(y0, o_y0); y1 = max(y1, o_y1);
+            }
+        }
+        const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+        if (key >= 0 && last) {
+            const int k = key >> 1;
+            atomicAdd(ws.area + k, len);
+            atomicMin(&ws.box[k].x0, x0); atomicMin(&ws.box[k].y0, y0);
+            atomicMax(&ws.box[k].x1, x1); atomicMax(&ws.box[k].y1, y1);
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t max_u64(uint64_t a, uint64_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+        const uint64_t other = ((uint64_t)hi << 32) | lo;
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+// pass 4: one workgroup per plane.  n_kept = the regions of at least min_area pixels; then M rounds of a block-wide maximum of
+// cc_rank_key over the root list, each strictly below the previous winner (the scheme of cvlm_topk_select_wide): row m of the table.
+__global__ __launch_bounds__(256) void cc_select_kernel(int words, void* workspace, const int* __restrict__ n_comp, int M, int min_area,
+                                                        int* __restrict__ comps, int* __restrict__ n_kept) {
+    __shared__ uint64_t red[4];
+    __shared__ int cnt[4];
+    const PlaneWs ws = plane_ws(workspace, blockIdx.x, (int64_t)words * 32);
+    const int n = n_comp[blockIdx.x];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (n_kept) {
+        int c = 0;
+        for (int i = threadIdx.x; i < n; i += 256) c += ws.area[ws.list[i] >> 1] >= min_area ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) cnt[wave] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) n_kept[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    }
+    uint64_t prev = ~0ull;
+    for (int m = 0; m < M; ++m) {
+        uint64_t best = 0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int seed = ws.list[i];
+            const uint64_t key = cc_rank_key(ws.area[seed >> 1], seed);
+            if (key < prev && key > best) best = key;
+        }
+        best = wave_max_u64(best);
+        __syncthreads();                                            // the previous round's reads of red are done
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        best = max_u64(max_u64(red[0], red[1]), max_u64(red[2], red[3]));
+        if (threadIdx.x == 0) {
+            int* row = comps + ((int64_t)blockIdx.x * M + m) * 6;
+            if (best) {
+                const int seed = cc_key_seed(best);
+                const cc_box b = ws.box[seed >> 1];
+                row[0] = (int)(best >> 32); row[1] = b.x0; row[2] = b.y0; row[3] = b.x1; row[4] = b.y1; row[5] = seed;
+            } else {
+                row[0] = 0; row[1] = row[2] = row[3] = row[4] = row[5] = -1;
+            }
+        }
+        prev = best;                                                // 0 once the list is exhausted: nothing is below it
+    }
+}
+
+// pass 5: the plane without its regions below min_area, whole words in the stored order, and its area and box reduced per workgroup
+// as cvlm_mask_pack reduces them: five atomics per workgroup that kept a pixel.
+__global__ __launch_bounds__(256) void cc_keep_kernel(const uint32_t* __restrict__ bits, int words, int wpr, const void* workspace, int min_area,
+                                                      uint32_t* __restrict__ kept_bits, int* __restrict__ kept_area, int* __restrict__ kept_box) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    const PlaneWs ws = plane_ws(const_cast<void*>(workspace), blockIdx.y, (int64_t)words * 32);
+    unsigned cnt = 0, x0 = 0xffffffffu, y0 = 0xffffffffu;
+    int x1 = -1, y1 = -1;
+    if (wi < words) {
+        const int64_t at = (int64_t)blockIdx.y * words + wi;
+        const uint32_t w = cc_unpack(bits[at]);
+        const uint32_t kept = w ? cc_keep_word(w, wi * 32, ws.parent, ws.area, min_area) : 0u;
+        kept_bits[at] = cc_pack(kept);
+        if (kept) {
+            const int y = wi / wpr, xw = (wi - y * wpr) * 32;
+            cnt = __popc(kept);
+            x0 = xw + __builtin_ctz(kept); x1 = xw + 31 - __builtin_clz(kept);
+            y0 = y; y1 = y;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
+        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
+    }
+    __shared__ unsigned red[4][5];
+    if ((threadIdx.x & 63) == 0) {
+        unsigned* r = red[threadIdx.x >> 6];
+        r[0] = cnt; r[1] = x0; r[2] = y0; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned c = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+        if (c) {
+            const int p = blockIdx.y;
+            atomicAdd(&kept_area[p], (int)c);
+            atomicMin((unsigned*)&kept_box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
+            atomicMin((unsigned*)&kept_box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
+            atomicMax(&kept_box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
+            atomicMax(&kept_box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
+        }
+    }
+}
+
+// what both entries refuse, workspace aside
+bool cc_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t min_area,
+                    const int32_t* n_comp, const int32_t* comps, const int32_t* n_kept, const uint32_t* kept_bits, const int32_t* kept_area,
+                    const int32_t* kept_box) {
+    if (!bits || !n_comp || (((uintptr_t)bits) & 3) != 0 || (((uintptr_t)kept_bits) & 3) != 0) return true;
+    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if ((connectivity != 4 && connectivity != 8) || M < 0 || M > CC_MAXM || (M > 0) != (comps != nullptr) || min_area < 0) return true;
+    const bool keep = min_area > 0;
+    return keep != (n_kept != nullptr) || keep != (kept_bits != nullptr) || keep != (kept_area != nullptr) || keep != (kept_box != nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t cvlm_mask_components_workspace_bytes(int32_t P, int32_t H, int32_t W) {
+    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return -1;
+    return plane_ws_bytes((int64_t)H * W) * P;
+}
+
+int cvlm_mask_components(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t min_area,
+                         void* workspace, int64_t workspace_bytes, int32_t* n_comp, int32_t* comps, int32_t* n_kept, uint32_t* kept_bits,
+                         int32_t* kept_area, int32_t* kept_box, void* stream) {
+    if (cc_bad_request(bits, P, H, W, connectivity, M, min_area, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)) return CVLM_E_BADARG;
+    const int64_t HW = (int64_t)H * W;
+    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_ws_bytes(HW)) return CVLM_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int words = (int)(HW / 32), wpr = W / 32;
+    const int gx = (words + 255) / 256;
+    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_ws_bytes(HW));   // planes per round
+    hipLaunchKernelGGL(cc_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_comp, (int*)kept_area, (int*)kept_box, (int)P);
+    CVLM_CHECK_LAUNCH();
+    for (int p0 = 0; p0 < P; p0 += fit) {
+        const int np = std::min(fit, P - p0);
+        const uint32_t* src = bits + (int64_t)p0 * words;
+        hipLaunchKernelGGL(cc_seed_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, workspace);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(cc_join_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, (int)connectivity, workspace);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(cc_flatten_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, workspace, (int*)n_comp + p0);
+        CVLM_CHECK_LAUNCH();
+        if (M > 0 || min_area > 0) {
+            hipLaunchKernelGGL(cc_select_kernel, dim3(np), dim3(256), 0, st, words, workspace, (const int*)n_comp + p0, (int)M, (int)min_area,
+                               comps ? (int*)comps + (int64_t)p0 * M * 6 : (int*)nullptr, n_kept ? (int*)n_kept + p0 : (int*)nullptr);
+            CVLM_CHECK_LAUNCH();
+        }
+        if (min_area > 0) {
+            hipLaunchKernelGGL(cc_keep_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, (const void*)workspace, (int)min_area,
+                               kept_bits + (int64_t)p0 * words, (int*)kept_area + p0, (int*)kept_box + 4 * (int64_t)p0);
+            CVLM_CHECK_LAUNCH();
+        }
+    }
+    return 0;
+}
+
+// The same passes on host memory, plane by plane and word by word, through the functions of components_logic.h.
+int cvlm_debug_mask_components_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t min_area,
+                                    int32_t* n_comp, int32_t* comps, int32_t* n_kept, uint32_t* kept_bits, int32_t* kept_area,
+                                    int32_t* kept_box) {
+    if (cc_bad_request(bits, P, H, W, connectivity, M, min_area, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)) return CVLM_E_BADARG;
+    const int64_t HW = (int64_t)H * W;
+    const int words = (int)(HW / 32), wpr = W / 32;
+    std::vector<char> mem((size_t)plane_ws_bytes(HW));
+    const PlaneWs ws = plane_ws(mem.data(), 0, HW);
+    for (int p = 0; p < P; ++p) {
+        const uint32_t* src = bits + (int64_t)p * words;
+        for (int wi = 0; wi < words; ++wi) cc_seed_word(src, wi, wpr, ws.parent, ws.area, ws.box);
+        for (int wi = 0; wi < words; ++wi) cc_join_word(src, wi, wpr, connectivity, ws.parent);
+        int n = 0;
+        for (int wi = 0; wi < words; ++wi) {
+            const uint32_t w = cc_unpack(src[wi]);
+            for (uint32_t rest = w; rest;) {
+                int s, e;
+                cc_next_run(w, rest, s, e);
+                const int me = wi * 32 + s, root = cc_find(ws.parent, me);
+                if (root == me) { ws.list[n++] = me; continue; }
+                ws.parent[me >> 1] = root;
+                const cc_box b = ws.box[me >> 1];
+                cc_box& r = ws.box[root >> 1];
+                ws.area[root >> 1] += e - s;
+                r.x0 = std::min(r.x0, b.x0); r.y0 = std::min(r.y0, b.y0); r.x1 = std::max(r.x1, b.x1); r.y1 = std::max(r.y1, b.y1);
+            }
+        }
+        n_comp[p] = n;
+        if (n_kept) {
+            int c = 0;
+            for (int i = 0; i < n; ++i) c += ws.area[ws.list[i] >> 1] >= min_area ? 1 : 0;
+            n_kept[p] = c;
+        }
+        uint64_t prev = ~0ull;
+        for (int m = 0; m < M; ++m) {
+            uint64_t best = 0;
+            for (int i = 0; i < n; ++i) {
+                const uint64_t key = cc_rank_key(ws.area[ws.list[i] >> 1], ws.list[i]);
+                if (key < prev && key > best) best = key;
+            }
+            int* row = comps + ((int64_t)p * M + m) * 6;
+            if (best) {
+                const int seed = cc_key_seed(best);
+                const cc_box b = ws.box[seed >> 1];
+                row[0] = (int)(best >> 32); row[1] = b.x0; row[2] = b.y0; row[3] = b.x1; row[4] = b.y1; row[5] = seed;
+            } else {
+                row[0] = 0; row[1] = row[2] = row[3] = row[4] = row[5] = -1;
+            }
+            prev = best;
+        }
+        if (min_area > 0) {
+            int a = 0, x0 = -1, y0 = -1, x1 = -1, y1 = -1;
+            for (int wi = 0; wi < words; ++wi) {
+                const uint32_t w = cc_unpack(src[wi]);
+                const uint32_t kept = w ? cc_keep_word(w, wi * 32, ws.parent, ws.area, min_area) : 0u;
+                kept_bits[(int64_t)p * words + wi] = cc_pack(kept);
+                if (!kept) continue;
+                const int y = wi / wpr, xw = (wi - y * wpr) * 32, lo = xw + __builtin_ctz(kept), hi = xw + 31 - __builtin_clz(kept);
+                a += __builtin_popcount(kept);
+                x0 = x0 < 0 ? lo : std::min(x0, lo); y0 = y0 < 0 ? y : y0;
+                x1 = std::max(x1, hi); y1 = y;
+            }
+            kept_area[p] = a;
+            kept_box[4 * p + 0] = x0; kept_box[4 * p + 1] = y0; kept_box[4 * p + 2] = x1; kept_box[4 * p + 3] = y1;
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

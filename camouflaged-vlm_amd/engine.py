@@ -1396,9 +1396,20 @@ class ClassHypotheses:
     area: InitVar[Optional[torch.Tensor]] = None
     box: InitVar[Optional[torch.Tensor]] = None
     inter: InitVar[Optional[torch.Tensor]] = None   # overlaps=True: (B, K, K) int32 |mask a AND mask b| per image, diagonal = area
+    # components= / min_area=, otherwise None; pseudo-fields like `mask_bits`, all int32 but kept_bits.  n_comp (B, K):
+    # connected regions of each mask; comps (B, K, M, 6): its M largest, descending, as (area, x0, y0, x1, y1, seed), filler rows
+    # (0, -1, -1, -1, -1, -1); with min_area >= 1 n_kept (B, K): regions of at least min_area pixels, kept_bits (B, K, S * S / 8) uint8:
+    # mask_bits without the smaller ones, kept_area (B, K) and kept_box (B, K, 4) of that.  `inter` stays the overlaps of mask_bits.
+    n_comp: InitVar[Optional[torch.Tensor]] = None
+    comps: InitVar[Optional[torch.Tensor]] = None
+    n_kept: InitVar[Optional[torch.Tensor]] = None
+    kept_bits: InitVar[Optional[torch.Tensor]] = None
+    kept_area: InitVar[Optional[torch.Tensor]] = None
+    kept_box: InitVar[Optional[torch.Tensor]] = None
 
-    def __post_init__(self, iou, mask_bits, area, box, inter):
+    def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box):
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
+        self.n_comp, self.comps, self.n_kept, self.kept_bits, self.kept_area, self.kept_box = n_comp, comps, n_kept, kept_bits, kept_area, kept_box
 
 
 @dataclass
@@ -1490,6 +1501,40 @@ def compact_request(*, masks="logits", overlaps=False, n: int, K: int, who: str 
     if overlaps and n * K > OVERLAP_MAXP:
         raise ValueError(f"{who}: overlaps=True takes at most {OVERLAP_MAXP} hypotheses in all (cvlm_mask_overlap), got {n} x {K}")
     return masks != "bits", masks != "logits", bool(overlaps)
+
+
+COMPONENTS_MAXM = 64              # rows of the table cvlm_mask_components selects
+COMPONENTS_WS_CAP = 256 << 20     # bytes of the "cls_comp" workspace at most; beyond it the entry walks the planes in rounds
+
+
+def components_request(*, components=None, min_area=0, connectivity=8, masks="bits", side: Optional[int] = None, who: str = "decode"):
+    """Every check of the components= / min_area= / connectivity= arguments of Cascade.infer_classes / decode / mask_components
+    (DESIGN.md §14), on the host, before anything is launched (ValueError) -> (asked for, M, min_area, connectivity).  components=None
+    with min_area=0 asks for nothing; components=0 asks for the counts without a table.  side: the width of the model's masks."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if components is not None and not (is_int(components) and 0 <= int(components) <= COMPONENTS_MAXM):
+        raise ValueError(f"{who}: components must be None or an int in [0, {COMPONENTS_MAXM}], got {components!r}")
+    if not (is_int(min_area) and int(min_area) >= 0):
+        raise ValueError(f"{who}: min_area must be a non-negative int, got {min_area!r}")
+    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
+        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
+    asked = components is not None or int(min_area) > 0
+    if asked and masks == "logits":
+        raise ValueError(f"{who}: components= / min_area= label packed masks: ask for masks='bits' or 'both'")
+    if asked and side is not None and side % 32 != 0:
+        raise ValueError(f"{who}: components= / min_area= need rows of whole 32-pixel words, the masks are {side} wide")
+    return asked, int(components or 0), int(min_area), int(connectivity)
+
+
+@dataclass
+class MaskComponents:
+    """Connected regions of N packed masks (Cascade.mask_components); every tensor int32 on the device but kept_bits."""
+    n_comp: torch.Tensor                    # (N,) regions per mask
+    comps: Optional[torch.Tensor]           # (N, M, 6) the M largest as (area, x0, y0, x1, y1, seed), descending; None with components=0
+    n_kept: Optional[torch.Tensor]          # min_area >= 1: (N,) regions of at least min_area pixels, otherwise None like the next three
+    kept_bits: Optional[torch.Tensor]       # (N, H * W / 8) uint8 the mask without the smaller regions
+    kept_area: Optional[torch.Tensor]       # (N,)
+    kept_box: Optional[torch.Tensor]        # (N, 4) inclusive (x0, y0, x1, y1), -1 for an empty result
 
 
 @dataclass
@@ -2008,9 +2053,56 @@ class Cascade(_Base):
         hip.mask_pack(planes, bits, area, box)
         return bits, area, box
 
+    # ---- connected components of packed masks -----------------------------------------------------------------------
+    def _component_outputs(self, lead: tuple, nbytes: int, comp):
+        """The result's own (n_comp, comps, n_kept, kept_bits, kept_area, kept_box) for planes of shape `lead`, None where not asked for."""
+        asked, M, min_area, _ = comp
+        if not asked:
+            return (None,) * 6
+        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
+        if min_area < 1:
+            return i32(), i32(M, 6) if M else None, None, None, None, None
+        return (i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32(), i32(4))
+
+    def _components(self, bits: torch.Tensor, H: int, W: int, comp, out, p0: int, p1: int) -> None:
+        """cvlm_mask_components of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's tensors `out`.  The
+        workspace "cls_comp" grows to what these planes want in flight, up to COMPONENTS_WS_CAP (and never below one plane's)."""
+        asked, M, min_area, connectivity = comp
+        if not asked:
+            return
+        want = min(hip.mask_components_workspace_bytes(p1 - p0, H, W), max(COMPONENTS_WS_CAP, hip.mask_components_workspace_bytes(1, H, W)))
+        ws = self.ws._get("u8", "cls_comp", want, torch.uint8, False)
+        rows = [None if t is None else t.view(-1, *t.shape[t.dim() - k:])[p0:p1] for t, k in zip(out, (0, 2, 0, 1, 0, 1))]   # k: own dims
+        hip.mask_components(bits, H, W, connectivity, min_area, ws, *rows)
+
+    def mask_components(self, bits: torch.Tensor, H: int, W: int, *, components: Optional[int] = 1, min_area: int = 0,
+                        connectivity: int = 8) -> "MaskComponents":
+        """Connected regions of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits (W % 32 == 0):
+        the number of regions, the `components` largest with their boxes and seeds and, with min_area >= 1, the masks without
+        their regions below min_area pixels, with area and box (cvlm_mask_components) -> MaskComponents.  Launches
+        on the caller's stream; ValueError before them for anything else."""
+        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, who="mask_components")
+        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
+                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"mask_components: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
+        H, W = int(H), int(W)
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
+                or not 1 <= int(bits.shape[0]) <= 65535:
+            raise ValueError(f"mask_components: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
+        if not bits.is_cuda:
+            raise ValueError("mask_components: bits must be on the device")
+        bits = bits.detach().contiguous()
+        if bits.data_ptr() % 4 != 0:
+            bits = bits.clone()
+        N = int(bits.shape[0])
+        out = self._component_outputs((N,), H * W // 8, (True,) + comp[1:])
+        self._components(bits, H, W, (True,) + comp[1:], out, 0, N)
+        return MaskComponents(*out)
+
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
-                      masks: str = "logits", overlaps: bool = False) -> ClassHypotheses:
+                      masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
+                      connectivity: int = 8) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2035,11 +2127,18 @@ class Cascade(_Base):
         cvlm_mask_overlap launch behind the last chunk.  "bits" returns no `masks` and no `edges`: the planes of a chunk live in a
         workspace buffer of class_chunk() planes, from which `_alpha` reads them, the edge maps are not resized, and no (B, K, S, S)
         tensor exists; the decoder's launches are those of the default call, so every other field keeps its bits.  The default,
-        masks="logits", overlaps=False, makes exactly the launches and allocations it made before."""
+        masks="logits", overlaps=False, makes exactly the launches and allocations it made before.
+        components= / min_area= / connectivity= (`components_request`, checked with the rest; they need masks="bits" or
+        "both"): components=M adds `n_comp` and `comps`, the connected regions of each packed mask and its M largest; min_area >= 1 adds
+        `n_kept`, `kept_bits`, `kept_area` and `kept_box`, the mask without its regions below min_area pixels -- cvlm_mask_components
+        on each chunk's rows of `mask_bits`, right behind cvlm_mask_pack.  A descriptor, not a rule: nothing is ranked or chosen between
+        hypotheses.  Without them the call makes exactly the launches and allocations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
         want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=B, K=K, who="infer_classes")
+        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size,
+                                  who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2058,6 +2157,7 @@ class Cascade(_Base):
             pred = torch.empty(B, K, dtype=torch.int64, device=dev)
             iou = torch.empty(B, K, device=dev) if quality else None
             compact = self._compact_outputs(B, K, want_bits, want_inter)
+            regions = self._component_outputs((B, K), S * S // 8, comp)
             mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
@@ -2075,15 +2175,18 @@ class Cascade(_Base):
                 self._mask_logits(fr, sp, n, out=planes, edge_out=eplanes, iou_out=iou.view(P)[p0:p1] if quality else None,
                                   edge_low=not want_logits)
                 self._pack_chunk(planes, compact, p0, p1)
+                if comp[0]:
+                    self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
                 self._class_stage2(planes, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
             if want_inter:
                 hip.mask_overlap(compact[0], compact[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact if t is not None))
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
-                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3])
+                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
+                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)))
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2119,7 +2222,8 @@ class Cascade(_Base):
     def decode(self, enc: EncodedImages, *, classes: Optional[torch.Tensor] = None, topk: Optional[int] = None,
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
-               overlaps: bool = False) -> ClassHypotheses:
+               overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
+               connectivity: int = 8) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2135,7 +2239,8 @@ class Cascade(_Base):
         from enc.pass1_features against it -- one head launch, no encoder launch, no CLIP forward --; the returned pass1_logits are
         the re-scored ones.
         masks= / overlaps=: as in `infer_classes`, checked by `compact_request` with the rest; with stage2=False and
-        masks="bits" the chunk's planes are only packed."""
+        masks="bits" the chunk's planes are only packed.
+        components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2147,6 +2252,7 @@ class Cascade(_Base):
         images, K, host_classes = decode_request(same_engine=enc.engine is self, B=enc.B, n_cls=n_cls, D=D, classes=classes, topk=topk,
                                                  text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
         want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=len(images), K=K)
+        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2177,6 +2283,7 @@ class Cascade(_Base):
         pred = torch.empty(n, K, dtype=torch.int64, device=dev) if stage2 else None
         iou = torch.empty(n, K, device=dev) if quality else None
         compact = self._compact_outputs(n, K, want_bits, want_inter)
+        regions = self._component_outputs((n, K), S * S // 8, comp)
         mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
         for p0 in range(0, P, chunk):
@@ -2190,6 +2297,8 @@ class Cascade(_Base):
             self._mask_logits((enc.state, of, B), sp, m, out=planes, edge_out=eplanes,
                               iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not want_logits)
             self._pack_chunk(planes, compact, p0, p1)
+            if comp[0]:
+                self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
             if stage2:
                 self._class_stage2(planes, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
         if want_inter:
@@ -2198,7 +2307,8 @@ class Cascade(_Base):
             iou.masked_fill_(cls < 0, float("nan"))
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
-                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3])
+                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
+                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)))
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

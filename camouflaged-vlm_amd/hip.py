@@ -59,6 +59,9 @@ _SIGNATURES = {
     "cvlm_mask_joint_hist": "i:ppiiipps",
     "cvlm_mask_pack": "i:pilippps",
     "cvlm_mask_overlap": "i:piilps",
+    "cvlm_mask_components_workspace_bytes": "l:iii",
+    "cvlm_mask_components": "i:piiiiiiplpppppps",
+    "cvlm_debug_mask_components_host": "i:piiiiiipppppp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -732,6 +735,57 @@ def mask_overlap(bits: torch.Tensor, inter: torch.Tensor) -> None:
     assert inter.dtype == torch.int32 and tuple(inter.shape) == (n, K, K) and inter.is_contiguous()
     _on_current_device(bits)
     _call("cvlm_mask_overlap", bits.data_ptr(), n, K, nbytes // 4, inter.data_ptr())
+
+
+def mask_components_workspace_bytes(P: int, H: int, W: int) -> int:
+    """Bytes cvlm_mask_components wants to keep all P planes of H x W in flight (14 per pixel and plane); P = 1: the minimum it takes."""
+    n = load().cvlm_mask_components_workspace_bytes(P, H, W)
+    if n < 0:
+        raise RuntimeError(f"cvlm_mask_components_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
+    return n
+
+
+def _components_args(bits: torch.Tensor, H: int, W: int, n_comp, comps, n_kept, kept_bits, kept_area, kept_box):
+    """Shape and dtype checks shared by `mask_components` and `mask_components_host` -> (P, M)."""
+    P = int(bits.shape[0])
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
+    assert n_comp.dtype == torch.int32 and tuple(n_comp.shape) == (P,) and n_comp.is_contiguous()
+    M = 0
+    if comps is not None:
+        M = int(comps.shape[1])
+        assert comps.dtype == torch.int32 and tuple(comps.shape) == (P, M, 6) and comps.is_contiguous()
+    assert len({t is None for t in (n_kept, kept_bits, kept_area, kept_box)}) == 1
+    if n_kept is not None:
+        assert n_kept.dtype == torch.int32 and tuple(n_kept.shape) == (P,) and n_kept.is_contiguous()
+        assert kept_bits.dtype == torch.uint8 and tuple(kept_bits.shape) == (P, H * W // 8) and kept_bits.is_contiguous()
+        assert kept_area.dtype == torch.int32 and tuple(kept_area.shape) == (P,) and kept_area.is_contiguous()
+        assert kept_box.dtype == torch.int32 and tuple(kept_box.shape) == (P, 4) and kept_box.is_contiguous()
+    return P, M
+
+
+def mask_components(bits: torch.Tensor, H: int, W: int, connectivity: int, min_area: int, workspace: torch.Tensor, n_comp: torch.Tensor,
+                    comps: Optional[torch.Tensor] = None, n_kept: Optional[torch.Tensor] = None, kept_bits: Optional[torch.Tensor] = None,
+                    kept_area: Optional[torch.Tensor] = None, kept_box: Optional[torch.Tensor] = None) -> None:
+    """bits uint8 [P][H * W / 8] (mask_pack's planes) -> n_comp int32 [P], comps int32 [P][M][6] = (area, x0, y0, x1, y1, seed) of the M
+    largest regions (M = comps.shape[1]; None: no table) and, with min_area >= 1, n_kept [P], kept_bits like bits, kept_area [P],
+    kept_box [P][4] (all four or none).  workspace: uint8, at least mask_components_workspace_bytes(1, H, W) bytes; fewer than P planes'
+    worth makes the entry walk the planes in rounds (include/cvlm.h)."""
+    P, M = _components_args(bits, H, W, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _on_current_device(bits)
+    _call("cvlm_mask_components", bits.data_ptr(), P, H, W, connectivity, M, min_area, workspace.data_ptr(), workspace.numel(),
+          n_comp.data_ptr(), _p(comps), _p(n_kept), _p(kept_bits), _p(kept_area), _p(kept_box))
+
+
+def mask_components_host(bits: torch.Tensor, H: int, W: int, connectivity: int, min_area: int, n_comp: torch.Tensor,
+                         comps: Optional[torch.Tensor] = None, n_kept: Optional[torch.Tensor] = None, kept_bits: Optional[torch.Tensor] = None,
+                         kept_area: Optional[torch.Tensor] = None, kept_box: Optional[torch.Tensor] = None) -> None:
+    """`mask_components` on HOST tensors without a device (cvlm_debug_mask_components_host: the kernels' per-thread functions run
+    sequentially on the CPU)."""
+    P, M = _components_args(bits, H, W, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_components_host", bits.data_ptr(), P, H, W, connectivity, M, min_area, n_comp.data_ptr(), _p(comps), _p(n_kept),
+          _p(kept_bits), _p(kept_area), _p(kept_box))
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:
