@@ -3,6 +3,7 @@
 // logic -- runs of a word, neighbour rule, find, union, kept-word filter -- is components_logic.h, shared with the sequential host
 // entry at the end of this file.  One thread per word in every pass but the selection; no thread ever waits for another workgroup:
 // every find / union loop lowers a label on each iteration.  All results are integer sums, minima, maxima and counts.
+// Holes (cvlm_mask_holes) are the same passes on the clear pixels at the dual connectivity: the hl_ kernels below.
 #include <algorithm>
 #include <vector>
 
@@ -55,11 +56,12 @@ __global__ __launch_bounds__(256) void cc_join_kernel(const uint32_t* __restrict
 // root are summed in registers first (a segmented scan over equal neighbours), and the last lane of each such group issues the five
 // atomics -- a region that fills the plane costs five atomics per wave and step, not per word.  Every lane stays in the loop until
 // the wave has no run left, so ballots and shuffles always see the whole wave.
-__global__ __launch_bounds__(256) void cc_flatten_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace,
-                                                         int* __restrict__ n_comp) {
+// FLIP = CC_SET: the set pixels (cvlm_mask_components); CC_CLEAR: the clear ones (cvlm_mask_holes), through the same scan.
+template <uint32_t FLIP>
+__device__ __forceinline__ void cc_flatten_body(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace, int* __restrict__ n_comp) {
     const int wi = blockIdx.x * 256 + threadIdx.x;
     const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
-    const uint32_t w = wi < words ? cc_unpack(bits[(int64_t)blockIdx.y * words + wi]) : 0u;
+    const uint32_t w = wi < words ? cc_fetch(bits + (int64_t)blockIdx.y * words, wi, FLIP) : 0u;
     const int wc = wi < words ? wi : 0;                             // past the plane's end: no run, and no index to overflow
     const int y = wc / wpr, xw = (wc - y * wpr) * 32, base = wc * 32;
     const int lane = threadIdx.x & 63;
@@ -104,6 +106,10 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(const uint32_t* __restr
             atomicMax(&ws.box[k].x1, x1); atomicMax(&ws.box[k].y1, y1);
         }
     }
+}
+__global__ __launch_bounds__(256) void cc_flatten_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace,
+                                                         int* __restrict__ n_comp) {
+    cc_flatten_body<CC_SET>(bits, words, wpr, workspace, n_comp);
 }
 
 __device__ __forceinline__ uint64_t max_u64(uint64_t a, uint64_t b) { return a > b ? a : b; }
@@ -207,6 +213,121 @@ __global__ __launch_bounds__(256) void cc_keep_kernel(const uint32_t* __restrict
     }
 }
 
+// ---- holes (cvlm_mask_holes): the passes above on the CLEAR pixels, at the dual connectivity -----------------------------
+// n_filled = 0, filled_area = 0 for all P planes; n_holes is written by the flatten pass's counter and then by the selection
+__global__ __launch_bounds__(256) void hl_init_kernel(int* __restrict__ n_holes, int* __restrict__ n_filled, int* __restrict__ filled_area, int P) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    n_holes[p] = 0;
+    if (n_filled) { n_filled[p] = 0; filled_area[p] = 0; }
+}
+
+__global__ __launch_bounds__(256) void hl_seed_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    if (wi >= words) return;
+    const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
+    cc_seed_word(bits + (int64_t)blockIdx.y * words, wi, wpr, ws.parent, ws.area, ws.box, CC_CLEAR);
+}
+
+// background_connectivity: the dual of the caller's
+__global__ __launch_bounds__(256) void hl_join_kernel(const uint32_t* __restrict__ bits, int words, int wpr, int background_connectivity,
+                                                      void* workspace) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    if (wi >= words) return;
+    const PlaneWs ws = plane_ws(workspace, blockIdx.y, (int64_t)words * 32);
+    cc_join_word(bits + (int64_t)blockIdx.y * words, wi, wpr, background_connectivity, ws.parent, CC_CLEAR);
+}
+
+// n_regions: the counter of the list of background roots, the border's region(s) among them
+__global__ __launch_bounds__(256) void hl_flatten_kernel(const uint32_t* __restrict__ bits, int words, int wpr, void* workspace,
+                                                         int* __restrict__ n_regions) {
+    cc_flatten_body<CC_CLEAR>(bits, words, wpr, workspace, n_regions);
+}
+
+// pass 4: one workgroup per plane.  n_holes arrives as the length of the list of background roots and leaves as the number of those
+// whose box misses the border; n_filled = the holes below fill_below; then cc_select_kernel's rounds over the holes alone.
+__global__ __launch_bounds__(256) void hl_select_kernel(int words, int wpr, void* workspace, int* __restrict__ n_holes, int M, int fill_below,
+                                                        int* __restrict__ holes, int* __restrict__ n_filled) {
+    __shared__ uint64_t red[4];
+    __shared__ int cnt[4][2];
+    const PlaneWs ws = plane_ws(workspace, blockIdx.x, (int64_t)words * 32);
+    const int H = words / wpr, W = wpr * 32;
+    const int n = n_holes[blockIdx.x];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int c = 0, f = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int k = ws.list[i] >> 1;
+        if (cc_box_inside(ws.box[k], H, W)) { ++c; f += ws.area[k] < fill_below ? 1 : 0; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); f += __shfl_xor(f, o, 64); }
+    if (lane == 0) { cnt[wave][0] = c; cnt[wave][1] = f; }
+    __syncthreads();                                                // every thread has read n by now
+    if (threadIdx.x == 0) {
+        n_holes[blockIdx.x] = cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0];
+        if (n_filled) n_filled[blockIdx.x] = cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
+    }
+    uint64_t prev = ~0ull;
+    for (int m = 0; m < M; ++m) {
+        uint64_t best = 0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int seed = ws.list[i];
+            const uint64_t key = cc_rank_key(ws.area[seed >> 1], seed);
+            if (key < prev && key > best && cc_box_inside(ws.box[seed >> 1], H, W)) best = key;
+        }
+        best = wave_max_u64(best);
+        __syncthreads();
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        best = max_u64(max_u64(red[0], red[1]), max_u64(red[2], red[3]));
+        if (threadIdx.x == 0) {
+            int* row = holes + ((int64_t)blockIdx.x * M + m) * 6;
+            if (best) {
+                const int seed = cc_key_seed(best);
+                const cc_box b = ws.box[seed >> 1];
+                row[0] = (int)(best >> 32); row[1] = b.x0; row[2] = b.y0; row[3] = b.x1; row[4] = b.y1; row[5] = seed;
+            } else {
+                row[0] = 0; row[1] = row[2] = row[3] = row[4] = row[5] = -1;
+            }
+        }
+        prev = best;
+    }
+}
+
+// pass 5: the plane with its holes below fill_below set, whole words in the stored order; its area reduced per workgroup to one atomic
+__global__ __launch_bounds__(256) void hl_fill_kernel(const uint32_t* __restrict__ bits, int words, int wpr, const void* workspace, int fill_below,
+                                                      uint32_t* __restrict__ filled_bits, int* __restrict__ filled_area) {
+    const int wi = blockIdx.x * 256 + threadIdx.x;
+    const PlaneWs ws = plane_ws(const_cast<void*>(workspace), blockIdx.y, (int64_t)words * 32);
+    int cnt = 0;
+    if (wi < words) {
+        const int64_t at = (int64_t)blockIdx.y * words + wi;
+        const uint32_t set = cc_unpack(bits[at]);
+        const uint32_t filled = ~set ? set | cc_fill_word(~set, wi * 32, ws.parent, ws.area, ws.box, words / wpr, wpr * 32, fill_below) : set;
+        filled_bits[at] = cc_pack(filled);
+        cnt = __popc(filled);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    __shared__ int red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = red[0] + red[1] + red[2] + red[3];
+        if (c) atomicAdd(&filled_area[blockIdx.y], c);
+    }
+}
+
+// what both hole entries refuse, workspace aside
+bool hl_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t fill_below,
+                    const int32_t* n_holes, const int32_t* holes, const int32_t* n_filled, const uint32_t* filled_bits, const int32_t* filled_area) {
+    if (!bits || !n_holes || (((uintptr_t)bits) & 3) != 0 || (((uintptr_t)filled_bits) & 3) != 0) return true;
+    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if ((connectivity != 4 && connectivity != 8) || M < 0 || M > CC_MAXM || (M > 0) != (holes != nullptr) || fill_below < 0) return true;
+    const bool fill = fill_below > 0;
+    return fill != (n_filled != nullptr) || fill != (filled_bits != nullptr) || fill != (filled_area != nullptr);
+}
+
 // what both entries refuse, workspace aside
 bool cc_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t min_area,
                     const int32_t* n_comp, const int32_t* comps, const int32_t* n_kept, const uint32_t* kept_bits, const int32_t* kept_area,
@@ -216,6 +337,28 @@ bool cc_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32
     if ((connectivity != 4 && connectivity != 8) || M < 0 || M > CC_MAXM || (M > 0) != (comps != nullptr) || min_area < 0) return true;
     const bool keep = min_area > 0;
     return keep != (n_kept != nullptr) || keep != (kept_bits != nullptr) || keep != (kept_area != nullptr) || keep != (kept_box != nullptr);
+}
+
+// Passes 1 to 3 of one plane on host memory, word by word, through the functions of components_logic.h -> the length of ws.list
+int host_label_plane(const uint32_t* src, int words, int wpr, int connectivity, const PlaneWs& ws, uint32_t flip) {
+    for (int wi = 0; wi < words; ++wi) cc_seed_word(src, wi, wpr, ws.parent, ws.area, ws.box, flip);
+    for (int wi = 0; wi < words; ++wi) cc_join_word(src, wi, wpr, connectivity, ws.parent, flip);
+    int n = 0;
+    for (int wi = 0; wi < words; ++wi) {
+        const uint32_t w = cc_fetch(src, wi, flip);
+        for (uint32_t rest = w; rest;) {
+            int s, e;
+            cc_next_run(w, rest, s, e);
+            const int me = wi * 32 + s, root = cc_find(ws.parent, me);
+            if (root == me) { ws.list[n++] = me; continue; }
+            ws.parent[me >> 1] = root;
+            const cc_box b = ws.box[me >> 1];
+            cc_box& r = ws.box[root >> 1];
+            ws.area[root >> 1] += e - s;
+            r.x0 = std::min(r.x0, b.x0); r.y0 = std::min(r.y0, b.y0); r.x1 = std::max(r.x1, b.x1); r.y1 = std::max(r.y1, b.y1);
+        }
+    }
+    return n;
 }
 
 }  // namespace
@@ -273,23 +416,7 @@ int cvlm_debug_mask_components_host(const uint32_t* bits, int32_t P, int32_t H, 
     const PlaneWs ws = plane_ws(mem.data(), 0, HW);
     for (int p = 0; p < P; ++p) {
         const uint32_t* src = bits + (int64_t)p * words;
-        for (int wi = 0; wi < words; ++wi) cc_seed_word(src, wi, wpr, ws.parent, ws.area, ws.box);
-        for (int wi = 0; wi < words; ++wi) cc_join_word(src, wi, wpr, connectivity, ws.parent);
-        int n = 0;
-        for (int wi = 0; wi < words; ++wi) {
-            const uint32_t w = cc_unpack(src[wi]);
-            for (uint32_t rest = w; rest;) {
-                int s, e;
-                cc_next_run(w, rest, s, e);
-                const int me = wi * 32 + s, root = cc_find(ws.parent, me);
-                if (root == me) { ws.list[n++] = me; continue; }
-                ws.parent[me >> 1] = root;
-                const cc_box b = ws.box[me >> 1];
-                cc_box& r = ws.box[root >> 1];
-                ws.area[root >> 1] += e - s;
-                r.x0 = std::min(r.x0, b.x0); r.y0 = std::min(r.y0, b.y0); r.x1 = std::max(r.x1, b.x1); r.y1 = std::max(r.y1, b.y1);
-            }
-        }
+        const int n = host_label_plane(src, words, wpr, connectivity, ws, CC_SET);
         n_comp[p] = n;
         if (n_kept) {
             int c = 0;
@@ -327,6 +454,91 @@ int cvlm_debug_mask_components_host(const uint32_t* bits, int32_t P, int32_t H, 
             }
             kept_area[p] = a;
             kept_box[4 * p + 0] = x0; kept_box[4 * p + 1] = y0; kept_box[4 * p + 2] = x1; kept_box[4 * p + 3] = y1;
+        }
+    }
+    return 0;
+}
+
+int64_t cvlm_mask_holes_workspace_bytes(int32_t P, int32_t H, int32_t W) { return cvlm_mask_components_workspace_bytes(P, H, W); }
+
+int cvlm_mask_holes(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t fill_below,
+                    void* workspace, int64_t workspace_bytes, int32_t* n_holes, int32_t* holes, int32_t* n_filled,
+                    uint32_t* filled_bits, int32_t* filled_area, void* stream) {
+    if (hl_bad_request(bits, P, H, W, connectivity, M, fill_below, n_holes, holes, n_filled, filled_bits, filled_area)) return CVLM_E_BADARG;
+    const int64_t HW = (int64_t)H * W;
+    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_ws_bytes(HW)) return CVLM_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int words = (int)(HW / 32), wpr = W / 32;
+    const int gx = (words + 255) / 256;
+    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_ws_bytes(HW));   // planes per round
+    hipLaunchKernelGGL(hl_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_holes, (int*)n_filled, (int*)filled_area, (int)P);
+    CVLM_CHECK_LAUNCH();
+    for (int p0 = 0; p0 < P; p0 += fit) {
+        const int np = std::min(fit, P - p0);
+        const uint32_t* src = bits + (int64_t)p0 * words;
+        hipLaunchKernelGGL(hl_seed_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, workspace);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(hl_join_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, cc_dual(connectivity), workspace);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(hl_flatten_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, workspace, (int*)n_holes + p0);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(hl_select_kernel, dim3(np), dim3(256), 0, st, words, wpr, workspace, (int*)n_holes + p0, (int)M, (int)fill_below,
+                           holes ? (int*)holes + (int64_t)p0 * M * 6 : (int*)nullptr, n_filled ? (int*)n_filled + p0 : (int*)nullptr);
+        CVLM_CHECK_LAUNCH();
+        if (fill_below > 0) {
+            hipLaunchKernelGGL(hl_fill_kernel, dim3(gx, np), dim3(256), 0, st, src, words, wpr, (const void*)workspace, (int)fill_below,
+                               filled_bits + (int64_t)p0 * words, (int*)filled_area + p0);
+            CVLM_CHECK_LAUNCH();
+        }
+    }
+    return 0;
+}
+
+// The same passes on host memory, as cvlm_debug_mask_components_host runs them.
+int cvlm_debug_mask_holes_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t fill_below,
+                               int32_t* n_holes, int32_t* holes, int32_t* n_filled, uint32_t* filled_bits, int32_t* filled_area) {
+    if (hl_bad_request(bits, P, H, W, connectivity, M, fill_below, n_holes, holes, n_filled, filled_bits, filled_area)) return CVLM_E_BADARG;
+    const int64_t HW = (int64_t)H * W;
+    const int words = (int)(HW / 32), wpr = W / 32;
+    std::vector<char> mem((size_t)plane_ws_bytes(HW));
+    const PlaneWs ws = plane_ws(mem.data(), 0, HW);
+    for (int p = 0; p < P; ++p) {
+        const uint32_t* src = bits + (int64_t)p * words;
+        const int n = host_label_plane(src, words, wpr, cc_dual(connectivity), ws, CC_CLEAR);
+        int c = 0, f = 0;
+        for (int i = 0; i < n; ++i) {
+            const int k = ws.list[i] >> 1;
+            if (cc_box_inside(ws.box[k], H, W)) { ++c; f += ws.area[k] < fill_below ? 1 : 0; }
+        }
+        n_holes[p] = c;
+        if (n_filled) n_filled[p] = f;
+        uint64_t prev = ~0ull;
+        for (int m = 0; m < M; ++m) {
+            uint64_t best = 0;
+            for (int i = 0; i < n; ++i) {
+                const int seed = ws.list[i];
+                const uint64_t key = cc_rank_key(ws.area[seed >> 1], seed);
+                if (key < prev && key > best && cc_box_inside(ws.box[seed >> 1], H, W)) best = key;
+            }
+            int* row = holes + ((int64_t)p * M + m) * 6;
+            if (best) {
+                const int seed = cc_key_seed(best);
+                const cc_box b = ws.box[seed >> 1];
+                row[0] = (int)(best >> 32); row[1] = b.x0; row[2] = b.y0; row[3] = b.x1; row[4] = b.y1; row[5] = seed;
+            } else {
+                row[0] = 0; row[1] = row[2] = row[3] = row[4] = row[5] = -1;
+            }
+            prev = best;
+        }
+        if (fill_below > 0) {
+            int a = 0;
+            for (int wi = 0; wi < words; ++wi) {
+                const uint32_t set = cc_unpack(src[wi]);
+                const uint32_t filled = ~set ? set | cc_fill_word(~set, wi * 32, ws.parent, ws.area, ws.box, H, W, fill_below) : set;
+                filled_bits[(int64_t)p * words + wi] = cc_pack(filled);
+                a += __builtin_popcount(filled);
+            }
+            filled_area[p] = a;
         }
     }
     return 0;

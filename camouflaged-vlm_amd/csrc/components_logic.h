@@ -1,6 +1,6 @@
 // Connected components of packed masks: the per-thread logic of cvlm_mask_components, written once for the device
 // kernels (components.hip) and for the sequential host entry cvlm_debug_mask_components_host, which runs these same functions word by
-// word on the CPU.  No HIP call, no allocation.
+// word on the CPU.  No HIP call, no allocation.  cvlm_mask_holes runs the same logic on the complement: see cc_fetch.
 //
 // A plane is H rows of W / 32 words; a word never straddles a row.  In memory a word is in numpy.packbits' order (what cvlm_mask_pack
 // stores); cc_unpack turns it into bit i = pixel i of the word, so that a horizontal RUN is a maximal group of consecutive set bits.
@@ -82,10 +82,17 @@ CC_HD void cc_union(int* parent, int a, int b) {
     }
 }
 
+// ---- the word fetch -------------------------------------------------------------------------------------------------------------------
+// Every pass reads its words through cc_fetch.  flip = 0 (CC_SET) labels the SET pixels, cvlm_mask_components; flip = ~0 (CC_CLEAR)
+// labels the CLEAR ones, the background regions of cvlm_mask_holes: the same runs, rule and forest on the complement.
+// W % 32 == 0, so a complemented word has no tail bits to mask.
+constexpr uint32_t CC_SET = 0u, CC_CLEAR = 0xffffffffu;
+CC_HD uint32_t cc_fetch(const uint32_t* bits, int wi, uint32_t flip) { return cc_unpack(bits[wi]) ^ flip; }
+
 // ---- pass 1: every run of word wi becomes a region of its own ----------------------------------------------------------------------------
 // bits: the plane's stored words; wi = y * wpr + c.
-CC_HD void cc_seed_word(const uint32_t* bits, int wi, int wpr, int* parent, int* area, cc_box* box) {
-    const uint32_t w = cc_unpack(bits[wi]);
+CC_HD void cc_seed_word(const uint32_t* bits, int wi, int wpr, int* parent, int* area, cc_box* box, uint32_t flip = CC_SET) {
+    const uint32_t w = cc_fetch(bits, wi, flip);
     const int y = wi / wpr, xw = (wi - y * wpr) * 32, base = wi * 32;
     for (uint32_t rest = w; rest;) {
         int s, e;
@@ -102,16 +109,16 @@ CC_HD void cc_seed_word(const uint32_t* bits, int wi, int wpr, int* parent, int*
 // the word above that it touches -- shares a column with (4), or a column or a diagonal (8: the run widened by one bit each way) --,
 // and (c) for 8, its corner bits with the facing corner bit of the words above-left and above-right, unless the word above already
 // links them.  Runs of the row above that continue into neighbouring words are joined there by (a) of their own words.
-CC_HD void cc_join_word(const uint32_t* bits, int wi, int wpr, int connectivity, int* parent) {
-    const uint32_t w = cc_unpack(bits[wi]);
+CC_HD void cc_join_word(const uint32_t* bits, int wi, int wpr, int connectivity, int* parent, uint32_t flip = CC_SET) {
+    const uint32_t w = cc_fetch(bits, wi, flip);
     if (!w) return;
     const int y = wi / wpr, c = wi - y * wpr, base = wi * 32;
     if ((w & 1u) && c > 0) {
-        const uint32_t left = cc_unpack(bits[wi - 1]);
+        const uint32_t left = cc_fetch(bits, wi - 1, flip);
         if (left >> 31) cc_union(parent, base, base - 32 + cc_run_start(left, 31));
     }
     if (y == 0) return;
-    const uint32_t up = cc_unpack(bits[wi - wpr]);
+    const uint32_t up = cc_fetch(bits, wi - wpr, flip);
     const int ubase = base - wpr * 32;
     for (uint32_t rest = w; rest && up;) {
         int s, e;
@@ -126,11 +133,11 @@ CC_HD void cc_join_word(const uint32_t* bits, int wi, int wpr, int connectivity,
     }
     if (connectivity != 8) return;
     if ((w & 1u) && c > 0 && !(up & 1u)) {
-        const uint32_t ul = cc_unpack(bits[wi - wpr - 1]);
+        const uint32_t ul = cc_fetch(bits, wi - wpr - 1, flip);
         if (ul >> 31) cc_union(parent, base, ubase - 32 + cc_run_start(ul, 31));
     }
     if ((w >> 31) && c < wpr - 1 && !(up >> 31)) {
-        const uint32_t ur = cc_unpack(bits[wi - wpr + 1]);
+        const uint32_t ur = cc_fetch(bits, wi - wpr + 1, flip);
         if (ur & 1u) cc_union(parent, base + cc_run_start(w, 31), ubase + 32);
     }
 }
@@ -151,4 +158,23 @@ CC_HD uint32_t cc_keep_word(uint32_t w, int base, const int* parent, const int* 
         if (area[root >> 1] < min_area) kept &= ~cc_span(s, e);
     }
     return kept;
+}
+
+// ---- holes ----------------------------------------------------------------------------------------------------------------
+// A background region is a hole exactly when its box misses the plane's border.
+CC_HD bool cc_box_inside(const cc_box& b, int H, int W) { return b.x0 > 0 && b.y0 > 0 && b.x1 < W - 1 && b.y1 < H - 1; }
+// The dual: foreground connectivity 8 makes the background 4-connected, and the reverse.
+CC_HD int cc_dual(int connectivity) { return connectivity == 8 ? 4 : 8; }
+
+// The bits of word wi that filling adds: every run of w = the word's CLEAR pixels whose region is a hole of fewer than fill_below
+// pixels.  parent is flat by now.
+CC_HD uint32_t cc_fill_word(uint32_t w, int base, const int* parent, const int* area, const cc_box* box, int H, int W, int fill_below) {
+    uint32_t add = 0u;
+    for (uint32_t rest = w; rest;) {
+        int s, e;
+        cc_next_run(w, rest, s, e);
+        const int k = parent[(base + s) >> 1] >> 1;
+        if (area[k] < fill_below && cc_box_inside(box[k], H, W)) add |= cc_span(s, e);
+    }
+    return add;
 }

@@ -1406,10 +1406,21 @@ class ClassHypotheses:
     kept_bits: InitVar[Optional[torch.Tensor]] = None
     kept_area: InitVar[Optional[torch.Tensor]] = None
     kept_box: InitVar[Optional[torch.Tensor]] = None
+    # holes= / fill_holes=, otherwise None; pseudo-fields like `n_comp`, all int32 but filled_bits.  n_holes (B, K): holes
+    # of each mask -- regions of its clear pixels that miss the border, connected at the dual of `connectivity`; holes (B, K, M, 6): its M
+    # largest in the row format of `comps`; with fill_holes >= 1 n_filled (B, K): holes of fewer than fill_holes pixels, filled_bits
+    # (B, K, S * S / 8) uint8: mask_bits with exactly those set, filled_area (B, K) of that.  `kept_*` and `inter` stay functions of mask_bits.
+    n_holes: InitVar[Optional[torch.Tensor]] = None
+    holes: InitVar[Optional[torch.Tensor]] = None
+    n_filled: InitVar[Optional[torch.Tensor]] = None
+    filled_bits: InitVar[Optional[torch.Tensor]] = None
+    filled_area: InitVar[Optional[torch.Tensor]] = None
 
-    def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box):
+    def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
+                      n_holes, holes, n_filled, filled_bits, filled_area):
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
         self.n_comp, self.comps, self.n_kept, self.kept_bits, self.kept_area, self.kept_box = n_comp, comps, n_kept, kept_bits, kept_area, kept_box
+        self.n_holes, self.holes, self.n_filled, self.filled_bits, self.filled_area = n_holes, holes, n_filled, filled_bits, filled_area
 
 
 @dataclass
@@ -1535,6 +1546,40 @@ class MaskComponents:
     kept_bits: Optional[torch.Tensor]       # (N, H * W / 8) uint8 the mask without the smaller regions
     kept_area: Optional[torch.Tensor]       # (N,)
     kept_box: Optional[torch.Tensor]        # (N, 4) inclusive (x0, y0, x1, y1), -1 for an empty result
+
+
+HOLES_MAXM = 64                   # rows of the table cvlm_mask_holes selects
+HOLE_FIELDS = ("n_holes", "holes", "n_filled", "filled_bits", "filled_area")
+
+
+def holes_request(*, holes=None, fill_holes=0, connectivity=8, masks="bits", side: Optional[int] = None, who: str = "decode"):
+    """Every check of the holes= / fill_holes= arguments of Cascade.infer_classes / decode / mask_holes, on the host,
+    before anything is launched (ValueError) -> (asked for, M, fill_below, connectivity).  holes=None with fill_holes=0 asks for nothing;
+    holes=0 asks for the counts without a table.  connectivity is the foreground's, shared with components=.  side: the width of the
+    model's masks."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if holes is not None and not (is_int(holes) and 0 <= int(holes) <= HOLES_MAXM):
+        raise ValueError(f"{who}: holes must be None or an int in [0, {HOLES_MAXM}], got {holes!r}")
+    if not (is_int(fill_holes) and 0 <= int(fill_holes) < 2 ** 31):
+        raise ValueError(f"{who}: fill_holes must be a non-negative int, got {fill_holes!r}")
+    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
+        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
+    asked = holes is not None or int(fill_holes) > 0
+    if asked and masks == "logits":
+        raise ValueError(f"{who}: holes= / fill_holes= label packed masks: ask for masks='bits' or 'both'")
+    if asked and side is not None and side % 32 != 0:
+        raise ValueError(f"{who}: holes= / fill_holes= need rows of whole 32-pixel words, the masks are {side} wide")
+    return asked, int(holes or 0), int(fill_holes), int(connectivity)
+
+
+@dataclass
+class MaskHoles:
+    """Holes of N packed masks (Cascade.mask_holes); every tensor int32 on the device but filled_bits."""
+    n_holes: torch.Tensor                   # (N,) holes per mask
+    holes: Optional[torch.Tensor]           # (N, M, 6) the M largest as (area, x0, y0, x1, y1, seed), descending; None with holes=0
+    n_filled: Optional[torch.Tensor]        # fill_holes >= 1: (N,) holes of fewer than fill_holes pixels, otherwise None like the next two
+    filled_bits: Optional[torch.Tensor]     # (N, H * W / 8) uint8 the mask with exactly those holes set
+    filled_area: Optional[torch.Tensor]     # (N,)
 
 
 @dataclass
@@ -2099,10 +2144,58 @@ class Cascade(_Base):
         self._components(bits, H, W, (True,) + comp[1:], out, 0, N)
         return MaskComponents(*out)
 
+    # ---- holes of packed masks ----------------------------------------------------------------------------------------
+    def _hole_outputs(self, lead: tuple, nbytes: int, hreq):
+        """The result's own (n_holes, holes, n_filled, filled_bits, filled_area) for planes of shape `lead`, None where not asked for."""
+        asked, M, fill_below, _ = hreq
+        if not asked:
+            return (None,) * 5
+        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
+        if fill_below < 1:
+            return i32(), i32(M, 6) if M else None, None, None, None
+        return i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32()
+
+    def _holes(self, bits: torch.Tensor, H: int, W: int, hreq, out, p0: int, p1: int) -> None:
+        """cvlm_mask_holes of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's tensors `out`.  The workspace
+        is `_components`' "cls_comp", grow-only under the same COMPONENTS_WS_CAP: the two entries are ordered on one stream."""
+        asked, M, fill_below, connectivity = hreq
+        if not asked:
+            return
+        want = min(hip.mask_holes_workspace_bytes(p1 - p0, H, W), max(COMPONENTS_WS_CAP, hip.mask_holes_workspace_bytes(1, H, W)))
+        ws = self.ws._get("u8", "cls_comp", want, torch.uint8, False)
+        rows = [None if t is None else t.view(-1, *t.shape[t.dim() - k:])[p0:p1] for t, k in zip(out, (0, 2, 0, 1, 0))]   # k: own dims
+        hip.mask_holes(bits, H, W, connectivity, fill_below, ws, *rows)
+
+    def mask_holes(self, bits: torch.Tensor, H: int, W: int, *, holes: Optional[int] = 1, fill_holes: int = 0,
+                   connectivity: int = 8) -> "MaskHoles":
+        """Holes of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits (W % 32 == 0): the number
+        of holes, the `holes` largest with their boxes and seeds and, with fill_holes >= 1, the masks with their holes of fewer than
+        fill_holes pixels set, with their area (cvlm_mask_holes) -> MaskHoles.  connectivity is the foreground's; the
+        clear pixels connect at its dual.  SAM's post-processing, fill then despeckle, is
+        mask_components(mask_holes(bits, H, W, fill_holes=t).filled_bits, H, W, min_area=t).  Launches on the caller's stream;
+        ValueError before them for anything else."""
+        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, who="mask_holes")
+        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
+                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"mask_holes: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
+        H, W = int(H), int(W)
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
+                or not 1 <= int(bits.shape[0]) <= 65535:
+            raise ValueError(f"mask_holes: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
+        if not bits.is_cuda:
+            raise ValueError("mask_holes: bits must be on the device")
+        bits = bits.detach().contiguous()
+        if bits.data_ptr() % 4 != 0:
+            bits = bits.clone()
+        N = int(bits.shape[0])
+        out = self._hole_outputs((N,), H * W // 8, (True,) + hreq[1:])
+        self._holes(bits, H, W, (True,) + hreq[1:], out, 0, N)
+        return MaskHoles(*out)
+
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
-                      connectivity: int = 8) -> ClassHypotheses:
+                      connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2132,13 +2225,21 @@ class Cascade(_Base):
         "both"): components=M adds `n_comp` and `comps`, the connected regions of each packed mask and its M largest; min_area >= 1 adds
         `n_kept`, `kept_bits`, `kept_area` and `kept_box`, the mask without its regions below min_area pixels -- cvlm_mask_components
         on each chunk's rows of `mask_bits`, right behind cvlm_mask_pack.  A descriptor, not a rule: nothing is ranked or chosen between
-        hypotheses.  Without them the call makes exactly the launches and allocations it made before."""
+        hypotheses.  Without them the call makes exactly the launches and allocations it made before.
+        holes= / fill_holes= (`holes_request`, checked with the rest; they need masks="bits" or "both" and share
+        connectivity=): holes=M adds `n_holes` and `holes`, the holes of each packed mask and its M largest; fill_holes >= 1 adds
+        `n_filled`, `filled_bits` and `filled_area`, the mask with its holes of fewer than fill_holes pixels set -- cvlm_mask_holes on
+        each chunk's rows of `mask_bits`, behind cvlm_mask_components.  Independent of components=: `kept_*` stay functions of
+        `mask_bits`; SAM's order, fill then despeckle, is mask_components(mask_holes(bits, ...).filled_bits, ...).  Without them the
+        call makes exactly the launches and allocations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
         want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=B, K=K, who="infer_classes")
         comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size,
                                   who="infer_classes")
+        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size,
+                             who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2158,6 +2259,7 @@ class Cascade(_Base):
             iou = torch.empty(B, K, device=dev) if quality else None
             compact = self._compact_outputs(B, K, want_bits, want_inter)
             regions = self._component_outputs((B, K), S * S // 8, comp)
+            pits = self._hole_outputs((B, K), S * S // 8, hreq)
             mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
@@ -2177,16 +2279,19 @@ class Cascade(_Base):
                 self._pack_chunk(planes, compact, p0, p1)
                 if comp[0]:
                     self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
+                if hreq[0]:
+                    self._holes(compact[0].view(P, -1)[p0:p1], S, S, hreq, pits, p0, p1)
                 self._class_stage2(planes, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
             if want_inter:
                 hip.mask_overlap(compact[0], compact[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions if t is not None))
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
-                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)))
+                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
+                               **dict(zip(HOLE_FIELDS, pits)))
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2223,7 +2328,7 @@ class Cascade(_Base):
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
-               connectivity: int = 8) -> ClassHypotheses:
+               connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2240,7 +2345,8 @@ class Cascade(_Base):
         the re-scored ones.
         masks= / overlaps=: as in `infer_classes`, checked by `compact_request` with the rest; with stage2=False and
         masks="bits" the chunk's planes are only packed.
-        components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest."""
+        components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest.
+        holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2253,6 +2359,7 @@ class Cascade(_Base):
                                                  text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
         want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=len(images), K=K)
         comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size)
+        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2284,6 +2391,7 @@ class Cascade(_Base):
         iou = torch.empty(n, K, device=dev) if quality else None
         compact = self._compact_outputs(n, K, want_bits, want_inter)
         regions = self._component_outputs((n, K), S * S // 8, comp)
+        pits = self._hole_outputs((n, K), S * S // 8, hreq)
         mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
         for p0 in range(0, P, chunk):
@@ -2299,6 +2407,8 @@ class Cascade(_Base):
             self._pack_chunk(planes, compact, p0, p1)
             if comp[0]:
                 self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
+            if hreq[0]:
+                self._holes(compact[0].view(P, -1)[p0:p1], S, S, hreq, pits, p0, p1)
             if stage2:
                 self._class_stage2(planes, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
         if want_inter:
@@ -2308,7 +2418,8 @@ class Cascade(_Base):
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
-                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)))
+                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
+                               **dict(zip(HOLE_FIELDS, pits)))
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

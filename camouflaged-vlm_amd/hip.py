@@ -62,6 +62,9 @@ _SIGNATURES = {
     "cvlm_mask_components_workspace_bytes": "l:iii",
     "cvlm_mask_components": "i:piiiiiiplpppppps",
     "cvlm_debug_mask_components_host": "i:piiiiiipppppp",
+    "cvlm_mask_holes_workspace_bytes": "l:iii",
+    "cvlm_mask_holes": "i:piiiiiiplppppps",
+    "cvlm_debug_mask_holes_host": "i:piiiiiippppp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -786,6 +789,56 @@ def mask_components_host(bits: torch.Tensor, H: int, W: int, connectivity: int, 
     assert not bits.is_cuda
     _call("cvlm_debug_mask_components_host", bits.data_ptr(), P, H, W, connectivity, M, min_area, n_comp.data_ptr(), _p(comps), _p(n_kept),
           _p(kept_bits), _p(kept_area), _p(kept_box))
+
+
+def mask_holes_workspace_bytes(P: int, H: int, W: int) -> int:
+    """Bytes cvlm_mask_holes wants to keep all P planes of H x W in flight (14 per pixel and plane); P = 1: the minimum it takes."""
+    n = load().cvlm_mask_holes_workspace_bytes(P, H, W)
+    if n < 0:
+        raise RuntimeError(f"cvlm_mask_holes_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
+    return n
+
+
+def _holes_args(bits: torch.Tensor, H: int, W: int, n_holes, holes, n_filled, filled_bits, filled_area):
+    """Shape and dtype checks shared by `mask_holes` and `mask_holes_host` -> (P, M)."""
+    P = int(bits.shape[0])
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
+    assert n_holes.dtype == torch.int32 and tuple(n_holes.shape) == (P,) and n_holes.is_contiguous()
+    M = 0
+    if holes is not None:
+        M = int(holes.shape[1])
+        assert holes.dtype == torch.int32 and tuple(holes.shape) == (P, M, 6) and holes.is_contiguous()
+    assert len({t is None for t in (n_filled, filled_bits, filled_area)}) == 1
+    if n_filled is not None:
+        assert n_filled.dtype == torch.int32 and tuple(n_filled.shape) == (P,) and n_filled.is_contiguous()
+        assert filled_bits.dtype == torch.uint8 and tuple(filled_bits.shape) == (P, H * W // 8) and filled_bits.is_contiguous()
+        assert filled_area.dtype == torch.int32 and tuple(filled_area.shape) == (P,) and filled_area.is_contiguous()
+    return P, M
+
+
+def mask_holes(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below: int, workspace: torch.Tensor, n_holes: torch.Tensor,
+               holes: Optional[torch.Tensor] = None, n_filled: Optional[torch.Tensor] = None, filled_bits: Optional[torch.Tensor] = None,
+               filled_area: Optional[torch.Tensor] = None) -> None:
+    """bits uint8 [P][H * W / 8] (mask_pack's planes) -> n_holes int32 [P], holes int32 [P][M][6] = (area, x0, y0, x1, y1, seed) of the M
+    largest holes (M = holes.shape[1]; None: no table) and, with fill_below >= 1, n_filled [P], filled_bits like bits, filled_area [P]
+    (all three or none).  connectivity is the FOREGROUND's; the clear pixels connect at its dual.  workspace: uint8, at least
+    mask_holes_workspace_bytes(1, H, W) bytes; fewer than P planes' worth makes the entry walk the planes in rounds (include/cvlm.h)."""
+    P, M = _holes_args(bits, H, W, n_holes, holes, n_filled, filled_bits, filled_area)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _on_current_device(bits)
+    _call("cvlm_mask_holes", bits.data_ptr(), P, H, W, connectivity, M, fill_below, workspace.data_ptr(), workspace.numel(),
+          n_holes.data_ptr(), _p(holes), _p(n_filled), _p(filled_bits), _p(filled_area))
+
+
+def mask_holes_host(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below: int, n_holes: torch.Tensor,
+                    holes: Optional[torch.Tensor] = None, n_filled: Optional[torch.Tensor] = None, filled_bits: Optional[torch.Tensor] = None,
+                    filled_area: Optional[torch.Tensor] = None) -> None:
+    """`mask_holes` on HOST tensors without a device (cvlm_debug_mask_holes_host: the kernels' per-thread functions run sequentially on
+    the CPU)."""
+    P, M = _holes_args(bits, H, W, n_holes, holes, n_filled, filled_bits, filled_area)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_holes_host", bits.data_ptr(), P, H, W, connectivity, M, fill_below, n_holes.data_ptr(), _p(holes), _p(n_filled),
+          _p(filled_bits), _p(filled_area))
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

@@ -520,6 +520,52 @@ int cvlm_debug_mask_components_host(const uint32_t* bits, int32_t P, int32_t H, 
                                     int32_t min_area, int32_t* n_comp, int32_t* comps, int32_t* n_kept, uint32_t* kept_bits,
                                     int32_t* kept_area, int32_t* kept_box);
 
+/* Holes of packed masks: how many holes a mask has, its M largest with their boxes, and the mask with its pinholes
+ * closed -- what the reference asks cv2.findContours(..., RETR_CCOMP) (GenericMask.has_holes, models/utils/visualizer.py:110-136) and
+ * what SAM's remove_small_regions(mask, area_thresh, "holes") does on the host.  The definition:
+ *   A HOLE of a plane is a connected region of its CLEAR pixels that contains no pixel of the plane's border (x = 0, x = W - 1,
+ *   y = 0, y = H - 1).  Clear pixels are connected at the DUAL of the foreground connectivity: connectivity = 8 (the default) makes
+ *   background regions 4-connected, and connectivity = 4 makes them 8-connected.  connectivity = 8 is the cv2.RETR_CCOMP hierarchy
+ *   and scipy.ndimage.binary_fill_holes with its default structure.  Regions never connect across a row end or across planes, as for
+ *   cvlm_mask_components.  A region misses the border exactly when its inclusive box satisfies x0 > 0, y0 > 0, x1 < W - 1 and
+ *   y1 < H - 1: the box the flatten pass already accumulates decides, and no second labelling is needed.  A hole lies inside the
+ *   mask's own box, so filling never changes `box`: no filled box is returned.
+ * bits u32 [P][H * W / 32]: P planes exactly as cvlm_mask_pack writes them, W % 32 == 0.  All outputs are int32 / whole words and are
+ * initialised by the call, so a launch sequence replays:
+ *   n_holes [P]       the number of holes of each plane;
+ *   holes [P][M][6]   the M largest holes in descending area, ties to the lower seed: (area, x0, y0, x1, y1, seed), the box inclusive,
+ *                     seed = the hole's lowest pixel index; rows past n_holes read (0, -1, -1, -1, -1, -1) -- the row format and
+ *                     the rules of `comps`.  0 <= M <= 64; holes is NULL exactly when M = 0;
+ *   with fill_below >= 1 (all three NULL exactly when fill_below = 0):
+ *   n_filled [P]      the number of holes of FEWER than fill_below pixels (strict, SAM's `s < area_thresh`);
+ *   filled_bits       [P][H * W / 32] the plane with exactly those holes set, whole words in the same bit order;
+ *   filled_area [P]   its number of set bits.  fill_below = 1 reproduces the input plane and cvlm_mask_pack's area; any
+ *                     fill_below >= H * W fills every hole.
+ * The passes are cvlm_mask_components' run on the complement: a thread owns a word and the runs of ~word are the background runs
+ * (W % 32 == 0: no tail bits to mask); run start i owns slot i >> 1; the join pass applies the neighbour rule at the dual
+ * connectivity; the flatten pass points every run at its root, adds lengths and boxes to the root by integer atomics after the
+ * in-register segmented sum across lanes that share a root (the border's region of a sparse mask fills the plane: five atomics per
+ * wave, not per word) and lists the roots; a one-workgroup-per-plane pass looks only at the roots whose box misses the border,
+ * counts n_holes and n_filled and selects the M rows by rounds of a block-wide maximum of (area, -seed); a last pass ORs into each
+ * word every background run whose root is a hole below fill_below, stores the word whole and reduces the area per workgroup to one
+ * atomic.  No thread waits for another workgroup, no cooperative launch; exact and reproducible whatever the schedule.  64-bit offsets.
+ * workspace: as cvlm_mask_components' -- caller-owned, 16-byte aligned, no initialisation needed; 14 bytes per pixel and plane keeps
+ * all P planes in flight, one plane is the minimum, with anything in between the launcher walks the planes in rounds.  No
+ * allocation, no synchronisation, no pointer kept.  cvlm_mask_holes_workspace_bytes returns -1 outside the bounds below.
+ * CVLM_E_BADARG, before anything touches the device: bits or n_holes NULL, bits or filled_bits not 4-byte aligned, P outside
+ * [1, 65535], H or W <= 0, W % 32 != 0, H * W >= 2^31, connectivity not 4 or 8, M outside [0, 64], holes without M or the reverse,
+ * fill_below < 0, any of the three fill pointers inconsistent with fill_below, a workspace that is NULL, not 16-byte aligned or below
+ * the one-plane minimum. */
+int64_t cvlm_mask_holes_workspace_bytes(int32_t P, int32_t H, int32_t W);
+int cvlm_mask_holes(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t fill_below,
+                    void* workspace, int64_t workspace_bytes, int32_t* n_holes, int32_t* holes, int32_t* n_filled,
+                    uint32_t* filled_bits, int32_t* filled_area, void* stream);
+/* Outside the ABI contract: cvlm_mask_holes on HOST memory, no stream and no workspace -- the same per-thread functions
+ * (csrc/components_logic.h) run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_holes_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M,
+                               int32_t fill_below, int32_t* n_holes, int32_t* holes, int32_t* n_filled, uint32_t* filled_bits,
+                               int32_t* filled_area);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
