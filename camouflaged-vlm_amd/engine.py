@@ -228,6 +228,11 @@ class SamEncoder(_Base):
                  prefix: str = "image_encoder."):
         super().__init__(device, precision)
         self.g = g
+        # The rows of the residual stream, of the LayerNorm and of the attention output are embed_dim halves long and are GEMM operands
+        # as they lie (lda = K), while Linear pads K to a multiple of 32: a width between two multiples (240 = 3 heads of 80) would make
+        # qkv / proj / lin1 read every row at the padded pitch -- wrong numbers, and M * (K - embed_dim) halves past the buffer's end
+        if g.embed_dim % 32 != 0:
+            raise ValueError(f"SamEncoder: embed_dim = {g.embed_dim} is not a multiple of 32 (the GEMMs' contraction step): this width is not supported")
         # residual stream / hidden rows as 128-byte-row images: CVLM_GEMM_AIL = 1 (default) always, b batches only (M > 4096), 0 never
         self.act_il = os.environ.get("CVLM_GEMM_AIL", "1") != "0"
         self.act_il_small = os.environ.get("CVLM_GEMM_AIL", "1") not in ("0", "b")

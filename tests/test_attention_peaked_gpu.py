@@ -255,7 +255,8 @@ MODE2 = ([(14, 20, f) for f in GAUSS + WPEAK + RAMP] + [(14, 64, f) for f in GAU
 @pytest.mark.parametrize("ws,G,fam", MODE2, ids=[f"w{w}-G{G}-{_fid(f)}" for w, G, f in MODE2])
 def test_window_relpos_peaked(hip, ws, G, fam):
     """Mode 2: window 14 takes win2 for (3, 3), (2, 2), (1, 2) (padded windows on G = 20 and 64), the generic kernel with 7 waves for (3, 1),
-    (1, 1); windows 8 (4 waves) and 12 (7 waves) the generic kernel for every split."""
+    (1, 1); windows 8 (4 waves) and 12 (7 waves) the generic kernel for every split.
+    Bn = 2, two heads: at most 100 pairs, one per workgroup of win2; tests/test_attention_window_pairs_gpu.py is where pairs follow each other."""
     Bn, Hh, hd = 2, 2, 80
     D, S = Hh * hd, G * G
     kernel_of = lambda sp: WIN2 if (ws == 14 and sp in ((3, 3), (2, 2), (1, 2))) else GENERIC64

@@ -766,10 +766,28 @@ def test_attention_is_deterministic_under_load(hip):
             assert all(torch.equal(outs[0], o) for o in outs[1:]), (sp, kw["mode"])
 
 
+def ref_window_attention(x, pad, rel_h, rel_w, Bn, G, ws, Hh, hd, scale):
+    """image_encoder.py:488-504, 507-553 on token-major qkv rows x [Bn*G*G][3*Hh*hd]: pad the token map with the pad vector (= qkv of a
+    zero token), partition, attend with the rel-pos bias, unpartition -> [Bn*G*G][Hh*hd], in the precision of its arguments"""
+    D = Hh * hd
+    Gp = -(-G // ws) * ws
+    xp = pad.expand(Bn, Gp, Gp, 3 * D).clone()
+    xp[:, :G, :G] = x.reshape(Bn, G, G, 3 * D)
+    nw = Gp // ws
+    win = xp.reshape(Bn, nw, ws, nw, ws, 3 * D).permute(0, 1, 3, 2, 4, 5).reshape(Bn * nw * nw, ws * ws, 3, Hh, hd)
+    win = win.permute(2, 0, 3, 1, 4).reshape(3, -1, ws * ws, hd)
+    bias = relpos_bias(win[0], rel_h, rel_w, ws)
+    o = ref_attention(win[0], win[1], win[2], scale, bias=bias)
+    o = o.reshape(Bn * nw * nw, Hh, ws * ws, hd).permute(0, 2, 1, 3).reshape(Bn, nw, nw, ws, ws, D)
+    return o.permute(0, 1, 3, 2, 4, 5).reshape(Bn, Gp, Gp, D)[:, :G, :G].reshape(Bn * G * G, D)
+
+
 @pytest.mark.parametrize("hm", [False, True])
 @pytest.mark.parametrize("split", [(3, 3), (2, 2), (1, 2), (3, 1), (1, 1)])
 @pytest.mark.parametrize("G", [20, 64])
 def test_attention_window_relpos(hip, G, split, hm):
+    """Bn = 2, two heads: 16 (G = 20) or 100 (G = 64) pairs, so every workgroup of the persistent kernel runs one pair and exits;
+    tests/test_attention_window_pairs_gpu.py is where pairs follow each other in a workgroup."""
     ws, Bn, Hh, hd = 14, 2, 2, 80
     D, S = Hh * hd, G * G
     qkv = rnd(Bn * S, 3 * D, seed=21)
@@ -781,18 +799,8 @@ def test_attention_window_relpos(hip, G, split, hm):
     Qk = hip.H2(torch.stack([to_head_major(Q.t[i], Bn, S, Hh, hd) for i in range(2)])) if hm else Q
     hip.attention(Qk, out, Bn, S, Hh, hd, mode=2, grid=G, window=ws, pad=P, rel_h=RH, rel_w=RW,
                   split_qk=split[0], split_pv=split[1], head_major=hm)
-    # reference: pad the token map with the pad vector (= qkv of a zero token), partition, attend, unpartition
-    x = Q.float().cpu().double().reshape(Bn, G, G, 3 * D)
-    Gp = -(-G // ws) * ws
-    xp = P.float().cpu().double().expand(Bn, Gp, Gp, 3 * D).clone()
-    xp[:, :G, :G] = x
-    nw = Gp // ws
-    win = xp.reshape(Bn, nw, ws, nw, ws, 3 * D).permute(0, 1, 3, 2, 4, 5).reshape(Bn * nw * nw, ws * ws, 3, Hh, hd)
-    win = win.permute(2, 0, 3, 1, 4).reshape(3, -1, ws * ws, hd)
-    bias = relpos_bias(win[0], RH.float().cpu().double(), RW.float().cpu().double(), ws)
-    o = ref_attention(win[0], win[1], win[2], hd ** -0.5, bias=bias)
-    o = o.reshape(Bn * nw * nw, Hh, ws * ws, hd).permute(0, 2, 1, 3).reshape(Bn, nw, nw, ws, ws, D)
-    o = o.permute(0, 1, 3, 2, 4, 5).reshape(Bn, Gp, Gp, D)[:, :G, :G].reshape(Bn * S, D)
+    o = ref_window_attention(Q.float().cpu().double(), P.float().cpu().double(), RH.float().cpu().double(), RW.float().cpu().double(),
+                             Bn, G, ws, Hh, hd, hd ** -0.5)
     err = relerr(out.float(), o)
     print(f"window attention G={G} split={split} head-major={hm}: {err:.2e}")
     assert err < SPLIT_TOL[split]
