@@ -485,6 +485,16 @@ __global__ __launch_bounds__(MH_TILE) void mask_head_multi_kernel(const float* _
     if (edge_prob) edge_prob[(int64_t)p * HW + pix0 + tid] = s;
 }
 
+// Source coordinate of an output index, align_corners = False, as float32 F.interpolate states it: scale * (o + 0.5) - 0.5 with the
+// product rounded before the subtraction, clamped at 0.  Left to the compiler the two became one fused multiply-add, whose
+// coordinate differs from the stated formula's in its last bit at some indices -- up to 2.6e-6 of a plane's maximum in the blend
+// (37 x 53 -> 101 x 67), and a different answer from one compiler to the next.
+__device__ __forceinline__ float bilinear_src(float scale, int o) {
+#pragma clang fp contract(off)
+    const float f = scale * ((float)o + 0.5f) - 0.5f;
+    return f < 0.f ? 0.f : f;
+}
+
 __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ in, int hin, int win,
                                                        float* __restrict__ out, int hout, int wout, int sigmoid_in,
                                                        int64_t total) {
@@ -492,8 +502,7 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int ox = (int)(i % wout), oy = (int)((i / wout) % hout);
         const int64_t n = i / ((int64_t)wout * hout);
-        float fy = sy * ((float)oy + 0.5f) - 0.5f; fy = fy < 0.f ? 0.f : fy;
-        float fx = sx * ((float)ox + 0.5f) - 0.5f; fx = fx < 0.f ? 0.f : fx;
+        const float fy = bilinear_src(sy, oy), fx = bilinear_src(sx, ox);
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = y0 + (y0 < hin - 1 ? 1 : 0), x1 = x0 + (x0 < win - 1 ? 1 : 0);
         const float ly = fy - (float)y0, lx = fx - (float)x0;
@@ -1258,7 +1267,8 @@ int cvlm_overwrite_rows(float* x, int32_t B, int32_t L, int32_t W, int32_t first
 
 int cvlm_gather_rows(const float* x, int32_t B, int32_t L, int32_t W, const int32_t* idx, int32_t fixed, float* out,
                      void* stream) {
-    if (!x || !out || (W & 3)) return CVLM_E_BADARG;
+    if (!x || !out || (W & 3) || B <= 0 || L <= 0 || W <= 0) return CVLM_E_BADARG;
+    if (!idx && (fixed < 0 || fixed >= L)) return CVLM_E_BADARG;     // the fixed row is the launcher's to check, idx[] the caller's
     const int64_t total = (int64_t)B * (W >> 2);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, L, W, idx,
                        fixed, out, total);
@@ -1268,7 +1278,8 @@ int cvlm_gather_rows(const float* x, int32_t B, int32_t L, int32_t W, const int3
 
 int cvlm_gather_rows_h2(const void* x_hi, const void* x_lo, float scale, int32_t B, int32_t L, int32_t W, const int32_t* idx,
                         int32_t fixed, float* out, void* stream) {
-    if (!x_hi || !x_lo || !out || (W & 3) || B <= 0 || L <= 0) return CVLM_E_BADARG;
+    if (!x_hi || !x_lo || !out || (W & 3) || B <= 0 || L <= 0 || W <= 0) return CVLM_E_BADARG;
+    if (!idx && (fixed < 0 || fixed >= L)) return CVLM_E_BADARG;
     const int64_t total = (int64_t)B * (W >> 2);
     hipLaunchKernelGGL(gather_rows_h2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const half_t*)x_hi,
                        (const half_t*)x_lo, scale, L, W, idx, fixed, out, total);

@@ -158,14 +158,21 @@ int cvlm_debug_gemm_plan(const cvlm_gemm_args* args, int have_ws, int cus, cvlm_
  * Replaces nn.LayerNorm (image_encoder.py:432,444; alpha_clip_rw/model.py:162-168;
  * transformer_maskdecoder_edge.py:180-212) and LayerNorm2d on NHWC rows (common.py:31-43).
  * x f32 [M][D] (ldx); add optional f32 [M % add_rows][D]; sum_out optional f32 (x + add);
- * outputs: out_f32 and/or h2 (ld = D). */
+ * outputs: out_f32 and/or h2 (ld = D); out_lo may be NULL (hi plane only).
+ * Aliasing: out_f32 may be x itself, or sum_out may (same base, ldx == D; one of the two, they hold different values) -- a wave
+ * holds its whole row in registers before its first store and no wave touches another's row; the engine normalises its streams in
+ * place this way, with and without `add`.  No other overlap between the buffers is allowed.
+ * CVLM_E_BADARG: x, gamma or beta NULL, M or D <= 0, D % 4 != 0, D > 2048, ldx % 4 != 0, add given with add_rows <= 0. */
 int cvlm_layernorm(const float* x, int64_t ldx, const float* add, int32_t add_rows, float* sum_out,
                    const float* gamma, const float* beta, float eps, int32_t act,
                    float* out_f32, void* out_hi, void* out_lo, int32_t M, int32_t D, void* stream);
 
 /* out = a + b[m % b_rows] (row-broadcast add), f32 and/or h2 outputs; scale applied to the sum.
  * Replaces the PE adds / `x + pos_embed` / `src + dense` (image_encoder.py:140,
- * transformer_maskdecoder_edge.py:177-209, mask_decoder_edge.py:157). */
+ * transformer_maskdecoder_edge.py:177-209, mask_decoder_edge.py:157).  b == NULL: out = a * scale.
+ * Aliasing: out_f32 may be a itself (every element is read and written by the same lane, once) -- `x + pos_embed` in place.
+ * No other overlap between the buffers is allowed.
+ * CVLM_E_BADARG: a NULL, M or D <= 0, D % 4 != 0, b given with b_rows <= 0. */
 int cvlm_add_rows(const float* a, const float* b, int32_t b_rows, float scale, float* out_f32,
                   void* out_hi, void* out_lo, int32_t M, int32_t D, void* stream);
 
@@ -337,11 +344,14 @@ int cvlm_overwrite_rows(float* x, int32_t B, int32_t L, int32_t W, int32_t first
 
 /* Gather one row per sequence: out[b] = x[b][idx[b]] (idx NULL -> row `fixed`), x f32 [B][L][W].
  * Replaces the CLS pick `x[:, 0, :]` (alpha_clip_rw/model.py:556) and the EOT pick
- * `x[arange, tokenized_prompts.argmax(-1)]` (cocotrainers/mapleAlphaCLIP.py:76). */
+ * `x[arange, tokenized_prompts.argmax(-1)]` (cocotrainers/mapleAlphaCLIP.py:76).
+ * idx int32 [B] on the device, entries in [0, L): the caller's contract (the launcher cannot see them).
+ * CVLM_E_BADARG: x or out NULL, B, L or W <= 0, W % 4 != 0, and with idx == NULL a `fixed` outside [0, L). */
 int cvlm_gather_rows(const float* x, int32_t B, int32_t L, int32_t W, const int32_t* idx, int32_t fixed,
                      float* out, void* stream);
 /* ABI 5: the same pick from a residual stream kept in h2 planes: out[b] = (hi + lo)[b][idx[b]] * scale (f32).  The class-token
- * rows at the end of the LayerNorm-folded CLIP vision tower (alpha_clip_rw/model.py:556). */
+ * rows at the end of the LayerNorm-folded CLIP vision tower (alpha_clip_rw/model.py:556).  idx and the refusals as for
+ * cvlm_gather_rows (both planes are required). */
 int cvlm_gather_rows_h2(const void* x_hi, const void* x_lo, float scale, int32_t B, int32_t L, int32_t W, const int32_t* idx,
                         int32_t fixed, float* out, void* stream);
 
