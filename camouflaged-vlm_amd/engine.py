@@ -1420,9 +1420,17 @@ class ClassHypotheses:
     n_filled: InitVar[Optional[torch.Tensor]] = None
     filled_bits: InitVar[Optional[torch.Tensor]] = None
     filled_area: InitVar[Optional[torch.Tensor]] = None
+    # band=r, otherwise None; pseudo-fields like `mask_bits`.  band_bits (B, K, S * S / 8) uint8: the edge band of each
+    # mask, dilation & ~erosion by the (2 r + 1)^2 square -- r = 2 is the band the reference trains its edge head against; band_area
+    # (B, K) int32: its set bits; with overlaps=True band_inter (B, K, K) int32 |band a AND band b| per image, diagonal = band_area.
+    # A function of mask_bits alone: `kept_*`, `filled_*`, `comps`, `holes` and `inter` stay what they were.
+    band_bits: InitVar[Optional[torch.Tensor]] = None
+    band_area: InitVar[Optional[torch.Tensor]] = None
+    band_inter: InitVar[Optional[torch.Tensor]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
-                      n_holes, holes, n_filled, filled_bits, filled_area):
+                      n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter):
+        self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
         self.n_comp, self.comps, self.n_kept, self.kept_bits, self.kept_area, self.kept_box = n_comp, comps, n_kept, kept_bits, kept_area, kept_box
         self.n_holes, self.holes, self.n_filled, self.filled_bits, self.filled_area = n_holes, holes, n_filled, filled_bits, filled_area
@@ -1585,6 +1593,37 @@ class MaskHoles:
     n_filled: Optional[torch.Tensor]        # fill_holes >= 1: (N,) holes of fewer than fill_holes pixels, otherwise None like the next two
     filled_bits: Optional[torch.Tensor]     # (N, H * W / 8) uint8 the mask with exactly those holes set
     filled_area: Optional[torch.Tensor]     # (N,)
+
+
+MORPH_MAXR = 16                   # the largest radius cvlm_mask_morph takes
+BAND_FIELDS = ("band_bits", "band_area", "band_inter")
+
+
+def morph_request(*, band=None, masks="bits", overlaps=False, side: Optional[int] = None, who: str = "decode"):
+    """Every check of the band= argument of Cascade.infer_classes / decode, on the host, before anything is launched
+    (ValueError) -> (asked for, radius, band_inter wanted).  band=None asks for nothing; band=r asks for the edge band by the
+    (2 r + 1)^2 square, and with overlaps=True for the bands' pairwise intersections as well.  side: the width of the model's masks."""
+    if band is None:
+        return False, 0, False
+    if isinstance(band, (bool, np.bool_)) or not isinstance(band, (int, np.integer)) or not 1 <= int(band) <= MORPH_MAXR:
+        raise ValueError(f"{who}: band must be None or an int in [1, {MORPH_MAXR}], got {band!r}")
+    if masks == "logits":
+        raise ValueError(f"{who}: band= is derived from packed masks: ask for masks='bits' or 'both'")
+    if side is not None and side % 32 != 0:
+        raise ValueError(f"{who}: band= needs rows of whole 32-pixel words, the masks are {side} wide")
+    return True, int(band), bool(overlaps)
+
+
+@dataclass
+class MaskMorph:
+    """Dilation, erosion and edge band of N packed masks (Cascade.mask_morph): planes uint8 (N, H * W / 8), areas int32
+    (N,), on the device; a pair that was not asked for is None."""
+    dil_bits: Optional[torch.Tensor]
+    dil_area: Optional[torch.Tensor]
+    ero_bits: Optional[torch.Tensor]
+    ero_area: Optional[torch.Tensor]
+    band_bits: Optional[torch.Tensor]
+    band_area: Optional[torch.Tensor]
 
 
 @dataclass
@@ -2197,10 +2236,64 @@ class Cascade(_Base):
         self._holes(bits, H, W, (True,) + hreq[1:], out, 0, N)
         return MaskHoles(*out)
 
+    # ---- morphology of packed masks -----------------------------------------------------------------------------------
+    def _band_outputs(self, n: int, K: int, nbytes: int, mreq):
+        """The result's own (band_bits, band_area, band_inter) for n x K hypotheses, None where not asked for."""
+        asked, _, want_inter = mreq
+        if not asked:
+            return None, None, None
+        dev = self.device
+        return (torch.empty(n, K, nbytes, dtype=torch.uint8, device=dev), torch.empty(n, K, dtype=torch.int32, device=dev),
+                torch.empty(n, K, K, dtype=torch.int32, device=dev) if want_inter else None)
+
+    @staticmethod
+    def _band(bits: torch.Tensor, H: int, W: int, mreq, out, p0: int, p1: int) -> None:
+        """cvlm_mask_morph, band only, of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's band_bits /
+        band_area.  No workspace."""
+        band_bits, band_area, _ = out
+        hip.mask_morph(bits, H, W, mreq[1], band_bits=band_bits.view(-1, band_bits.shape[-1])[p0:p1], band_area=band_area.view(-1)[p0:p1])
+
+    def mask_morph(self, bits: torch.Tensor, H: int, W: int, *, radius: int = 2, dilate: bool = False, erode: bool = False,
+                   band: bool = True) -> "MaskMorph":
+        """Dilation, erosion and edge band = dilation & ~erosion of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g.
+        `pack_masks`' bits (W % 32 == 0), by the (2 radius + 1)^2 square, 1 <= radius <= 16, each with its area (cvlm_mask_morph,
+        DESIGN.md §16) -> MaskMorph, None where an output was not asked for.  Pixels outside the plane are clear to dilation and set to
+        erosion, as max_pool2d's padding has it: radius=2 is the band the reference trains its edge head against.  Opening and closing
+        are compositions through this utility: opening = mask_morph(mask_morph(bits, ..., erode=True, band=False).ero_bits, ...,
+        dilate=True, band=False).dil_bits, closing the reverse; a SAM-style chain is
+        mask_components(mask_holes(mask_morph(bits, H, W, dilate=True, band=False).dil_bits, H, W, fill_holes=t).filled_bits, H, W,
+        min_area=t).  Launches on the caller's stream; ValueError before them for anything else."""
+        if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MORPH_MAXR:
+            raise ValueError(f"mask_morph: radius must be an int in [1, {MORPH_MAXR}], got {radius!r}")
+        for name, v in (("dilate", dilate), ("erode", erode), ("band", band)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"mask_morph: {name} must be a bool, got {type(v).__name__}")
+        if not (dilate or erode or band):
+            raise ValueError("mask_morph: nothing asked for: at least one of dilate, erode and band")
+        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
+                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"mask_morph: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
+        H, W = int(H), int(W)
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
+                or not 1 <= int(bits.shape[0]) <= 65535:
+            raise ValueError(f"mask_morph: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
+        if not bits.is_cuda:
+            raise ValueError("mask_morph: bits must be on the device")
+        bits = bits.detach().contiguous()
+        if bits.data_ptr() % 4 != 0:
+            bits = bits.clone()
+        N = int(bits.shape[0])
+        out = []
+        for asked in (dilate, erode, band):
+            out += [torch.empty_like(bits), torch.empty(N, dtype=torch.int32, device=bits.device)] if asked else [None, None]
+        hip.mask_morph(bits, H, W, int(radius), *out)
+        return MaskMorph(*out)
+
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
-                      connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0) -> ClassHypotheses:
+                      connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
+                      band: Optional[int] = None) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2236,7 +2329,14 @@ class Cascade(_Base):
         `n_filled`, `filled_bits` and `filled_area`, the mask with its holes of fewer than fill_holes pixels set -- cvlm_mask_holes on
         each chunk's rows of `mask_bits`, behind cvlm_mask_components.  Independent of components=: `kept_*` stay functions of
         `mask_bits`; SAM's order, fill then despeckle, is mask_components(mask_holes(bits, ...).filled_bits, ...).  Without them the
-        call makes exactly the launches and allocations it made before."""
+        call makes exactly the launches and allocations it made before.
+        band=r (`morph_request`, checked with the rest; needs masks="bits" or "both"): adds `band_bits` and `band_area`,
+        the edge band of each packed mask -- dilation & ~erosion by the (2 r + 1)^2 square, r = 2 the band the reference trains its
+        edge head against -- by cvlm_mask_morph on each chunk's rows of `mask_bits`, right behind cvlm_mask_pack, into the result's own
+        tensors: no workspace.  With overlaps=True also `band_inter`, the bands' pairwise intersections, one more cvlm_mask_overlap
+        launch behind the last chunk: boundary agreement of two hypotheses is band_inter / (band_area_a + band_area_b - band_inter),
+        and the caller divides.  Independent of components= and holes=.  Without it the call makes exactly the launches and
+        allocations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
@@ -2245,6 +2345,7 @@ class Cascade(_Base):
                                   who="infer_classes")
         hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size,
                              who="infer_classes")
+        mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size, who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2265,6 +2366,7 @@ class Cascade(_Base):
             compact = self._compact_outputs(B, K, want_bits, want_inter)
             regions = self._component_outputs((B, K), S * S // 8, comp)
             pits = self._hole_outputs((B, K), S * S // 8, hreq)
+            bands = self._band_outputs(B, K, S * S // 8, mreq)
             mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
@@ -2282,6 +2384,8 @@ class Cascade(_Base):
                 self._mask_logits(fr, sp, n, out=planes, edge_out=eplanes, iou_out=iou.view(P)[p0:p1] if quality else None,
                                   edge_low=not want_logits)
                 self._pack_chunk(planes, compact, p0, p1)
+                if mreq[0]:
+                    self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
                 if comp[0]:
                     self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
                 if hreq[0]:
@@ -2289,14 +2393,16 @@ class Cascade(_Base):
                 self._class_stage2(planes, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
             if want_inter:
                 hip.mask_overlap(compact[0], compact[3])
+            if mreq[2]:
+                hip.mask_overlap(bands[0], bands[2])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits if t is not None))
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)))
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2333,7 +2439,7 @@ class Cascade(_Base):
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
-               connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0) -> ClassHypotheses:
+               connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2351,7 +2457,8 @@ class Cascade(_Base):
         masks= / overlaps=: as in `infer_classes`, checked by `compact_request` with the rest; with stage2=False and
         masks="bits" the chunk's planes are only packed.
         components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest.
-        holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest."""
+        holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest.
+        band=: as in `infer_classes`, checked by `morph_request` with the rest."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2365,6 +2472,7 @@ class Cascade(_Base):
         want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=len(images), K=K)
         comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size)
+        mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2397,6 +2505,7 @@ class Cascade(_Base):
         compact = self._compact_outputs(n, K, want_bits, want_inter)
         regions = self._component_outputs((n, K), S * S // 8, comp)
         pits = self._hole_outputs((n, K), S * S // 8, hreq)
+        bands = self._band_outputs(n, K, S * S // 8, mreq)
         mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
         for p0 in range(0, P, chunk):
@@ -2410,6 +2519,8 @@ class Cascade(_Base):
             self._mask_logits((enc.state, of, B), sp, m, out=planes, edge_out=eplanes,
                               iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not want_logits)
             self._pack_chunk(planes, compact, p0, p1)
+            if mreq[0]:
+                self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
             if comp[0]:
                 self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
             if hreq[0]:
@@ -2418,13 +2529,15 @@ class Cascade(_Base):
                 self._class_stage2(planes, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
         if want_inter:
             hip.mask_overlap(compact[0], compact[3])
+        if mreq[2]:
+            hip.mask_overlap(bands[0], bands[2])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)))
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

@@ -65,6 +65,8 @@ _SIGNATURES = {
     "cvlm_mask_holes_workspace_bytes": "l:iii",
     "cvlm_mask_holes": "i:piiiiiiplppppps",
     "cvlm_debug_mask_holes_host": "i:piiiiiippppp",
+    "cvlm_mask_morph": "i:piiiipppppps",
+    "cvlm_debug_mask_morph_host": "i:piiiipppppp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -839,6 +841,42 @@ def mask_holes_host(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_
     assert not bits.is_cuda
     _call("cvlm_debug_mask_holes_host", bits.data_ptr(), P, H, W, connectivity, M, fill_below, n_holes.data_ptr(), _p(holes), _p(n_filled),
           _p(filled_bits), _p(filled_area))
+
+
+def _morph_args(bits: torch.Tensor, H: int, W: int, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area) -> int:
+    """Shape and dtype checks shared by `mask_morph` and `mask_morph_host` -> P."""
+    P = int(bits.shape[0])
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
+    for plane, area in ((dil_bits, dil_area), (ero_bits, ero_area), (band_bits, band_area)):
+        assert (plane is None) == (area is None)
+        if plane is not None:
+            assert plane.dtype == torch.uint8 and tuple(plane.shape) == (P, H * W // 8) and plane.is_contiguous()
+            assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+            assert plane.device == bits.device and area.device == bits.device
+    return P
+
+
+def mask_morph(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: Optional[torch.Tensor] = None,
+               dil_area: Optional[torch.Tensor] = None, ero_bits: Optional[torch.Tensor] = None, ero_area: Optional[torch.Tensor] = None,
+               band_bits: Optional[torch.Tensor] = None, band_area: Optional[torch.Tensor] = None) -> None:
+    """bits uint8 [P][H * W / 8] (mask_pack's planes) -> dilation, erosion and band = dil & ~ero by the (2 * radius + 1)^2 square, each
+    a pair (planes like bits, popcount int32 [P]); a pair is given whole or not at all, at least one is asked for, and no output may
+    overlap the input or another output.  Pixels outside the plane are clear to dilation and set to erosion (include/cvlm.h)."""
+    P = _morph_args(bits, H, W, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area)
+    _on_current_device(bits)
+    _call("cvlm_mask_morph", bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area), _p(band_bits),
+          _p(band_area))
+
+
+def mask_morph_host(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: Optional[torch.Tensor] = None,
+                    dil_area: Optional[torch.Tensor] = None, ero_bits: Optional[torch.Tensor] = None, ero_area: Optional[torch.Tensor] = None,
+                    band_bits: Optional[torch.Tensor] = None, band_area: Optional[torch.Tensor] = None) -> None:
+    """`mask_morph` on HOST tensors without a device (cvlm_debug_mask_morph_host: the kernel's per-thread functions run sequentially on
+    the CPU)."""
+    P = _morph_args(bits, H, W, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_morph_host", bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area),
+          _p(band_bits), _p(band_area))
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

@@ -576,6 +576,37 @@ int cvlm_debug_mask_holes_host(const uint32_t* bits, int32_t P, int32_t H, int32
                                int32_t fill_below, int32_t* n_holes, int32_t* holes, int32_t* n_filled, uint32_t* filled_bits,
                                int32_t* filled_area);
 
+/* Morphology of packed masks: dilation, erosion and the edge band of a mask -- what the reference derives its edge
+ * target from (models/sam_maskdecoder_edge.py:441-445: two max_pool2d of kernel 5, stride 1, padding 2, band = dilated - eroded > 0)
+ * and what cv2.dilate / cv2.erode do on the host (datasets/de_transform.py:20-30).  The definition:
+ *   The structuring element is the (2 * radius + 1)^2 square, 1 <= radius <= 16.  N(y, x) is the set of pixels (y', x') INSIDE the
+ *   plane with |y - y'| <= radius and |x - x'| <= radius.  dil(y, x) = OR of the plane over N(y, x), ero(y, x) = AND of the plane over
+ *   N(y, x), band = dil & ~ero.  Pixels outside the plane influence neither operator: dilation sees them clear and erosion sees them
+ *   set, as max_pool2d's -inf padding does; radius = 2 is the reference's band.  ero is a subset of the plane and the plane a subset of
+ *   dil; ero(X) = ~dil(~X); nothing wraps from x = W - 1 to x = 0 of the next row and nothing crosses from one plane into the next.
+ * bits u32 [P][H * W / 32]: P planes exactly as cvlm_mask_pack writes them (pixel i = y * W + x is bit 7 - (i & 7) of byte i >> 3),
+ * W % 32 == 0 so that a word never straddles a row.  Three output pairs, each a plane array like `bits` and its popcount per plane
+ * int32 [P]: (dil_bits, dil_area), (ero_bits, ero_area), (band_bits, band_area).  Both pointers of a pair are NULL or neither is; at
+ * least one pair must be asked for; band may be asked for alone, and then neither dil nor ero is stored.  The areas are initialised
+ * by the call (an init launch zeroes them), so a launch sequence replays.
+ * One kernel, grid (tile of 16 word columns x 128 rows, plane): a workgroup runs the horizontal pass of its tile's rows and of
+ * `radius` halo rows above and below -- the 96-pixel window left | centre | right ORed with itself shifted by 1 .. radius columns each
+ * way by doubling, on the word for dilation and on its complement for erosion, words beyond a row's end as 0 to both -- and stages the
+ * two results of every word in LDS; the vertical pass ORs the dilated and ANDs the eroded words over the rows max(0, y - radius) ..
+ * min(H - 1, y + radius), clipped at the plane's first and last row instead of filling halo rows.  16-byte loads where bits is 16-byte
+ * aligned and W % 128 == 0, element loads otherwise.  Words are stored whole; no atomics on the planes; the areas are __popc sums
+ * reduced by wave shuffles and LDS to at most one integer atomic per output, workgroup and plane: exact and reproducible whatever the
+ * schedule.  64-bit offsets.  No workspace, no allocation, no synchronisation, no pointer kept.
+ * CVLM_E_BADARG, before anything touches the device: bits NULL, any plane pointer not 4-byte aligned, P outside [1, 65535], H or
+ * W <= 0, W % 32 != 0, H * W >= 2^31, radius outside [1, 16], no output pair asked for, a pair with one NULL, an output plane range
+ * that intersects the input's or another output's (the kernel reads halo rows: it cannot run in place). */
+int cvlm_mask_morph(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t radius, uint32_t* dil_bits, int32_t* dil_area,
+                    uint32_t* ero_bits, int32_t* ero_area, uint32_t* band_bits, int32_t* band_area, void* stream);
+/* Outside the ABI contract: cvlm_mask_morph on HOST memory, no stream -- the same per-thread functions (csrc/morph_logic.h) run
+ * sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_morph_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t radius, uint32_t* dil_bits,
+                               int32_t* dil_area, uint32_t* ero_bits, int32_t* ero_area, uint32_t* band_bits, int32_t* band_area);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
