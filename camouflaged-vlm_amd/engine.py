@@ -1427,9 +1427,21 @@ class ClassHypotheses:
     band_bits: InitVar[Optional[torch.Tensor]] = None
     band_area: InitVar[Optional[torch.Tensor]] = None
     band_inter: InitVar[Optional[torch.Tensor]] = None
+    # edge_threshold=t, otherwise None; pseudo-fields like `mask_bits`.  edge_bits (B, K, S * S / 8) uint8: the edge head's
+    # probability map of each hypothesis, resized from the decoder's low-resolution map and compared `> t` in one kernel (cvlm_edge_pack;
+    # `edges` is never materialised for it); edge_area (B, K) int32: its set bits; with band=r edge_band (B, K) int32 = |edge_bits AND
+    # band_bits| -- edge_band / edge_area is the share of the predicted edge on the mask's band, edge_band / band_area the share of the
+    # band it covers, 2 edge_band / (edge_area + band_area) the hard form of the reference's edge Dice; with overlaps=True edge_inter
+    # (B, K, K) int32 |edge a AND edge b| per image, diagonal = edge_area.  A hypothesis of class -1 has zero bits and zero counts.
+    edge_bits: InitVar[Optional[torch.Tensor]] = None
+    edge_area: InitVar[Optional[torch.Tensor]] = None
+    edge_band: InitVar[Optional[torch.Tensor]] = None
+    edge_inter: InitVar[Optional[torch.Tensor]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
-                      n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter):
+                      n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter,
+                      edge_bits, edge_area, edge_band, edge_inter):
+        self.edge_bits, self.edge_area, self.edge_band, self.edge_inter = edge_bits, edge_area, edge_band, edge_inter
         self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
         self.n_comp, self.comps, self.n_kept, self.kept_bits, self.kept_area, self.kept_box = n_comp, comps, n_kept, kept_bits, kept_area, kept_box
@@ -1624,6 +1636,45 @@ class MaskMorph:
     ero_area: Optional[torch.Tensor]
     band_bits: Optional[torch.Tensor]
     band_area: Optional[torch.Tensor]
+
+
+EDGE_FIELDS = ("edge_bits", "edge_area", "edge_band", "edge_inter")
+
+
+def _edge_threshold(edge_threshold, who: str) -> float:
+    """The threshold as the float32 the kernel compares against, or ValueError: a real number (no bool, no NaN) strictly between 0
+    and 1 whose float32 rounding is strictly between 0 and 1 as well."""
+    if isinstance(edge_threshold, (bool, np.bool_)) or not isinstance(edge_threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}: edge_threshold must be a real number strictly between 0 and 1, got {edge_threshold!r}")
+    t = float(edge_threshold)
+    with np.errstate(over="ignore", under="ignore"):
+        t32 = float(np.float32(t))
+    if not (0.0 < t < 1.0 and 0.0 < t32 < 1.0):                      # NaN fails every comparison
+        raise ValueError(f"{who}: edge_threshold must lie strictly between 0 and 1, in float32 as well, got {edge_threshold!r}")
+    return t32
+
+
+def edge_request(*, edge_threshold=None, masks="bits", overlaps=False, band=None, side: Optional[int] = None, who: str = "decode"):
+    """Every check of the edge_threshold= argument of Cascade.infer_classes / decode, on the host, before anything is
+    launched (ValueError) -> (asked for, the threshold as float32's value, edge_band wanted, edge_inter wanted).  None asks for
+    nothing.  The packed edge map sits beside packed masks -- masks="bits" or "both" --; with band= the call also counts the edge
+    pixels on each mask's band, with overlaps=True the pairwise intersections of the edge maps.  side: the width of the model's masks."""
+    if edge_threshold is None:
+        return False, 0.0, False, False
+    t = _edge_threshold(edge_threshold, who)
+    if masks == "logits":
+        raise ValueError(f"{who}: edge_threshold= packs the edge map beside packed masks: ask for masks='bits' or 'both'")
+    if side is not None and side % 32 != 0:
+        raise ValueError(f"{who}: edge_threshold= needs rows of whole 32-pixel words, the masks are {side} wide")
+    return True, t, band is not None, bool(overlaps)
+
+
+@dataclass
+class EdgeBits:
+    """N packed edge maps (Cascade.pack_edges), on the device."""
+    bits: torch.Tensor              # (N, H * W / 8) uint8, numpy.packbits' order
+    area: torch.Tensor              # (N,) int32 set bits
+    inter: Optional[torch.Tensor]   # (N,) int32 |bits AND with_bits|; None without with_bits
 
 
 @dataclass
@@ -2253,6 +2304,68 @@ class Cascade(_Base):
         band_bits, band_area, _ = out
         hip.mask_morph(bits, H, W, mreq[1], band_bits=band_bits.view(-1, band_bits.shape[-1])[p0:p1], band_area=band_area.view(-1)[p0:p1])
 
+    # ---- packed edge maps -------------------------------------------------------------------------------------------
+    def _edge_outputs(self, n: int, K: int, nbytes: int, ereq):
+        """The result's own (edge_bits, edge_area, edge_band, edge_inter) for n x K hypotheses, None where not asked for."""
+        asked, _, want_band, want_inter = ereq
+        if not asked:
+            return None, None, None, None
+        dev = self.device
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        return (torch.empty(n, K, nbytes, dtype=torch.uint8, device=dev), i32(n, K), i32(n, K) if want_band else None,
+                i32(n, K, K) if want_inter else None)
+
+    def _edge_bits(self, n: int, ereq, out, bands, p0: int, p1: int) -> None:
+        """cvlm_edge_pack of a chunk's low-resolution edge map -- where MaskDecoder left it, workspace buffer "low_edge", n x 4G x 4G
+        -- into rows p0 .. p1 - 1 of the result's edge_bits / edge_area and, with band=, edge_band against the chunk's rows of
+        band_bits.  One call, no workspace; the full-resolution edge map is not formed."""
+        g = self.g
+        S, L = g.inp_size, 4 * g.grid
+        low = self.decoder.ws.f32("low_edge", n, L * L).view(n, L, L)
+        bits, area, on_band, _ = out
+        with_bits = with_inter = None
+        if on_band is not None:
+            with_bits, with_inter = bands[0].view(-1, bands[0].shape[-1])[p0:p1], on_band.view(-1)[p0:p1]
+        hip.edge_pack(low, S, S, ereq[1], bits.view(-1, bits.shape[-1])[p0:p1], area.view(-1)[p0:p1], with_bits, with_inter)
+
+    def pack_edges(self, prob: torch.Tensor, size=None, *, threshold: float, with_bits: Optional[torch.Tensor] = None) -> "EdgeBits":
+        """Packed edge maps of any (N, h, w) or (N, 1, h, w) f32 probability planes on this engine's device (cvlm_edge_pack, DESIGN.md
+        §17) -> EdgeBits: bits uint8 (N, H * W / 8) in numpy.packbits' order, set where the align_corners=False bilinear value at
+        size = (H, W) is > threshold, and their area.  size=None means (h, w), a pure threshold pack: that is how
+        `infer_test_multimask(...).edges` is packed; a low-resolution map takes size=(S, S).  with_bits: (N, H * W / 8) uint8 packed
+        planes, e.g. `mask_morph`'s band_bits: `inter` = |bits AND with_bits| per plane.  0 < threshold < 1, W % 32 == 0.  One launch
+        pair on the caller's stream; ValueError before it for anything else."""
+        t = _edge_threshold(threshold, "pack_edges")
+        if not isinstance(prob, torch.Tensor) or prob.dtype != torch.float32 or prob.dim() not in (3, 4) or \
+                (prob.dim() == 4 and prob.shape[1] != 1):
+            raise ValueError("pack_edges: prob must be a float32 tensor (N, h, w) or (N, 1, h, w)")
+        N, (h, w) = int(prob.shape[0]), (int(v) for v in prob.shape[-2:])
+        if size is None:
+            size = (h, w)
+        if not isinstance(size, (tuple, list)) or len(size) != 2 or \
+                any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in size):
+            raise ValueError(f"pack_edges: size must be None or a pair of ints (H, W), got {size!r}")
+        H, W = (int(v) for v in size)
+        if not 1 <= N <= 65535 or h < 1 or w < 1 or h * w >= 2 ** 31 or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"pack_edges: {N} planes of {h} x {w} to {H} x {W}: 1 .. 65535 planes, W a multiple of 32, both sizes "
+                             "below 2^31 pixels")
+        if not prob.is_cuda:
+            raise ValueError("pack_edges: prob must be on the device")
+        if with_bits is not None:
+            if not isinstance(with_bits, torch.Tensor) or with_bits.dtype != torch.uint8 or tuple(with_bits.shape) != (N, H * W // 8):
+                raise ValueError(f"pack_edges: with_bits must be a uint8 tensor ({N}, {H * W // 8})")
+            if with_bits.device != prob.device:
+                raise ValueError("pack_edges: with_bits must be on prob's device")
+            with_bits = with_bits.detach().contiguous()
+            if with_bits.data_ptr() % 4 != 0:
+                with_bits = with_bits.clone()
+        planes = prob.detach().contiguous().view(N, h, w)
+        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=prob.device)
+        area = torch.empty(N, dtype=torch.int32, device=prob.device)
+        inter = torch.empty(N, dtype=torch.int32, device=prob.device) if with_bits is not None else None
+        hip.edge_pack(planes, H, W, t, bits, area, with_bits, inter)
+        return EdgeBits(bits, area, inter)
+
     def mask_morph(self, bits: torch.Tensor, H: int, W: int, *, radius: int = 2, dilate: bool = False, erode: bool = False,
                    band: bool = True) -> "MaskMorph":
         """Dilation, erosion and edge band = dilation & ~erosion of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g.
@@ -2293,7 +2406,7 @@ class Cascade(_Base):
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                       connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
-                      band: Optional[int] = None) -> ClassHypotheses:
+                      band: Optional[int] = None, edge_threshold: Optional[float] = None) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2336,7 +2449,15 @@ class Cascade(_Base):
         tensors: no workspace.  With overlaps=True also `band_inter`, the bands' pairwise intersections, one more cvlm_mask_overlap
         launch behind the last chunk: boundary agreement of two hypotheses is band_inter / (band_area_a + band_area_b - band_inter),
         and the caller divides.  Independent of components= and holes=.  Without it the call makes exactly the launches and
-        allocations it made before."""
+        allocations it made before.
+        edge_threshold=t (`edge_request`, checked with the rest; 0 < t < 1, needs masks="bits" or "both"): adds `edge_bits`
+        and `edge_area`, the edge head's probability map of each hypothesis as bits -- one cvlm_edge_pack call per chunk, right behind
+        the band, that resizes the decoder's low-resolution edge map, compares `> t` and packs, into the result's own tensors: no
+        workspace, and no full-resolution edge map even with masks="both", so edge_bits is the same function of the decoder's output
+        in both modes (it may differ from `edges > t` only where |edges - t| <= 2^-21).  With band=r also `edge_band`, the edge pixels
+        on each mask's band; with overlaps=True also `edge_inter`, one more cvlm_mask_overlap launch behind the last chunk.  The
+        decoder's launches are those of the call without it.  Nothing is chosen here and there is no default threshold: the
+        reference trains and evaluates the soft map.  Without it the call makes exactly the launches and allocations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
@@ -2346,6 +2467,8 @@ class Cascade(_Base):
         hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size,
                              who="infer_classes")
         mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size, who="infer_classes")
+        ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size,
+                            who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2367,6 +2490,7 @@ class Cascade(_Base):
             regions = self._component_outputs((B, K), S * S // 8, comp)
             pits = self._hole_outputs((B, K), S * S // 8, hreq)
             bands = self._band_outputs(B, K, S * S // 8, mreq)
+            edged = self._edge_outputs(B, K, S * S // 8, ereq)
             mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
             for p0 in range(0, P, chunk):
@@ -2386,6 +2510,8 @@ class Cascade(_Base):
                 self._pack_chunk(planes, compact, p0, p1)
                 if mreq[0]:
                     self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
+                if ereq[0]:
+                    self._edge_bits(n, ereq, edged, bands, p0, p1)
                 if comp[0]:
                     self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
                 if hreq[0]:
@@ -2395,14 +2521,16 @@ class Cascade(_Base):
                 hip.mask_overlap(compact[0], compact[3])
             if mreq[2]:
                 hip.mask_overlap(bands[0], bands[2])
+            if ereq[3]:
+                hip.mask_overlap(edged[0], edged[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands if t is not None))
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)))
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2439,7 +2567,8 @@ class Cascade(_Base):
                text: Optional[torch.Tensor] = None, images: Optional[Sequence[int]] = None, quality: bool = False,
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
-               connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None) -> ClassHypotheses:
+               connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None,
+               edge_threshold: Optional[float] = None) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2458,7 +2587,8 @@ class Cascade(_Base):
         masks="bits" the chunk's planes are only packed.
         components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest.
         holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest.
-        band=: as in `infer_classes`, checked by `morph_request` with the rest."""
+        band=: as in `infer_classes`, checked by `morph_request` with the rest.
+        edge_threshold=: as in `infer_classes`, checked by `edge_request` with the rest."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2473,6 +2603,7 @@ class Cascade(_Base):
         comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size)
+        ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2506,6 +2637,7 @@ class Cascade(_Base):
         regions = self._component_outputs((n, K), S * S // 8, comp)
         pits = self._hole_outputs((n, K), S * S // 8, hreq)
         bands = self._band_outputs(n, K, S * S // 8, mreq)
+        edged = self._edge_outputs(n, K, S * S // 8, ereq)
         mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
         for p0 in range(0, P, chunk):
@@ -2521,6 +2653,8 @@ class Cascade(_Base):
             self._pack_chunk(planes, compact, p0, p1)
             if mreq[0]:
                 self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
+            if ereq[0]:
+                self._edge_bits(m, ereq, edged, bands, p0, p1)
             if comp[0]:
                 self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
             if hreq[0]:
@@ -2531,13 +2665,15 @@ class Cascade(_Base):
             hip.mask_overlap(compact[0], compact[3])
         if mreq[2]:
             hip.mask_overlap(bands[0], bands[2])
+        if ereq[3]:
+            hip.mask_overlap(edged[0], edged[3])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)))
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

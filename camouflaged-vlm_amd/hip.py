@@ -67,6 +67,9 @@ _SIGNATURES = {
     "cvlm_debug_mask_holes_host": "i:piiiiiippppp",
     "cvlm_mask_morph": "i:piiiipppppps",
     "cvlm_debug_mask_morph_host": "i:piiiipppppp",
+    "cvlm_edge_pack": "i:piiiiifpppps",
+    "cvlm_debug_edge_pack_host": "i:piiiiifpppp",
+    "cvlm_debug_edge_pack_staged": "i:iiii",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -877,6 +880,52 @@ def mask_morph_host(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: O
     assert not bits.is_cuda
     _call("cvlm_debug_mask_morph_host", bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area),
           _p(band_bits), _p(band_area))
+
+
+def _edge_args(prob: torch.Tensor, hout: int, wout: int, bits, area, with_bits, with_inter) -> Tuple[int, int, int]:
+    """Shape and dtype checks shared by `edge_pack` and `edge_pack_host` -> (P, hin, win)."""
+    P, hin, win = (int(v) for v in prob.shape)
+    nbytes = hout * wout // 8
+    assert prob.dtype == torch.float32 and prob.is_contiguous() and wout % 32 == 0
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, nbytes) and bits.is_contiguous()
+    assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+    assert (with_bits is None) == (with_inter is None)
+    if with_bits is not None:
+        assert with_bits.dtype == torch.uint8 and tuple(with_bits.shape) == (P, nbytes) and with_bits.is_contiguous()
+        assert with_inter.dtype == torch.int32 and tuple(with_inter.shape) == (P,) and with_inter.is_contiguous()
+    assert all(t is None or t.device == prob.device for t in (bits, area, with_bits, with_inter))
+    return P, hin, win
+
+
+def edge_pack(prob: torch.Tensor, hout: int, wout: int, threshold: float, bits: torch.Tensor, area: torch.Tensor,
+              with_bits: Optional[torch.Tensor] = None, with_inter: Optional[torch.Tensor] = None) -> None:
+    """prob f32 [P][hin][win] -> bits uint8 [P][hout * wout / 8] in numpy.packbits' order, bit set iff the align_corners=False bilinear
+    value at that output pixel -- float32, one rounding per operation -- is > threshold (0 < threshold < 1; NaN clear, +inf set), area
+    int32 [P] = set bits; with_bits (planes like bits) and with_inter int32 [P] = popcount(bits & with_bits) together or not at all.
+    No output may overlap an input or another output (include/cvlm.h)."""
+    P, hin, win = _edge_args(prob, hout, wout, bits, area, with_bits, with_inter)
+    _on_current_device(prob)
+    _call("cvlm_edge_pack", prob.data_ptr(), P, hin, win, hout, wout, threshold, bits.data_ptr(), area.data_ptr(), _p(with_bits),
+          _p(with_inter))
+
+
+def edge_pack_host(prob: torch.Tensor, hout: int, wout: int, threshold: float, bits: torch.Tensor, area: torch.Tensor,
+                   with_bits: Optional[torch.Tensor] = None, with_inter: Optional[torch.Tensor] = None) -> None:
+    """`edge_pack` on HOST tensors without a device (cvlm_debug_edge_pack_host: the kernel's per-pixel functions run sequentially on
+    the CPU)."""
+    P, hin, win = _edge_args(prob, hout, wout, bits, area, with_bits, with_inter)
+    assert not prob.is_cuda
+    _call("cvlm_debug_edge_pack_host", prob.data_ptr(), P, hin, win, hout, wout, threshold, bits.data_ptr(), area.data_ptr(), _p(with_bits),
+          _p(with_inter))
+
+
+def edge_pack_staged(hin: int, win: int, hout: int, wout: int) -> bool:
+    """Whether cvlm_edge_pack runs these sizes through the instance that stages each tile's source footprint in LDS (True) or through
+    the one that reads the planes directly (False): the launcher's own choice function (cvlm_debug_edge_pack_staged)."""
+    rc = load().cvlm_debug_edge_pack_staged(hin, win, hout, wout)
+    if rc < 0:
+        raise RuntimeError(f"cvlm_debug_edge_pack_staged({hin}, {win}, {hout}, {wout}): sizes outside the entry's bounds")
+    return bool(rc)
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

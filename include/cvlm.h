@@ -607,6 +607,48 @@ int cvlm_mask_morph(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32
 int cvlm_debug_mask_morph_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t radius, uint32_t* dil_bits,
                                int32_t* dil_area, uint32_t* ero_bits, int32_t* ero_area, uint32_t* band_bits, int32_t* band_area);
 
+/* Packed edge maps: the edge head's probability planes resized, thresholded and packed in one kernel -- the bits of
+ * the map the reference upsamples into a full-resolution f32 plane (models/sam_maskdecoder_edge.py:298-302: sigmoid of the edge
+ * head, postprocess_masks) and trains against the band of the mask (:441-447: edge_dice_loss(pred_edge, gt_edge), gt_edge the
+ * dilated - eroded band that cvlm_mask_morph's radius 2 gives).  That f32 plane is never written here.  The definition:
+ *   prob f32 [P][hin][win]: P low-resolution planes.  v(y, x), the align_corners = False bilinear value at output pixel (y, x), is
+ *   computed in float32 with ONE ROUNDING PER WRITTEN OPERATION and no contraction of a product into a sum:
+ *     sy = (float)hin / (float)hout, sx = (float)win / (float)wout, divided on the host by the launcher;
+ *     f(o) = max(s * ((float)o + 0.5f) - 0.5f, 0), the product rounded before the subtraction;
+ *     i0 = (int)f capped at n_in - 1, i1 = i0 + (i0 < n_in - 1), l = f - (float)i0;
+ *     row(y') = (1 - lx) * p[y'][x0] + lx * p[y'][x1];   v = (1 - ly) * row(y0) + ly * row(y1).
+ *   The same formulas hold for hout < hin or wout < win (two taps per axis, no area averaging).  The cap on i0 changes nothing where
+ *   (int)f is a pixel of the plane; it keeps the index inside it where float32 no longer resolves pixels (beyond 2^22 per row).
+ *   Bit (y, x) is set iff v(y, x) > threshold: NaN compares false (a NaN source pixel clears the output pixels that read it, as NaN
+ *   planes give zero bits in cvlm_mask_pack), +inf is set.  These are the operations cvlm_bilinear writes, but there the blend is
+ *   left to the compiler's contraction, so this entry's bits are NOT defined as `cvlm_bilinear(prob) > threshold`: the two may differ
+ *   where |v - threshold| is within the few roundings by which two evaluation orders differ (2^-21 for operands in [0, 1]).
+ * bits u8 [P][hout * wout / 8] in cvlm_mask_pack's order (pixel i = y * wout + x is bit 7 - (i & 7) of byte i >> 3), wout % 32 == 0,
+ * stored as whole 32-bit words; area int32 [P] = set bits per plane.  with_bits / with_inter: both NULL, or with_bits P packed
+ * planes of the output's shape (the caller passes band_bits) and with_inter int32 [P] = popcount(bits[p] & with_bits[p]).  area and
+ * with_inter are initialised by the call (an init launch zeroes them), so a launch sequence replays.
+ * One kernel, grid (tile of 256 columns x 64 rows, plane): a wave covers the 256 pixels of one output row, 4 per lane, whose column
+ * taps it computes once per tile; the row taps are wave-uniform; lanes 8g .. 8g + 7 OR their nibbles into a word by three
+ * xor-shuffles and lane 8g stores it (cvlm_mask_pack's step).  Two instances: one stages the tile's source footprint (18 x 66
+ * floats at the model's 4 x) in LDS, so that each source value is read from memory once per tile, the other reads prob directly;
+ * the launcher takes the first when a bound on the footprint fits 19 KiB (up-scales of about 2 x and more) --
+ * cvlm_debug_edge_pack_staged answers which.  Words are stored whole, no atomics on planes; the sums are __popc counts reduced by
+ * wave shuffles and LDS to at most one integer atomic per output, workgroup and plane: exact and reproducible whatever the schedule.
+ * 64-bit offsets.  No workspace, no allocation, no synchronisation, no pointer kept.
+ * CVLM_E_BADARG, before anything touches the device: prob, bits or area NULL, bits or with_bits not 4-byte aligned, P outside
+ * [1, 65535], hin, win, hout or wout <= 0, wout % 32 != 0, hout * wout >= 2^31, hin * win >= 2^31, threshold not finite or outside
+ * the open interval (0, 1), exactly one of with_bits / with_inter NULL, an output range (bits, area, with_inter) that intersects
+ * prob's, with_bits' or another output's. */
+int cvlm_edge_pack(const float* prob, int32_t P, int32_t hin, int32_t win, int32_t hout, int32_t wout, float threshold, uint8_t* bits,
+                   int32_t* area, const uint8_t* with_bits, int32_t* with_inter, void* stream);
+/* Outside the ABI contract: cvlm_edge_pack on HOST memory, no stream -- the same per-pixel functions (csrc/edgepack_logic.h) run
+ * sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_edge_pack_host(const float* prob, int32_t P, int32_t hin, int32_t win, int32_t hout, int32_t wout, float threshold,
+                              uint8_t* bits, int32_t* area, const uint8_t* with_bits, int32_t* with_inter);
+/* Outside the ABI contract: the instance cvlm_edge_pack launches for these sizes, a pure function of them: 1 the one that stages
+ * the footprint in LDS, 0 the one that reads prob directly, CVLM_E_BADARG for sizes cvlm_edge_pack refuses. */
+int cvlm_debug_edge_pack_staged(int32_t hin, int32_t win, int32_t hout, int32_t wout);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
