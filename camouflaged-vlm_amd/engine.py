@@ -15,7 +15,7 @@ import math
 import os
 import warnings
 from dataclasses import InitVar, dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1437,10 +1437,15 @@ class ClassHypotheses:
     edge_area: InitVar[Optional[torch.Tensor]] = None
     edge_band: InitVar[Optional[torch.Tensor]] = None
     edge_inter: InitVar[Optional[torch.Tensor]] = None
+    # rle="mask" / "kept" / "filled" (DESIGN.md §18), otherwise None; a pseudo-field like `mask_bits`.  The COCO run-length encoding of
+    # mask_bits, kept_bits or filled_bits of all B * K hypotheses, plane p = b * K + k: a MaskRle, on the device.  A hypothesis of
+    # class -1 has zero bits and therefore the single count S * S.
+    rle: InitVar[Optional["MaskRle"]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
                       n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter,
-                      edge_bits, edge_area, edge_band, edge_inter):
+                      edge_bits, edge_area, edge_band, edge_inter, rle):
+        self.rle = rle
         self.edge_bits, self.edge_area, self.edge_band, self.edge_inter = edge_bits, edge_area, edge_band, edge_inter
         self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
@@ -1675,6 +1680,68 @@ class EdgeBits:
     bits: torch.Tensor              # (N, H * W / 8) uint8, numpy.packbits' order
     area: torch.Tensor              # (N,) int32 set bits
     inter: Optional[torch.Tensor]   # (N,) int32 |bits AND with_bits|; None without with_bits
+
+
+RLE_WS_CAP = 64 << 20             # bytes of the "cls_rle" workspace at most; beyond it cvlm_mask_rle_emit walks the planes in rounds
+RLE_SOURCES = {"mask": "mask_bits", "kept": "kept_bits", "filled": "filled_bits"}
+
+
+def rle_request(*, rle=None, masks="bits", min_area=0, fill_holes=0, side: Optional[int] = None, who: str = "decode"):
+    """Every check of the rle= argument of Cascade.infer_classes / decode, on the host, before anything is launched
+    (ValueError) -> the name of the field to encode, or None.  rle=None asks for nothing; "mask", "kept" and "filled" ask for the COCO
+    run-length encoding of mask_bits, kept_bits (needs min_area >= 1) or filled_bits (needs fill_holes >= 1).  side: the width of the
+    model's masks."""
+    if rle is None:
+        return None
+    if not isinstance(rle, str) or rle not in RLE_SOURCES:
+        raise ValueError(f"{who}: rle must be None or one of {tuple(RLE_SOURCES)}, got {rle!r}")
+    if masks == "logits":
+        raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if rle == "kept" and not (is_int(min_area) and int(min_area) >= 1):
+        raise ValueError(f"{who}: rle='kept' encodes kept_bits: ask for min_area >= 1")
+    if rle == "filled" and not (is_int(fill_holes) and int(fill_holes) >= 1):
+        raise ValueError(f"{who}: rle='filled' encodes filled_bits: ask for fill_holes >= 1")
+    if side is not None and side % 32 != 0:
+        raise ValueError(f"{who}: rle= needs rows of whole 32-pixel words, the masks are {side} wide")
+    return RLE_SOURCES[rle]
+
+
+@dataclass
+class MaskRle:
+    """COCO run-length encoding of N packed masks (Cascade.mask_rle), on the device: plane p's n_runs[p] counts are
+    counts[offsets[p] : offsets[p + 1]] -- the lengths of the alternating runs of 0s and 1s of its pixels in column-major order,
+    starting with the 0s.  An interchange format, not a compression: a ragged mask has more bytes of counts than of bits."""
+    counts: torch.Tensor            # (total,) int32
+    offsets: torch.Tensor           # (N + 1,) int64, offsets[0] = 0, offsets[N] = total
+    n_runs: torch.Tensor            # (N,) int32
+    size: Tuple[int, int]           # (H, W)
+    # (1,) int32 on the device, 0 unless cvlm_mask_rle_emit had to drop a count; `check` and `to_coco` read it.  Init-only, not a field.
+    status: InitVar[Optional[torch.Tensor]] = None
+
+    def __post_init__(self, status):
+        self.status = status
+
+    def check(self) -> None:
+        """RuntimeError if the emit dropped a count (synchronises).  The slices come from the call's own count of the same bits, so
+        this says that the bits changed between the two passes or that the library is broken."""
+        if self.status is not None and int(self.status.item()) != 0:
+            raise RuntimeError("mask_rle: cvlm_mask_rle_emit dropped counts that did not fit their slices: were the bits written "
+                               "while the call ran?")
+
+    def to_coco(self, compressed: bool = False) -> list:
+        """On the host: one {"size": [H, W], "counts": ...} per plane, what pycocotools and the reference's GenericMask
+        (models/utils/visualizer.py:72-101) take; counts is a list of ints, or with compressed=True COCO's string as bytes
+        (rle.counts_to_string).  One copy of each of the three tensors; synchronises."""
+        from . import rle as _rle
+        self.check()
+        counts, offsets = self.counts.cpu().numpy(), self.offsets.cpu().numpy()
+        H, W = self.size
+        out = []
+        for p in range(offsets.size - 1):
+            c = counts[offsets[p]:offsets[p + 1]]
+            out.append({"size": [int(H), int(W)], "counts": _rle.counts_to_string(c) if compressed else c.tolist()})
+        return out
 
 
 @dataclass
@@ -2402,11 +2469,52 @@ class Cascade(_Base):
         hip.mask_morph(bits, H, W, int(radius), *out)
         return MaskMorph(*out)
 
+    # ---- run-length encoding of packed masks ------------------------------------------------------------------------
+    def mask_rle(self, bits: torch.Tensor, H: int, W: int) -> "MaskRle":
+        """COCO run-length encoding of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits or
+        `mask_components`' kept_bits (W % 32 == 0; H any) -> MaskRle.  cvlm_mask_rle_count, torch.cumsum of the run counts on the device,
+        ONE device-to-host read of the total -- the call's only synchronisation, and the size of `counts` is known before it is
+        allocated --, then cvlm_mask_rle_emit through the grow-only workspace "cls_rle", capped at RLE_WS_CAP (beyond it the entry
+        walks the planes in rounds).  The emit's status word stays on the device: `MaskRle.check()` / `to_coco()` read it.  Launches on
+        the caller's stream; ValueError before them for anything else."""
+        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
+                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+            raise ValueError(f"mask_rle: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
+        H, W = int(H), int(W)
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
+                or not 1 <= int(bits.shape[0]) <= 65535:
+            raise ValueError(f"mask_rle: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
+        if not bits.is_cuda:
+            raise ValueError("mask_rle: bits must be on the device")
+        bits = bits.detach().contiguous()
+        if bits.data_ptr() % 4 != 0:
+            bits = bits.clone()
+        N, dev = int(bits.shape[0]), bits.device
+        n_runs = torch.empty(N, dtype=torch.int32, device=dev)
+        hip.mask_rle_count(bits, H, W, n_runs)
+        offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
+        total = int(offsets[N].item())                               # the one synchronisation
+        counts = torch.empty(total, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        want = min(hip.mask_rle_workspace_bytes(N, H, W), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, H, W)))
+        ws = self.ws._get("u8", "cls_rle", want, torch.uint8, False)
+        hip.mask_rle_emit(bits, H, W, offsets, counts, status, ws)
+        return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=(H, W), status=status)
+
+    def _rle_of(self, source: Optional[str], fields: dict, S: int) -> Optional["MaskRle"]:
+        """rle= of infer_classes / decode: `mask_rle` of the result's own planes named by `rle_request`, all n * K of them at once."""
+        if source is None:
+            return None
+        planes = fields[source]
+        return self.mask_rle(planes.view(-1, planes.shape[-1]), S, S)
+
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                       connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
-                      band: Optional[int] = None, edge_threshold: Optional[float] = None) -> ClassHypotheses:
+                      band: Optional[int] = None, edge_threshold: Optional[float] = None,
+                      rle: Optional[str] = None) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2457,7 +2565,13 @@ class Cascade(_Base):
         in both modes (it may differ from `edges > t` only where |edges - t| <= 2^-21).  With band=r also `edge_band`, the edge pixels
         on each mask's band; with overlaps=True also `edge_inter`, one more cvlm_mask_overlap launch behind the last chunk.  The
         decoder's launches are those of the call without it.  Nothing is chosen here and there is no default threshold: the
-        reference trains and evaluates the soft map.  Without it the call makes exactly the launches and allocations it made before."""
+        reference trains and evaluates the soft map.  Without it the call makes exactly the launches and allocations it made before.
+        rle="mask" / "kept" / "filled" (`rle_request`, checked with the rest; needs masks="bits" or "both", "kept" needs
+        min_area >= 1, "filled" fill_holes >= 1): adds `rle`, the COCO run-length encoding of mask_bits, kept_bits or filled_bits of
+        all B * K hypotheses -- `mask_rle`, once, behind the last chunk where cvlm_mask_overlap runs: two count launches, a cumsum,
+        one read of the total (a synchronisation of the host with the side stream) and the emit's launches.  An interchange format
+        for pycocotools, the COCO / LVIS evaluators and the reference's GenericMask, not a compression: see DESIGN.md §18 for sizes.
+        Without it the call makes exactly the launches, allocations and synchronisations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
@@ -2469,6 +2583,7 @@ class Cascade(_Base):
         mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size, who="infer_classes")
         ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size,
                             who="infer_classes")
+        rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size, who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2525,12 +2640,15 @@ class Cascade(_Base):
                 hip.mask_overlap(edged[0], edged[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
+            runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3]}, S)
+        coded = () if runs is None else (runs.counts, runs.offsets, runs.n_runs, runs.status)
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged if t is not None))
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged + coded
+                        if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs)
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2568,7 +2686,7 @@ class Cascade(_Base):
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None,
-               edge_threshold: Optional[float] = None) -> ClassHypotheses:
+               edge_threshold: Optional[float] = None, rle: Optional[str] = None) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2588,7 +2706,9 @@ class Cascade(_Base):
         components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest.
         holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest.
         band=: as in `infer_classes`, checked by `morph_request` with the rest.
-        edge_threshold=: as in `infer_classes`, checked by `edge_request` with the rest."""
+        edge_threshold=: as in `infer_classes`, checked by `edge_request` with the rest.
+        rle=: as in `infer_classes`, checked by `rle_request` with the rest; its one read synchronises the host with
+        the caller's stream."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2604,6 +2724,7 @@ class Cascade(_Base):
         hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size)
         mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size)
         ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size)
+        rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2669,11 +2790,12 @@ class Cascade(_Base):
             hip.mask_overlap(edged[0], edged[3])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
+        runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3]}, S)
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)))
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

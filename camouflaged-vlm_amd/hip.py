@@ -70,6 +70,10 @@ _SIGNATURES = {
     "cvlm_edge_pack": "i:piiiiifpppps",
     "cvlm_debug_edge_pack_host": "i:piiiiifpppp",
     "cvlm_debug_edge_pack_staged": "i:iiii",
+    "cvlm_mask_rle_workspace_bytes": "l:iii",
+    "cvlm_mask_rle_count": "i:piiips",
+    "cvlm_mask_rle_emit": "i:piiipplppls",
+    "cvlm_debug_mask_rle_host": "i:piiippplp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -926,6 +930,59 @@ def edge_pack_staged(hin: int, win: int, hout: int, wout: int) -> bool:
     if rc < 0:
         raise RuntimeError(f"cvlm_debug_edge_pack_staged({hin}, {win}, {hout}, {wout}): sizes outside the entry's bounds")
     return bool(rc)
+
+
+def mask_rle_workspace_bytes(P: int, H: int, W: int) -> int:
+    """Bytes cvlm_mask_rle_emit wants to keep all P planes of H x W in flight (12 per 32 pixels and plane); P = 1: the minimum it takes."""
+    n = load().cvlm_mask_rle_workspace_bytes(P, H, W)
+    if n < 0:
+        raise RuntimeError(f"cvlm_mask_rle_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
+    return n
+
+
+def _rle_args(bits: torch.Tensor, H: int, W: int, n_runs, offsets, counts, status) -> int:
+    """Shape and dtype checks shared by `mask_rle_count`, `mask_rle_emit` and `mask_rle_host` -> P."""
+    P = int(bits.shape[0])
+    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
+    if n_runs is not None:
+        assert n_runs.dtype == torch.int32 and tuple(n_runs.shape) == (P,) and n_runs.is_contiguous() and n_runs.device == bits.device
+    if counts is not None:
+        assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
+        assert counts.dtype == torch.int32 and counts.dim() == 1 and counts.is_contiguous() and counts.numel() >= 1
+        assert status.dtype == torch.int32 and status.numel() == 1
+        assert all(t.device == bits.device for t in (offsets, counts, status))
+    return P
+
+
+def mask_rle_count(bits: torch.Tensor, H: int, W: int, n_runs: torch.Tensor) -> None:
+    """bits uint8 [P][H * W / 8] (mask_pack's planes) -> n_runs int32 [P]: the counts of each plane's COCO run-length encoding
+    (column-major, starting with the run of 0s; include/cvlm.h).  Two launches, no workspace."""
+    P = _rle_args(bits, H, W, n_runs, None, None, None)
+    _on_current_device(bits)
+    _call("cvlm_mask_rle_count", bits.data_ptr(), P, H, W, n_runs.data_ptr())
+
+
+def mask_rle_emit(bits: torch.Tensor, H: int, W: int, offsets: torch.Tensor, counts: torch.Tensor, status: torch.Tensor,
+                  workspace: torch.Tensor) -> None:
+    """bits uint8 [P][H * W / 8] -> counts int32 [total]: plane p's run counts from counts[offsets[p]] on, inside its slice
+    [offsets[p], offsets[p + 1]) (offsets int64 [P + 1], on the device); a count that would leave its slice or counts is dropped and
+    status int32 [1] becomes 1, otherwise 0.  workspace: uint8, at least mask_rle_workspace_bytes(1, H, W) bytes; fewer than P planes'
+    worth makes the entry walk the planes in rounds (include/cvlm.h)."""
+    P = _rle_args(bits, H, W, None, offsets, counts, status)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
+    _on_current_device(bits)
+    _call("cvlm_mask_rle_emit", bits.data_ptr(), P, H, W, offsets.data_ptr(), counts.data_ptr(), counts.numel(), status.data_ptr(),
+          workspace.data_ptr(), workspace.numel())
+
+
+def mask_rle_host(bits: torch.Tensor, H: int, W: int, n_runs: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                  counts: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
+    """`mask_rle_count` and, with counts, `mask_rle_emit` on HOST tensors without a device (cvlm_debug_mask_rle_host: the kernels'
+    per-thread functions run sequentially on the CPU)."""
+    P = _rle_args(bits, H, W, n_runs, offsets, counts, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_rle_host", bits.data_ptr(), P, H, W, n_runs.data_ptr(), _p(offsets), _p(counts),
+          0 if counts is None else counts.numel(), _p(status))
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

@@ -649,6 +649,44 @@ int cvlm_debug_edge_pack_host(const float* prob, int32_t P, int32_t hin, int32_t
  * the footprint in LDS, 0 the one that reads prob directly, CVLM_E_BADARG for sizes cvlm_edge_pack refuses. */
 int cvlm_debug_edge_pack_staged(int32_t hin, int32_t win, int32_t hout, int32_t wout);
 
+/* Run-length encoding of packed masks: COCO's RLE, the form pycocotools, the LVIS / COCO evaluators and the
+ * reference's own visualizer read (models/utils/visualizer.py:72-101: GenericMask takes "a COCO-style RLE" dict).  The definition,
+ * all integers: a plane has H rows and W columns, f[j] = m[y][x] for j = x * H + y (column-major); t_0 < ... < t_{T-1} are the j in
+ * [0, H * W) with f[j] != f[j - 1], taking f[-1] = 0; n_runs = T + 1 and the counts are c[k] = t_k - t_{k-1} with t_{-1} = 0 and
+ * t_T = H * W: alternating runs of 0s and 1s starting with the 0s.  An all-clear plane gives [H * W], an all-set plane [0, H * W].
+ * bits u32 [P][H * W / 32]: P planes exactly as cvlm_mask_pack writes them, W % 32 == 0; H need not be a multiple of 32.  Nothing
+ * crosses from the last pixel of one plane into the next.
+ * cvlm_mask_rle_count: n_runs int32 [P].  An init launch sets every n_runs[p] = 1, then one kernel forms for every word the
+ * transition word -- in "bit i = pixel i" form m[y] ^ m[y - 1] for y >= 1 and, for row 0, m[0] ^ ((m[H - 1] << 1) | carry), carry =
+ * bit 31 of row H - 1's PREVIOUS word, 0 at word 0 -- and adds its popcount: whole-word loads, wave shuffles and LDS, at most one
+ * integer atomic per workgroup that found something.  No workspace.
+ * cvlm_mask_rle_emit: offsets int64 [P + 1], counts int32 [total], status int32 [1], all device memory.  Plane p's n_runs[p] counts
+ * are written from counts[offsets[p]] on; its slice is [offsets[p], offsets[p + 1]), so gaps between planes are allowed when the
+ * slices are larger than n_runs[p].  Before EVERY store the kernel checks k < offsets[p + 1] - offsets[p], 0 <= offsets[p] and
+ * offsets[p + 1] <= total; a failed check drops the store and ORs 1 into status[0], which the call zeroes first: no input makes a
+ * kernel store outside counts[0, total).  Per round of planes three launches: (1) tiles of 16 word columns x 128 rows stage their
+ * transition words in LDS and gather, per pixel column and 32 rows, the column's bits into one word of the STREAM -- the H * W
+ * transition bits in position order -- by a whole-word store when H % 32 == 0, otherwise by integer ORs into a stream the call has
+ * zeroed (they commute: the bits do not depend on the schedule); (2) one workgroup per plane scans the stream: per word the
+ * transitions before it and the position of the last of them, and one thread writes the tail run; (3) one thread per stream word
+ * stores position - previous position for each of its set bits.  No thread waits for another workgroup; 64-bit offsets.
+ * workspace: caller-owned, 16-byte aligned, contents need no initialisation.  cvlm_mask_rle_workspace_bytes(P, H, W) = P planes'
+ * worth: 12 bytes per 32 pixels (0.375 byte per pixel and plane; rounded up to 16 bytes per plane); CVLM_E_BADARG for sizes the
+ * entries refuse.  The one-plane size is the minimum; with fewer than P planes' worth the planes go in rounds queued on the stream.
+ * No allocation, no synchronisation, no pointer kept; every output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: bits, n_runs, offsets, counts or status NULL, bits / n_runs / counts / status
+ * not 4-byte aligned, offsets not 8-byte aligned, P outside [1, 65535], H or W <= 0, W % 32 != 0, H * W >= 2^31, total < 1, a
+ * workspace that is NULL, not 16-byte aligned or below the one-plane size. */
+int64_t cvlm_mask_rle_workspace_bytes(int32_t P, int32_t H, int32_t W);
+int cvlm_mask_rle_count(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, void* stream);
+int cvlm_mask_rle_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, const int64_t* offsets, int32_t* counts, int64_t total,
+                       int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* Outside the ABI contract: count and emit on HOST memory, no stream, no workspace -- the same per-thread functions
+ * (csrc/rle_logic.h) run sequentially on the CPU.  counts == NULL: only n_runs is written and offsets / total / status are not
+ * looked at.  Same outputs, same refusals. */
+int cvlm_debug_mask_rle_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, const int64_t* offsets,
+                             int32_t* counts, int64_t total, int32_t* status);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
