@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void rl_init_kernel(int* __restrict__ n_runs, 
 }
 
 // n_runs[blockIdx.y] += the transitions of RL_COUNT_WORDS words of the plane
-__global__ __launch_bounds__(256) void rl_count_kernel(const uint32_t* __restrict__ bits, int H, int wpr, int* __restrict__ n_runs) {
+__global__ __launch_bounds__(256) void rl_count_kernel(const uint32_t* __restrict__ bits, int H, int wpr, int Wt, int* __restrict__ n_runs) {
     __shared__ int red[4];
     const int words = H * wpr;                                        // < 2^26
     const uint32_t* src = bits + (int64_t)blockIdx.y * words;         // 64-bit: P * H * W / 32 passes 2^31 words at large P
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void rl_count_kernel(const uint32_t* __restric
         const int wi = blockIdx.x * RL_COUNT_WORDS + i * 256 + threadIdx.x;
         if (wi < words) {
             const int y = wi / wpr;
-            n += __popc(rl_transition(src, y, wi - y * wpr, H, wpr));
+            n += __popc(rl_transition(src, y, wi - y * wpr, H, wpr, Wt));
         }
     }
 #pragma unroll
@@ -57,9 +57,9 @@ __global__ __launch_bounds__(256) void rl_count_kernel(const uint32_t* __restric
 // Tile blockIdx.x = (row tile) * col_tiles + (column tile) of plane blockIdx.y of the round.  stream: the round's workspace, planes
 // ws_stride words apart.  ALIGNED (H % 32 == 0): a column block is one whole stream word and is stored; otherwise it straddles two
 // words that other blocks share, the launcher has zeroed the stream and the non-zero parts are ORed in -- integer atomics that
-// commute, so the stream's bits do not depend on the schedule.
+// commute, so the stream's bits do not depend on the schedule.  Pixel columns at or beyond the true width Wt are no part of the stream.
 template <bool ALIGNED>
-__global__ __launch_bounds__(256) void rl_transpose_kernel(const uint32_t* __restrict__ bits, int H, int wpr, int col_tiles,
+__global__ __launch_bounds__(256) void rl_transpose_kernel(const uint32_t* __restrict__ bits, int H, int wpr, int Wt, int col_tiles,
                                                            uint32_t* __restrict__ stream, int64_t ws_stride) {
     __shared__ uint32_t s_t[RL_TH * RL_TW];
     const int tr = blockIdx.x / col_tiles, tc = blockIdx.x - tr * col_tiles;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void rl_transpose_kernel(const uint32_t* __res
 
     const int cl = threadIdx.x & 15, c = c0 + cl;
     if (c < wpr)
-        for (int r = threadIdx.x >> 4; r < rows; r += 16) s_t[r * RL_TW + cl] = rl_transition(src, y0 + r, c, H, wpr);
+        for (int r = threadIdx.x >> 4; r < rows; r += 16) s_t[r * RL_TW + cl] = rl_transition(src, y0 + r, c, H, wpr, Wt);
     __syncthreads();
 
 #pragma unroll 1
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void rl_transpose_kernel(const uint32_t* __res
         const int o = i * 256 + threadIdx.x;
         const int bit = o & 31, ocl = (o >> 5) & 15, rb = o >> 9;
         const int n = min(32, rows - 32 * rb);
-        if (c0 + ocl >= wpr || n <= 0) continue;
+        if (32 * (c0 + ocl) + bit >= Wt || n <= 0) continue;
         const uint32_t v = rl_gather(s_t + 32 * rb * RL_TW + ocl, RL_TW, n, bit);
         int word;
         uint32_t lo, hi;
@@ -92,10 +92,10 @@ __global__ __launch_bounds__(256) void rl_transpose_kernel(const uint32_t* __res
     }
 }
 
-// One workgroup per plane of the round: for every stream word the transitions before it (rank) and the position of the last of
-// them (prev), then the tail run.  Sequential over slabs of RL_SCAN words with a carry; inside a slab a wave scan by shuffles and the
+// One workgroup per plane of the round: for every one of the stream's `words` words (HW = H * Wt bits, the last word may be partly
+// filled) the transitions before it (rank) and the position of the last of them (prev), then the tail run, which ends at HW.  Sequential over slabs of RL_SCAN words with a carry; inside a slab a wave scan by shuffles and the
 // waves' totals through LDS, double-buffered by the slab's parity: one barrier per slab.
-__global__ __launch_bounds__(RL_SCAN) void rl_scan_kernel(uint32_t* __restrict__ ws, int64_t ws_stride, int words, int p0,
+__global__ __launch_bounds__(RL_SCAN) void rl_scan_kernel(uint32_t* __restrict__ ws, int64_t ws_stride, int words, int HW, int p0,
                                                           const int64_t* __restrict__ offsets, int32_t* __restrict__ counts, int64_t total,
                                                           int* __restrict__ status) {
     __shared__ int s_sum[2][RL_SCAN / 64], s_max[2][RL_SCAN / 64];
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(RL_SCAN) void rl_scan_kernel(uint32_t* __restrict__
     if (threadIdx.x == 0) {
         const int p = p0 + blockIdx.x;
         const int64_t off = offsets[p], end = offsets[p + 1];
-        if (rl_emit_tail(words * 32, carry_sum, carry_max, counts, off, end - off, off >= 0 && end <= total)) atomicOr(status, 1);
+        if (rl_emit_tail(HW, carry_sum, carry_max, counts, off, end - off, off >= 0 && end <= total)) atomicOr(status, 1);
     }
 }
 
@@ -154,10 +154,11 @@ __global__ __launch_bounds__(256) void rl_emit_kernel(const uint32_t* __restrict
     if (rl_emit_word(w, k, rank[k], rank[words + k], counts, off, end - off, off >= 0 && end <= total)) atomicOr(status, 1);
 }
 
-// what every entry refuses
-bool rl_bad_planes(const uint32_t* bits, int32_t P, int32_t H, int32_t W) {
+// what every entry refuses; Wt: the true width, the last word of a row holds at least one of its columns
+bool rl_bad_planes(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt) {
     if (!bits || (((uintptr_t)bits) & 3) != 0) return true;
-    return P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31);
+    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    return Wt > W || Wt <= W - 32;
 }
 
 bool rl_bad_emit(const int64_t* offsets, const int32_t* counts, int64_t total, const int32_t* status) {
@@ -165,34 +166,27 @@ bool rl_bad_emit(const int64_t* offsets, const int32_t* counts, int64_t total, c
     return (((uintptr_t)offsets) & 7) != 0 || ((((uintptr_t)counts) | ((uintptr_t)status)) & 3) != 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t cvlm_mask_rle_workspace_bytes(int32_t P, int32_t H, int32_t W) {
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return CVLM_E_BADARG;
-    return (int64_t)P * rl_plane_ws_bytes((int64_t)H * W);
-}
-
-int cvlm_mask_rle_count(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, void* stream) {
-    if (rl_bad_planes(bits, P, H, W) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
+int rl_count(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, void* stream) {
+    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int wpr = W / 32, words = H * wpr;                          // < 2^26: the grid fits
     hipLaunchKernelGGL(rl_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_runs, (int)P, (int*)nullptr);
     CVLM_CHECK_LAUNCH();
     hipLaunchKernelGGL(rl_count_kernel, dim3((words + RL_COUNT_WORDS - 1) / RL_COUNT_WORDS, P), dim3(256), 0, st, bits, (int)H, wpr,
-                       (int*)n_runs);
+                       (int)Wt, (int*)n_runs);
     CVLM_CHECK_LAUNCH();
     return 0;
 }
 
-int cvlm_mask_rle_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, const int64_t* offsets, int32_t* counts, int64_t total,
-                       int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (rl_bad_planes(bits, P, H, W) || rl_bad_emit(offsets, counts, total, status)) return CVLM_E_BADARG;
+// The plane's words are H * W / 32 apart and sized the workspace; the stream has H * Wt bits.
+int rl_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, const int64_t* offsets, int32_t* counts, int64_t total,
+            int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (rl_bad_planes(bits, P, H, W, Wt) || rl_bad_emit(offsets, counts, total, status)) return CVLM_E_BADARG;
     const int64_t plane_bytes = rl_plane_ws_bytes((int64_t)H * W);
     if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_bytes) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int wpr = W / 32, words = H * wpr;
+    const int HW = H * Wt, swords = (int)(((int64_t)HW + 31) / 32);   // the stream: swords <= words, equal when Wt = W
     const int col_tiles = (wpr + RL_TW - 1) / RL_TW, row_tiles = (H + RL_TH - 1) / RL_TH;   // words < 2^26: the grids fit
     const bool aligned = H % 32 == 0;
     const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_bytes);              // planes per round
@@ -204,44 +198,46 @@ int cvlm_mask_rle_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, co
         const int n = std::min(fit, P - p0);
         const uint32_t* src = bits + (int64_t)p0 * words;
         if (aligned) {
-            hipLaunchKernelGGL(rl_transpose_kernel<true>, dim3(col_tiles * row_tiles, n), dim3(256), 0, st, src, (int)H, wpr, col_tiles, ws,
-                               ws_stride);
+            hipLaunchKernelGGL(rl_transpose_kernel<true>, dim3(col_tiles * row_tiles, n), dim3(256), 0, st, src, (int)H, wpr, (int)Wt,
+                               col_tiles, ws, ws_stride);
         } else {
             const hipError_t e = hipMemsetAsync(ws, 0, (size_t)n * plane_bytes, st);
             if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(rl_transpose_kernel<false>, dim3(col_tiles * row_tiles, n), dim3(256), 0, st, src, (int)H, wpr, col_tiles, ws,
-                               ws_stride);
+            hipLaunchKernelGGL(rl_transpose_kernel<false>, dim3(col_tiles * row_tiles, n), dim3(256), 0, st, src, (int)H, wpr, (int)Wt,
+                               col_tiles, ws, ws_stride);
         }
         CVLM_CHECK_LAUNCH();
-        hipLaunchKernelGGL(rl_scan_kernel, dim3(n), dim3(RL_SCAN), 0, st, ws, ws_stride, words, p0, offsets, counts, total, (int*)status);
+        hipLaunchKernelGGL(rl_scan_kernel, dim3(n), dim3(RL_SCAN), 0, st, ws, ws_stride, swords, HW, p0, offsets, counts, total,
+                           (int*)status);
         CVLM_CHECK_LAUNCH();
-        hipLaunchKernelGGL(rl_emit_kernel, dim3((words + 255) / 256, n), dim3(256), 0, st, (const uint32_t*)ws, ws_stride, words, p0, offsets,
-                           counts, total, (int*)status);
+        hipLaunchKernelGGL(rl_emit_kernel, dim3((swords + 255) / 256, n), dim3(256), 0, st, (const uint32_t*)ws, ws_stride, swords, p0,
+                           offsets, counts, total, (int*)status);
         CVLM_CHECK_LAUNCH();
     }
     return 0;
 }
 
 // The same functions on host memory, plane by plane and word by word, through rle_logic.h.  counts == NULL: only n_runs.
-int cvlm_debug_mask_rle_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, const int64_t* offsets,
-                             int32_t* counts, int64_t total, int32_t* status) {
-    if (rl_bad_planes(bits, P, H, W) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
+int rl_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, const int64_t* offsets, int32_t* counts,
+            int64_t total, int32_t* status) {
+    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
     if (counts && rl_bad_emit(offsets, counts, total, status)) return CVLM_E_BADARG;
     const int wpr = W / 32, words = H * wpr;
-    std::vector<uint32_t> t((size_t)words), stream((size_t)words);
+    const int HW = H * Wt, swords = (int)(((int64_t)HW + 31) / 32);
+    std::vector<uint32_t> t((size_t)words), stream((size_t)swords);
     if (counts) status[0] = 0;
     for (int p = 0; p < P; ++p) {
         const uint32_t* src = bits + (int64_t)p * words;
         int n = 0;
         for (int y = 0; y < H; ++y)
             for (int c = 0; c < wpr; ++c) {
-                t[(size_t)y * wpr + c] = rl_transition(src, y, c, H, wpr);
+                t[(size_t)y * wpr + c] = rl_transition(src, y, c, H, wpr, Wt);
                 n += __builtin_popcount(t[(size_t)y * wpr + c]);
             }
         n_runs[p] = 1 + n;
         if (!counts) continue;
         std::fill(stream.begin(), stream.end(), 0u);
-        for (int x = 0; x < W; ++x)
+        for (int x = 0; x < Wt; ++x)
             for (int y = 0; y < H; y += 32) {
                 const uint32_t v = rl_gather(t.data() + (size_t)y * wpr + (x >> 5), wpr, std::min(32, H - y), x & 31);
                 int word;
@@ -253,16 +249,55 @@ int cvlm_debug_mask_rle_host(const uint32_t* bits, int32_t P, int32_t H, int32_t
         const int64_t off = offsets[p], end = offsets[p + 1];
         const bool ok = off >= 0 && end <= total;
         int rank = 0, prev = 0;
-        for (int k = 0; k < words; ++k) {
+        for (int k = 0; k < swords; ++k) {
             const uint32_t w = stream[(size_t)k];
             if (!w) continue;
             status[0] |= rl_emit_word(w, k, rank, prev, counts, off, end - off, ok);
             rank += __builtin_popcount(w);
             prev = rl_last(w, k);
         }
-        status[0] |= rl_emit_tail(words * 32, rank, prev, counts, off, end - off, ok);
+        status[0] |= rl_emit_tail(HW, rank, prev, counts, off, end - off, ok);
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t cvlm_mask_rle_workspace_bytes(int32_t P, int32_t H, int32_t W) {
+    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return CVLM_E_BADARG;
+    return (int64_t)P * rl_plane_ws_bytes((int64_t)H * W);
+}
+
+// The planes of cvlm_mask_pack: every column of every word is the image's, Wt = W
+int cvlm_mask_rle_count(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, void* stream) {
+    return rl_count(bits, P, H, W, W, n_runs, stream);
+}
+
+int cvlm_mask_rle_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, const int64_t* offsets, int32_t* counts, int64_t total,
+                       int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    return rl_emit(bits, P, H, W, W, offsets, counts, total, status, workspace, workspace_bytes, stream);
+}
+
+int cvlm_debug_mask_rle_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, const int64_t* offsets,
+                             int32_t* counts, int64_t total, int32_t* status) {
+    return rl_host(bits, P, H, W, W, n_runs, offsets, counts, total, status);
+}
+
+// Planes whose rows end inside their last word (cvlm_mask_pack_sized's): W - 32 < Wt <= W
+int cvlm_mask_rle_count_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, void* stream) {
+    return rl_count(bits, P, H, W, Wt, n_runs, stream);
+}
+
+int cvlm_mask_rle_emit_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, const int64_t* offsets, int32_t* counts,
+                         int64_t total, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    return rl_emit(bits, P, H, W, Wt, offsets, counts, total, status, workspace, workspace_bytes, stream);
+}
+
+int cvlm_debug_mask_rle_host_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, const int64_t* offsets,
+                               int32_t* counts, int64_t total, int32_t* status) {
+    return rl_host(bits, P, H, W, Wt, n_runs, offsets, counts, total, status);
 }
 
 }  // extern "C"

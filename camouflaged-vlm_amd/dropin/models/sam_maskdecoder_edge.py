@@ -134,7 +134,7 @@ class SAM(nn.Module):
 
     def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False, vocab=None, masks="logits",
                       overlaps=False, components=None, min_area=0, connectivity=8, holes=None, fill_holes=0, band=None,
-                      edge_threshold=None, rle=None):
+                      edge_threshold=None, rle=None, sizes=None, sized_level=128):
         """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
         the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
         decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
@@ -143,7 +143,9 @@ class SAM(nn.Module):
         fill_holes=: its holes and the mask with its pinholes closed, band=: its edge band (:441-445 at radius 2), edge_threshold=:
         the edge head's map (:298-302) above that threshold as bits, counted on the band it is trained against (:441-447), rle="mask" /
         "kept" / "filled": those planes as COCO run-length counts (`rle`, engine.MaskRle), as engine.Cascade.infer_classes documents
-        them.  -> engine.ClassHypotheses (INTEGRATION.md, "K class hypotheses per image")."""
+        them; sizes= / sized_level=: the masks at each image's own (h, w) -- what test_ovcos_maskdecoder_edge.py:116-130 resizes to -- as
+        bits of the uint8 mask >= sized_level (`sized`, engine.SizedMasks), rle="sized": those as COCO RLE with each image's own "size".
+        -> engine.ClassHypotheses (INTEGRATION.md, "K class hypotheses per image")."""
         H, W = input.shape[-2:]
         assert H == self.inp_size and W == self.inp_size, \
             f"Input image size ({H}*{W}) doesn't match model ({self.inp_size}*{self.inp_size})."
@@ -151,7 +153,7 @@ class SAM(nn.Module):
                                             clip_zero_mask.float().contiguous(), classes=classes, topk=topk, quality=quality,
                                             vocab=self._vocab(vocab), masks=masks, overlaps=overlaps, components=components,
                                             min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
-                                            edge_threshold=edge_threshold, rle=rle)
+                                            edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level)
 
     def pack_masks(self, logits):
         """EXTENSION, not a reference method: (bits, area, box) of (N, S, S) or (N, 1, S, S) f32 mask logits, e.g. `infer_test`'s:
@@ -181,6 +183,17 @@ class SAM(nn.Module):
         -- the map :298-302 return -- resized to `size` (None: as they are), compared `> threshold` and packed in numpy.packbits'
         order, with their areas and their intersections with `with_bits` -> engine.EdgeBits (engine.Cascade.pack_edges)."""
         return self.cascade().pack_edges(prob, size, threshold=threshold, with_bits=with_bits)
+
+    def pack_masks_sized(self, logits, sizes, *, level=128):
+        """EXTENSION, not a reference method: (N, S, S) or (N, 1, S, S) f32 mask logits, e.g. `infer_test`'s, as packed masks at each
+        image's own size sizes[i] = (h, w): the bits of sigmoid -> cv2.resize -> * 255 (test_ovcos_maskdecoder_edge.py:103,116-130) >=
+        level -> engine.SizedMasks (engine.Cascade.pack_masks_sized)."""
+        return self.cascade().pack_masks_sized(logits, sizes, level=level)
+
+    def mask_rle_sized(self, sized):
+        """EXTENSION, not a reference method: COCO run-length encoding of an engine.SizedMasks, "size": [h, w] of each image
+        -> engine.MaskRle (engine.Cascade.mask_rle_sized)."""
+        return self.cascade().mask_rle_sized(sized)
 
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
@@ -212,7 +225,7 @@ class SAM(nn.Module):
     def decode_classes(self, enc, **kw):
         """EXTENSION, not a reference method: K prompts per encoded image -- `classes=`, `topk=` or caller-supplied text rows
         `text=` (what sam_text_proj takes at :342-344), optionally for a subset `images=`, with `quality=` / `stage2=` / `masks=` /
-        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
+        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` / `sizes=` / `sized_level=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
         with.  No encoder launch.  -> engine.ClassHypotheses."""
         self._vocab(kw.get("vocab"))
         return self.cascade().decode(enc, **kw)

@@ -1441,11 +1441,17 @@ class ClassHypotheses:
     # mask_bits, kept_bits or filled_bits of all B * K hypotheses, plane p = b * K + k: a MaskRle, on the device.  A hypothesis of
     # class -1 has zero bits and therefore the single count S * S.
     rle: InitVar[Optional["MaskRle"]] = None
+    # sizes=[(h, w), ...], otherwise None; a pseudo-field like `mask_bits`.  The masks of all B * K hypotheses at the
+    # size of each hypothesis's own image, plane p = b * K + k: a SizedMasks, on the device -- the bits of the reference's uint8 mask
+    # (sigmoid, cv2.resize to (h, w), * 255) >= sized_level, with their areas and boxes in the image's own coordinates.  With
+    # rle="sized", `rle` encodes these planes and its `to_coco()` carries each image's own "size".  A hypothesis of class -1 has zero
+    # bits, area 0 and box -1.
+    sized: InitVar[Optional["SizedMasks"]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
                       n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter,
-                      edge_bits, edge_area, edge_band, edge_inter, rle):
-        self.rle = rle
+                      edge_bits, edge_area, edge_band, edge_inter, rle, sized):
+        self.rle, self.sized = rle, sized
         self.edge_bits, self.edge_area, self.edge_band, self.edge_inter = edge_bits, edge_area, edge_band, edge_inter
         self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
@@ -1684,6 +1690,8 @@ class EdgeBits:
 
 RLE_WS_CAP = 64 << 20             # bytes of the "cls_rle" workspace at most; beyond it cvlm_mask_rle_emit walks the planes in rounds
 RLE_SOURCES = {"mask": "mask_bits", "kept": "kept_bits", "filled": "filled_bits"}
+RLE_SIZED = "sized"               # rle="sized": the planes of `sized` (sizes=), each at its image's own size
+SIZED_MAX_SIDE = 16384            # h and w of a sized plane (csrc/sized_logic.h: SZ_MAX_SIDE)
 
 
 def rle_request(*, rle=None, masks="bits", min_area=0, fill_holes=0, side: Optional[int] = None, who: str = "decode"):
@@ -1693,8 +1701,12 @@ def rle_request(*, rle=None, masks="bits", min_area=0, fill_holes=0, side: Optio
     model's masks."""
     if rle is None:
         return None
+    if isinstance(rle, str) and rle == RLE_SIZED:                    # the sized planes (DESIGN.md §19): `sized_request` holds it against sizes=
+        if masks == "logits":
+            raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
+        return RLE_SIZED
     if not isinstance(rle, str) or rle not in RLE_SOURCES:
-        raise ValueError(f"{who}: rle must be None or one of {tuple(RLE_SOURCES)}, got {rle!r}")
+        raise ValueError(f"{who}: rle must be None or one of {tuple(RLE_SOURCES) + (RLE_SIZED,)}, got {rle!r}")
     if masks == "logits":
         raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
     is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
@@ -1718,9 +1730,17 @@ class MaskRle:
     size: Tuple[int, int]           # (H, W)
     # (1,) int32 on the device, 0 unless cvlm_mask_rle_emit had to drop a count; `check` and `to_coco` read it.  Init-only, not a field.
     status: InitVar[Optional[torch.Tensor]] = None
+    # per-plane (h, w) on the host where the planes differ in size (Cascade.mask_rle_sized), otherwise None and every
+    # plane is `size`; `to_coco` writes each plane's own.  Init-only, not a field; `size` is then None unless all planes agree.
+    sizes: InitVar[Optional[Sequence[Tuple[int, int]]]] = None
 
-    def __post_init__(self, status):
+    def __post_init__(self, status, sizes):
         self.status = status
+        self.sizes = None if sizes is None else [(int(h), int(w)) for h, w in sizes]
+
+    def size_of(self, p: int) -> Tuple[int, int]:
+        """(H, W) of plane p."""
+        return self.sizes[p] if self.sizes is not None else self.size
 
     def check(self) -> None:
         """RuntimeError if the emit dropped a count (synchronises).  The slices come from the call's own count of the same bits, so
@@ -1730,18 +1750,97 @@ class MaskRle:
                                "while the call ran?")
 
     def to_coco(self, compressed: bool = False) -> list:
-        """On the host: one {"size": [H, W], "counts": ...} per plane, what pycocotools and the reference's GenericMask
-        (models/utils/visualizer.py:72-101) take; counts is a list of ints, or with compressed=True COCO's string as bytes
-        (rle.counts_to_string).  One copy of each of the three tensors; synchronises."""
+        """On the host: one {"size": [H, W], "counts": ...} per plane (each plane's own size where they differ), what pycocotools and
+        the reference's GenericMask (models/utils/visualizer.py:72-101) take; counts is a list of ints, or with compressed=True COCO's
+        string as bytes (rle.counts_to_string).  One copy of each of the three tensors; synchronises."""
         from . import rle as _rle
         self.check()
         counts, offsets = self.counts.cpu().numpy(), self.offsets.cpu().numpy()
-        H, W = self.size
         out = []
         for p in range(offsets.size - 1):
+            H, W = self.size_of(p)
             c = counts[offsets[p]:offsets[p + 1]]
             out.append({"size": [int(H), int(W)], "counts": _rle.counts_to_string(c) if compressed else c.tolist()})
         return out
+
+
+def sized_tables(plane_sizes):
+    """Host tables of sized planes for a list of per-plane (h, w): dims int32 (P, 2), byte offsets int64 (P + 1) --
+    plane p is h rows of ceil(w / 32) 32-bit words, the planes lie back to back -- and the largest plane's word count."""
+    dims = np.asarray(plane_sizes, dtype=np.int32).reshape(-1, 2)
+    words = dims[:, 0].astype(np.int64) * ((dims[:, 1].astype(np.int64) + 31) // 32)
+    offsets = np.zeros(dims.shape[0] + 1, dtype=np.int64)
+    np.cumsum(4 * words, out=offsets[1:])
+    return dims, offsets, int(words.max())
+
+
+def sized_request(*, sizes=None, sized_level=128, n: int, masks="bits", rle=None, who: str = "decode"):
+    """Every check of the sizes= / sized_level= arguments of Cascade.infer_classes / decode and of Cascade.pack_masks_sized (DESIGN.md
+    §19), on the host, before anything is launched (ValueError) -> None when nothing is asked for, otherwise (the n (h, w) pairs as
+    ints, the level).  sizes: one (h, w) per image of the call, 1 <= h, w <= 16384; sized_level: an int in 1 .. 255, the level the
+    reference's uint8 mask is compared with (128: the half; 1: demo.py's `> 0` overlay).  They need packed masks (masks="bits" or
+    "both"), and rle="sized" needs sizes=."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not is_int(sized_level) or not 1 <= int(sized_level) <= 255:
+        raise ValueError(f"{who}: sized_level must be an int in [1, 255], got {sized_level!r}")
+    if sizes is None:
+        if isinstance(rle, str) and rle == RLE_SIZED:
+            raise ValueError(f"{who}: rle='sized' encodes the sized planes: give sizes=")
+        return None
+    if masks == "logits":
+        raise ValueError(f"{who}: sizes= packs masks at the images' sizes: ask for masks='bits' or 'both'")
+    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
+        raise ValueError(f"{who}: sizes must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
+    if len(sizes) != n:
+        raise ValueError(f"{who}: sizes holds {len(sizes)} pairs for {n} images")
+    out = []
+    for pair in sizes:
+        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+            raise ValueError(f"{who}: sizes must hold (h, w) pairs, got {pair!r}")
+        h, w = pair
+        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+            raise ValueError(f"{who}: a size of sizes= must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
+        out.append((int(h), int(w)))
+    return out, int(sized_level)
+
+
+@dataclass
+class SizedMasks:
+    """Packed masks at each image's own size (Cascade.pack_masks_sized, sizes= of infer_classes / decode).  Plane p has
+    the size sizes[p] = (h, w) and is h rows of ws = ceil(w / 32) 32-bit words in numpy.packbits' order -- the bit order of `mask_bits`
+    -- from byte offsets[p] of the flat tensor `bits` on; the pad bits of a row, columns w .. 32 ws - 1, are 0, so that
+    `mask_components(plane rows, h, 32 * ws)` and its kin run on one image's planes as they are.  A bit is the reference's uint8 mask
+    -- sigmoid, cv2.resize(INTER_LINEAR) to (h, w), (. * 255).astype(uint8) -- compared `>= level`.  At the model's own size these are
+    NOT `mask_bits` (logit > 0): they go through the resize's arithmetic with weights 1 and 0 and compare a probability with level / 255."""
+    bits: torch.Tensor              # (total bytes,) uint8 on the device
+    offsets: torch.Tensor           # (P + 1,) int64 on the device, in bytes, multiples of 4; offsets[P] = bits.numel()
+    area: torch.Tensor              # (P,) int32 set bits
+    box: torch.Tensor               # (P, 4) int32 inclusive (x0, y0, x1, y1) in the image's own coordinates, -1 for an empty plane
+    status: torch.Tensor            # int32 on the device, one word per cvlm_mask_pack_sized call: non-zero if a plane was refused
+    sizes: list                     # P (h, w) pairs, on the host
+    level: int = 128
+
+    def byte_range(self, p: int) -> Tuple[int, int]:
+        """Where plane p lies in `bits`, from the sizes alone (the planes lie back to back): no read of the device."""
+        _, offsets, _ = sized_tables(self.sizes)
+        return int(offsets[p]), int(offsets[p + 1])
+
+    def plane(self, p: int) -> torch.Tensor:
+        """Plane p as a uint8 view (h, 4 * ws) of `bits`: rows in numpy.packbits' order."""
+        h, w = self.sizes[p]
+        lo, hi = self.byte_range(p)
+        return self.bits[lo:hi].view(h, 4 * ((w + 31) // 32))
+
+    def to_numpy(self, p: int) -> np.ndarray:
+        """Plane p as a bool array (h, w) on the host (synchronises)."""
+        h, w = self.sizes[p]
+        return np.unpackbits(self.plane(p).cpu().numpy(), axis=1)[:, :w].astype(bool)
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
+        says that the library is broken."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("pack_masks_sized: cvlm_mask_pack_sized refused a plane whose slice did not fit its size")
 
 
 @dataclass
@@ -2502,10 +2601,101 @@ class Cascade(_Base):
         hip.mask_rle_emit(bits, H, W, offsets, counts, status, ws)
         return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=(H, W), status=status)
 
+    # ---- masks at each image's own size ---------------------------------------------------------------------------
+    def _sized_outputs(self, sreq, K: int, n_calls: int):
+        """sizes= of infer_classes / decode: the result's own SizedMasks for K hypotheses per image and the device table of the planes'
+        (h, w) -- built on the host and uploaded once, before the chunk loop -> (SizedMasks, dims, largest word count) or None."""
+        if sreq is None:
+            return None
+        sizes, level = sreq
+        per_plane = [s for s in sizes for _ in range(K)]
+        dims, offsets, max_words = sized_tables(per_plane)
+        dev, P = self.device, len(per_plane)
+        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
+                         area=torch.empty(P, dtype=torch.int32, device=dev), box=torch.empty(P, 4, dtype=torch.int32, device=dev),
+                         status=torch.empty(n_calls, dtype=torch.int32, device=dev), sizes=per_plane, level=level)
+        return out, torch.from_numpy(dims).to(dev), max_words
+
+    @staticmethod
+    def _pack_sized_chunk(planes: torch.Tensor, sized, p0: int, p1: int, call: int) -> None:
+        """cvlm_mask_pack_sized of a chunk's full-resolution planes into the planes p0 .. p1 - 1 of the result's SizedMasks: one call
+        whatever sizes the chunk holds, no workspace."""
+        if sized is None:
+            return
+        out, dims, max_words = sized
+        hip.mask_pack_sized(planes[:p1 - p0], dims[p0:p1], out.offsets[p0:p1 + 1], out.level, out.bits, max_words, out.area[p0:p1],
+                            out.box[p0:p1], out.status[call:call + 1])
+
+    def pack_masks_sized(self, logits: torch.Tensor, sizes, *, level: int = 128) -> "SizedMasks":
+        """Packed masks of any (N, Hs, Ws) or (N, 1, Hs, Ws) f32 mask logits on this engine's device at a size of each plane's own:
+        sizes holds N (h, w) pairs -> SizedMasks (cvlm_mask_pack_sized).  A bit is set where the reference's uint8 mask
+        -- sigmoid, cv2.resize(INTER_LINEAR) to (h, w), * 255 (test_ovcos_maskdecoder_edge.py:103,116-130; demo.py:117-131) -- is >=
+        level: 128 is the half, 1 the demo's `> 0` overlay.  At (Hs, Ws) itself the bits are NOT `pack_masks`' (logit > 0): they go
+        through the same arithmetic with weights 1 and 0.  One launch pair on the caller's stream whatever the mix of sizes, the two
+        small tables uploaded before it; no workspace.  ValueError before anything is launched for anything else."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (3, 4) or \
+                (logits.dim() == 4 and logits.shape[1] != 1):
+            raise ValueError("pack_masks_sized: logits must be a float32 tensor (N, H, W) or (N, 1, H, W)")
+        N, (Hs, Ws) = int(logits.shape[0]), (int(v) for v in logits.shape[-2:])
+        if not 1 <= N <= 65535 or Hs < 1 or Ws < 1 or Hs * Ws >= 2 ** 31:
+            raise ValueError(f"pack_masks_sized: {N} planes of {Hs} x {Ws}: 1 .. 65535 planes of fewer than 2^31 pixels")
+        if not logits.is_cuda:
+            raise ValueError("pack_masks_sized: logits must be on the device")
+        sreq = sized_request(sizes=sizes, sized_level=level, n=N, who="pack_masks_sized")
+        if sreq is None:
+            raise ValueError("pack_masks_sized: sizes must be a sequence of (h, w) pairs, got None")
+        sized = self._sized_outputs(sreq, 1, 1)
+        self._pack_sized_chunk(logits.detach().contiguous().view(N, Hs, Ws), sized, 0, N, 0)
+        return sized[0]
+
+    def mask_rle_sized(self, sized: "SizedMasks") -> "MaskRle":
+        """COCO run-length encoding of sized planes -> MaskRle whose `to_coco()` writes each plane's own "size": [h, w],
+        what an evaluator holds against an annotation of the original image.  One cvlm_mask_rle_count_w call per run of consecutive
+        planes of one size -- per image where the planes come from the engine --, one torch.cumsum, ONE read of the total (the call's
+        only synchronisation), then one cvlm_mask_rle_emit_w call per run through the workspace "cls_rle", all on absolute offsets
+        into one `counts`.  The status words of the runs are folded into one on the device."""
+        if not isinstance(sized, SizedMasks):
+            raise ValueError(f"mask_rle_sized: sized must be a SizedMasks, got {type(sized).__name__}")
+        sizes = sized.sizes
+        P, dev = len(sizes), sized.bits.device
+        if not 1 <= P <= 65535 or not sized.bits.is_cuda:
+            raise ValueError("mask_rle_sized: 1 .. 65535 planes on the device")
+        _, host_off, _ = sized_tables(sizes)
+        runs, a = [], 0                                               # (first plane, one past the last) of each run of equal sizes
+        for p in range(1, P + 1):
+            if p == P or sizes[p] != sizes[a]:
+                runs.append((a, p))
+                a = p
+        n_runs = torch.empty(P, dtype=torch.int32, device=dev)
+        rows = lambda a, b: sized.bits[int(host_off[a]):int(host_off[b])].view(b - a, -1)
+        for a, b in runs:
+            h, w = sizes[a]
+            hip.mask_rle_count_w(rows(a, b), h, 32 * ((w + 31) // 32), w, n_runs[a:b])
+        offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
+        total = int(offsets[P].item())                               # the one synchronisation
+        counts = torch.empty(total, dtype=torch.int32, device=dev)
+        status = torch.empty(len(runs), dtype=torch.int32, device=dev)
+        want = 0
+        for a, b in runs:
+            h, w = sizes[a]
+            pitch = 32 * ((w + 31) // 32)
+            want = max(want, min(hip.mask_rle_workspace_bytes(b - a, h, pitch), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, h, pitch))))
+        ws = self.ws._get("u8", "cls_rle", want, torch.uint8, False)
+        for i, (a, b) in enumerate(runs):
+            h, w = sizes[a]
+            hip.mask_rle_emit_w(rows(a, b), h, 32 * ((w + 31) // 32), w, offsets[a:b + 1], counts, status[i:i + 1], ws)
+        same = all(s == sizes[0] for s in sizes)
+        return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=sizes[0] if same else None,
+                       status=torch.amax(status, 0, keepdim=True), sizes=sizes)
+
     def _rle_of(self, source: Optional[str], fields: dict, S: int) -> Optional["MaskRle"]:
-        """rle= of infer_classes / decode: `mask_rle` of the result's own planes named by `rle_request`, all n * K of them at once."""
+        """rle= of infer_classes / decode: `mask_rle` of the result's own planes named by `rle_request`, all n * K of them at once;
+        rle="sized": `mask_rle_sized` of the result's sized planes."""
         if source is None:
             return None
+        if source == RLE_SIZED:
+            return self.mask_rle_sized(fields[RLE_SIZED][0])
         planes = fields[source]
         return self.mask_rle(planes.view(-1, planes.shape[-1]), S, S)
 
@@ -2514,7 +2704,7 @@ class Cascade(_Base):
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                       connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
                       band: Optional[int] = None, edge_threshold: Optional[float] = None,
-                      rle: Optional[str] = None) -> ClassHypotheses:
+                      rle: Optional[str] = None, sizes=None, sized_level: int = 128) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2571,7 +2761,16 @@ class Cascade(_Base):
         all B * K hypotheses -- `mask_rle`, once, behind the last chunk where cvlm_mask_overlap runs: two count launches, a cumsum,
         one read of the total (a synchronisation of the host with the side stream) and the emit's launches.  An interchange format
         for pycocotools, the COCO / LVIS evaluators and the reference's GenericMask, not a compression: see DESIGN.md §18 for sizes.
-        Without it the call makes exactly the launches, allocations and synchronisations it made before."""
+        Without it the call makes exactly the launches, allocations and synchronisations it made before.
+        sizes= / sized_level= (`sized_request`, checked with the rest; they need masks="bits" or "both"): sizes holds one
+        (h, w) per image, the size of the ORIGINAL image the evaluation compares at; adds `sized`, a SizedMasks with the K masks of
+        image b at (h_b, w_b) -- the bits of the reference's uint8 mask (sigmoid, cv2.resize to (h, w), * 255) >= sized_level, with
+        areas and boxes in the image's coordinates -- by one cvlm_mask_pack_sized call per chunk on the chunk's full-resolution planes,
+        right behind cvlm_mask_pack, into the result's own tensors: no workspace, and with masks="bits" still no f32 plane in the
+        result.  The two tables of the planes are built on the host and uploaded once, before the first chunk.  rle="sized" (needs
+        sizes=) encodes those planes, `mask_rle_sized`, behind the last chunk: `rle.to_coco()` then carries "size": [h, w] of each
+        image, which an evaluator can hold against an annotation.  Without sizes= the call makes exactly the launches, allocations and
+        synchronisations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
@@ -2584,6 +2783,7 @@ class Cascade(_Base):
         ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size,
                             who="infer_classes")
         rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size, who="infer_classes")
+        sreq = sized_request(sizes=sizes, sized_level=sized_level, n=B, masks=masks, rle=rle, who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2608,6 +2808,7 @@ class Cascade(_Base):
             edged = self._edge_outputs(B, K, S * S // 8, ereq)
             mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
+            sized = self._sized_outputs(sreq, K, -(-P // chunk))
             for p0 in range(0, P, chunk):
                 p1 = min(P, p0 + chunk)
                 n = p1 - p0
@@ -2623,6 +2824,7 @@ class Cascade(_Base):
                 self._mask_logits(fr, sp, n, out=planes, edge_out=eplanes, iou_out=iou.view(P)[p0:p1] if quality else None,
                                   edge_low=not want_logits)
                 self._pack_chunk(planes, compact, p0, p1)
+                self._pack_sized_chunk(planes, sized, p0, p1, p0 // chunk)
                 if mreq[0]:
                     self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
                 if ereq[0]:
@@ -2640,15 +2842,17 @@ class Cascade(_Base):
                 hip.mask_overlap(edged[0], edged[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
-            runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3]}, S)
+            runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
         coded = () if runs is None else (runs.counts, runs.offsets, runs.n_runs, runs.status)
+        fitted = () if sized is None else (sized[0].bits, sized[0].offsets, sized[0].area, sized[0].box, sized[0].status)
         self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged + coded
+                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged + coded + fitted
                         if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs)
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
+                               sized=None if sized is None else sized[0])
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2686,7 +2890,8 @@ class Cascade(_Base):
                stage2: bool = True, vocab: Optional[Vocabulary] = None, masks: str = "logits",
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None,
-               edge_threshold: Optional[float] = None, rle: Optional[str] = None) -> ClassHypotheses:
+               edge_threshold: Optional[float] = None, rle: Optional[str] = None, sizes=None,
+               sized_level: int = 128) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2708,7 +2913,9 @@ class Cascade(_Base):
         band=: as in `infer_classes`, checked by `morph_request` with the rest.
         edge_threshold=: as in `infer_classes`, checked by `edge_request` with the rest.
         rle=: as in `infer_classes`, checked by `rle_request` with the rest; its one read synchronises the host with
-        the caller's stream."""
+        the caller's stream.
+        sizes= / sized_level=: as in `infer_classes`, checked by `sized_request` with the rest; one (h, w) per decoded
+        row -- per entry of `images` --, and rle="sized" encodes the sized planes."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2725,6 +2932,7 @@ class Cascade(_Base):
         mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size)
         ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size)
         rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size)
+        sreq = sized_request(sizes=sizes, sized_level=sized_level, n=len(images), masks=masks, rle=rle)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -2761,6 +2969,7 @@ class Cascade(_Base):
         edged = self._edge_outputs(n, K, S * S // 8, ereq)
         mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
+        sized = self._sized_outputs(sreq, K, -(-P // chunk))
         for p0 in range(0, P, chunk):
             p1 = min(P, p0 + chunk)
             m = p1 - p0
@@ -2772,6 +2981,7 @@ class Cascade(_Base):
             self._mask_logits((enc.state, of, B), sp, m, out=planes, edge_out=eplanes,
                               iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not want_logits)
             self._pack_chunk(planes, compact, p0, p1)
+            self._pack_sized_chunk(planes, sized, p0, p1, p0 // chunk)
             if mreq[0]:
                 self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
             if ereq[0]:
@@ -2790,12 +3000,13 @@ class Cascade(_Base):
             hip.mask_overlap(edged[0], edged[3])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
-        runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3]}, S)
+        runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs)
+                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
+                               sized=None if sized is None else sized[0])
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

@@ -74,6 +74,11 @@ _SIGNATURES = {
     "cvlm_mask_rle_count": "i:piiips",
     "cvlm_mask_rle_emit": "i:piiipplppls",
     "cvlm_debug_mask_rle_host": "i:piiippplp",
+    "cvlm_mask_rle_count_w": "i:piiiips",
+    "cvlm_mask_rle_emit_w": "i:piiiipplppls",
+    "cvlm_debug_mask_rle_host_w": "i:piiiippplp",
+    "cvlm_mask_pack_sized": "i:piiippipllppps",
+    "cvlm_debug_mask_pack_sized_host": "i:piiippipllppp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -983,6 +988,79 @@ def mask_rle_host(bits: torch.Tensor, H: int, W: int, n_runs: torch.Tensor, offs
     assert not bits.is_cuda
     _call("cvlm_debug_mask_rle_host", bits.data_ptr(), P, H, W, n_runs.data_ptr(), _p(offsets), _p(counts),
           0 if counts is None else counts.numel(), _p(status))
+
+
+def _rle_w_args(bits: torch.Tensor, H: int, W: int, Wt: int) -> None:
+    assert W % 32 == 0 and W - 32 < Wt <= W, "the true width ends inside the last word of the row pitch"
+
+
+def mask_rle_count_w(bits: torch.Tensor, H: int, W: int, Wt: int, n_runs: torch.Tensor) -> None:
+    """`mask_rle_count` of planes uint8 [P][H * W / 8] whose rows hold Wt <= W pixels, W - 32 < Wt (cvlm_mask_pack_sized's planes): the
+    counts of the encoding of the H x Wt image (include/cvlm.h: cvlm_mask_rle_count_w)."""
+    _rle_w_args(bits, H, W, Wt)
+    P = _rle_args(bits, H, W, n_runs, None, None, None)
+    _on_current_device(bits)
+    _call("cvlm_mask_rle_count_w", bits.data_ptr(), P, H, W, Wt, n_runs.data_ptr())
+
+
+def mask_rle_emit_w(bits: torch.Tensor, H: int, W: int, Wt: int, offsets: torch.Tensor, counts: torch.Tensor, status: torch.Tensor,
+                    workspace: torch.Tensor) -> None:
+    """`mask_rle_emit` of planes uint8 [P][H * W / 8] whose rows hold Wt <= W pixels (cvlm_mask_rle_emit_w); the workspace is
+    mask_rle_workspace_bytes of the pitch W."""
+    _rle_w_args(bits, H, W, Wt)
+    P = _rle_args(bits, H, W, None, offsets, counts, status)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
+    _on_current_device(bits)
+    _call("cvlm_mask_rle_emit_w", bits.data_ptr(), P, H, W, Wt, offsets.data_ptr(), counts.data_ptr(), counts.numel(), status.data_ptr(),
+          workspace.data_ptr(), workspace.numel())
+
+
+def mask_rle_host_w(bits: torch.Tensor, H: int, W: int, Wt: int, n_runs: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                    counts: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
+    """`mask_rle_count_w` and, with counts, `mask_rle_emit_w` on HOST tensors without a device (cvlm_debug_mask_rle_host_w)."""
+    _rle_w_args(bits, H, W, Wt)
+    P = _rle_args(bits, H, W, n_runs, offsets, counts, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_rle_host_w", bits.data_ptr(), P, H, W, Wt, n_runs.data_ptr(), _p(offsets), _p(counts),
+          0 if counts is None else counts.numel(), _p(status))
+
+
+def _sized_args(logits, dims, offsets, level, bits, area, box, status) -> Tuple[int, int, int]:
+    """Shape and dtype checks shared by `mask_pack_sized` and `mask_pack_sized_host` -> (P, Hs, Ws)."""
+    P, Hs, Ws = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
+    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
+    assert isinstance(level, int) and (area is None) == (box is None)
+    if area is not None:
+        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == logits.device for t in (dims, offsets, bits, area, box, status))
+    return P, Hs, Ws
+
+
+def mask_pack_sized(logits: torch.Tensor, dims: torch.Tensor, offsets: torch.Tensor, level: int, bits: torch.Tensor, max_words: int,
+                    area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """logits f32 [P][Hs][Ws] -> the planes of `cvlm_mask_to_u8(...) >= level` at each plane's own size dims[p] = (h, w), packed as h rows of
+    ceil(w / 32) words in numpy.packbits' order from byte offsets[p] of the flat uint8 tensor `bits` on (offsets int64 [P + 1]); area
+    int32 [P] and box int32 [P][4] together or not at all; status int32 [1] becomes 1 if a plane's slice did not fit its size or left
+    `bits` -- that plane is skipped --, otherwise 0.  max_words: the largest h * ceil(w / 32) of the call (include/cvlm.h)."""
+    P, Hs, Ws = _sized_args(logits, dims, offsets, level, bits, area, box, status)
+    _on_current_device(logits)
+    _call("cvlm_mask_pack_sized", logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level, bits.data_ptr(), bits.numel(),
+          int(max_words), _p(area), _p(box), status.data_ptr())
+
+
+def mask_pack_sized_host(logits: torch.Tensor, dims: torch.Tensor, offsets: torch.Tensor, level: int, bits: torch.Tensor, max_words: int,
+                         area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """`mask_pack_sized` on HOST tensors without a device (cvlm_debug_mask_pack_sized_host: the kernel's per-pixel functions run
+    sequentially on the CPU)."""
+    P, Hs, Ws = _sized_args(logits, dims, offsets, level, bits, area, box, status)
+    assert not logits.is_cuda
+    _call("cvlm_debug_mask_pack_sized_host", logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level, bits.data_ptr(),
+          bits.numel(), int(max_words), _p(area), _p(box), status.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

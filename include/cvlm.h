@@ -686,6 +686,51 @@ int cvlm_mask_rle_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, co
  * looked at.  Same outputs, same refusals. */
 int cvlm_debug_mask_rle_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t* n_runs, const int64_t* offsets,
                              int32_t* counts, int64_t total, int32_t* status);
+/* The same three entries for planes whose rows end INSIDE their last word: W is the row pitch in pixels, W % 32 == 0 as
+ * above, and Wt, W - 32 < Wt <= W, the plane's true width -- the sized planes of cvlm_mask_pack_sized have W = 32 * ceil(Wt / 32).
+ * Column-major order puts the pad columns Wt .. W - 1 behind the image, so they are cut off, not encoded: the transition words are
+ * masked to the columns below Wt (a transition bit is a function of its own column and the one before it, so whatever the pad bits
+ * hold changes nothing), the stream has exactly H * Wt bits, and the tail run ends at H * Wt -- the encoding of the H x Wt image, which
+ * the encoding of the padded plane is not (its last count is longer, and a set pixel (H - 1, Wt - 1) adds a transition at H * Wt).
+ * Everything behind the transpose only sees a shorter stream.  The entries above are the case Wt = W of the same kernels.  Workspace:
+ * cvlm_mask_rle_workspace_bytes(P, H, W) of the pitch.  CVLM_E_BADARG as above, and for Wt outside (W - 32, W]. */
+int cvlm_mask_rle_count_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, void* stream);
+int cvlm_mask_rle_emit_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, const int64_t* offsets, int32_t* counts,
+                         int64_t total, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int cvlm_debug_mask_rle_host_w(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, const int64_t* offsets,
+                               int32_t* counts, int64_t total, int32_t* status);
+
+/* Packed masks at each image's own size: what the reference's evaluation loop and demo look at -- sigmoid, cv2.resize
+ * (INTER_LINEAR) to the image's own (h, w), `* 255` as uint8 (test_ovcos_maskdecoder_edge.py:103,116-130; demo.py:117-131) -- compared
+ * with a level and packed, from the full-resolution logit planes in one pass, for planes of any mix of sizes.
+ * logits f32 [P][Hs][Ws]; dims int32 [P][2] = (h, w) of each plane, 1 <= h, w <= 16384; offsets int64 [P + 1] in BYTES into bits, all
+ * three device memory.  Plane p is h rows of ws = ceil(w / 32) 32-bit words from bits + offsets[p] on, in numpy.packbits' order
+ * (cvlm_mask_pack's bit order: pixel x of a row is bit 7 - (x & 7) of the row's byte x >> 3); the pad bits of a row, columns w ..
+ * 32 ws - 1, are written as 0.  bit(y, x) = (v(y, x) * 255.0f >= (float)level), v the value cvlm_mask_to_u8 forms: four taps through
+ * the fp32 sigmoid, source coordinates in double rounded to float, column weights zeroed at the border, row indices clamped, the
+ * horizontal blend then the vertical one, each two fp32 products and one fp32 sum; h = Hs, w = Ws runs the same arithmetic with
+ * weights 1 and 0.  For finite v that is "cvlm_mask_to_u8's byte >= level": level 128 is the half, level 1 the demo's `> 0` overlay.
+ * A NaN compares false: a NaN plane gives zero bits, area 0, box -1.  At (Hs, Ws) these are NOT cvlm_mask_pack's bits (logit > 0).
+ * area int32 [P], box int32 [P][4] = inclusive (x0, y0, x1, y1) in the plane's own coordinates, -1 for an empty plane; NULL together.
+ * status int32 [1]: the call zeroes it.  Before EVERY store the kernel checks 1 <= h, w <= 16384, offsets[p + 1] - offsets[p] ==
+ * 4 h ws, 0 <= offsets[p], offsets[p] % 4 == 0 and offsets[p + 1] <= bits_bytes; a plane that fails is not read, not stored, keeps
+ * area 0 and box -1 and ORs 1 into status[0]: no table content makes the kernel store outside bits[0, bits_bytes) or read outside
+ * logits.  max_words: the largest h * ws of the call, which sizes the grid (a smaller value costs time, not correctness).
+ * One launch after the init launch (status, area, box), grid (workgroups of the largest plane, P): a wave takes 64 consecutive pixels
+ * of one output row, each lane forms its pixel -- lanes at x >= w read nothing and give 0 --, one ballot holds both words, bit
+ * reversal + byte swap put them into packbits' order and lanes 0 and 32 store them; counts and box corners are reduced per
+ * workgroup and reach memory as at most five integer atomics per workgroup that found a set pixel.  64-bit offsets.  No workspace,
+ * no allocation, no synchronisation.  CVLM_E_BADARG, before anything touches the device: a NULL pointer (area and box may be NULL
+ * together), logits / bits / dims / area / box / status not 4-byte aligned, offsets not 8-byte aligned, P outside [1, 65535], Hs or Ws
+ * <= 0, Hs * Ws >= 2^31, level outside [1, 255], bits_bytes < 4, max_words outside [1, 16384 * 512]. */
+int cvlm_mask_pack_sized(const float* logits, int32_t P, int32_t Hs, int32_t Ws, const int32_t* dims, const int64_t* offsets,
+                         int32_t level, uint8_t* bits, int64_t bits_bytes, int64_t max_words, int32_t* area, int32_t* box,
+                         int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_mask_pack_sized on HOST memory, no stream -- the same per-pixel functions (csrc/sized_logic.h) run
+ * sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_pack_sized_host(const float* logits, int32_t P, int32_t Hs, int32_t Ws, const int32_t* dims, const int64_t* offsets,
+                                    int32_t level, uint8_t* bits, int64_t bits_bytes, int64_t max_words, int32_t* area, int32_t* box,
+                                    int32_t* status);
 
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
