@@ -134,7 +134,7 @@ class SAM(nn.Module):
 
     def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False, vocab=None, masks="logits",
                       overlaps=False, components=None, min_area=0, connectivity=8, holes=None, fill_holes=0, band=None,
-                      edge_threshold=None, rle=None, sizes=None, sized_level=128):
+                      edge_threshold=None, rle=None, sizes=None, sized_level=128, ground_truth=None):
         """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
         the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
         decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
@@ -144,7 +144,9 @@ class SAM(nn.Module):
         the edge head's map (:298-302) above that threshold as bits, counted on the band it is trained against (:441-447), rle="mask" /
         "kept" / "filled": those planes as COCO run-length counts (`rle`, engine.MaskRle), as engine.Cascade.infer_classes documents
         them; sizes= / sized_level=: the masks at each image's own (h, w) -- what test_ovcos_maskdecoder_edge.py:116-130 resizes to -- as
-        bits of the uint8 mask >= sized_level (`sized`, engine.SizedMasks), rle="sized": those as COCO RLE with each image's own "size".
+        bits of the uint8 mask >= sized_level (`sized`, engine.SizedMasks), rle="sized": those as COCO RLE with each image's own "size";
+        ground_truth=(gt, gt_image): the sized planes' intersections with the annotations of their image (`gt_overlaps`,
+        engine.SizedOverlaps, whose `iou()` is the COCO IoU).
         -> engine.ClassHypotheses (INTEGRATION.md, "K class hypotheses per image")."""
         H, W = input.shape[-2:]
         assert H == self.inp_size and W == self.inp_size, \
@@ -153,7 +155,8 @@ class SAM(nn.Module):
                                             clip_zero_mask.float().contiguous(), classes=classes, topk=topk, quality=quality,
                                             vocab=self._vocab(vocab), masks=masks, overlaps=overlaps, components=components,
                                             min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
-                                            edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level)
+                                            edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level,
+                                            ground_truth=ground_truth)
 
     def pack_masks(self, logits):
         """EXTENSION, not a reference method: (bits, area, box) of (N, S, S) or (N, 1, S, S) f32 mask logits, e.g. `infer_test`'s:
@@ -195,6 +198,16 @@ class SAM(nn.Module):
         -> engine.MaskRle (engine.Cascade.mask_rle_sized)."""
         return self.cascade().mask_rle_sized(sized)
 
+    def rle_decode(self, rles, *, stats=True):
+        """EXTENSION, not a reference method: COCO run-length annotations -- a list of {"size": [h, w], "counts": ...} dicts, or an
+        engine.MaskRle on the device -- as packed masks at each annotation's own size -> engine.SizedMasks (engine.Cascade.rle_decode)."""
+        return self.cascade().rle_decode(rles, stats=stats)
+
+    def mask_inter_sized(self, a, b, *, pairs=None, a_image=None, b_image=None):
+        """EXTENSION, not a reference method: intersections of pairs of planes of two engine.SizedMasks, detections against annotations
+        -> engine.SizedOverlaps, whose `iou(iscrowd)` is pycocotools' rleIou (engine.Cascade.mask_inter_sized)."""
+        return self.cascade().mask_inter_sized(a, b, pairs=pairs, a_image=a_image, b_image=b_image)
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads
@@ -225,7 +238,7 @@ class SAM(nn.Module):
     def decode_classes(self, enc, **kw):
         """EXTENSION, not a reference method: K prompts per encoded image -- `classes=`, `topk=` or caller-supplied text rows
         `text=` (what sam_text_proj takes at :342-344), optionally for a subset `images=`, with `quality=` / `stage2=` / `masks=` /
-        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` / `sizes=` / `sized_level=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
+        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` / `sizes=` / `sized_level=` / `ground_truth=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
         with.  No encoder launch.  -> engine.ClassHypotheses."""
         self._vocab(kw.get("vocab"))
         return self.cascade().decode(enc, **kw)

@@ -1447,11 +1447,15 @@ class ClassHypotheses:
     # rle="sized", `rle` encodes these planes and its `to_coco()` carries each image's own "size".  A hypothesis of class -1 has zero
     # bits, area 0 and box -1.
     sized: InitVar[Optional["SizedMasks"]] = None
+    # ground_truth=(gt, gt_image) (needs sizes=), otherwise None; a pseudo-field like `sized`.  The intersections of the
+    # sized planes with the annotations of their own image: a SizedOverlaps over all pairs (p = b * K + k, q) with gt_image[q] == b,
+    # ordered by p, then q; `gt_overlaps.iou(iscrowd)` is the COCO IoU of each pair.
+    gt_overlaps: InitVar[Optional["SizedOverlaps"]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
                       n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter,
-                      edge_bits, edge_area, edge_band, edge_inter, rle, sized):
-        self.rle, self.sized = rle, sized
+                      edge_bits, edge_area, edge_band, edge_inter, rle, sized, gt_overlaps):
+        self.rle, self.sized, self.gt_overlaps = rle, sized, gt_overlaps
         self.edge_bits, self.edge_area, self.edge_band, self.edge_inter = edge_bits, edge_area, edge_band, edge_inter
         self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
@@ -1814,11 +1818,11 @@ class SizedMasks:
     NOT `mask_bits` (logit > 0): they go through the resize's arithmetic with weights 1 and 0 and compare a probability with level / 255."""
     bits: torch.Tensor              # (total bytes,) uint8 on the device
     offsets: torch.Tensor           # (P + 1,) int64 on the device, in bytes, multiples of 4; offsets[P] = bits.numel()
-    area: torch.Tensor              # (P,) int32 set bits
-    box: torch.Tensor               # (P, 4) int32 inclusive (x0, y0, x1, y1) in the image's own coordinates, -1 for an empty plane
+    area: Optional[torch.Tensor]    # (P,) int32 set bits; None from rle_decode(stats=False), like box
+    box: Optional[torch.Tensor]     # (P, 4) int32 inclusive (x0, y0, x1, y1) in the image's own coordinates, -1 for an empty plane
     status: torch.Tensor            # int32 on the device, one word per cvlm_mask_pack_sized call: non-zero if a plane was refused
     sizes: list                     # P (h, w) pairs, on the host
-    level: int = 128
+    level: int = 128                # 0: not a threshold -- the planes were decoded from run counts (Cascade.rle_decode, DESIGN.md §20)
 
     def byte_range(self, p: int) -> Tuple[int, int]:
         """Where plane p lies in `bits`, from the sizes alone (the planes lie back to back): no read of the device."""
@@ -1840,7 +1844,151 @@ class SizedMasks:
         """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
         says that the library is broken."""
         if bool(self.status.ne(0).any().item()):
+            if self.level == 0:
+                raise RuntimeError("rle_decode: cvlm_mask_rle_decode refused a plane: counts that are negative or do not sum to h * w, "
+                                   "or a slice that does not fit")
             raise RuntimeError("pack_masks_sized: cvlm_mask_pack_sized refused a plane whose slice did not fit its size")
+
+
+def rle_decode_request(rles, who: str = "rle_decode"):
+    """Every check of a list of COCO run-length dicts {"size": [h, w], "counts": list | bytes | str}, on the host, before
+    anything is launched (ValueError) -> (counts int32 (total,), run offsets int64 (P + 1,) in elements of counts, the P (h, w) pairs).
+    A string is COCO's compressed form (rle.string_to_counts).  h and w are ints in [1, 16384]; the counts are non-negative -- zeros are
+    legal anywhere, pycocotools emits them -- and sum to h * w."""
+    from . import rle as _rle
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if isinstance(rles, (str, bytes, dict)) or not hasattr(rles, "__len__") or not hasattr(rles, "__iter__"):
+        raise ValueError(f"{who}: rles must be a sequence of COCO dicts, got {type(rles).__name__}")
+    if not 1 <= len(rles) <= 65535:
+        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(rles)}")
+    sizes, parts = [], []
+    for i, d in enumerate(rles):
+        if not isinstance(d, dict) or "size" not in d or "counts" not in d:
+            raise ValueError(f"{who}: entry {i} must be a dict with 'size' and 'counts'")
+        size = d["size"]
+        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
+            raise ValueError(f"{who}: entry {i}: size must be [h, w], got {size!r}")
+        h, w = size
+        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+            raise ValueError(f"{who}: entry {i}: size must be two ints in [1, {SIZED_MAX_SIDE}], got {size!r}")
+        c = d["counts"]
+        if isinstance(c, (bytes, str)):
+            c = _rle.string_to_counts(c)
+        else:
+            if isinstance(c, dict) or not hasattr(c, "__len__"):
+                raise ValueError(f"{who}: entry {i}: counts must be a list of ints, bytes or str, got {type(c).__name__}")
+            if not isinstance(c, np.ndarray) and not all(is_int(v) for v in c):
+                raise ValueError(f"{who}: entry {i}: counts must hold ints")
+            c = np.asarray(c)
+            if c.ndim != 1 or (c.size and c.dtype.kind not in "iu"):
+                raise ValueError(f"{who}: entry {i}: counts must be a flat sequence of ints")
+            c = c.astype(np.int64)
+        if c.size == 0 or bool((c < 0).any()) or int(c.sum()) != int(h) * int(w):
+            raise ValueError(f"{who}: entry {i}: {c.size} counts summing to {int(c.sum())} do not describe a plane of {h} x {w}")
+        sizes.append((int(h), int(w)))
+        parts.append(c.astype(np.int32))
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    np.cumsum([p.size for p in parts], out=offsets[1:])
+    return np.concatenate(parts), offsets, sizes
+
+
+def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, who: str = "mask_inter_sized"):
+    """Every check of the pairs of Cascade.mask_inter_sized that the host can make, before anything is launched
+    (ValueError) -> int32 (N, 2) on the host, or the caller's device tensor as it is.  Either pairs= -- (N, 2) ints (plane of a, plane of
+    b), in range; a tensor on the device is only checked by shape and left to the kernel --, or a_image= and b_image=, one image id per
+    plane of each: all (p, q) with a_image[p] == b_image[q], ordered by p, then q.  1 <= N <= 2^20."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    Pa, Pb = len(a_sizes), len(b_sizes)
+    if (pairs is None) == (a_image is None and b_image is None) or (a_image is None) != (b_image is None):
+        raise ValueError(f"{who}: give either pairs= or both a_image= and b_image=")
+    if pairs is not None:
+        if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+            if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype not in (torch.int32, torch.int64) or not 1 <= pairs.shape[0] <= 1 << 20:
+                raise ValueError(f"{who}: pairs on the device must be an integer tensor (N, 2), 1 <= N <= 2^20")
+            return pairs
+        try:
+            arr = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs)
+        except Exception as e:
+            raise ValueError(f"{who}: pairs must be (N, 2) ints") from e
+        if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype.kind not in "iu" or not 1 <= arr.shape[0] <= 1 << 20:
+            raise ValueError(f"{who}: pairs must be (N, 2) ints, 1 <= N <= 2^20")
+        if bool((arr < 0).any()) or bool((arr[:, 0] >= Pa).any()) or bool((arr[:, 1] >= Pb).any()):
+            raise ValueError(f"{who}: a pair names a plane outside [0, {Pa}) x [0, {Pb})")
+        return np.ascontiguousarray(arr.astype(np.int32))
+    ids = []
+    for name, seq, P in (("a_image", a_image, Pa), ("b_image", b_image, Pb)):
+        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
+            raise ValueError(f"{who}: {name} must hold one int per plane, {P} of them")
+        ids.append(np.asarray([int(v) for v in seq], dtype=np.int64))
+    p, q = np.nonzero(ids[0][:, None] == ids[1][None, :])             # row-major: ordered by p, then q
+    if not 1 <= p.size <= 1 << 20:
+        raise ValueError(f"{who}: the image ids give {p.size} pairs, 1 .. 2^20 are taken")
+    return np.ascontiguousarray(np.stack([p, q], axis=1).astype(np.int32))
+
+
+def ground_truth_request(ground_truth, sreq, n: int, who: str = "decode"):
+    """Every check of the ground_truth= argument of Cascade.infer_classes / decode, on the host, before anything is
+    launched (ValueError) -> None when nothing is asked for, otherwise (gt, the image id of each of its planes).  ground_truth is (gt,
+    gt_image): a SizedMasks with areas -- `rle_decode` of the annotations -- and one id in [0, n) per plane of it, the image of the call
+    the annotation belongs to; it needs sizes=, and every gt.sizes[q] must be the size of image gt_image[q]."""
+    if ground_truth is None:
+        return None
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not isinstance(ground_truth, (tuple, list)) or len(ground_truth) != 2 or not isinstance(ground_truth[0], SizedMasks):
+        raise ValueError(f"{who}: ground_truth must be (SizedMasks, image id of each of its planes)")
+    gt, ids = ground_truth
+    if sreq is None:
+        raise ValueError(f"{who}: ground_truth= is held against the sized planes: give sizes=")
+    if gt.area is None or not gt.bits.is_cuda:
+        raise ValueError(f"{who}: ground_truth= needs planes on the device with their areas (rle_decode(stats=True))")
+    if isinstance(ids, (str, bytes)) or not hasattr(ids, "__len__") or len(ids) != len(gt.sizes) or not all(is_int(v) for v in ids):
+        raise ValueError(f"{who}: ground_truth= needs one int image id per annotation, {len(gt.sizes)} of them")
+    ids = [int(v) for v in ids]
+    if not 1 <= len(ids) <= 65535:
+        raise ValueError(f"{who}: ground_truth= takes 1 .. 65535 annotations")
+    sizes = sreq[0]
+    for q, b in enumerate(ids):
+        if not 0 <= b < n:
+            raise ValueError(f"{who}: annotation {q} names image {b} of {n}")
+        if tuple(gt.sizes[q]) != tuple(sizes[b]):
+            raise ValueError(f"{who}: annotation {q} is {tuple(gt.sizes[q])}, image {b} is {tuple(sizes[b])}")
+    return gt, ids
+
+
+@dataclass
+class SizedOverlaps:
+    """Intersections of pairs of sized planes (Cascade.mask_inter_sized, ground_truth= of infer_classes / decode), on the
+    device.  Pair i is (plane pairs[i, 0] of a, plane pairs[i, 1] of b); inter[i] = |a AND b| in pixels, -1 for a refused pair (planes
+    of different sizes, an index or a table that does not fit)."""
+    pairs: torch.Tensor             # (N, 2) int32
+    inter: torch.Tensor             # (N,) int32
+    area_a: torch.Tensor            # (N,) int32 the area of each pair's plane of a
+    area_b: torch.Tensor            # (N,) int32 the area of each pair's plane of b
+    status: torch.Tensor            # (1,) int32, non-zero if a pair was refused
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a pair (synchronises)."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("mask_inter_sized: cvlm_mask_inter_sized refused a pair: sizes that differ, an index or a table that does not fit")
+
+    def iou(self, iscrowd=None) -> np.ndarray:
+        """The COCO IoU of each pair, float64 (N,), on the host: pycocotools' rleIou.  -1 where inter is -1; 0 where inter is 0;
+        inter / area_a where iscrowd[q] is true for the pair's plane q of b (a crowd annotation: the share of the detection inside
+        it); inter / (area_a + area_b - inter) otherwise.  iscrowd: None or one truth value per plane of b.  ONE read of the device
+        (synchronises)."""
+        table = torch.stack([self.pairs[:, 1], self.inter, self.area_a, self.area_b]).cpu().numpy().astype(np.int64)
+        q, inter, a, b = table
+        crowd = np.zeros(q.shape, dtype=bool)
+        if iscrowd is not None:
+            flags = np.asarray(iscrowd).astype(bool).reshape(-1)
+            ok = (q >= 0) & (q < flags.size)
+            crowd[ok] = flags[q[ok]]
+        out = np.zeros(q.shape, dtype=np.float64)
+        pos = inter > 0
+        union = np.where(crowd, a, a + b - inter)
+        out[pos] = inter[pos] / union[pos].astype(np.float64)
+        out[inter < 0] = -1.0
+        return out
 
 
 @dataclass
@@ -2689,6 +2837,72 @@ class Cascade(_Base):
         return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=sizes[0] if same else None,
                        status=torch.amax(status, 0, keepdim=True), sizes=sizes)
 
+    # ---- COCO annotations on the device --------------------------------------------------------------------------------
+    def rle_decode(self, rles, *, stats: bool = True) -> "SizedMasks":
+        """COCO run-length annotations -> SizedMasks on this engine's device (cvlm_mask_rle_decode): ground truth in the
+        format of the predictions, on which `mask_inter_sized`, `mask_rle_sized` and -- per image -- `mask_components`, `mask_holes` and
+        `mask_morph` run.  rles: a list of {"size": [h, w], "counts": list | bytes | str}, checked by `rle_decode_request` on the host
+        before anything is launched (ValueError) and uploaded once; or a MaskRle already on the device, e.g. `mask_rle_sized`'s: then
+        nothing is copied to the host and nothing synchronises -- the kernel's own checks are the only ones, and `check()` of the
+        result reports what they refused (a refused plane is zero).  stats=False: no `area` and no `box`.  The result has level 0:
+        not a threshold.  The workspace is the grow-only "cls_rle", capped at RLE_WS_CAP (beyond it the entry walks the planes in
+        rounds).  Launches on the caller's stream."""
+        dev = self.device
+        if isinstance(rles, MaskRle):
+            P = int(rles.n_runs.shape[0])
+            sizes = [tuple(rles.size_of(p)) for p in range(P)]
+            if not 1 <= P <= 65535 or not rles.counts.is_cuda or rles.counts.dtype != torch.int32 or rles.counts.numel() < 1 or \
+                    any(not 1 <= v <= SIZED_MAX_SIDE for s in sizes for v in s):
+                raise ValueError("rle_decode: a MaskRle of 1 .. 65535 planes on the device, sides in [1, 16384]")
+            counts, run_offsets = rles.counts.contiguous(), rles.offsets.contiguous()
+        else:
+            c, o, sizes = rle_decode_request(rles)
+            P = len(sizes)
+            counts, run_offsets = torch.from_numpy(c).to(dev), torch.from_numpy(o).to(dev)
+        dims, offsets, _ = sized_tables(sizes)
+        max_pixels = max(h * w for h, w in sizes)
+        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
+                         area=torch.empty(P, dtype=torch.int32, device=dev) if stats else None,
+                         box=torch.empty(P, 4, dtype=torch.int32, device=dev) if stats else None,
+                         status=torch.empty(1, dtype=torch.int32, device=dev), sizes=[(int(h), int(w)) for h, w in sizes], level=0)
+        one = hip.mask_rle_decode_workspace_bytes(1, max_pixels)
+        ws = self.ws._get("u8", "cls_rle", min(P * one, max(RLE_WS_CAP, one)), torch.uint8, False)
+        hip.mask_rle_decode(counts, run_offsets, torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box,
+                            out.status, ws)
+        return out
+
+    def mask_inter_sized(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, a_image=None, b_image=None) -> "SizedOverlaps":
+        """Intersections of pairs of sized planes -> SizedOverlaps (cvlm_mask_inter_sized): detections `a` against
+        annotations `b` (they may be the same object).  Either pairs= -- (N, 2) (plane of a, plane of b) -- or a_image= and b_image=, one
+        image id per plane of each: all (p, q) with a_image[p] == b_image[q], ordered by p, then q; `pairs_request` checks them on the
+        host before anything is launched (ValueError).  Two planes of different sizes give inter = -1, as pycocotools' rleIou does.
+        One upload of the pair table and of the two small size tables, one launch pair, two gathers of the areas; no workspace, no
+        synchronisation: `SizedOverlaps.iou()` does the one read."""
+        for name, s in (("a", a), ("b", b)):
+            if not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535:
+                raise ValueError(f"mask_inter_sized: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas")
+        table = pairs_request(a.sizes, b.sizes, pairs=pairs, a_image=a_image, b_image=b_image)
+        dev = a.bits.device
+        tab = table.to(torch.int32).contiguous() if isinstance(table, torch.Tensor) else torch.from_numpy(table).to(dev)
+        N = int(tab.shape[0])
+        a_dims, _, a_words = sized_tables(a.sizes)
+        b_dims, _, b_words = (a_dims, None, a_words) if b is a else sized_tables(b.sizes)
+        a_dims = torch.from_numpy(a_dims).to(dev)
+        b_dims = a_dims if b is a else torch.from_numpy(b_dims).to(dev)
+        inter = torch.empty(N, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        hip.mask_inter_sized(a.bits, a.offsets, a_dims, b.bits, b.offsets, b_dims, tab, max(a_words, b_words), inter, status)
+        pick = lambda s, col: s.area.index_select(0, tab[:, col].long().clamp_(0, len(s.sizes) - 1))
+        return SizedOverlaps(pairs=tab, inter=inter, area_a=pick(a, 0), area_b=pick(b, 1), status=status)
+
+    def _gt_overlaps(self, greq, sized, n: int, K: int) -> Optional["SizedOverlaps"]:
+        """ground_truth= of infer_classes / decode: `mask_inter_sized` of the result's sized planes with the annotations of each plane's
+        own image, once, behind the last chunk."""
+        if greq is None:
+            return None
+        gt, ids = greq
+        return self.mask_inter_sized(sized[0], gt, a_image=[b for b in range(n) for _ in range(K)], b_image=ids)
+
     def _rle_of(self, source: Optional[str], fields: dict, S: int) -> Optional["MaskRle"]:
         """rle= of infer_classes / decode: `mask_rle` of the result's own planes named by `rle_request`, all n * K of them at once;
         rle="sized": `mask_rle_sized` of the result's sized planes."""
@@ -2704,7 +2918,7 @@ class Cascade(_Base):
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                       connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
                       band: Optional[int] = None, edge_threshold: Optional[float] = None,
-                      rle: Optional[str] = None, sizes=None, sized_level: int = 128) -> ClassHypotheses:
+                      rle: Optional[str] = None, sizes=None, sized_level: int = 128, ground_truth=None) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2770,7 +2984,13 @@ class Cascade(_Base):
         result.  The two tables of the planes are built on the host and uploaded once, before the first chunk.  rle="sized" (needs
         sizes=) encodes those planes, `mask_rle_sized`, behind the last chunk: `rle.to_coco()` then carries "size": [h, w] of each
         image, which an evaluator can hold against an annotation.  Without sizes= the call makes exactly the launches, allocations and
-        synchronisations it made before."""
+        synchronisations it made before.
+        ground_truth=(gt, gt_image) (`ground_truth_request`, checked with the rest; needs sizes=): gt is a SizedMasks of
+        annotations -- `rle_decode` of their COCO RLEs -- and gt_image[q] the image of the call annotation q belongs to, whose size it
+        must have; adds `gt_overlaps`, a SizedOverlaps with the intersection of every hypothesis's sized plane with every annotation of
+        its own image -- pairs (b * K + k, q) ordered by the plane, then q --, by one cvlm_mask_inter_sized call behind the last chunk;
+        `gt_overlaps.iou(iscrowd)` is the COCO IoU.  Nothing is matched or chosen.  Without it the call makes exactly the launches,
+        allocations and synchronisations it made before."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
@@ -2784,6 +3004,7 @@ class Cascade(_Base):
                             who="infer_classes")
         rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size, who="infer_classes")
         sreq = sized_request(sizes=sizes, sized_level=sized_level, n=B, masks=masks, rle=rle, who="infer_classes")
+        greq = ground_truth_request(ground_truth, sreq, B, who="infer_classes")
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
@@ -2843,16 +3064,19 @@ class Cascade(_Base):
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
             runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
+            held = self._gt_overlaps(greq, sized, B, K)
         coded = () if runs is None else (runs.counts, runs.offsets, runs.n_runs, runs.status)
         fitted = () if sized is None else (sized[0].bits, sized[0].offsets, sized[0].area, sized[0].box, sized[0].status)
-        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)),
+        truth = () if greq is None else (greq[0].bits, greq[0].offsets, greq[0].area)
+        over = () if held is None else (held.pairs, held.inter, held.area_a, held.area_b, held.status)
+        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)) + truth,
                   tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged + coded + fitted
-                        if t is not None))
+                        + over if t is not None))
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
                                **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
-                               sized=None if sized is None else sized[0])
+                               sized=None if sized is None else sized[0], gt_overlaps=held)
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -2891,7 +3115,7 @@ class Cascade(_Base):
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None,
                edge_threshold: Optional[float] = None, rle: Optional[str] = None, sizes=None,
-               sized_level: int = 128) -> ClassHypotheses:
+               sized_level: int = 128, ground_truth=None) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2915,7 +3139,9 @@ class Cascade(_Base):
         rle=: as in `infer_classes`, checked by `rle_request` with the rest; its one read synchronises the host with
         the caller's stream.
         sizes= / sized_level=: as in `infer_classes`, checked by `sized_request` with the rest; one (h, w) per decoded
-        row -- per entry of `images` --, and rle="sized" encodes the sized planes."""
+        row -- per entry of `images` --, and rle="sized" encodes the sized planes.
+        ground_truth=(gt, gt_image): as in `infer_classes`, checked by `ground_truth_request` with the rest; gt_image[q]
+        names a decoded row -- an entry of `images` --, not an image of `enc`."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -2933,6 +3159,7 @@ class Cascade(_Base):
         ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size)
         rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size)
         sreq = sized_request(sizes=sizes, sized_level=sized_level, n=len(images), masks=masks, rle=rle)
+        greq = ground_truth_request(ground_truth, sreq, len(images))
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
@@ -3001,12 +3228,13 @@ class Cascade(_Base):
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
         runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
+        held = self._gt_overlaps(greq, sized, n, K)
         self._fold_guard_arm(torch.cuda.current_stream())
         return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
                                mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
                                **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
                                **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
-                               sized=None if sized is None else sized[0])
+                               sized=None if sized is None else sized[0], gt_overlaps=held)
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""

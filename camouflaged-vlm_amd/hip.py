@@ -79,6 +79,11 @@ _SIGNATURES = {
     "cvlm_debug_mask_rle_host_w": "i:piiiippplp",
     "cvlm_mask_pack_sized": "i:piiippipllppps",
     "cvlm_debug_mask_pack_sized_host": "i:piiippipllppp",
+    "cvlm_mask_rle_decode_workspace_bytes": "l:il",
+    "cvlm_mask_rle_decode": "i:plpppilplppppls",
+    "cvlm_debug_mask_rle_decode_host": "i:plpppilplppp",
+    "cvlm_mask_inter_sized": "i:plppiplppipilpps",
+    "cvlm_debug_mask_inter_sized_host": "i:plppiplppipilpp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -1061,6 +1066,96 @@ def mask_pack_sized_host(logits: torch.Tensor, dims: torch.Tensor, offsets: torc
     assert not logits.is_cuda
     _call("cvlm_debug_mask_pack_sized_host", logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level, bits.data_ptr(),
           bits.numel(), int(max_words), _p(area), _p(box), status.data_ptr())
+
+
+def mask_rle_decode_workspace_bytes(P: int, max_pixels: int) -> int:
+    """Bytes cvlm_mask_rle_decode wants to keep all P planes of at most max_pixels pixels in flight (16 + one bit per pixel and plane);
+    P = 1: the minimum it takes."""
+    n = load().cvlm_mask_rle_decode_workspace_bytes(P, max_pixels)
+    if n < 0:
+        raise RuntimeError(f"cvlm_mask_rle_decode_workspace_bytes({P}, {max_pixels}): sizes outside the entry's bounds")
+    return n
+
+
+def _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status) -> int:
+    """Shape and dtype checks shared by `mask_rle_decode` and `mask_rle_decode_host` -> P."""
+    P = int(dims.shape[0])
+    assert counts.dtype == torch.int32 and counts.dim() == 1 and counts.is_contiguous() and counts.numel() >= 1
+    assert run_offsets.dtype == torch.int64 and tuple(run_offsets.shape) == (P + 1,) and run_offsets.is_contiguous()
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (P + 1,) and bit_offsets.is_contiguous()
+    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous() and (area is None) == (box is None)
+    if area is not None:
+        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == counts.device for t in (run_offsets, dims, bit_offsets, bits, area, box, status))
+    return P
+
+
+def mask_rle_decode(counts: torch.Tensor, run_offsets: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor, max_pixels: int,
+                    bits: torch.Tensor, area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor,
+                    workspace: torch.Tensor) -> None:
+    """COCO run counts -> sized planes (include/cvlm.h: cvlm_mask_rle_decode): plane p's counts are counts[run_offsets[p] :
+    run_offsets[p + 1]] (int32 [total], int64 [P + 1]), its size dims[p] = (h, w), and it is written as h rows of ceil(w / 32) words in
+    numpy.packbits' order from byte bit_offsets[p] of the flat uint8 tensor `bits` on; area int32 [P] and box int32 [P][4] together or not
+    at all.  status int32 [1] becomes 1 if a plane was refused -- counts that are negative or do not sum to h * w, a slice or a table that
+    does not fit; such a plane is zero where its table holds and untouched where it does not --, otherwise 0.  max_pixels: the largest
+    h * w of the call.  workspace: uint8, at least mask_rle_decode_workspace_bytes(1, max_pixels) bytes; fewer than P planes' worth makes
+    the entry walk the planes in rounds."""
+    P = _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == counts.device
+    _on_current_device(counts)
+    _call("cvlm_mask_rle_decode", counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(), bit_offsets.data_ptr(), P,
+          int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(), workspace.data_ptr(), workspace.numel())
+
+
+def mask_rle_decode_host(counts: torch.Tensor, run_offsets: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor, max_pixels: int,
+                         bits: torch.Tensor, area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """`mask_rle_decode` on HOST tensors without a device (cvlm_debug_mask_rle_decode_host: the kernels' per-thread functions run
+    sequentially on the CPU)."""
+    P = _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status)
+    assert not counts.is_cuda
+    _call("cvlm_debug_mask_rle_decode_host", counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(),
+          bit_offsets.data_ptr(), P, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr())
+
+
+def _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status) -> Tuple[int, int, int]:
+    """Shape and dtype checks shared by `mask_inter_sized` and `mask_inter_sized_host` -> (Pa, Pb, N)."""
+    Pa, Pb, N = int(a_dims.shape[0]), int(b_dims.shape[0]), int(pairs.shape[0])
+    for bits, offsets, dims, P in ((a_bits, a_offsets, a_dims, Pa), (b_bits, b_offsets, b_dims, Pb)):
+        assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
+        assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
+        assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert pairs.dtype == torch.int32 and tuple(pairs.shape) == (N, 2) and pairs.is_contiguous()
+    assert inter.dtype == torch.int32 and tuple(inter.shape) == (N,) and inter.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == a_bits.device for t in (a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status))
+    return Pa, Pb, N
+
+
+def mask_inter_sized(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_bits: torch.Tensor, b_offsets: torch.Tensor,
+                     b_dims: torch.Tensor, pairs: torch.Tensor, max_words: int, inter: torch.Tensor, status: torch.Tensor) -> None:
+    """Two sets of sized planes (flat uint8 bits, byte offsets int64 [P + 1], dims int32 [P][2]; they may be the same tensors) and pairs
+    int32 [N][2] = (plane of A, plane of B) -> inter int32 [N] = |A[a] AND B[b]| over the columns below w (include/cvlm.h:
+    cvlm_mask_inter_sized); a pair with an index out of range, a table that does not fit or two different sizes gives -1 and status
+    int32 [1] = 1, otherwise 0.  max_words: the largest h * ceil(w / 32) of the call."""
+    Pa, Pb, N = _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status)
+    _on_current_device(a_bits)
+    _call("cvlm_mask_inter_sized", a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa, b_bits.data_ptr(),
+          b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words), inter.data_ptr(),
+          status.data_ptr())
+
+
+def mask_inter_sized_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_bits: torch.Tensor,
+                          b_offsets: torch.Tensor, b_dims: torch.Tensor, pairs: torch.Tensor, max_words: int, inter: torch.Tensor,
+                          status: torch.Tensor) -> None:
+    """`mask_inter_sized` on HOST tensors without a device (cvlm_debug_mask_inter_sized_host)."""
+    Pa, Pb, N = _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status)
+    assert not a_bits.is_cuda
+    _call("cvlm_debug_mask_inter_sized_host", a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa,
+          b_bits.data_ptr(), b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words),
+          inter.data_ptr(), status.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:
