@@ -22,6 +22,12 @@ import torch
 
 from . import hip
 from .hip import ACT_ABS_POST, ACT_GELU, ACT_NONE, ACT_QUICKGELU, ACT_RELU, H2
+# the packed-mask family lives in maskpost.py; its public names stay importable from here
+from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIELDS, HOLE_FIELDS, HOLES_MAXM, MASK_MODES, MORPH_MAXR,
+                       OVERLAP_MAXK, OVERLAP_MAXP, RLE_SIZED, RLE_SOURCES, RLE_WS_CAP, SIZED_MAX_SIDE, EdgeBits, MaskComponents, MaskHoles,
+                       MaskMorph, MaskPost, MaskRle, MaskUtilities, SizedMasks, SizedOverlaps, _edge_threshold, compact_request,
+                       components_request, edge_request, ground_truth_request, holes_request, morph_request, pairs_request,
+                       rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry
 
 
@@ -1533,464 +1539,6 @@ def decode_request(*, same_engine: bool, B: int, n_cls: int, D: int, classes=Non
     return images, int(classes.shape[1]), host
 
 
-MASK_MODES = ("logits", "bits", "both")
-OVERLAP_MAXK = 1024        # hypotheses per image cvlm_mask_overlap takes
-OVERLAP_MAXP = 65535       # planes in all it takes
-
-
-def compact_request(*, masks="logits", overlaps=False, n: int, K: int, who: str = "decode"):
-    """Every check of the masks= / overlaps= arguments of Cascade.infer_classes / decode, on the host, before anything
-    is launched (ValueError) -> (want_logits, want_bits, want_inter).  n images with K hypotheses each."""
-    if not isinstance(masks, str) or masks not in MASK_MODES:
-        raise ValueError(f"{who}: masks must be one of {MASK_MODES}, got {masks!r}")
-    if not isinstance(overlaps, (bool, np.bool_)):
-        raise ValueError(f"{who}: overlaps must be a bool, got {type(overlaps).__name__}")
-    if overlaps and masks == "logits":
-        raise ValueError(f"{who}: overlaps=True counts packed masks: ask for masks='bits' or 'both'")
-    if overlaps and K > OVERLAP_MAXK:
-        raise ValueError(f"{who}: overlaps=True takes at most {OVERLAP_MAXK} hypotheses per image (cvlm_mask_overlap), got K = {K}")
-    if overlaps and n * K > OVERLAP_MAXP:
-        raise ValueError(f"{who}: overlaps=True takes at most {OVERLAP_MAXP} hypotheses in all (cvlm_mask_overlap), got {n} x {K}")
-    return masks != "bits", masks != "logits", bool(overlaps)
-
-
-COMPONENTS_MAXM = 64              # rows of the table cvlm_mask_components selects
-COMPONENTS_WS_CAP = 256 << 20     # bytes of the "cls_comp" workspace at most; beyond it the entry walks the planes in rounds
-
-
-def components_request(*, components=None, min_area=0, connectivity=8, masks="bits", side: Optional[int] = None, who: str = "decode"):
-    """Every check of the components= / min_area= / connectivity= arguments of Cascade.infer_classes / decode / mask_components
-    (DESIGN.md §14), on the host, before anything is launched (ValueError) -> (asked for, M, min_area, connectivity).  components=None
-    with min_area=0 asks for nothing; components=0 asks for the counts without a table.  side: the width of the model's masks."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if components is not None and not (is_int(components) and 0 <= int(components) <= COMPONENTS_MAXM):
-        raise ValueError(f"{who}: components must be None or an int in [0, {COMPONENTS_MAXM}], got {components!r}")
-    if not (is_int(min_area) and int(min_area) >= 0):
-        raise ValueError(f"{who}: min_area must be a non-negative int, got {min_area!r}")
-    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
-        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
-    asked = components is not None or int(min_area) > 0
-    if asked and masks == "logits":
-        raise ValueError(f"{who}: components= / min_area= label packed masks: ask for masks='bits' or 'both'")
-    if asked and side is not None and side % 32 != 0:
-        raise ValueError(f"{who}: components= / min_area= need rows of whole 32-pixel words, the masks are {side} wide")
-    return asked, int(components or 0), int(min_area), int(connectivity)
-
-
-@dataclass
-class MaskComponents:
-    """Connected regions of N packed masks (Cascade.mask_components); every tensor int32 on the device but kept_bits."""
-    n_comp: torch.Tensor                    # (N,) regions per mask
-    comps: Optional[torch.Tensor]           # (N, M, 6) the M largest as (area, x0, y0, x1, y1, seed), descending; None with components=0
-    n_kept: Optional[torch.Tensor]          # min_area >= 1: (N,) regions of at least min_area pixels, otherwise None like the next three
-    kept_bits: Optional[torch.Tensor]       # (N, H * W / 8) uint8 the mask without the smaller regions
-    kept_area: Optional[torch.Tensor]       # (N,)
-    kept_box: Optional[torch.Tensor]        # (N, 4) inclusive (x0, y0, x1, y1), -1 for an empty result
-
-
-HOLES_MAXM = 64                   # rows of the table cvlm_mask_holes selects
-HOLE_FIELDS = ("n_holes", "holes", "n_filled", "filled_bits", "filled_area")
-
-
-def holes_request(*, holes=None, fill_holes=0, connectivity=8, masks="bits", side: Optional[int] = None, who: str = "decode"):
-    """Every check of the holes= / fill_holes= arguments of Cascade.infer_classes / decode / mask_holes, on the host,
-    before anything is launched (ValueError) -> (asked for, M, fill_below, connectivity).  holes=None with fill_holes=0 asks for nothing;
-    holes=0 asks for the counts without a table.  connectivity is the foreground's, shared with components=.  side: the width of the
-    model's masks."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if holes is not None and not (is_int(holes) and 0 <= int(holes) <= HOLES_MAXM):
-        raise ValueError(f"{who}: holes must be None or an int in [0, {HOLES_MAXM}], got {holes!r}")
-    if not (is_int(fill_holes) and 0 <= int(fill_holes) < 2 ** 31):
-        raise ValueError(f"{who}: fill_holes must be a non-negative int, got {fill_holes!r}")
-    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
-        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
-    asked = holes is not None or int(fill_holes) > 0
-    if asked and masks == "logits":
-        raise ValueError(f"{who}: holes= / fill_holes= label packed masks: ask for masks='bits' or 'both'")
-    if asked and side is not None and side % 32 != 0:
-        raise ValueError(f"{who}: holes= / fill_holes= need rows of whole 32-pixel words, the masks are {side} wide")
-    return asked, int(holes or 0), int(fill_holes), int(connectivity)
-
-
-@dataclass
-class MaskHoles:
-    """Holes of N packed masks (Cascade.mask_holes); every tensor int32 on the device but filled_bits."""
-    n_holes: torch.Tensor                   # (N,) holes per mask
-    holes: Optional[torch.Tensor]           # (N, M, 6) the M largest as (area, x0, y0, x1, y1, seed), descending; None with holes=0
-    n_filled: Optional[torch.Tensor]        # fill_holes >= 1: (N,) holes of fewer than fill_holes pixels, otherwise None like the next two
-    filled_bits: Optional[torch.Tensor]     # (N, H * W / 8) uint8 the mask with exactly those holes set
-    filled_area: Optional[torch.Tensor]     # (N,)
-
-
-MORPH_MAXR = 16                   # the largest radius cvlm_mask_morph takes
-BAND_FIELDS = ("band_bits", "band_area", "band_inter")
-
-
-def morph_request(*, band=None, masks="bits", overlaps=False, side: Optional[int] = None, who: str = "decode"):
-    """Every check of the band= argument of Cascade.infer_classes / decode, on the host, before anything is launched
-    (ValueError) -> (asked for, radius, band_inter wanted).  band=None asks for nothing; band=r asks for the edge band by the
-    (2 r + 1)^2 square, and with overlaps=True for the bands' pairwise intersections as well.  side: the width of the model's masks."""
-    if band is None:
-        return False, 0, False
-    if isinstance(band, (bool, np.bool_)) or not isinstance(band, (int, np.integer)) or not 1 <= int(band) <= MORPH_MAXR:
-        raise ValueError(f"{who}: band must be None or an int in [1, {MORPH_MAXR}], got {band!r}")
-    if masks == "logits":
-        raise ValueError(f"{who}: band= is derived from packed masks: ask for masks='bits' or 'both'")
-    if side is not None and side % 32 != 0:
-        raise ValueError(f"{who}: band= needs rows of whole 32-pixel words, the masks are {side} wide")
-    return True, int(band), bool(overlaps)
-
-
-@dataclass
-class MaskMorph:
-    """Dilation, erosion and edge band of N packed masks (Cascade.mask_morph): planes uint8 (N, H * W / 8), areas int32
-    (N,), on the device; a pair that was not asked for is None."""
-    dil_bits: Optional[torch.Tensor]
-    dil_area: Optional[torch.Tensor]
-    ero_bits: Optional[torch.Tensor]
-    ero_area: Optional[torch.Tensor]
-    band_bits: Optional[torch.Tensor]
-    band_area: Optional[torch.Tensor]
-
-
-EDGE_FIELDS = ("edge_bits", "edge_area", "edge_band", "edge_inter")
-
-
-def _edge_threshold(edge_threshold, who: str) -> float:
-    """The threshold as the float32 the kernel compares against, or ValueError: a real number (no bool, no NaN) strictly between 0
-    and 1 whose float32 rounding is strictly between 0 and 1 as well."""
-    if isinstance(edge_threshold, (bool, np.bool_)) or not isinstance(edge_threshold, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{who}: edge_threshold must be a real number strictly between 0 and 1, got {edge_threshold!r}")
-    t = float(edge_threshold)
-    with np.errstate(over="ignore", under="ignore"):
-        t32 = float(np.float32(t))
-    if not (0.0 < t < 1.0 and 0.0 < t32 < 1.0):                      # NaN fails every comparison
-        raise ValueError(f"{who}: edge_threshold must lie strictly between 0 and 1, in float32 as well, got {edge_threshold!r}")
-    return t32
-
-
-def edge_request(*, edge_threshold=None, masks="bits", overlaps=False, band=None, side: Optional[int] = None, who: str = "decode"):
-    """Every check of the edge_threshold= argument of Cascade.infer_classes / decode, on the host, before anything is
-    launched (ValueError) -> (asked for, the threshold as float32's value, edge_band wanted, edge_inter wanted).  None asks for
-    nothing.  The packed edge map sits beside packed masks -- masks="bits" or "both" --; with band= the call also counts the edge
-    pixels on each mask's band, with overlaps=True the pairwise intersections of the edge maps.  side: the width of the model's masks."""
-    if edge_threshold is None:
-        return False, 0.0, False, False
-    t = _edge_threshold(edge_threshold, who)
-    if masks == "logits":
-        raise ValueError(f"{who}: edge_threshold= packs the edge map beside packed masks: ask for masks='bits' or 'both'")
-    if side is not None and side % 32 != 0:
-        raise ValueError(f"{who}: edge_threshold= needs rows of whole 32-pixel words, the masks are {side} wide")
-    return True, t, band is not None, bool(overlaps)
-
-
-@dataclass
-class EdgeBits:
-    """N packed edge maps (Cascade.pack_edges), on the device."""
-    bits: torch.Tensor              # (N, H * W / 8) uint8, numpy.packbits' order
-    area: torch.Tensor              # (N,) int32 set bits
-    inter: Optional[torch.Tensor]   # (N,) int32 |bits AND with_bits|; None without with_bits
-
-
-RLE_WS_CAP = 64 << 20             # bytes of the "cls_rle" workspace at most; beyond it cvlm_mask_rle_emit walks the planes in rounds
-RLE_SOURCES = {"mask": "mask_bits", "kept": "kept_bits", "filled": "filled_bits"}
-RLE_SIZED = "sized"               # rle="sized": the planes of `sized` (sizes=, DESIGN.md §19), each at its image's own size
-SIZED_MAX_SIDE = 16384            # h and w of a sized plane (csrc/sized_logic.h: SZ_MAX_SIDE)
-
-
-def rle_request(*, rle=None, masks="bits", min_area=0, fill_holes=0, side: Optional[int] = None, who: str = "decode"):
-    """Every check of the rle= argument of Cascade.infer_classes / decode, on the host, before anything is launched
-    (ValueError) -> the name of the field to encode, or None.  rle=None asks for nothing; "mask", "kept" and "filled" ask for the COCO
-    run-length encoding of mask_bits, kept_bits (needs min_area >= 1) or filled_bits (needs fill_holes >= 1).  side: the width of the
-    model's masks."""
-    if rle is None:
-        return None
-    if isinstance(rle, str) and rle == RLE_SIZED:                    # the sized planes (DESIGN.md §19): `sized_request` holds it against sizes=
-        if masks == "logits":
-            raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
-        return RLE_SIZED
-    if not isinstance(rle, str) or rle not in RLE_SOURCES:
-        raise ValueError(f"{who}: rle must be None or one of {tuple(RLE_SOURCES) + (RLE_SIZED,)}, got {rle!r}")
-    if masks == "logits":
-        raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if rle == "kept" and not (is_int(min_area) and int(min_area) >= 1):
-        raise ValueError(f"{who}: rle='kept' encodes kept_bits: ask for min_area >= 1")
-    if rle == "filled" and not (is_int(fill_holes) and int(fill_holes) >= 1):
-        raise ValueError(f"{who}: rle='filled' encodes filled_bits: ask for fill_holes >= 1")
-    if side is not None and side % 32 != 0:
-        raise ValueError(f"{who}: rle= needs rows of whole 32-pixel words, the masks are {side} wide")
-    return RLE_SOURCES[rle]
-
-
-@dataclass
-class MaskRle:
-    """COCO run-length encoding of N packed masks (Cascade.mask_rle), on the device: plane p's n_runs[p] counts are
-    counts[offsets[p] : offsets[p + 1]] -- the lengths of the alternating runs of 0s and 1s of its pixels in column-major order,
-    starting with the 0s.  An interchange format, not a compression: a ragged mask has more bytes of counts than of bits."""
-    counts: torch.Tensor            # (total,) int32
-    offsets: torch.Tensor           # (N + 1,) int64, offsets[0] = 0, offsets[N] = total
-    n_runs: torch.Tensor            # (N,) int32
-    size: Tuple[int, int]           # (H, W)
-    # (1,) int32 on the device, 0 unless cvlm_mask_rle_emit had to drop a count; `check` and `to_coco` read it.  Init-only, not a field.
-    status: InitVar[Optional[torch.Tensor]] = None
-    # per-plane (h, w) on the host where the planes differ in size (Cascade.mask_rle_sized, DESIGN.md §19), otherwise None and every
-    # plane is `size`; `to_coco` writes each plane's own.  Init-only, not a field; `size` is then None unless all planes agree.
-    sizes: InitVar[Optional[Sequence[Tuple[int, int]]]] = None
-
-    def __post_init__(self, status, sizes):
-        self.status = status
-        self.sizes = None if sizes is None else [(int(h), int(w)) for h, w in sizes]
-
-    def size_of(self, p: int) -> Tuple[int, int]:
-        """(H, W) of plane p."""
-        return self.sizes[p] if self.sizes is not None else self.size
-
-    def check(self) -> None:
-        """RuntimeError if the emit dropped a count (synchronises).  The slices come from the call's own count of the same bits, so
-        this says that the bits changed between the two passes or that the library is broken."""
-        if self.status is not None and int(self.status.item()) != 0:
-            raise RuntimeError("mask_rle: cvlm_mask_rle_emit dropped counts that did not fit their slices: were the bits written "
-                               "while the call ran?")
-
-    def to_coco(self, compressed: bool = False) -> list:
-        """On the host: one {"size": [H, W], "counts": ...} per plane (each plane's own size where they differ), what pycocotools and
-        the reference's GenericMask (models/utils/visualizer.py:72-101) take; counts is a list of ints, or with compressed=True COCO's
-        string as bytes (rle.counts_to_string).  One copy of each of the three tensors; synchronises."""
-        from . import rle as _rle
-        self.check()
-        counts, offsets = self.counts.cpu().numpy(), self.offsets.cpu().numpy()
-        out = []
-        for p in range(offsets.size - 1):
-            H, W = self.size_of(p)
-            c = counts[offsets[p]:offsets[p + 1]]
-            out.append({"size": [int(H), int(W)], "counts": _rle.counts_to_string(c) if compressed else c.tolist()})
-        return out
-
-
-def sized_tables(plane_sizes):
-    """Host tables of sized planes for a list of per-plane (h, w): dims int32 (P, 2), byte offsets int64 (P + 1) --
-    plane p is h rows of ceil(w / 32) 32-bit words, the planes lie back to back -- and the largest plane's word count."""
-    dims = np.asarray(plane_sizes, dtype=np.int32).reshape(-1, 2)
-    words = dims[:, 0].astype(np.int64) * ((dims[:, 1].astype(np.int64) + 31) // 32)
-    offsets = np.zeros(dims.shape[0] + 1, dtype=np.int64)
-    np.cumsum(4 * words, out=offsets[1:])
-    return dims, offsets, int(words.max())
-
-
-def sized_request(*, sizes=None, sized_level=128, n: int, masks="bits", rle=None, who: str = "decode"):
-    """Every check of the sizes= / sized_level= arguments of Cascade.infer_classes / decode and of Cascade.pack_masks_sized (DESIGN.md
-    §19), on the host, before anything is launched (ValueError) -> None when nothing is asked for, otherwise (the n (h, w) pairs as
-    ints, the level).  sizes: one (h, w) per image of the call, 1 <= h, w <= 16384; sized_level: an int in 1 .. 255, the level the
-    reference's uint8 mask is compared with (128: the half; 1: demo.py's `> 0` overlay).  They need packed masks (masks="bits" or
-    "both"), and rle="sized" needs sizes=."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not is_int(sized_level) or not 1 <= int(sized_level) <= 255:
-        raise ValueError(f"{who}: sized_level must be an int in [1, 255], got {sized_level!r}")
-    if sizes is None:
-        if isinstance(rle, str) and rle == RLE_SIZED:
-            raise ValueError(f"{who}: rle='sized' encodes the sized planes: give sizes=")
-        return None
-    if masks == "logits":
-        raise ValueError(f"{who}: sizes= packs masks at the images' sizes: ask for masks='bits' or 'both'")
-    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
-        raise ValueError(f"{who}: sizes must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
-    if len(sizes) != n:
-        raise ValueError(f"{who}: sizes holds {len(sizes)} pairs for {n} images")
-    out = []
-    for pair in sizes:
-        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
-            raise ValueError(f"{who}: sizes must hold (h, w) pairs, got {pair!r}")
-        h, w = pair
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: a size of sizes= must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
-        out.append((int(h), int(w)))
-    return out, int(sized_level)
-
-
-@dataclass
-class SizedMasks:
-    """Packed masks at each image's own size (Cascade.pack_masks_sized, sizes= of infer_classes / decode).  Plane p has
-    the size sizes[p] = (h, w) and is h rows of ws = ceil(w / 32) 32-bit words in numpy.packbits' order -- the bit order of `mask_bits`
-    -- from byte offsets[p] of the flat tensor `bits` on; the pad bits of a row, columns w .. 32 ws - 1, are 0, so that
-    `mask_components(plane rows, h, 32 * ws)` and its kin run on one image's planes as they are.  A bit is the reference's uint8 mask
-    -- sigmoid, cv2.resize(INTER_LINEAR) to (h, w), (. * 255).astype(uint8) -- compared `>= level`.  At the model's own size these are
-    NOT `mask_bits` (logit > 0): they go through the resize's arithmetic with weights 1 and 0 and compare a probability with level / 255."""
-    bits: torch.Tensor              # (total bytes,) uint8 on the device
-    offsets: torch.Tensor           # (P + 1,) int64 on the device, in bytes, multiples of 4; offsets[P] = bits.numel()
-    area: Optional[torch.Tensor]    # (P,) int32 set bits; None from rle_decode(stats=False), like box
-    box: Optional[torch.Tensor]     # (P, 4) int32 inclusive (x0, y0, x1, y1) in the image's own coordinates, -1 for an empty plane
-    status: torch.Tensor            # int32 on the device, one word per cvlm_mask_pack_sized call: non-zero if a plane was refused
-    sizes: list                     # P (h, w) pairs, on the host
-    level: int = 128                # 0: not a threshold -- the planes were decoded from run counts (Cascade.rle_decode, DESIGN.md §20)
-
-    def byte_range(self, p: int) -> Tuple[int, int]:
-        """Where plane p lies in `bits`, from the sizes alone (the planes lie back to back): no read of the device."""
-        _, offsets, _ = sized_tables(self.sizes)
-        return int(offsets[p]), int(offsets[p + 1])
-
-    def plane(self, p: int) -> torch.Tensor:
-        """Plane p as a uint8 view (h, 4 * ws) of `bits`: rows in numpy.packbits' order."""
-        h, w = self.sizes[p]
-        lo, hi = self.byte_range(p)
-        return self.bits[lo:hi].view(h, 4 * ((w + 31) // 32))
-
-    def to_numpy(self, p: int) -> np.ndarray:
-        """Plane p as a bool array (h, w) on the host (synchronises)."""
-        h, w = self.sizes[p]
-        return np.unpackbits(self.plane(p).cpu().numpy(), axis=1)[:, :w].astype(bool)
-
-    def check(self) -> None:
-        """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
-        says that the library is broken."""
-        if bool(self.status.ne(0).any().item()):
-            if self.level == 0:
-                raise RuntimeError("rle_decode: cvlm_mask_rle_decode refused a plane: counts that are negative or do not sum to h * w, "
-                                   "or a slice that does not fit")
-            raise RuntimeError("pack_masks_sized: cvlm_mask_pack_sized refused a plane whose slice did not fit its size")
-
-
-def rle_decode_request(rles, who: str = "rle_decode"):
-    """Every check of a list of COCO run-length dicts {"size": [h, w], "counts": list | bytes | str}, on the host, before
-    anything is launched (ValueError) -> (counts int32 (total,), run offsets int64 (P + 1,) in elements of counts, the P (h, w) pairs).
-    A string is COCO's compressed form (rle.string_to_counts).  h and w are ints in [1, 16384]; the counts are non-negative -- zeros are
-    legal anywhere, pycocotools emits them -- and sum to h * w."""
-    from . import rle as _rle
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if isinstance(rles, (str, bytes, dict)) or not hasattr(rles, "__len__") or not hasattr(rles, "__iter__"):
-        raise ValueError(f"{who}: rles must be a sequence of COCO dicts, got {type(rles).__name__}")
-    if not 1 <= len(rles) <= 65535:
-        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(rles)}")
-    sizes, parts = [], []
-    for i, d in enumerate(rles):
-        if not isinstance(d, dict) or "size" not in d or "counts" not in d:
-            raise ValueError(f"{who}: entry {i} must be a dict with 'size' and 'counts'")
-        size = d["size"]
-        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
-            raise ValueError(f"{who}: entry {i}: size must be [h, w], got {size!r}")
-        h, w = size
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: entry {i}: size must be two ints in [1, {SIZED_MAX_SIDE}], got {size!r}")
-        c = d["counts"]
-        if isinstance(c, (bytes, str)):
-            c = _rle.string_to_counts(c)
-        else:
-            if isinstance(c, dict) or not hasattr(c, "__len__"):
-                raise ValueError(f"{who}: entry {i}: counts must be a list of ints, bytes or str, got {type(c).__name__}")
-            if not isinstance(c, np.ndarray) and not all(is_int(v) for v in c):
-                raise ValueError(f"{who}: entry {i}: counts must hold ints")
-            c = np.asarray(c)
-            if c.ndim != 1 or (c.size and c.dtype.kind not in "iu"):
-                raise ValueError(f"{who}: entry {i}: counts must be a flat sequence of ints")
-            c = c.astype(np.int64)
-        if c.size == 0 or bool((c < 0).any()) or int(c.sum()) != int(h) * int(w):
-            raise ValueError(f"{who}: entry {i}: {c.size} counts summing to {int(c.sum())} do not describe a plane of {h} x {w}")
-        sizes.append((int(h), int(w)))
-        parts.append(c.astype(np.int32))
-    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
-    np.cumsum([p.size for p in parts], out=offsets[1:])
-    return np.concatenate(parts), offsets, sizes
-
-
-def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, who: str = "mask_inter_sized"):
-    """Every check of the pairs of Cascade.mask_inter_sized that the host can make, before anything is launched
-    (ValueError) -> int32 (N, 2) on the host, or the caller's device tensor as it is.  Either pairs= -- (N, 2) ints (plane of a, plane of
-    b), in range; a tensor on the device is only checked by shape and left to the kernel --, or a_image= and b_image=, one image id per
-    plane of each: all (p, q) with a_image[p] == b_image[q], ordered by p, then q.  1 <= N <= 2^20."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    Pa, Pb = len(a_sizes), len(b_sizes)
-    if (pairs is None) == (a_image is None and b_image is None) or (a_image is None) != (b_image is None):
-        raise ValueError(f"{who}: give either pairs= or both a_image= and b_image=")
-    if pairs is not None:
-        if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
-            if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype not in (torch.int32, torch.int64) or not 1 <= pairs.shape[0] <= 1 << 20:
-                raise ValueError(f"{who}: pairs on the device must be an integer tensor (N, 2), 1 <= N <= 2^20")
-            return pairs
-        try:
-            arr = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs)
-        except Exception as e:
-            raise ValueError(f"{who}: pairs must be (N, 2) ints") from e
-        if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype.kind not in "iu" or not 1 <= arr.shape[0] <= 1 << 20:
-            raise ValueError(f"{who}: pairs must be (N, 2) ints, 1 <= N <= 2^20")
-        if bool((arr < 0).any()) or bool((arr[:, 0] >= Pa).any()) or bool((arr[:, 1] >= Pb).any()):
-            raise ValueError(f"{who}: a pair names a plane outside [0, {Pa}) x [0, {Pb})")
-        return np.ascontiguousarray(arr.astype(np.int32))
-    ids = []
-    for name, seq, P in (("a_image", a_image, Pa), ("b_image", b_image, Pb)):
-        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
-            raise ValueError(f"{who}: {name} must hold one int per plane, {P} of them")
-        ids.append(np.asarray([int(v) for v in seq], dtype=np.int64))
-    p, q = np.nonzero(ids[0][:, None] == ids[1][None, :])             # row-major: ordered by p, then q
-    if not 1 <= p.size <= 1 << 20:
-        raise ValueError(f"{who}: the image ids give {p.size} pairs, 1 .. 2^20 are taken")
-    return np.ascontiguousarray(np.stack([p, q], axis=1).astype(np.int32))
-
-
-def ground_truth_request(ground_truth, sreq, n: int, who: str = "decode"):
-    """Every check of the ground_truth= argument of Cascade.infer_classes / decode, on the host, before anything is
-    launched (ValueError) -> None when nothing is asked for, otherwise (gt, the image id of each of its planes).  ground_truth is (gt,
-    gt_image): a SizedMasks with areas -- `rle_decode` of the annotations -- and one id in [0, n) per plane of it, the image of the call
-    the annotation belongs to; it needs sizes=, and every gt.sizes[q] must be the size of image gt_image[q]."""
-    if ground_truth is None:
-        return None
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not isinstance(ground_truth, (tuple, list)) or len(ground_truth) != 2 or not isinstance(ground_truth[0], SizedMasks):
-        raise ValueError(f"{who}: ground_truth must be (SizedMasks, image id of each of its planes)")
-    gt, ids = ground_truth
-    if sreq is None:
-        raise ValueError(f"{who}: ground_truth= is held against the sized planes: give sizes=")
-    if gt.area is None or not gt.bits.is_cuda:
-        raise ValueError(f"{who}: ground_truth= needs planes on the device with their areas (rle_decode(stats=True))")
-    if isinstance(ids, (str, bytes)) or not hasattr(ids, "__len__") or len(ids) != len(gt.sizes) or not all(is_int(v) for v in ids):
-        raise ValueError(f"{who}: ground_truth= needs one int image id per annotation, {len(gt.sizes)} of them")
-    ids = [int(v) for v in ids]
-    if not 1 <= len(ids) <= 65535:
-        raise ValueError(f"{who}: ground_truth= takes 1 .. 65535 annotations")
-    sizes = sreq[0]
-    for q, b in enumerate(ids):
-        if not 0 <= b < n:
-            raise ValueError(f"{who}: annotation {q} names image {b} of {n}")
-        if tuple(gt.sizes[q]) != tuple(sizes[b]):
-            raise ValueError(f"{who}: annotation {q} is {tuple(gt.sizes[q])}, image {b} is {tuple(sizes[b])}")
-    return gt, ids
-
-
-@dataclass
-class SizedOverlaps:
-    """Intersections of pairs of sized planes (Cascade.mask_inter_sized, ground_truth= of infer_classes / decode), on the
-    device.  Pair i is (plane pairs[i, 0] of a, plane pairs[i, 1] of b); inter[i] = |a AND b| in pixels, -1 for a refused pair (planes
-    of different sizes, an index or a table that does not fit)."""
-    pairs: torch.Tensor             # (N, 2) int32
-    inter: torch.Tensor             # (N,) int32
-    area_a: torch.Tensor            # (N,) int32 the area of each pair's plane of a
-    area_b: torch.Tensor            # (N,) int32 the area of each pair's plane of b
-    status: torch.Tensor            # (1,) int32, non-zero if a pair was refused
-
-    def check(self) -> None:
-        """RuntimeError if the kernel refused a pair (synchronises)."""
-        if int(self.status.item()) != 0:
-            raise RuntimeError("mask_inter_sized: cvlm_mask_inter_sized refused a pair: sizes that differ, an index or a table that does not fit")
-
-    def iou(self, iscrowd=None) -> np.ndarray:
-        """The COCO IoU of each pair, float64 (N,), on the host: pycocotools' rleIou.  -1 where inter is -1; 0 where inter is 0;
-        inter / area_a where iscrowd[q] is true for the pair's plane q of b (a crowd annotation: the share of the detection inside
-        it); inter / (area_a + area_b - inter) otherwise.  iscrowd: None or one truth value per plane of b.  ONE read of the device
-        (synchronises)."""
-        table = torch.stack([self.pairs[:, 1], self.inter, self.area_a, self.area_b]).cpu().numpy().astype(np.int64)
-        q, inter, a, b = table
-        crowd = np.zeros(q.shape, dtype=bool)
-        if iscrowd is not None:
-            flags = np.asarray(iscrowd).astype(bool).reshape(-1)
-            ok = (q >= 0) & (q < flags.size)
-            crowd[ok] = flags[q[ok]]
-        out = np.zeros(q.shape, dtype=np.float64)
-        pos = inter > 0
-        union = np.where(crowd, a, a + b - inter)
-        out[pos] = inter[pos] / union[pos].astype(np.float64)
-        out[inter < 0] = -1.0
-        return out
-
-
 @dataclass
 class MaskSet:
     """The edge decoder's multimask output for a batch (Cascade.infer_test_multimask; models/mmseg/models/sam/mask_decoder_edge.py:
@@ -2005,7 +1553,7 @@ class MaskSet:
 # ================================================================================================
 # The cascade  (models/sam_maskdecoder_edge.py:331-357 + demo.py:116-122)
 # ================================================================================================
-class Cascade(_Base):
+class Cascade(_Base, MaskUtilities):
     def __init__(self, sd: Dict[str, torch.Tensor], g: SamGeometry, c: ClipGeometry, device,
                  precision: Precision = Precision(), clip: Optional[ClipModel] = None):
         super().__init__(device, precision)
@@ -2463,456 +2011,6 @@ class Cascade(_Base):
             pred[b_lo * K + k:(b_hi - 1) * K + k + 1:K].copy_(pr[q:q + m])
             q += m
 
-    # ---- packed masks, areas, boxes and overlaps -----------------------------------------------------------------
-    def _compact_outputs(self, n: int, K: int, want_bits: bool, want_inter: bool):
-        """The result's own (mask_bits, area, box, inter) for n x K hypotheses, None where not asked for."""
-        if not want_bits:
-            return None, None, None, None
-        dev, S = self.device, self.g.inp_size
-        return (torch.empty(n, K, S * S // 8, dtype=torch.uint8, device=dev), torch.empty(n, K, dtype=torch.int32, device=dev),
-                torch.empty(n, K, 4, dtype=torch.int32, device=dev),
-                torch.empty(n, K, K, dtype=torch.int32, device=dev) if want_inter else None)
-
-    def _chunk_planes(self, mflat: Optional[torch.Tensor], eflat: Optional[torch.Tensor], p0: int, p1: int):
-        """Where the full-resolution planes of the prompts p0 <= p < p1 go: the result's tensors, or with masks="bits" the workspace
-        buffer "cls_planes" of at most class_chunk() planes and no edge map -> (mask planes, edge planes or None)."""
-        if mflat is not None:
-            return mflat[p0:p1], eflat[p0:p1]
-        S = self.g.inp_size
-        return self.ws.f32("cls_planes", p1 - p0, S, S), None
-
-    @staticmethod
-    def _pack_chunk(planes: torch.Tensor, compact, p0: int, p1: int) -> None:
-        """cvlm_mask_pack of a chunk's planes into rows p0 .. p1 - 1 of the result's mask_bits / area / box."""
-        bits, area, box, _ = compact
-        if bits is not None:
-            hip.mask_pack(planes, bits.view(-1, bits.shape[-1])[p0:p1], area.view(-1)[p0:p1], box.view(-1, 4)[p0:p1])
-
-    def pack_masks(self, logits: torch.Tensor):
-        """(bits, area, box) of any (N, S, S) or (N, 1, S, S) f32 mask logits on this engine's device, e.g. `infer_test`'s: bits uint8
-        (N, S * S / 8) = logits > 0 in numpy.packbits' order, area int32 (N,), box int32 (N, 4) inclusive (x0, y0, x1, y1), -1 for an
-        empty mask (cvlm_mask_pack).  One launch pair on the caller's stream; ValueError before it for anything else."""
-        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (3, 4) or \
-                (logits.dim() == 4 and logits.shape[1] != 1):
-            raise ValueError("pack_masks: logits must be a float32 tensor (N, H, W) or (N, 1, H, W)")
-        N, (H, W) = int(logits.shape[0]), (int(v) for v in logits.shape[-2:])
-        if not 1 <= N <= 65535 or H * W < 1 or (H * W) % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"pack_masks: {N} planes of {H} x {W}: 1 .. 65535 planes of a multiple of 32 pixels below 2^31")
-        if not logits.is_cuda:
-            raise ValueError("pack_masks: logits must be on the device")
-        planes = logits.detach().contiguous().view(N, H, W)
-        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=logits.device)
-        area = torch.empty(N, dtype=torch.int32, device=logits.device)
-        box = torch.empty(N, 4, dtype=torch.int32, device=logits.device)
-        hip.mask_pack(planes, bits, area, box)
-        return bits, area, box
-
-    # ---- connected components of packed masks (DESIGN.md §14) -----------------------------------------------------------------------
-    def _component_outputs(self, lead: tuple, nbytes: int, comp):
-        """The result's own (n_comp, comps, n_kept, kept_bits, kept_area, kept_box) for planes of shape `lead`, None where not asked for."""
-        asked, M, min_area, _ = comp
-        if not asked:
-            return (None,) * 6
-        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
-        if min_area < 1:
-            return i32(), i32(M, 6) if M else None, None, None, None, None
-        return (i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32(), i32(4))
-
-    def _components(self, bits: torch.Tensor, H: int, W: int, comp, out, p0: int, p1: int) -> None:
-        """cvlm_mask_components of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's tensors `out`.  The
-        workspace "cls_comp" grows to what these planes want in flight, up to COMPONENTS_WS_CAP (and never below one plane's)."""
-        asked, M, min_area, connectivity = comp
-        if not asked:
-            return
-        want = min(hip.mask_components_workspace_bytes(p1 - p0, H, W), max(COMPONENTS_WS_CAP, hip.mask_components_workspace_bytes(1, H, W)))
-        ws = self.ws._get("u8", "cls_comp", want, torch.uint8, False)
-        rows = [None if t is None else t.view(-1, *t.shape[t.dim() - k:])[p0:p1] for t, k in zip(out, (0, 2, 0, 1, 0, 1))]   # k: own dims
-        hip.mask_components(bits, H, W, connectivity, min_area, ws, *rows)
-
-    def mask_components(self, bits: torch.Tensor, H: int, W: int, *, components: Optional[int] = 1, min_area: int = 0,
-                        connectivity: int = 8) -> "MaskComponents":
-        """Connected regions of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits (W % 32 == 0):
-        the number of regions, the `components` largest with their boxes and seeds and, with min_area >= 1, the masks without
-        their regions below min_area pixels, with area and box (cvlm_mask_components) -> MaskComponents.  Launches
-        on the caller's stream; ValueError before them for anything else."""
-        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, who="mask_components")
-        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
-                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"mask_components: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
-        H, W = int(H), int(W)
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
-                or not 1 <= int(bits.shape[0]) <= 65535:
-            raise ValueError(f"mask_components: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
-        if not bits.is_cuda:
-            raise ValueError("mask_components: bits must be on the device")
-        bits = bits.detach().contiguous()
-        if bits.data_ptr() % 4 != 0:
-            bits = bits.clone()
-        N = int(bits.shape[0])
-        out = self._component_outputs((N,), H * W // 8, (True,) + comp[1:])
-        self._components(bits, H, W, (True,) + comp[1:], out, 0, N)
-        return MaskComponents(*out)
-
-    # ---- holes of packed masks (DESIGN.md §15) ----------------------------------------------------------------------------------------
-    def _hole_outputs(self, lead: tuple, nbytes: int, hreq):
-        """The result's own (n_holes, holes, n_filled, filled_bits, filled_area) for planes of shape `lead`, None where not asked for."""
-        asked, M, fill_below, _ = hreq
-        if not asked:
-            return (None,) * 5
-        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
-        if fill_below < 1:
-            return i32(), i32(M, 6) if M else None, None, None, None
-        return i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32()
-
-    def _holes(self, bits: torch.Tensor, H: int, W: int, hreq, out, p0: int, p1: int) -> None:
-        """cvlm_mask_holes of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's tensors `out`.  The workspace
-        is `_components`' "cls_comp", grow-only under the same COMPONENTS_WS_CAP: the two entries are ordered on one stream."""
-        asked, M, fill_below, connectivity = hreq
-        if not asked:
-            return
-        want = min(hip.mask_holes_workspace_bytes(p1 - p0, H, W), max(COMPONENTS_WS_CAP, hip.mask_holes_workspace_bytes(1, H, W)))
-        ws = self.ws._get("u8", "cls_comp", want, torch.uint8, False)
-        rows = [None if t is None else t.view(-1, *t.shape[t.dim() - k:])[p0:p1] for t, k in zip(out, (0, 2, 0, 1, 0))]   # k: own dims
-        hip.mask_holes(bits, H, W, connectivity, fill_below, ws, *rows)
-
-    def mask_holes(self, bits: torch.Tensor, H: int, W: int, *, holes: Optional[int] = 1, fill_holes: int = 0,
-                   connectivity: int = 8) -> "MaskHoles":
-        """Holes of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits (W % 32 == 0): the number
-        of holes, the `holes` largest with their boxes and seeds and, with fill_holes >= 1, the masks with their holes of fewer than
-        fill_holes pixels set, with their area (cvlm_mask_holes) -> MaskHoles.  connectivity is the foreground's; the
-        clear pixels connect at its dual.  SAM's post-processing, fill then despeckle, is
-        mask_components(mask_holes(bits, H, W, fill_holes=t).filled_bits, H, W, min_area=t).  Launches on the caller's stream;
-        ValueError before them for anything else."""
-        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, who="mask_holes")
-        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
-                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"mask_holes: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
-        H, W = int(H), int(W)
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
-                or not 1 <= int(bits.shape[0]) <= 65535:
-            raise ValueError(f"mask_holes: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
-        if not bits.is_cuda:
-            raise ValueError("mask_holes: bits must be on the device")
-        bits = bits.detach().contiguous()
-        if bits.data_ptr() % 4 != 0:
-            bits = bits.clone()
-        N = int(bits.shape[0])
-        out = self._hole_outputs((N,), H * W // 8, (True,) + hreq[1:])
-        self._holes(bits, H, W, (True,) + hreq[1:], out, 0, N)
-        return MaskHoles(*out)
-
-    # ---- morphology of packed masks (DESIGN.md §16) -----------------------------------------------------------------------------------
-    def _band_outputs(self, n: int, K: int, nbytes: int, mreq):
-        """The result's own (band_bits, band_area, band_inter) for n x K hypotheses, None where not asked for."""
-        asked, _, want_inter = mreq
-        if not asked:
-            return None, None, None
-        dev = self.device
-        return (torch.empty(n, K, nbytes, dtype=torch.uint8, device=dev), torch.empty(n, K, dtype=torch.int32, device=dev),
-                torch.empty(n, K, K, dtype=torch.int32, device=dev) if want_inter else None)
-
-    @staticmethod
-    def _band(bits: torch.Tensor, H: int, W: int, mreq, out, p0: int, p1: int) -> None:
-        """cvlm_mask_morph, band only, of the planes bits (p1 - p0, H * W / 8) into rows p0 .. p1 - 1 of the result's band_bits /
-        band_area.  No workspace."""
-        band_bits, band_area, _ = out
-        hip.mask_morph(bits, H, W, mreq[1], band_bits=band_bits.view(-1, band_bits.shape[-1])[p0:p1], band_area=band_area.view(-1)[p0:p1])
-
-    # ---- packed edge maps (DESIGN.md §17) -------------------------------------------------------------------------------------------
-    def _edge_outputs(self, n: int, K: int, nbytes: int, ereq):
-        """The result's own (edge_bits, edge_area, edge_band, edge_inter) for n x K hypotheses, None where not asked for."""
-        asked, _, want_band, want_inter = ereq
-        if not asked:
-            return None, None, None, None
-        dev = self.device
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-        return (torch.empty(n, K, nbytes, dtype=torch.uint8, device=dev), i32(n, K), i32(n, K) if want_band else None,
-                i32(n, K, K) if want_inter else None)
-
-    def _edge_bits(self, n: int, ereq, out, bands, p0: int, p1: int) -> None:
-        """cvlm_edge_pack of a chunk's low-resolution edge map -- where MaskDecoder left it, workspace buffer "low_edge", n x 4G x 4G
-        -- into rows p0 .. p1 - 1 of the result's edge_bits / edge_area and, with band=, edge_band against the chunk's rows of
-        band_bits.  One call, no workspace; the full-resolution edge map is not formed."""
-        g = self.g
-        S, L = g.inp_size, 4 * g.grid
-        low = self.decoder.ws.f32("low_edge", n, L * L).view(n, L, L)
-        bits, area, on_band, _ = out
-        with_bits = with_inter = None
-        if on_band is not None:
-            with_bits, with_inter = bands[0].view(-1, bands[0].shape[-1])[p0:p1], on_band.view(-1)[p0:p1]
-        hip.edge_pack(low, S, S, ereq[1], bits.view(-1, bits.shape[-1])[p0:p1], area.view(-1)[p0:p1], with_bits, with_inter)
-
-    def pack_edges(self, prob: torch.Tensor, size=None, *, threshold: float, with_bits: Optional[torch.Tensor] = None) -> "EdgeBits":
-        """Packed edge maps of any (N, h, w) or (N, 1, h, w) f32 probability planes on this engine's device (cvlm_edge_pack, DESIGN.md
-        §17) -> EdgeBits: bits uint8 (N, H * W / 8) in numpy.packbits' order, set where the align_corners=False bilinear value at
-        size = (H, W) is > threshold, and their area.  size=None means (h, w), a pure threshold pack: that is how
-        `infer_test_multimask(...).edges` is packed; a low-resolution map takes size=(S, S).  with_bits: (N, H * W / 8) uint8 packed
-        planes, e.g. `mask_morph`'s band_bits: `inter` = |bits AND with_bits| per plane.  0 < threshold < 1, W % 32 == 0.  One launch
-        pair on the caller's stream; ValueError before it for anything else."""
-        t = _edge_threshold(threshold, "pack_edges")
-        if not isinstance(prob, torch.Tensor) or prob.dtype != torch.float32 or prob.dim() not in (3, 4) or \
-                (prob.dim() == 4 and prob.shape[1] != 1):
-            raise ValueError("pack_edges: prob must be a float32 tensor (N, h, w) or (N, 1, h, w)")
-        N, (h, w) = int(prob.shape[0]), (int(v) for v in prob.shape[-2:])
-        if size is None:
-            size = (h, w)
-        if not isinstance(size, (tuple, list)) or len(size) != 2 or \
-                any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in size):
-            raise ValueError(f"pack_edges: size must be None or a pair of ints (H, W), got {size!r}")
-        H, W = (int(v) for v in size)
-        if not 1 <= N <= 65535 or h < 1 or w < 1 or h * w >= 2 ** 31 or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"pack_edges: {N} planes of {h} x {w} to {H} x {W}: 1 .. 65535 planes, W a multiple of 32, both sizes "
-                             "below 2^31 pixels")
-        if not prob.is_cuda:
-            raise ValueError("pack_edges: prob must be on the device")
-        if with_bits is not None:
-            if not isinstance(with_bits, torch.Tensor) or with_bits.dtype != torch.uint8 or tuple(with_bits.shape) != (N, H * W // 8):
-                raise ValueError(f"pack_edges: with_bits must be a uint8 tensor ({N}, {H * W // 8})")
-            if with_bits.device != prob.device:
-                raise ValueError("pack_edges: with_bits must be on prob's device")
-            with_bits = with_bits.detach().contiguous()
-            if with_bits.data_ptr() % 4 != 0:
-                with_bits = with_bits.clone()
-        planes = prob.detach().contiguous().view(N, h, w)
-        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=prob.device)
-        area = torch.empty(N, dtype=torch.int32, device=prob.device)
-        inter = torch.empty(N, dtype=torch.int32, device=prob.device) if with_bits is not None else None
-        hip.edge_pack(planes, H, W, t, bits, area, with_bits, inter)
-        return EdgeBits(bits, area, inter)
-
-    def mask_morph(self, bits: torch.Tensor, H: int, W: int, *, radius: int = 2, dilate: bool = False, erode: bool = False,
-                   band: bool = True) -> "MaskMorph":
-        """Dilation, erosion and edge band = dilation & ~erosion of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g.
-        `pack_masks`' bits (W % 32 == 0), by the (2 radius + 1)^2 square, 1 <= radius <= 16, each with its area (cvlm_mask_morph,
-        DESIGN.md §16) -> MaskMorph, None where an output was not asked for.  Pixels outside the plane are clear to dilation and set to
-        erosion, as max_pool2d's padding has it: radius=2 is the band the reference trains its edge head against.  Opening and closing
-        are compositions through this utility: opening = mask_morph(mask_morph(bits, ..., erode=True, band=False).ero_bits, ...,
-        dilate=True, band=False).dil_bits, closing the reverse; a SAM-style chain is
-        mask_components(mask_holes(mask_morph(bits, H, W, dilate=True, band=False).dil_bits, H, W, fill_holes=t).filled_bits, H, W,
-        min_area=t).  Launches on the caller's stream; ValueError before them for anything else."""
-        if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MORPH_MAXR:
-            raise ValueError(f"mask_morph: radius must be an int in [1, {MORPH_MAXR}], got {radius!r}")
-        for name, v in (("dilate", dilate), ("erode", erode), ("band", band)):
-            if not isinstance(v, (bool, np.bool_)):
-                raise ValueError(f"mask_morph: {name} must be a bool, got {type(v).__name__}")
-        if not (dilate or erode or band):
-            raise ValueError("mask_morph: nothing asked for: at least one of dilate, erode and band")
-        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
-                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"mask_morph: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
-        H, W = int(H), int(W)
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
-                or not 1 <= int(bits.shape[0]) <= 65535:
-            raise ValueError(f"mask_morph: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
-        if not bits.is_cuda:
-            raise ValueError("mask_morph: bits must be on the device")
-        bits = bits.detach().contiguous()
-        if bits.data_ptr() % 4 != 0:
-            bits = bits.clone()
-        N = int(bits.shape[0])
-        out = []
-        for asked in (dilate, erode, band):
-            out += [torch.empty_like(bits), torch.empty(N, dtype=torch.int32, device=bits.device)] if asked else [None, None]
-        hip.mask_morph(bits, H, W, int(radius), *out)
-        return MaskMorph(*out)
-
-    # ---- run-length encoding of packed masks (DESIGN.md §18) ------------------------------------------------------------------------
-    def mask_rle(self, bits: torch.Tensor, H: int, W: int) -> "MaskRle":
-        """COCO run-length encoding of any (N, H * W / 8) uint8 packed masks on this engine's device, e.g. `pack_masks`' bits or
-        `mask_components`' kept_bits (W % 32 == 0; H any) -> MaskRle.  cvlm_mask_rle_count, torch.cumsum of the run counts on the device,
-        ONE device-to-host read of the total -- the call's only synchronisation, and the size of `counts` is known before it is
-        allocated --, then cvlm_mask_rle_emit through the grow-only workspace "cls_rle", capped at RLE_WS_CAP (beyond it the entry
-        walks the planes in rounds).  The emit's status word stays on the device: `MaskRle.check()` / `to_coco()` read it.  Launches on
-        the caller's stream; ValueError before them for anything else."""
-        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
-                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
-            raise ValueError(f"mask_rle: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
-        H, W = int(H), int(W)
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
-                or not 1 <= int(bits.shape[0]) <= 65535:
-            raise ValueError(f"mask_rle: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
-        if not bits.is_cuda:
-            raise ValueError("mask_rle: bits must be on the device")
-        bits = bits.detach().contiguous()
-        if bits.data_ptr() % 4 != 0:
-            bits = bits.clone()
-        N, dev = int(bits.shape[0]), bits.device
-        n_runs = torch.empty(N, dtype=torch.int32, device=dev)
-        hip.mask_rle_count(bits, H, W, n_runs)
-        offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
-        total = int(offsets[N].item())                               # the one synchronisation
-        counts = torch.empty(total, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-        want = min(hip.mask_rle_workspace_bytes(N, H, W), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, H, W)))
-        ws = self.ws._get("u8", "cls_rle", want, torch.uint8, False)
-        hip.mask_rle_emit(bits, H, W, offsets, counts, status, ws)
-        return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=(H, W), status=status)
-
-    # ---- masks at each image's own size (DESIGN.md §19) ---------------------------------------------------------------------------
-    def _sized_outputs(self, sreq, K: int, n_calls: int):
-        """sizes= of infer_classes / decode: the result's own SizedMasks for K hypotheses per image and the device table of the planes'
-        (h, w) -- built on the host and uploaded once, before the chunk loop -> (SizedMasks, dims, largest word count) or None."""
-        if sreq is None:
-            return None
-        sizes, level = sreq
-        per_plane = [s for s in sizes for _ in range(K)]
-        dims, offsets, max_words = sized_tables(per_plane)
-        dev, P = self.device, len(per_plane)
-        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
-                         area=torch.empty(P, dtype=torch.int32, device=dev), box=torch.empty(P, 4, dtype=torch.int32, device=dev),
-                         status=torch.empty(n_calls, dtype=torch.int32, device=dev), sizes=per_plane, level=level)
-        return out, torch.from_numpy(dims).to(dev), max_words
-
-    @staticmethod
-    def _pack_sized_chunk(planes: torch.Tensor, sized, p0: int, p1: int, call: int) -> None:
-        """cvlm_mask_pack_sized of a chunk's full-resolution planes into the planes p0 .. p1 - 1 of the result's SizedMasks: one call
-        whatever sizes the chunk holds, no workspace."""
-        if sized is None:
-            return
-        out, dims, max_words = sized
-        hip.mask_pack_sized(planes[:p1 - p0], dims[p0:p1], out.offsets[p0:p1 + 1], out.level, out.bits, max_words, out.area[p0:p1],
-                            out.box[p0:p1], out.status[call:call + 1])
-
-    def pack_masks_sized(self, logits: torch.Tensor, sizes, *, level: int = 128) -> "SizedMasks":
-        """Packed masks of any (N, Hs, Ws) or (N, 1, Hs, Ws) f32 mask logits on this engine's device at a size of each plane's own:
-        sizes holds N (h, w) pairs -> SizedMasks (cvlm_mask_pack_sized).  A bit is set where the reference's uint8 mask
-        -- sigmoid, cv2.resize(INTER_LINEAR) to (h, w), * 255 (test_ovcos_maskdecoder_edge.py:103,116-130; demo.py:117-131) -- is >=
-        level: 128 is the half, 1 the demo's `> 0` overlay.  At (Hs, Ws) itself the bits are NOT `pack_masks`' (logit > 0): they go
-        through the same arithmetic with weights 1 and 0.  One launch pair on the caller's stream whatever the mix of sizes, the two
-        small tables uploaded before it; no workspace.  ValueError before anything is launched for anything else."""
-        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (3, 4) or \
-                (logits.dim() == 4 and logits.shape[1] != 1):
-            raise ValueError("pack_masks_sized: logits must be a float32 tensor (N, H, W) or (N, 1, H, W)")
-        N, (Hs, Ws) = int(logits.shape[0]), (int(v) for v in logits.shape[-2:])
-        if not 1 <= N <= 65535 or Hs < 1 or Ws < 1 or Hs * Ws >= 2 ** 31:
-            raise ValueError(f"pack_masks_sized: {N} planes of {Hs} x {Ws}: 1 .. 65535 planes of fewer than 2^31 pixels")
-        if not logits.is_cuda:
-            raise ValueError("pack_masks_sized: logits must be on the device")
-        sreq = sized_request(sizes=sizes, sized_level=level, n=N, who="pack_masks_sized")
-        if sreq is None:
-            raise ValueError("pack_masks_sized: sizes must be a sequence of (h, w) pairs, got None")
-        sized = self._sized_outputs(sreq, 1, 1)
-        self._pack_sized_chunk(logits.detach().contiguous().view(N, Hs, Ws), sized, 0, N, 0)
-        return sized[0]
-
-    def mask_rle_sized(self, sized: "SizedMasks") -> "MaskRle":
-        """COCO run-length encoding of sized planes -> MaskRle whose `to_coco()` writes each plane's own "size": [h, w],
-        what an evaluator holds against an annotation of the original image.  One cvlm_mask_rle_count_w call per run of consecutive
-        planes of one size -- per image where the planes come from the engine --, one torch.cumsum, ONE read of the total (the call's
-        only synchronisation), then one cvlm_mask_rle_emit_w call per run through the workspace "cls_rle", all on absolute offsets
-        into one `counts`.  The status words of the runs are folded into one on the device."""
-        if not isinstance(sized, SizedMasks):
-            raise ValueError(f"mask_rle_sized: sized must be a SizedMasks, got {type(sized).__name__}")
-        sizes = sized.sizes
-        P, dev = len(sizes), sized.bits.device
-        if not 1 <= P <= 65535 or not sized.bits.is_cuda:
-            raise ValueError("mask_rle_sized: 1 .. 65535 planes on the device")
-        _, host_off, _ = sized_tables(sizes)
-        runs, a = [], 0                                               # (first plane, one past the last) of each run of equal sizes
-        for p in range(1, P + 1):
-            if p == P or sizes[p] != sizes[a]:
-                runs.append((a, p))
-                a = p
-        n_runs = torch.empty(P, dtype=torch.int32, device=dev)
-        rows = lambda a, b: sized.bits[int(host_off[a]):int(host_off[b])].view(b - a, -1)
-        for a, b in runs:
-            h, w = sizes[a]
-            hip.mask_rle_count_w(rows(a, b), h, 32 * ((w + 31) // 32), w, n_runs[a:b])
-        offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
-        total = int(offsets[P].item())                               # the one synchronisation
-        counts = torch.empty(total, dtype=torch.int32, device=dev)
-        status = torch.empty(len(runs), dtype=torch.int32, device=dev)
-        want = 0
-        for a, b in runs:
-            h, w = sizes[a]
-            pitch = 32 * ((w + 31) // 32)
-            want = max(want, min(hip.mask_rle_workspace_bytes(b - a, h, pitch), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, h, pitch))))
-        ws = self.ws._get("u8", "cls_rle", want, torch.uint8, False)
-        for i, (a, b) in enumerate(runs):
-            h, w = sizes[a]
-            hip.mask_rle_emit_w(rows(a, b), h, 32 * ((w + 31) // 32), w, offsets[a:b + 1], counts, status[i:i + 1], ws)
-        same = all(s == sizes[0] for s in sizes)
-        return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=sizes[0] if same else None,
-                       status=torch.amax(status, 0, keepdim=True), sizes=sizes)
-
-    # ---- COCO annotations on the device (DESIGN.md §20) --------------------------------------------------------------------------------
-    def rle_decode(self, rles, *, stats: bool = True) -> "SizedMasks":
-        """COCO run-length annotations -> SizedMasks on this engine's device (cvlm_mask_rle_decode): ground truth in the
-        format of the predictions, on which `mask_inter_sized`, `mask_rle_sized` and -- per image -- `mask_components`, `mask_holes` and
-        `mask_morph` run.  rles: a list of {"size": [h, w], "counts": list | bytes | str}, checked by `rle_decode_request` on the host
-        before anything is launched (ValueError) and uploaded once; or a MaskRle already on the device, e.g. `mask_rle_sized`'s: then
-        nothing is copied to the host and nothing synchronises -- the kernel's own checks are the only ones, and `check()` of the
-        result reports what they refused (a refused plane is zero).  stats=False: no `area` and no `box`.  The result has level 0:
-        not a threshold.  The workspace is the grow-only "cls_rle", capped at RLE_WS_CAP (beyond it the entry walks the planes in
-        rounds).  Launches on the caller's stream."""
-        dev = self.device
-        if isinstance(rles, MaskRle):
-            P = int(rles.n_runs.shape[0])
-            sizes = [tuple(rles.size_of(p)) for p in range(P)]
-            if not 1 <= P <= 65535 or not rles.counts.is_cuda or rles.counts.dtype != torch.int32 or rles.counts.numel() < 1 or \
-                    any(not 1 <= v <= SIZED_MAX_SIDE for s in sizes for v in s):
-                raise ValueError("rle_decode: a MaskRle of 1 .. 65535 planes on the device, sides in [1, 16384]")
-            counts, run_offsets = rles.counts.contiguous(), rles.offsets.contiguous()
-        else:
-            c, o, sizes = rle_decode_request(rles)
-            P = len(sizes)
-            counts, run_offsets = torch.from_numpy(c).to(dev), torch.from_numpy(o).to(dev)
-        dims, offsets, _ = sized_tables(sizes)
-        max_pixels = max(h * w for h, w in sizes)
-        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
-                         area=torch.empty(P, dtype=torch.int32, device=dev) if stats else None,
-                         box=torch.empty(P, 4, dtype=torch.int32, device=dev) if stats else None,
-                         status=torch.empty(1, dtype=torch.int32, device=dev), sizes=[(int(h), int(w)) for h, w in sizes], level=0)
-        one = hip.mask_rle_decode_workspace_bytes(1, max_pixels)
-        ws = self.ws._get("u8", "cls_rle", min(P * one, max(RLE_WS_CAP, one)), torch.uint8, False)
-        hip.mask_rle_decode(counts, run_offsets, torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box,
-                            out.status, ws)
-        return out
-
-    def mask_inter_sized(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, a_image=None, b_image=None) -> "SizedOverlaps":
-        """Intersections of pairs of sized planes -> SizedOverlaps (cvlm_mask_inter_sized): detections `a` against
-        annotations `b` (they may be the same object).  Either pairs= -- (N, 2) (plane of a, plane of b) -- or a_image= and b_image=, one
-        image id per plane of each: all (p, q) with a_image[p] == b_image[q], ordered by p, then q; `pairs_request` checks them on the
-        host before anything is launched (ValueError).  Two planes of different sizes give inter = -1, as pycocotools' rleIou does.
-        One upload of the pair table and of the two small size tables, one launch pair, two gathers of the areas; no workspace, no
-        synchronisation: `SizedOverlaps.iou()` does the one read."""
-        for name, s in (("a", a), ("b", b)):
-            if not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535:
-                raise ValueError(f"mask_inter_sized: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas")
-        table = pairs_request(a.sizes, b.sizes, pairs=pairs, a_image=a_image, b_image=b_image)
-        dev = a.bits.device
-        tab = table.to(torch.int32).contiguous() if isinstance(table, torch.Tensor) else torch.from_numpy(table).to(dev)
-        N = int(tab.shape[0])
-        a_dims, _, a_words = sized_tables(a.sizes)
-        b_dims, _, b_words = (a_dims, None, a_words) if b is a else sized_tables(b.sizes)
-        a_dims = torch.from_numpy(a_dims).to(dev)
-        b_dims = a_dims if b is a else torch.from_numpy(b_dims).to(dev)
-        inter = torch.empty(N, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-        hip.mask_inter_sized(a.bits, a.offsets, a_dims, b.bits, b.offsets, b_dims, tab, max(a_words, b_words), inter, status)
-        pick = lambda s, col: s.area.index_select(0, tab[:, col].long().clamp_(0, len(s.sizes) - 1))
-        return SizedOverlaps(pairs=tab, inter=inter, area_a=pick(a, 0), area_b=pick(b, 1), status=status)
-
-    def _gt_overlaps(self, greq, sized, n: int, K: int) -> Optional["SizedOverlaps"]:
-        """ground_truth= of infer_classes / decode: `mask_inter_sized` of the result's sized planes with the annotations of each plane's
-        own image, once, behind the last chunk."""
-        if greq is None:
-            return None
-        gt, ids = greq
-        return self.mask_inter_sized(sized[0], gt, a_image=[b for b in range(n) for _ in range(K)], b_image=ids)
-
-    def _rle_of(self, source: Optional[str], fields: dict, S: int) -> Optional["MaskRle"]:
-        """rle= of infer_classes / decode: `mask_rle` of the result's own planes named by `rle_request`, all n * K of them at once;
-        rle="sized": `mask_rle_sized` of the result's sized planes."""
-        if source is None:
-            return None
-        if source == RLE_SIZED:
-            return self.mask_rle_sized(fields[RLE_SIZED][0])
-        planes = fields[source]
-        return self.mask_rle(planes.view(-1, planes.shape[-1]), S, S)
-
     def infer_classes(self, inp, clip_image, clip_mask, *, classes: Optional[torch.Tensor] = None,
                       topk: Optional[int] = None, quality: bool = False, vocab: Optional[Vocabulary] = None,
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
@@ -2938,76 +2036,20 @@ class Cascade(_Base):
         ranks.  quality=False makes exactly the launches it made before.
         vocab: a run-time vocabulary in place of the constructor's bank: `classes` / `topk` index it, pass 1 and stage 2
         score against it -- up to 65536 classes, topk <= 64 above 1024.
-        masks= / overlaps= (`compact_request`, checked with the rest before any launch): "bits" or "both" add
-        `mask_bits`, `area` and `box` -- cvlm_mask_pack on each chunk's full-resolution planes --, overlaps=True `inter`, one
-        cvlm_mask_overlap launch behind the last chunk.  "bits" returns no `masks` and no `edges`: the planes of a chunk live in a
-        workspace buffer of class_chunk() planes, from which `_alpha` reads them, the edge maps are not resized, and no (B, K, S, S)
-        tensor exists; the decoder's launches are those of the default call, so every other field keeps its bits.  The default,
-        masks="logits", overlaps=False, makes exactly the launches and allocations it made before.
-        components= / min_area= / connectivity= (`components_request`, checked with the rest; they need masks="bits" or
-        "both"): components=M adds `n_comp` and `comps`, the connected regions of each packed mask and its M largest; min_area >= 1 adds
-        `n_kept`, `kept_bits`, `kept_area` and `kept_box`, the mask without its regions below min_area pixels -- cvlm_mask_components
-        on each chunk's rows of `mask_bits`, right behind cvlm_mask_pack.  A descriptor, not a rule: nothing is ranked or chosen between
-        hypotheses.  Without them the call makes exactly the launches and allocations it made before.
-        holes= / fill_holes= (`holes_request`, checked with the rest; they need masks="bits" or "both" and share
-        connectivity=): holes=M adds `n_holes` and `holes`, the holes of each packed mask and its M largest; fill_holes >= 1 adds
-        `n_filled`, `filled_bits` and `filled_area`, the mask with its holes of fewer than fill_holes pixels set -- cvlm_mask_holes on
-        each chunk's rows of `mask_bits`, behind cvlm_mask_components.  Independent of components=: `kept_*` stay functions of
-        `mask_bits`; SAM's order, fill then despeckle, is mask_components(mask_holes(bits, ...).filled_bits, ...).  Without them the
-        call makes exactly the launches and allocations it made before.
-        band=r (`morph_request`, checked with the rest; needs masks="bits" or "both"): adds `band_bits` and `band_area`,
-        the edge band of each packed mask -- dilation & ~erosion by the (2 r + 1)^2 square, r = 2 the band the reference trains its
-        edge head against -- by cvlm_mask_morph on each chunk's rows of `mask_bits`, right behind cvlm_mask_pack, into the result's own
-        tensors: no workspace.  With overlaps=True also `band_inter`, the bands' pairwise intersections, one more cvlm_mask_overlap
-        launch behind the last chunk: boundary agreement of two hypotheses is band_inter / (band_area_a + band_area_b - band_inter),
-        and the caller divides.  Independent of components= and holes=.  Without it the call makes exactly the launches and
-        allocations it made before.
-        edge_threshold=t (`edge_request`, checked with the rest; 0 < t < 1, needs masks="bits" or "both"): adds `edge_bits`
-        and `edge_area`, the edge head's probability map of each hypothesis as bits -- one cvlm_edge_pack call per chunk, right behind
-        the band, that resizes the decoder's low-resolution edge map, compares `> t` and packs, into the result's own tensors: no
-        workspace, and no full-resolution edge map even with masks="both", so edge_bits is the same function of the decoder's output
-        in both modes (it may differ from `edges > t` only where |edges - t| <= 2^-21).  With band=r also `edge_band`, the edge pixels
-        on each mask's band; with overlaps=True also `edge_inter`, one more cvlm_mask_overlap launch behind the last chunk.  The
-        decoder's launches are those of the call without it.  Nothing is chosen here and there is no default threshold: the
-        reference trains and evaluates the soft map.  Without it the call makes exactly the launches and allocations it made before.
-        rle="mask" / "kept" / "filled" (`rle_request`, checked with the rest; needs masks="bits" or "both", "kept" needs
-        min_area >= 1, "filled" fill_holes >= 1): adds `rle`, the COCO run-length encoding of mask_bits, kept_bits or filled_bits of
-        all B * K hypotheses -- `mask_rle`, once, behind the last chunk where cvlm_mask_overlap runs: two count launches, a cumsum,
-        one read of the total (a synchronisation of the host with the side stream) and the emit's launches.  An interchange format
-        for pycocotools, the COCO / LVIS evaluators and the reference's GenericMask, not a compression: see DESIGN.md §18 for sizes.
-        Without it the call makes exactly the launches, allocations and synchronisations it made before.
-        sizes= / sized_level= (`sized_request`, checked with the rest; they need masks="bits" or "both"): sizes holds one
-        (h, w) per image, the size of the ORIGINAL image the evaluation compares at; adds `sized`, a SizedMasks with the K masks of
-        image b at (h_b, w_b) -- the bits of the reference's uint8 mask (sigmoid, cv2.resize to (h, w), * 255) >= sized_level, with
-        areas and boxes in the image's coordinates -- by one cvlm_mask_pack_sized call per chunk on the chunk's full-resolution planes,
-        right behind cvlm_mask_pack, into the result's own tensors: no workspace, and with masks="bits" still no f32 plane in the
-        result.  The two tables of the planes are built on the host and uploaded once, before the first chunk.  rle="sized" (needs
-        sizes=) encodes those planes, `mask_rle_sized`, behind the last chunk: `rle.to_coco()` then carries "size": [h, w] of each
-        image, which an evaluator can hold against an annotation.  Without sizes= the call makes exactly the launches, allocations and
-        synchronisations it made before.
-        ground_truth=(gt, gt_image) (`ground_truth_request`, checked with the rest; needs sizes=): gt is a SizedMasks of
-        annotations -- `rle_decode` of their COCO RLEs -- and gt_image[q] the image of the call annotation q belongs to, whose size it
-        must have; adds `gt_overlaps`, a SizedOverlaps with the intersection of every hypothesis's sized plane with every annotation of
-        its own image -- pairs (b * K + k, q) ordered by the plane, then q --, by one cvlm_mask_inter_sized call behind the last chunk;
-        `gt_overlaps.iou(iscrowd)` is the COCO IoU.  Nothing is matched or chosen.  Without it the call makes exactly the launches,
-        allocations and synchronisations it made before."""
+        masks= / overlaps=, components= / min_area= / connectivity=, holes= / fill_holes=, band=, edge_threshold=, rle=, sizes= /
+        sized_level= and ground_truth=: the packed outputs of each hypothesis's mask, one paragraph each under
+        `MaskPost`, the plan `decode` runs too; checked with the rest before any launch.  The defaults ask for none of them and make
+        exactly the launches, allocations and synchronisations of a call without them; rle='s one read synchronises the host with the
+        side stream."""
         B = int(inp.shape[0])
         vocab = self._vocab_of(vocab)
         K, host_classes = self._class_request(B, classes, topk, vocab)
-        want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=B, K=K, who="infer_classes")
-        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size,
-                                  who="infer_classes")
-        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size,
-                             who="infer_classes")
-        mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size, who="infer_classes")
-        ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size,
-                            who="infer_classes")
-        rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size, who="infer_classes")
-        sreq = sized_request(sizes=sizes, sized_level=sized_level, n=B, masks=masks, rle=rle, who="infer_classes")
-        greq = ground_truth_request(ground_truth, sreq, B, who="infer_classes")
+        post = MaskPost(who="infer_classes", n=B, K=K, side=self.g.inp_size, masks=masks, overlaps=overlaps, components=components,
+                        min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
+                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth)
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
-        P, S, T, C = B * K, g.inp_size, g.grid * g.grid, g.prompt_embed_dim
+        P, T, C = B * K, g.grid * g.grid, g.prompt_embed_dim
         txt_bank = self._bank(vocab)
         n_cls, D = txt_bank.shape
         idx_in = None if host_classes is None else host_classes.to(dev)
@@ -3017,19 +2059,12 @@ class Cascade(_Base):
             sel = self.ws.f32("cls_sel", P, D)
             self._select(score, B, n_cls, K, txt_bank, D, idx_in, cls, sel)
             vis, txt = self._project_prompts(img_f, sel, B, P)
-            m_out = torch.empty(B, K, S, S, device=dev) if want_logits else None
-            e_out = torch.empty(B, K, S, S, device=dev) if want_logits else None
+            post.allocate_planes(self)
             logits = torch.empty(B, K, n_cls, device=dev)
             pred = torch.empty(B, K, dtype=torch.int64, device=dev)
             iou = torch.empty(B, K, device=dev) if quality else None
-            compact = self._compact_outputs(B, K, want_bits, want_inter)
-            regions = self._component_outputs((B, K), S * S // 8, comp)
-            pits = self._hole_outputs((B, K), S * S // 8, hreq)
-            bands = self._band_outputs(B, K, S * S // 8, mreq)
-            edged = self._edge_outputs(B, K, S * S // 8, ereq)
-            mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
             chunk = self.class_chunk()
-            sized = self._sized_outputs(sreq, K, -(-P // chunk))
+            post.allocate(chunk)
             for p0 in range(0, P, chunk):
                 p1 = min(P, p0 + chunk)
                 n = p1 - p0
@@ -3041,42 +2076,17 @@ class Cascade(_Base):
                 sp = self.ws.f32("cls_sparse", n, 2, C)
                 self._per_prompt(vis, K, p0, p1, sp[:, 0])
                 sp[:, 1].copy_(txt[p0:p1])
-                planes, eplanes = self._chunk_planes(mflat, eflat, p0, p1)
+                planes, eplanes = post.chunk_planes(p0, p1)
                 self._mask_logits(fr, sp, n, out=planes, edge_out=eplanes, iou_out=iou.view(P)[p0:p1] if quality else None,
-                                  edge_low=not want_logits)
-                self._pack_chunk(planes, compact, p0, p1)
-                self._pack_sized_chunk(planes, sized, p0, p1, p0 // chunk)
-                if mreq[0]:
-                    self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
-                if ereq[0]:
-                    self._edge_bits(n, ereq, edged, bands, p0, p1)
-                if comp[0]:
-                    self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
-                if hreq[0]:
-                    self._holes(compact[0].view(P, -1)[p0:p1], S, S, hreq, pits, p0, p1)
+                                  edge_low=not post.want_logits)
+                post.chunk(planes, p0, p1, p0 // chunk)
                 self._class_stage2(planes, clip_image, B, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
-            if want_inter:
-                hip.mask_overlap(compact[0], compact[3])
-            if mreq[2]:
-                hip.mask_overlap(bands[0], bands[2])
-            if ereq[3]:
-                hip.mask_overlap(edged[0], edged[3])
             if quality:
                 iou.masked_fill_(cls < 0, float("nan"))
-            runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
-            held = self._gt_overlaps(greq, sized, B, K)
-        coded = () if runs is None else (runs.counts, runs.offsets, runs.n_runs, runs.status)
-        fitted = () if sized is None else (sized[0].bits, sized[0].offsets, sized[0].area, sized[0].box, sized[0].status)
-        truth = () if greq is None else (greq[0].bits, greq[0].offsets, greq[0].area)
-        over = () if held is None else (held.pairs, held.inter, held.area_a, held.area_b, held.status)
-        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)) + truth,
-                  tuple(t for t in (cls, score, m_out, e_out, logits, pred, iou) + compact + regions + pits + bands + edged + coded + fitted
-                        + over if t is not None))
-        return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
-                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
-                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
-                               sized=None if sized is None else sized[0], gt_overlaps=held)
+            post.finish()
+        self._end(tail, (inp, clip_image, clip_mask) + (() if idx_in is None else (idx_in,)) + post.inputs(),
+                  tuple(t for t in (cls, score, post.masks, post.edges, logits, pred, iou) if t is not None) + post.outputs())
+        return ClassHypotheses(classes=cls, pass1_logits=score, logits=logits, pred=pred, iou=iou, **post.fields())
 
     # ---- encode once, decode many times -------------------------------------------------------------------------
     def encode(self, inp, clip_image, clip_mask, vocab: Optional[Vocabulary] = None) -> EncodedImages:
@@ -3130,18 +2140,10 @@ class Cascade(_Base):
         vocab: the vocabulary to decode against, default the one `enc` was encoded with (enc.vocab).  Another one first re-scores pass 1
         from enc.pass1_features against it -- one head launch, no encoder launch, no CLIP forward --; the returned pass1_logits are
         the re-scored ones.
-        masks= / overlaps=: as in `infer_classes`, checked by `compact_request` with the rest; with stage2=False and
-        masks="bits" the chunk's planes are only packed.
-        components= / min_area= / connectivity=: as in `infer_classes`, checked by `components_request` with the rest.
-        holes= / fill_holes=: as in `infer_classes`, checked by `holes_request` with the rest.
-        band=: as in `infer_classes`, checked by `morph_request` with the rest.
-        edge_threshold=: as in `infer_classes`, checked by `edge_request` with the rest.
-        rle=: as in `infer_classes`, checked by `rle_request` with the rest; its one read synchronises the host with
-        the caller's stream.
-        sizes= / sized_level=: as in `infer_classes`, checked by `sized_request` with the rest; one (h, w) per decoded
-        row -- per entry of `images` --, and rle="sized" encodes the sized planes.
-        ground_truth=(gt, gt_image): as in `infer_classes`, checked by `ground_truth_request` with the rest; gt_image[q]
-        names a decoded row -- an entry of `images` --, not an image of `enc`."""
+        masks= .. ground_truth=: as in `infer_classes` (`MaskPost`, the same plan), checked with the rest.  With
+        stage2=False and masks="bits" the chunk's planes are only packed; rle='s one read synchronises the host with the caller's
+        stream; sizes= holds one (h, w) per decoded row -- per entry of `images` --, and gt_image[q] of ground_truth= names a decoded
+        row, not an image of `enc`."""
         if not isinstance(enc, EncodedImages):
             raise ValueError(f"decode: enc must come from Cascade.encode, got {type(enc).__name__}")
         if vocab is None:
@@ -3152,19 +2154,14 @@ class Cascade(_Base):
         n_cls, D = (int(v) for v in txt_bank.shape)
         images, K, host_classes = decode_request(same_engine=enc.engine is self, B=enc.B, n_cls=n_cls, D=D, classes=classes, topk=topk,
                                                  text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
-        want_logits, want_bits, want_inter = compact_request(masks=masks, overlaps=overlaps, n=len(images), K=K)
-        comp = components_request(components=components, min_area=min_area, connectivity=connectivity, masks=masks, side=self.g.inp_size)
-        hreq = holes_request(holes=holes, fill_holes=fill_holes, connectivity=connectivity, masks=masks, side=self.g.inp_size)
-        mreq = morph_request(band=band, masks=masks, overlaps=overlaps, side=self.g.inp_size)
-        ereq = edge_request(edge_threshold=edge_threshold, masks=masks, overlaps=overlaps, band=band, side=self.g.inp_size)
-        rsrc = rle_request(rle=rle, masks=masks, min_area=min_area, fill_holes=fill_holes, side=self.g.inp_size)
-        sreq = sized_request(sizes=sizes, sized_level=sized_level, n=len(images), masks=masks, rle=rle)
-        greq = ground_truth_request(ground_truth, sreq, len(images))
+        post = MaskPost(who="decode", n=len(images), K=K, side=self.g.inp_size, masks=masks, overlaps=overlaps, components=components,
+                        min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
+                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B
         n = len(images)
-        P, S, C = n * K, g.inp_size, g.prompt_embed_dim
+        P, C = n * K, g.prompt_embed_dim
         image_of = torch.tensor([i for i in images for _ in range(K)], dtype=torch.int32).to(dev)
         pass1 = enc.pass1_logits
         if vocab is not enc.vocab:                                   # another vocabulary: pass 1 re-scored from the kept features
@@ -3184,19 +2181,12 @@ class Cascade(_Base):
             idx_in = None if host_classes is None else host_classes.to(dev)
             self._select(score, n, n_cls, K, txt_bank, D, idx_in, cls, sel)
         txt = self._project_txt(sel, P)
-        m_out = torch.empty(n, K, S, S, device=dev) if want_logits else None
-        e_out = torch.empty(n, K, S, S, device=dev) if want_logits else None
+        post.allocate_planes(self)
         logits = torch.empty(n, K, n_cls, device=dev) if stage2 else None
         pred = torch.empty(n, K, dtype=torch.int64, device=dev) if stage2 else None
         iou = torch.empty(n, K, device=dev) if quality else None
-        compact = self._compact_outputs(n, K, want_bits, want_inter)
-        regions = self._component_outputs((n, K), S * S // 8, comp)
-        pits = self._hole_outputs((n, K), S * S // 8, hreq)
-        bands = self._band_outputs(n, K, S * S // 8, mreq)
-        edged = self._edge_outputs(n, K, S * S // 8, ereq)
-        mflat, eflat = (m_out.view(P, S, S), e_out.view(P, S, S)) if want_logits else (None, None)
         chunk = self.class_chunk()
-        sized = self._sized_outputs(sreq, K, -(-P // chunk))
+        post.allocate(chunk)
         for p0 in range(0, P, chunk):
             p1 = min(P, p0 + chunk)
             m = p1 - p0
@@ -3204,37 +2194,17 @@ class Cascade(_Base):
             sp = self.ws.f32("cls_sparse", m, 2, C)
             sp[:, 0].copy_(self._gather_blocks("dec_vis", enc.vis, of, m, B))
             sp[:, 1].copy_(txt[p0:p1])
-            planes, eplanes = self._chunk_planes(mflat, eflat, p0, p1)
+            planes, eplanes = post.chunk_planes(p0, p1)
             self._mask_logits((enc.state, of, B), sp, m, out=planes, edge_out=eplanes,
-                              iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not want_logits)
-            self._pack_chunk(planes, compact, p0, p1)
-            self._pack_sized_chunk(planes, sized, p0, p1, p0 // chunk)
-            if mreq[0]:
-                self._band(compact[0].view(P, -1)[p0:p1], S, S, mreq, bands, p0, p1)
-            if ereq[0]:
-                self._edge_bits(m, ereq, edged, bands, p0, p1)
-            if comp[0]:
-                self._components(compact[0].view(P, -1)[p0:p1], S, S, comp, regions, p0, p1)
-            if hreq[0]:
-                self._holes(compact[0].view(P, -1)[p0:p1], S, S, hreq, pits, p0, p1)
+                              iou_out=iou.view(P)[p0:p1] if quality else None, edge_low=not post.want_logits)
+            post.chunk(planes, p0, p1, p0 // chunk)
             if stage2:
                 self._class_stage2(planes, clip_image, n, K, p0, p1, logits.view(P, n_cls), pred.view(P), vocab, base=p0)
-        if want_inter:
-            hip.mask_overlap(compact[0], compact[3])
-        if mreq[2]:
-            hip.mask_overlap(bands[0], bands[2])
-        if ereq[3]:
-            hip.mask_overlap(edged[0], edged[3])
         if quality and cls is not None:
             iou.masked_fill_(cls < 0, float("nan"))
-        runs = self._rle_of(rsrc, {"mask_bits": compact[0], "kept_bits": regions[3], "filled_bits": pits[3], RLE_SIZED: sized}, S)
-        held = self._gt_overlaps(greq, sized, n, K)
+        post.finish()
         self._fold_guard_arm(torch.cuda.current_stream())
-        return ClassHypotheses(classes=cls, pass1_logits=score, masks=m_out, edges=e_out, logits=logits, pred=pred, iou=iou,
-                               mask_bits=compact[0], area=compact[1], box=compact[2], inter=compact[3],
-                               **dict(zip(("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box"), regions)),
-                               **dict(zip(HOLE_FIELDS, pits)), **dict(zip(BAND_FIELDS, bands)), **dict(zip(EDGE_FIELDS, edged)), rle=runs,
-                               sized=None if sized is None else sized[0], gt_overlaps=held)
+        return ClassHypotheses(classes=cls, pass1_logits=score, logits=logits, pred=pred, iou=iou, **post.fields())
 
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""
