@@ -5,12 +5,16 @@
 // Decoding is three launches per round of planes behind a memset: toggle the boundaries into the stream (one workgroup per plane),
 // prefix-XOR the stream (one workgroup per plane), transpose it into the rows.  All results are integers; no thread waits for another
 // workgroup.
+// COCO polygons (cvlm_mask_poly_decode) feed the same stream: the front walks a polygon's edges with the published
+// rleFrPoly's arithmetic (poly_logic.h) and toggles the boundary positions it finds; the prefix pass and the transposition are the
+// decoder's own, and a plane's further polygons are ORed in by one more launch.
 #include <algorithm>
 #include <vector>
 
 #include "../../include/cvlm.h"
 #include "common.h"
 #include "gt_logic.h"
+#include "poly_logic.h"
 
 namespace {
 
@@ -193,6 +197,29 @@ __global__ __launch_bounds__(256) void gd_transpose_kernel(const int* __restrict
     }
 }
 
+// The transposition on the host: the stream of a plane of h x w (NULL: a refused plane, zero words) -> its rows at dst, area and box
+// where they are asked for (initialised by the caller; an empty plane leaves them alone)
+void gd_rows_host(const uint32_t* stream, int64_t swords, int h, int w, uint32_t* dst, int32_t* area, int32_t* box) {
+    const int wsr = sz_words_per_row(w);
+    unsigned cnt = 0, x0 = 0xffffffffu, y0m = 0xffffffffu;
+    int x1 = -1, y1 = -1;
+    uint32_t v[32];
+    for (int c = 0; c < wsr; ++c)
+        for (int y0 = 0; y0 < h; y0 += 32) {
+            if (stream)
+                for (int i = 0; i < std::min(32, w - 32 * c); ++i) v[i] = gd_fetch(stream, swords, (32 * c + i) * h + y0);
+            for (int r = 0; r < std::min(32, h - y0); ++r) {
+                const uint32_t m = stream ? gd_row_word(v, 1, c, w, r) : 0u;
+                dst[sz_word_of(y0 + r, 32 * c, wsr)] = cc_pack(m);
+                if (m) gd_word_stats(m, c, y0 + r, cnt, x0, y0m, x1, y1);
+            }
+        }
+    if (area && cnt) {
+        area[0] = (int)cnt;
+        box[0] = (int)x0; box[1] = (int)y0m; box[2] = x1; box[3] = y1;
+    }
+}
+
 // what both decode entries refuse
 bool gd_bad(const int32_t* counts, int64_t total, const int64_t* run_offsets, const int32_t* dims, const int64_t* bit_offsets, int32_t P,
             int64_t max_pixels, const uint8_t* bits, int64_t nbytes, const int32_t* area, const int32_t* box, const int32_t* status) {
@@ -201,6 +228,182 @@ bool gd_bad(const int32_t* counts, int64_t total, const int64_t* run_offsets, co
         ((((uintptr_t)run_offsets) | ((uintptr_t)bit_offsets)) & 7) != 0)
         return true;
     return P < 1 || P > 65535 || total < 1 || nbytes < 4 || max_pixels < 1 || max_pixels > GT_MAX_PIXELS;
+}
+
+// ---- polygons ----------------------------------------------------------------------------------------------------------------
+// One polygon, xy[off, end), by the whole workgroup of GD_SCAN threads: every check first -- the slice, every coordinate, and the walk
+// points of all edges summed in 64 bits (at most 65535 edges of fewer than 2^20 points each) --, and only then the walk, in slabs of
+// GD_SCAN edges whose scaled vertices are staged in LDS: a wave per edge, round-robin, the lanes striding over the edge's points.
+// Each lane forms its point and the point before it -- for d = 0 the last point of the previous edge; the very first point of the
+// sequence has none -- and toggles the pair's boundary position, if it has one, by an integer XOR that commutes and cancels equal
+// positions.  -> false, the same for every thread: the polygon is refused and nothing was toggled.  s_sum / s_bad: GD_SCAN / 64
+// words of LDS each, s_x / s_y: GD_SCAN + 2 each, all free again on return.  s_span, where given: two words of LDS the caller has set
+// to (INT_MAX, -1); behind the caller's next barrier they hold the first and the last stream word the polygon toggled.
+__device__ bool gp_polygon(const double* __restrict__ xy, int64_t total, int64_t off, int64_t end, int h, int w, uint32_t* stream,
+                           long long* s_sum, int* s_bad, int* s_x, int* s_y, int* s_span) {
+    if (!pl_slice_ok(off, end, total)) return false;
+    const int k = (int)((end - off) >> 1);
+    const double* v = xy + off;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long pts = 0;
+    int bad = 0;
+    for (int j = threadIdx.x; j < k; j += GD_SCAN) {
+        const int jn = j + 1 < k ? j + 1 : 0;
+        const double x0 = v[2 * j], y0 = v[2 * j + 1], x1 = v[2 * jn], y1 = v[2 * jn + 1];
+        if (!pl_coord_ok(x0) || !pl_coord_ok(y0) || !pl_coord_ok(x1) || !pl_coord_ok(y1)) bad = 1;      // nothing of it becomes an int
+        else pts += pl_edge_of(pl_scale(x0), pl_scale(y0), pl_scale(x1), pl_scale(y1)).n;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pts += __shfl_xor(pts, o, 64);
+    const int wave_bad = __ballot(bad) != 0ull;
+    if (lane == 0) { s_sum[wave] = pts; s_bad[wave] = wave_bad; }
+    __syncthreads();
+    pts = 0;
+    bad = 0;
+#pragma unroll
+    for (int i = 0; i < GD_SCAN / 64; ++i) { pts += s_sum[i]; bad |= s_bad[i]; }
+    __syncthreads();                                                  // the LDS words may be written again
+    if (bad || pts > PL_MAX_POINTS) return false;
+    const int hw = h * w;
+    int lo = 0x7fffffff, hi = -1;                                     // the stream words this thread toggles
+    for (int j0 = 0; j0 < k; j0 += GD_SCAN) {                         // slabs of GD_SCAN edges, their scaled vertices staged in LDS
+        for (int i = threadIdx.x; i < GD_SCAN + 2; i += GD_SCAN) {    // slot i: vertex j0 - 1 + i; vertex k is vertex 0 again
+            const int j = j0 - 1 + i;
+            if (j >= 0 && j <= k) {
+                const int jj = j < k ? j : 0;
+                s_x[i] = pl_scale(v[2 * jj]);
+                s_y[i] = pl_scale(v[2 * jj + 1]);
+            }
+        }
+        __syncthreads();
+        const int m = min(GD_SCAN, k - j0);
+        for (int i = wave; i < m; i += GD_SCAN / 64) {
+            const pl_edge e = pl_edge_of(s_x[i + 1], s_y[i + 1], s_x[i + 2], s_y[i + 2]);
+            int lu = 0, lv = 0;                                       // the last point of the edge before this one
+            if (j0 + i > 0) {
+                const pl_edge b = pl_edge_of(s_x[i], s_y[i], s_x[i + 1], s_y[i + 1]);
+                pl_point(b, b.n - 1, lu, lv);
+            }
+            for (int d = lane; d < e.n; d += 64) {
+                int u, t, up = lu, tp = lv;
+                pl_point(e, d, u, t);
+                if (d > 0) pl_point(e, d - 1, up, tp);
+                else if (j0 + i == 0) continue;
+                int64_t pos;
+                int word;
+                uint32_t bit;
+                if (pl_candidate(up, tp, u, t, h, w, pos) && gd_toggle(pos, hw, word, bit)) {
+                    atomicXor(&stream[word], bit);
+                    lo = min(lo, word);
+                    hi = max(hi, word);
+                }
+            }
+        }
+        __syncthreads();                                              // the next slab stages into the same words
+    }
+    if (s_span) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
+        if (lane == 0 && hi >= 0) { atomicMin(&s_span[0], lo); atomicMax(&s_span[1], hi); }
+    }
+    return true;
+}
+
+// One workgroup per plane of the round, slot blockIdx.x of the zeroed accumulator streams: every check of the plane and of its list
+// of polygons, then its FIRST polygon into the stream.  layered: cvlm_mask_poly_decode runs gp_layers_kernel behind this one (Q > P);
+// without it a plane of several polygons is refused -- the call then holds a plane of none as well.  The verdict (slot word 0 = 1: whole
+// so far) is the last thing written; a refused plane ORs 1 into status and leaves the verdict 0.
+__global__ __launch_bounds__(GD_SCAN) void gp_toggle_kernel(const double* __restrict__ xy, int64_t total, const int64_t* __restrict__ poly_offsets,
+                                                            const int* __restrict__ plane_polys, int Q, const int* __restrict__ dims,
+                                                            const int64_t* __restrict__ bit_offsets, int64_t nbytes, int64_t max_pixels,
+                                                            int layered, int p0, uint32_t* __restrict__ ws, int64_t ws_stride,
+                                                            int* __restrict__ status) {
+    __shared__ long long s_sum[GD_SCAN / 64];
+    __shared__ int s_bad[GD_SCAN / 64], s_x[GD_SCAN + 2], s_y[GD_SCAN + 2];
+    const int p = p0 + blockIdx.x;
+    uint32_t* slot = ws + (int64_t)blockIdx.x * ws_stride;
+    const int h = dims[2 * p], w = dims[2 * p + 1];
+    const int q0 = plane_polys[p], q1 = plane_polys[p + 1];
+    bool good = gd_shape_ok(h, w, max_pixels) && sz_plane_ok(h, w, bit_offsets[p], bit_offsets[p + 1], nbytes) && pl_polys_ok(q0, q1, Q) &&
+                (layered || q1 - q0 == 1);
+    good = good && gp_polygon(xy, total, poly_offsets[q0], poly_offsets[q0 + 1], h, w, slot + GT_WS_HEAD, s_sum, s_bad, s_x, s_y, nullptr);
+    if (threadIdx.x == 0) {                                           // good is the same for every thread
+        if (good) slot[0] = 1u;
+        else atomicOr(status, 1);
+    }
+}
+
+// One workgroup per plane of the round, behind gp_toggle_kernel and gd_prefix_kernel: the plane's polygons 1, 2, ... one after the other.
+// Each is toggled into the plane's second stream `cur` (zero on entry), whose prefix XOR -- gd_prefix_kernel's pass -- is ORed into the
+// accumulator word by word while cur is cleared again: acc |= cur, cur = 0, the union.  cur is toggled by atomics, which the L2 runs;
+// so it is read back by loads of device scope, behind a device-wide fence and the barrier.  The pass starts at the slab of the first
+// word the polygon toggled and ends behind the last one as soon as the parity carried on is even: every word outside is zero in cur
+// and stays zero under the prefix XOR.  A refused polygon refuses the plane: the verdict goes back to 0 and status gets its 1.  A
+// plane of one polygon, or one already refused, leaves at once.
+__global__ __launch_bounds__(GD_SCAN) void gp_layers_kernel(const double* __restrict__ xy, int64_t total, const int64_t* __restrict__ poly_offsets,
+                                                            const int* __restrict__ plane_polys, const int* __restrict__ dims, int p0,
+                                                            uint32_t* __restrict__ ws, uint32_t* __restrict__ cur_ws, int64_t ws_stride,
+                                                            int* __restrict__ status) {
+    __shared__ long long s_sum[GD_SCAN / 64];
+    __shared__ int s_bad[GD_SCAN / 64], s_x[GD_SCAN + 2], s_y[GD_SCAN + 2], s_span[2];
+    __shared__ uint32_t s_par[2][GD_SCAN / 64];
+    uint32_t* slot = ws + (int64_t)blockIdx.x * ws_stride;
+    if (slot[0] == 0u) return;                                        // the whole workgroup; verdict 1: size and list passed their checks
+    const int p = p0 + blockIdx.x;
+    const int q0 = plane_polys[p], q1 = plane_polys[p + 1];
+    if (q1 - q0 < 2) return;
+    const int h = dims[2 * p], w = dims[2 * p + 1];
+    const int words = (int)gd_stream_words((int64_t)h * w);
+    uint32_t* acc = slot + GT_WS_HEAD;
+    uint32_t* cur = cur_ws + (int64_t)blockIdx.x * ws_stride + GT_WS_HEAD;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = q0 + 1; q < q1; ++q) {
+        if (threadIdx.x == 0) { s_span[0] = 0x7fffffff; s_span[1] = -1; }      // gp_polygon's barriers lie between this and its walk
+        if (!gp_polygon(xy, total, poly_offsets[q], poly_offsets[q + 1], h, w, cur, s_sum, s_bad, s_x, s_y, s_span)) {
+            if (threadIdx.x == 0) { slot[0] = 0u; atomicOr(status, 1); }
+            return;                                                   // the same for every thread
+        }
+        __threadfence();
+        __syncthreads();                                              // every toggle of the polygon has reached the L2
+        const int first = s_span[0], last = s_span[1];                // last < 0: the polygon toggled nothing
+        uint32_t carry = 0u;
+        for (int k0 = last < 0 ? words : first / GD_SCAN * GD_SCAN, slab = 0; k0 < words; k0 += GD_SCAN, slab ^= 1) {
+            const int k = k0 + threadIdx.x;
+            const uint32_t c = k < words ? __hip_atomic_load(&cur[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            const unsigned long long odd = __ballot(__popc(c) & 1);
+            const uint32_t below = (uint32_t)__popcll(odd & ((1ull << lane) - 1ull)) & 1u;
+            if (lane == 0) s_par[slab][wave] = (uint32_t)__popcll(odd) & 1u;
+            __syncthreads();
+            uint32_t before = carry, all = carry;
+#pragma unroll
+            for (int i = 0; i < GD_SCAN / 64; ++i) {
+                const uint32_t a = s_par[slab][i];
+                if (i < wave) before ^= a;
+                all ^= a;
+            }
+            if (k < words) {
+                const uint32_t m = gd_prefix_word(c, before ^ below);
+                if (m) acc[k] |= m;                                   // word k is this thread's in every layer
+                if (c) cur[k] = 0u;
+            }
+            carry = all;
+            if (k0 + GD_SCAN > last && !(carry & 1u)) break;          // the same for every thread: nothing but zeros from here on
+        }
+        __threadfence();
+        __syncthreads();                                              // cur is clear, s_span read, before the next polygon
+    }
+}
+
+// what both polygon entries refuse
+bool gp_bad(const double* xy, int64_t total, const int64_t* poly_offsets, const int32_t* plane_polys, const int32_t* dims,
+            const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, const uint8_t* bits, int64_t nbytes, const int32_t* area,
+            const int32_t* box, const int32_t* status) {
+    if (!xy || !poly_offsets || !plane_polys || !dims || !bit_offsets || !bits || !status || (area == nullptr) != (box == nullptr)) return true;
+    if (((((uintptr_t)plane_polys) | ((uintptr_t)dims) | ((uintptr_t)bits) | ((uintptr_t)area) | ((uintptr_t)box) | ((uintptr_t)status)) & 3) != 0 ||
+        ((((uintptr_t)xy) | ((uintptr_t)poly_offsets) | ((uintptr_t)bit_offsets)) & 7) != 0)
+        return true;
+    if (P < 1 || P > 65535 || Q < 1 || (int64_t)Q > (int64_t)P * PL_MAX_POLYS) return true;
+    return total < 1 || nbytes < 4 || max_pixels < 1 || max_pixels > GT_MAX_PIXELS;
 }
 
 // ---- intersections ------------------------------------------------------------------------------------------------------------------------
@@ -345,25 +548,120 @@ int cvlm_debug_mask_rle_decode_host(const int32_t* counts, int64_t total, const 
         }
         if (!good) status[0] |= 1;
         if (!table) continue;                                         // nothing of its slice is stored
-        const int wsr = sz_words_per_row(w);
-        uint32_t* dst = (uint32_t*)(bits + boff);
-        unsigned cnt = 0, x0 = 0xffffffffu, y0m = 0xffffffffu;
-        int x1 = -1, y1 = -1;
-        uint32_t v[32];
-        for (int c = 0; c < wsr; ++c)
-            for (int y0 = 0; y0 < h; y0 += 32) {
-                if (good)
-                    for (int i = 0; i < std::min(32, w - 32 * c); ++i) v[i] = gd_fetch(stream.data(), (int64_t)stream.size(), (32 * c + i) * h + y0);
-                for (int r = 0; r < std::min(32, h - y0); ++r) {
-                    const uint32_t m = good ? gd_row_word(v, 1, c, w, r) : 0u;
-                    dst[sz_word_of(y0 + r, 32 * c, wsr)] = cc_pack(m);
-                    if (m) gd_word_stats(m, c, y0 + r, cnt, x0, y0m, x1, y1);
+        gd_rows_host(good ? stream.data() : nullptr, (int64_t)stream.size(), h, w, (uint32_t*)(bits + boff), area ? area + p : nullptr,
+                     box ? box + 4 * p : nullptr);
+    }
+    return 0;
+}
+
+int64_t cvlm_mask_poly_decode_workspace_bytes(int32_t P, int64_t max_pixels) {
+    if (P < 1 || P > 65535 || max_pixels < 1 || max_pixels > GT_MAX_PIXELS) return CVLM_E_BADARG;
+    return (int64_t)P * 2 * gd_plane_ws_bytes(max_pixels);
+}
+
+int cvlm_mask_poly_decode(const double* xy, int64_t total, const int64_t* poly_offsets, const int32_t* plane_polys, const int32_t* dims,
+                          const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, uint8_t* bits, int64_t bits_bytes,
+                          int32_t* area, int32_t* box, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (gp_bad(xy, total, poly_offsets, plane_polys, dims, bit_offsets, P, Q, max_pixels, bits, bits_bytes, area, box, status)) return CVLM_E_BADARG;
+    const int64_t plane_bytes = gd_plane_ws_bytes(max_pixels);
+    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < 2 * plane_bytes) return CVLM_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int fit = (int)std::min<int64_t>(P, workspace_bytes / (2 * plane_bytes));       // planes per round
+    const int64_t ws_stride = plane_bytes / 4;
+    uint32_t* ws = (uint32_t*)workspace;                                                 // the round's accumulators, then its second streams
+    uint32_t* cur = ws + (int64_t)fit * ws_stride;
+    const int layered = Q > P;                                                           // some plane has several polygons
+    hipLaunchKernelGGL(gd_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)area, (int*)box, (int)P, (int*)status);
+    CVLM_CHECK_LAUNCH();
+    for (int p0 = 0; p0 < P; p0 += fit) {
+        const int n = std::min(fit, P - p0);
+        const hipError_t e = hipMemsetAsync(ws, 0, (size_t)(layered ? fit + n : n) * plane_bytes, st);   // verdicts 0, streams clear
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(gp_toggle_kernel, dim3(n), dim3(GD_SCAN), 0, st, xy, total, poly_offsets, (const int*)plane_polys, (int)Q,
+                           (const int*)dims, bit_offsets, bits_bytes, max_pixels, layered, p0, ws, ws_stride, (int*)status);
+        CVLM_CHECK_LAUNCH();
+        hipLaunchKernelGGL(gd_prefix_kernel, dim3(n), dim3(GD_SCAN), 0, st, (const int*)dims, p0, ws, ws_stride);
+        CVLM_CHECK_LAUNCH();
+        if (layered) {
+            hipLaunchKernelGGL(gp_layers_kernel, dim3(n), dim3(GD_SCAN), 0, st, xy, total, poly_offsets, (const int*)plane_polys,
+                               (const int*)dims, p0, ws, cur, ws_stride, (int*)status);
+            CVLM_CHECK_LAUNCH();
+        }
+        const int64_t by_work = (max_pixels + 16383) / 16384, want = (8192 + n - 1) / n;   // cvlm_mask_rle_decode's grid
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_work, want), 256));
+        if (area)
+            hipLaunchKernelGGL(gd_transpose_kernel<true>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
+                               (const uint32_t*)ws, ws_stride, (int*)area, (int*)box);
+        else
+            hipLaunchKernelGGL(gd_transpose_kernel<false>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
+                               (const uint32_t*)ws, ws_stride, (int*)nullptr, (int*)nullptr);
+        CVLM_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// The same functions on host memory, plane by plane and polygon by polygon, through poly_logic.h and gt_logic.h
+int cvlm_debug_mask_poly_decode_host(const double* xy, int64_t total, const int64_t* poly_offsets, const int32_t* plane_polys,
+                                     const int32_t* dims, const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, uint8_t* bits,
+                                     int64_t bits_bytes, int32_t* area, int32_t* box, int32_t* status) {
+    if (gp_bad(xy, total, poly_offsets, plane_polys, dims, bit_offsets, P, Q, max_pixels, bits, bits_bytes, area, box, status)) return CVLM_E_BADARG;
+    status[0] = 0;
+    std::vector<uint32_t> acc, cur;
+    for (int p = 0; p < P; ++p) {
+        if (area) {
+            area[p] = 0;
+            for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
+        }
+        const int h = dims[2 * p], w = dims[2 * p + 1];
+        const int q0 = plane_polys[p], q1 = plane_polys[p + 1];
+        const int64_t boff = bit_offsets[p];
+        const bool table = sz_plane_ok(h, w, boff, bit_offsets[p + 1], bits_bytes);
+        bool good = table && gd_shape_ok(h, w, max_pixels) && pl_polys_ok(q0, q1, Q) && (Q > P || q1 - q0 == 1);
+        if (good) {
+            const int hw = h * w;
+            const int64_t swords = gd_stream_words(hw);
+            acc.assign((size_t)swords, 0u);
+            for (int q = q0; q < q1 && good; ++q) {
+                const int64_t off = poly_offsets[q], end = poly_offsets[q + 1];
+                if (!pl_slice_ok(off, end, total)) { good = false; break; }
+                const int k = (int)((end - off) >> 1);
+                const double* v = xy + off;
+                int64_t pts = 0;
+                for (int j = 0; j < k && good; ++j) {
+                    const int jn = j + 1 < k ? j + 1 : 0;
+                    if (!pl_coord_ok(v[2 * j]) || !pl_coord_ok(v[2 * j + 1])) good = false;
+                    else if (pl_coord_ok(v[2 * jn]) && pl_coord_ok(v[2 * jn + 1]))
+                        pts += pl_edge_of(pl_scale(v[2 * j]), pl_scale(v[2 * j + 1]), pl_scale(v[2 * jn]), pl_scale(v[2 * jn + 1])).n;
+                }
+                if (!good || pts > PL_MAX_POINTS) { good = false; break; }
+                cur.assign((size_t)swords, 0u);
+                int up = 0, vp = 0;
+                bool first = true;
+                for (int j = 0; j < k; ++j) {
+                    const int jn = j + 1 < k ? j + 1 : 0;
+                    const pl_edge e = pl_edge_of(pl_scale(v[2 * j]), pl_scale(v[2 * j + 1]), pl_scale(v[2 * jn]), pl_scale(v[2 * jn + 1]));
+                    for (int d = 0; d < e.n; ++d) {
+                        int u, t, word;
+                        uint32_t bit;
+                        int64_t pos;
+                        pl_point(e, d, u, t);
+                        if (!first && pl_candidate(up, vp, u, t, h, w, pos) && gd_toggle(pos, hw, word, bit)) cur[(size_t)word] ^= bit;
+                        up = u; vp = t;
+                        first = false;
+                    }
+                }
+                uint32_t before = 0u;
+                for (int64_t i = 0; i < swords; ++i) {
+                    const uint32_t c = cur[(size_t)i];
+                    acc[(size_t)i] |= gd_prefix_word(c, before);
+                    before ^= (uint32_t)__builtin_popcount(c) & 1u;
                 }
             }
-        if (area && cnt) {
-            area[p] = (int)cnt;
-            box[4 * p + 0] = (int)x0; box[4 * p + 1] = (int)y0m; box[4 * p + 2] = x1; box[4 * p + 3] = y1;
         }
+        if (!good) status[0] |= 1;
+        if (!table) continue;                                         // nothing of its slice is stored
+        gd_rows_host(good ? acc.data() : nullptr, (int64_t)acc.size(), h, w, (uint32_t*)(bits + boff), area ? area + p : nullptr,
+                     box ? box + 4 * p : nullptr);
     }
     return 0;
 }

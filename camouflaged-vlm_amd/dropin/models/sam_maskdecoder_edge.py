@@ -203,6 +203,13 @@ class SAM(nn.Module):
         engine.MaskRle on the device -- as packed masks at each annotation's own size -> engine.SizedMasks (engine.Cascade.rle_decode)."""
         return self.cascade().rle_decode(rles, stats=stats)
 
+    def polygons_decode(self, anns, *, stats=True):
+        """EXTENSION, not a reference method: COCO polygon annotations -- a list of {"size": [h, w], "polygons": [[x0, y0, ...], ...]},
+        the list of polygons the reference's GenericMask takes (models/utils/visualizer.py:72-101) -- rasterised as pycocotools'
+        frPyObjects + merge + decode do, as packed masks at each annotation's own size -> engine.SizedMasks
+        (engine.Cascade.polygons_decode)."""
+        return self.cascade().polygons_decode(anns, stats=stats)
+
     def mask_inter_sized(self, a, b, *, pairs=None, a_image=None, b_image=None):
         """EXTENSION, not a reference method: intersections of pairs of planes of two engine.SizedMasks, detections against annotations
         -> engine.SizedOverlaps, whose `iou(iscrowd)` is pycocotools' rleIou (engine.Cascade.mask_inter_sized)."""

@@ -82,6 +82,9 @@ _SIGNATURES = {
     "cvlm_mask_rle_decode_workspace_bytes": "l:il",
     "cvlm_mask_rle_decode": "i:plpppilplppppls",
     "cvlm_debug_mask_rle_decode_host": "i:plpppilplppp",
+    "cvlm_mask_poly_decode_workspace_bytes": "l:il",
+    "cvlm_mask_poly_decode": "i:plppppiilplppppls",
+    "cvlm_debug_mask_poly_decode_host": "i:plppppiilplppp",
     "cvlm_mask_inter_sized": "i:plppiplppipilpps",
     "cvlm_debug_mask_inter_sized_host": "i:plppiplppipilpp",
     "cvlm_mask_wfm": "i:ppiiipppps",
@@ -1118,6 +1121,62 @@ def mask_rle_decode_host(counts: torch.Tensor, run_offsets: torch.Tensor, dims: 
     assert not counts.is_cuda
     _call("cvlm_debug_mask_rle_decode_host", counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(),
           bit_offsets.data_ptr(), P, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr())
+
+
+def mask_poly_decode_workspace_bytes(P: int, max_pixels: int) -> int:
+    """Bytes cvlm_mask_poly_decode wants to keep all P planes of at most max_pixels pixels in flight (two streams of 16 bytes + one bit
+    per pixel per plane); P = 1: the minimum it takes."""
+    n = load().cvlm_mask_poly_decode_workspace_bytes(P, max_pixels)
+    if n < 0:
+        raise RuntimeError(f"cvlm_mask_poly_decode_workspace_bytes({P}, {max_pixels}): sizes outside the entry's bounds")
+    return n
+
+
+def _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status) -> Tuple[int, int]:
+    """Shape and dtype checks shared by `mask_poly_decode` and `mask_poly_decode_host` -> (P, Q)."""
+    P, Q = int(dims.shape[0]), int(poly_offsets.shape[0]) - 1
+    assert xy.dtype == torch.float64 and xy.dim() == 1 and xy.is_contiguous() and xy.numel() >= 1
+    assert poly_offsets.dtype == torch.int64 and poly_offsets.dim() == 1 and Q >= 1 and poly_offsets.is_contiguous()
+    assert plane_polys.dtype == torch.int32 and tuple(plane_polys.shape) == (P + 1,) and plane_polys.is_contiguous()
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (P + 1,) and bit_offsets.is_contiguous()
+    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous() and (area is None) == (box is None)
+    if area is not None:
+        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
+        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == xy.device for t in (poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status))
+    return P, Q
+
+
+def mask_poly_decode(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_polys: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor,
+                     max_pixels: int, bits: torch.Tensor, area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor,
+                     workspace: torch.Tensor) -> None:
+    """COCO polygons -> sized planes (include/cvlm.h: cvlm_mask_poly_decode): polygon q is xy[poly_offsets[q] : poly_offsets[q + 1]]
+    (float64 [total] = x0, y0, x1, y1, ...; int64 [Q + 1] in doubles), plane p the union of the polygons plane_polys[p] ..
+    plane_polys[p + 1] - 1 (int32 [P + 1]) at the size dims[p] = (h, w), written like `mask_rle_decode`'s planes; area int32 [P] and box
+    int32 [P][4] together or not at all.  status int32 [1] becomes 1 if a plane was refused -- a coordinate that is no finite number or
+    beyond 65536, a polygon of fewer than 3 vertices or more than 2^24 walk points, a list, a slice or a table that does not fit; such a
+    plane is zero where its table holds and untouched where it does not --, otherwise 0.  max_pixels: the largest h * w of the call.
+    workspace: uint8, at least mask_poly_decode_workspace_bytes(1, max_pixels) bytes; fewer than P planes' worth makes the entry walk
+    the planes in rounds."""
+    P, Q = _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == xy.device
+    _on_current_device(xy)
+    _call("cvlm_mask_poly_decode", xy.data_ptr(), xy.numel(), poly_offsets.data_ptr(), plane_polys.data_ptr(), dims.data_ptr(),
+          bit_offsets.data_ptr(), P, Q, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(),
+          workspace.data_ptr(), workspace.numel())
+
+
+def mask_poly_decode_host(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_polys: torch.Tensor, dims: torch.Tensor,
+                          bit_offsets: torch.Tensor, max_pixels: int, bits: torch.Tensor, area: Optional[torch.Tensor],
+                          box: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """`mask_poly_decode` on HOST tensors without a device (cvlm_debug_mask_poly_decode_host: the kernels' per-thread functions run
+    sequentially on the CPU)."""
+    P, Q = _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status)
+    assert not xy.is_cuda
+    _call("cvlm_debug_mask_poly_decode_host", xy.data_ptr(), xy.numel(), poly_offsets.data_ptr(), plane_polys.data_ptr(), dims.data_ptr(),
+          bit_offsets.data_ptr(), P, Q, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr())
 
 
 def _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status) -> Tuple[int, int, int]:

@@ -305,6 +305,7 @@ class SizedMasks:
     status: torch.Tensor            # int32 on the device, one word per cvlm_mask_pack_sized call: non-zero if a plane was refused
     sizes: list                     # P (h, w) pairs, on the host
     level: int = 128                # 0: not a threshold -- the planes were decoded from run counts (Cascade.rle_decode)
+    #                                 or rasterised from polygons (Cascade.polygons_decode, §21)
 
     def byte_range(self, p: int) -> Tuple[int, int]:
         """Where plane p lies in `bits`, from the sizes alone (the planes lie back to back): no read of the device."""
@@ -327,9 +328,36 @@ class SizedMasks:
         says that the library is broken."""
         if bool(self.status.ne(0).any().item()):
             if self.level == 0:
-                raise RuntimeError("rle_decode: cvlm_mask_rle_decode refused a plane: counts that are negative or do not sum to h * w, "
-                                   "or a slice that does not fit")
+                raise RuntimeError("rle_decode / polygons_decode: cvlm_mask_rle_decode or cvlm_mask_poly_decode refused a plane: counts that "
+                                   "are negative or do not sum to h * w, a polygon outside the bounds, or a slice that does not fit")
             raise RuntimeError("pack_masks_sized: cvlm_mask_pack_sized refused a plane whose slice did not fit its size")
+
+    @staticmethod
+    def concat(parts) -> "SizedMasks":
+        """The planes of several SizedMasks of one device as one, in the order of `parts`, on the device and without a synchronisation:
+        `torch.cat` of bits, areas and boxes, each part's offsets shifted by the bytes before it, the sizes appended, the status words
+        ORed into one.  What it is for: `polygons_decode` of an image set's iscrowd = 0 annotations and `rle_decode` of its crowd regions
+        as ONE ground_truth= -- the image ids given with it carry the association, so the order is free.  Parts with
+        and without area / box do not mix (ValueError); the level is kept where all parts share it and is 0 otherwise."""
+        if isinstance(parts, SizedMasks) or not hasattr(parts, "__len__") or len(parts) < 1 or not all(isinstance(s, SizedMasks) for s in parts):
+            raise ValueError("SizedMasks.concat: a non-empty sequence of SizedMasks")
+        parts = list(parts)
+        if len({s.area is None for s in parts}) != 1 or any((s.area is None) != (s.box is None) for s in parts):
+            raise ValueError("SizedMasks.concat: parts with and without area / box do not mix")
+        if len({s.bits.device for s in parts}) != 1:
+            raise ValueError("SizedMasks.concat: the parts live on different devices")
+        sizes = [tuple(z) for s in parts for z in s.sizes]
+        starts = np.cumsum([0] + [sized_tables(s.sizes)[1][-1] for s in parts[:-1]])      # from the sizes alone: no read of the device
+        offsets = torch.cat([parts[0].offsets] + [s.offsets[1:] + int(b) for s, b in zip(parts[1:], starts[1:])])
+        stats = parts[0].area is not None
+        status = parts[0].status.reshape(-1).ne(0).any().to(torch.int32).reshape(1)
+        for s in parts[1:]:
+            status = status | s.status.reshape(-1).ne(0).any().to(torch.int32).reshape(1)
+        levels = {s.level for s in parts}
+        return SizedMasks(bits=torch.cat([s.bits for s in parts]), offsets=offsets,
+                          area=torch.cat([s.area for s in parts]) if stats else None,
+                          box=torch.cat([s.box for s in parts]) if stats else None, status=status, sizes=sizes,
+                          level=levels.pop() if len(levels) == 1 else 0)
 
 
 def rle_decode_request(rles, who: str = "rle_decode"):
@@ -372,6 +400,65 @@ def rle_decode_request(rles, who: str = "rle_decode"):
     offsets = np.zeros(len(parts) + 1, dtype=np.int64)
     np.cumsum([p.size for p in parts], out=offsets[1:])
     return np.concatenate(parts), offsets, sizes
+
+
+POLY_MAX_COORD = 65536.0          # |c| of a polygon's coordinates (csrc/poly_logic.h)
+POLY_MAX_VERTS = 65535            # vertices of a polygon, 3 at least
+POLY_MAX_POINTS = 1 << 24         # walk points of a polygon
+POLY_MAX_POLYS = 4096             # polygons of a plane
+
+
+def polygons_request(anns, who: str = "polygons_decode"):
+    """Every check of a list of COCO polygon annotations {"size": [h, w], "polygons": [[x0, y0, x1, y1, ...], ...]} --
+    `polygons` is what an iscrowd = 0 annotation's `segmentation` holds --, on the host, before anything is launched (ValueError) ->
+    (xy float64 (total,), polygon offsets int64 (Q + 1,) in doubles of xy, plane_polys int32 (P + 1,), the P (h, w) pairs).  1 ..
+    65535 planes; h and w ints in [1, 16384]; 1 .. 4096 polygons per plane; a polygon is a flat sequence of an even number of real
+    numbers, 3 .. 65535 vertices, finite, |c| <= 65536, and walks at most 2^24 points -- counted here as the kernel counts them, in
+    numpy over the polygon's vertices."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if isinstance(anns, (str, bytes, dict)) or not hasattr(anns, "__len__") or not hasattr(anns, "__iter__"):
+        raise ValueError(f"{who}: anns must be a sequence of dicts with 'size' and 'polygons', got {type(anns).__name__}")
+    if not 1 <= len(anns) <= 65535:
+        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(anns)}")
+    sizes, parts, per_plane = [], [], []
+    for i, d in enumerate(anns):
+        if not isinstance(d, dict) or "size" not in d or "polygons" not in d:
+            raise ValueError(f"{who}: entry {i} must be a dict with 'size' and 'polygons'")
+        size = d["size"]
+        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
+            raise ValueError(f"{who}: entry {i}: size must be [h, w], got {size!r}")
+        h, w = size
+        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+            raise ValueError(f"{who}: entry {i}: size must be two ints in [1, {SIZED_MAX_SIDE}], got {size!r}")
+        polys = d["polygons"]
+        if isinstance(polys, (str, bytes, dict)) or not hasattr(polys, "__len__") or not 1 <= len(polys) <= POLY_MAX_POLYS:
+            raise ValueError(f"{who}: entry {i}: polygons must be a list of 1 .. {POLY_MAX_POLYS} polygons")
+        for j, poly in enumerate(polys):
+            if isinstance(poly, (str, bytes, dict)) or not hasattr(poly, "__len__"):
+                raise ValueError(f"{who}: entry {i}, polygon {j}: a flat sequence of numbers, got {type(poly).__name__}")
+            try:
+                a = np.asarray(poly)
+            except Exception as e:
+                raise ValueError(f"{who}: entry {i}, polygon {j}: a flat sequence of numbers") from e
+            if a.ndim != 1 or a.dtype.kind not in "iuf" or (not isinstance(poly, np.ndarray) and any(isinstance(v, (bool, np.bool_)) for v in poly)):
+                raise ValueError(f"{who}: entry {i}, polygon {j}: a flat sequence of real numbers")
+            if a.size % 2 or not 6 <= a.size <= 2 * POLY_MAX_VERTS:
+                raise ValueError(f"{who}: entry {i}, polygon {j}: {a.size} numbers are no 3 .. {POLY_MAX_VERTS} vertices (x, y)")
+            a = a.astype(np.float64)
+            if not bool(np.isfinite(a).all()) or float(np.abs(a).max()) > POLY_MAX_COORD:
+                raise ValueError(f"{who}: entry {i}, polygon {j}: coordinates must be finite and within +-{POLY_MAX_COORD:.0f}")
+            v = (5.0 * a + 0.5).astype(np.int64).reshape(-1, 2)       # csrc/poly_logic.h: pl_scale; astype truncates toward zero
+            step = np.abs(np.roll(v, -1, axis=0) - v).max(axis=1) + 1   # pl_edge_of's n, the closing edge included
+            if int(step.sum()) > POLY_MAX_POINTS:
+                raise ValueError(f"{who}: entry {i}, polygon {j}: {int(step.sum())} walk points, at most {POLY_MAX_POINTS} are taken")
+            parts.append(a)
+        sizes.append((int(h), int(w)))
+        per_plane.append(len(polys))
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    np.cumsum([p.size for p in parts], out=offsets[1:])
+    plane_polys = np.zeros(len(sizes) + 1, dtype=np.int32)
+    np.cumsum(per_plane, out=plane_polys[1:])
+    return np.concatenate(parts), offsets, plane_polys, sizes
 
 
 def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, who: str = "mask_inter_sized"):
@@ -777,6 +864,31 @@ class MaskUtilities:
         ws = self.ws.scratch("cls_rle", min(P * one, max(RLE_WS_CAP, one)))
         hip.mask_rle_decode(counts, run_offsets, torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box,
                             out.status, ws)
+        return out
+
+    # ---- COCO polygon annotations on the device -------------------------------------------------------------------------
+    def polygons_decode(self, anns, *, stats: bool = True) -> "SizedMasks":
+        """COCO polygon annotations -> SizedMasks on this engine's device (cvlm_mask_poly_decode): what pycocotools'
+        frPyObjects + merge + decode give for an iscrowd = 0 annotation, bit for bit, as ground truth in the format of the predictions
+        -- `mask_inter_sized`, `mask_rle_sized` and ground_truth= of infer_classes / decode take it as it is; `SizedMasks.concat` joins it
+        with `rle_decode`'s crowd regions.  anns: a list of {"size": [h, w], "polygons": [[x0, y0, x1, y1, ...], ...]}, one plane per
+        entry, the union of its polygons; checked by `polygons_request` on the host before anything is launched (ValueError) and
+        uploaded once per table.  stats=False: no `area` and no `box`.  The result has level 0: not a threshold; `check()` reports a
+        plane the kernel refused.  The workspace is the grow-only "cls_rle", capped at RLE_WS_CAP (beyond it the entry walks the
+        planes in rounds).  Launches on the caller's stream, without a synchronisation."""
+        dev = self.device
+        xy, po, pp, sizes = polygons_request(anns)
+        P = len(sizes)
+        dims, offsets, _ = sized_tables(sizes)
+        max_pixels = max(h * w for h, w in sizes)
+        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
+                         area=torch.empty(P, dtype=torch.int32, device=dev) if stats else None,
+                         box=torch.empty(P, 4, dtype=torch.int32, device=dev) if stats else None,
+                         status=torch.empty(1, dtype=torch.int32, device=dev), sizes=sizes, level=0)
+        one = hip.mask_poly_decode_workspace_bytes(1, max_pixels)
+        ws = self.ws.scratch("cls_rle", min(P * one, max(RLE_WS_CAP, one)))
+        hip.mask_poly_decode(torch.from_numpy(xy).to(dev), torch.from_numpy(po).to(dev), torch.from_numpy(pp).to(dev),
+                             torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box, out.status, ws)
         return out
 
     def mask_inter_sized(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, a_image=None, b_image=None) -> "SizedOverlaps":

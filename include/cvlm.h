@@ -771,6 +771,44 @@ int cvlm_mask_rle_decode(const int32_t* counts, int64_t total, const int64_t* ru
 int cvlm_debug_mask_rle_decode_host(const int32_t* counts, int64_t total, const int64_t* run_offsets, const int32_t* dims,
                                     const int64_t* bit_offsets, int32_t P, int64_t max_pixels, uint8_t* bits, int64_t bits_bytes,
                                     int32_t* area, int32_t* box, int32_t* status);
+/* COCO polygon annotations on the device: what `segmentation` holds for every iscrowd = 0 annotation.
+ * cvlm_mask_poly_decode: xy double [total], the polygons' coordinates (x0, y0, x1, y1, ...) back to back; poly_offsets int64 [Q + 1] in
+ * DOUBLES of xy: polygon q is xy[poly_offsets[q], poly_offsets[q + 1]); plane_polys int32 [P + 1]: plane p is the UNION of the polygons
+ * [plane_polys[p], plane_polys[p + 1]); dims, bit_offsets, bits, area, box, status as cvlm_mask_rle_decode's; all device memory.  Plane p
+ * comes out as a sized plane, bit for bit what the published maskApi.c gives by rleFrPoly per polygon, rleMerge (union) and rleDecode:
+ * the vertices scaled by 5 and rounded, (int)(5.0 * c + 0.5); every edge walked along its longer axis, max(dx, dy) + 1 points, the
+ * minor coordinate (int)(start + s * t + 0.5) with s the slope as one double quotient -- every product, sum and quotient one IEEE double
+ * operation rounded on its own, never fused --; an edge of no length is its one point; every consecutive pair of points of the whole
+ * sequence whose column u changes gives, where (min(u, u') or u - 1, + 0.5) / 5 - 0.5 is an integer x in [0, w - 1], the boundary
+ * position x h + ceil(clamp((min(v, v') + 0.5) / 5 - 0.5, 0, h)) of cvlm_mask_rle_decode's stream; pixel j = x h + y is set iff an odd
+ * number of the polygon's positions lie at or before it.
+ * A plane is REFUSED whole -- zero bits, area 0, box -1, status[0] |= 1; the call zeroes status first -- if its list of polygons is
+ * empty, holds more than 4096 or leaves [0, Q); if a polygon's slice runs backwards, leaves [0, total), holds an odd number of doubles
+ * or fewer than 3 or more than 65535 vertices; if a coordinate is no finite number or |c| > 65536; if a polygon has more than 2^24 walk
+ * points (summed in 64 bits before any is walked); if h * w exceeds max_pixels; or if its bit table fails cvlm_mask_pack_sized's
+ * check: then nothing of its slice is stored.  Every check comes before the loads and stores it guards.
+ * Per round of planes a memset of the round's workspace and three or four launches: (1) one workgroup per plane checks the plane and
+ * walks its FIRST polygon, a wave per edge, toggling the boundary positions by integer XORs; (2) cvlm_mask_rle_decode's prefix XOR;
+ * (3) only when Q > P: one workgroup per plane takes the plane's further polygons one by one -- toggle into a second stream, prefix
+ * XOR, OR into the first, clear --; (4) cvlm_mask_rle_decode's transposition with area and box.  A plane of one polygon costs what a
+ * plane of run counts costs.  No thread waits for another workgroup; 64-bit offsets.
+ * workspace: caller-owned, 16-byte aligned, contents need no initialisation.  cvlm_mask_poly_decode_workspace_bytes(P, max_pixels) = P
+ * planes' worth: two streams per plane, each 16 bytes + one bit per pixel rounded up to 16 bytes; CVLM_E_BADARG for sizes the entry
+ * refuses.  The one-plane size is the minimum; with fewer than P planes' worth the planes go in rounds queued on the stream.  No
+ * allocation, no synchronisation, no pointer kept; every output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (area and box may be NULL together, not one of them), plane_polys /
+ * dims / bits / area / box / status not 4-byte aligned, xy / poly_offsets / bit_offsets not 8-byte aligned, P outside [1, 65535], Q
+ * outside [1, 4096 P], total < 1, bits_bytes < 4, max_pixels outside [1, 2^28], a workspace that is NULL, not 16-byte aligned or below
+ * the one-plane size. */
+int64_t cvlm_mask_poly_decode_workspace_bytes(int32_t P, int64_t max_pixels);
+int cvlm_mask_poly_decode(const double* xy, int64_t total, const int64_t* poly_offsets, const int32_t* plane_polys, const int32_t* dims,
+                          const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, uint8_t* bits, int64_t bits_bytes,
+                          int32_t* area, int32_t* box, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* Outside the ABI contract: cvlm_mask_poly_decode on HOST memory, no stream, no workspace -- the same per-thread functions
+ * (csrc/poly_logic.h, csrc/gt_logic.h) run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_poly_decode_host(const double* xy, int64_t total, const int64_t* poly_offsets, const int32_t* plane_polys,
+                                     const int32_t* dims, const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, uint8_t* bits,
+                                     int64_t bits_bytes, int32_t* area, int32_t* box, int32_t* status);
 /* cvlm_mask_inter_sized: two sets of sized planes A and B, each as bits / byte length / offsets int64 [P + 1] in bytes / dims int32
  * [P][2] / plane count (they may be the same memory), and pairs int32 [N][2] = (plane of A, plane of B), all device memory.  inter int32
  * [N]: inter[i] = popcount(A[a] AND B[b]) with the last word of each row masked to the columns below w -- whatever the pad bits hold
