@@ -6,7 +6,8 @@ gfx950 behind a C-ABI shared library (include/cvlm.h); this package holds the Py
   synth    deterministic synthetic weights / inputs
   hip      ctypes binding of libcvlm_hip.so (fails loudly when the library is missing)
   engine   weight packing + kernel launch schedule of the forward path
-  maskpost packed masks and what is derived from them (DESIGN.md 13-20): host checks, utilities, the plan of a call
+  maskpost packed masks and what is derived from them (DESIGN.md 13-22): host checks, utilities, the plan of a call
+  cocoeval COCO precision / recall from the matches made on the device, pure numpy
   dropin/  mirrors of the reference's ``models`` / ``cocotrainers`` call surface
 """
 import os as _os

@@ -22,12 +22,12 @@ import torch
 
 from . import hip
 from .hip import ACT_ABS_POST, ACT_GELU, ACT_NONE, ACT_QUICKGELU, ACT_RELU, H2
-# the packed-mask family (DESIGN.md §13 - §21) lives in maskpost.py; its public names stay importable from here
-from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIELDS, HOLE_FIELDS, HOLES_MAXM, MASK_MODES, MORPH_MAXR,
-                       OVERLAP_MAXK, OVERLAP_MAXP, RLE_SIZED, RLE_SOURCES, RLE_WS_CAP, SIZED_MAX_SIDE, EdgeBits, MaskComponents, MaskHoles,
-                       MaskMorph, MaskPost, MaskRle, MaskUtilities, SizedMasks, SizedOverlaps, _edge_threshold, compact_request,
-                       components_request, edge_request, ground_truth_request, holes_request, morph_request, pairs_request,
-                       polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
+# the packed-mask family (DESIGN.md §13 - §22) lives in maskpost.py; its public names stay importable from here
+from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIELDS, HOLE_FIELDS, HOLES_MAXM, MASK_MODES, MATCH_AREA_RNGS, MATCH_CAP,
+                       MATCH_IOU_THRS, MORPH_MAXR, OVERLAP_MAXK, OVERLAP_MAXP, RLE_SIZED, RLE_SOURCES, RLE_WS_CAP, SIZED_MAX_SIDE, CocoMatches,
+                       EdgeBits, MaskComponents, MaskHoles, MaskMorph, MaskPost, MaskRle, MaskUtilities, MatchRequest, SizedMasks, SizedOverlaps,
+                       _edge_threshold, compact_request, components_request, edge_request, ground_truth_request, holes_request, match_request,
+                       morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry
 
 

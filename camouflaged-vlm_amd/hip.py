@@ -87,6 +87,8 @@ _SIGNATURES = {
     "cvlm_debug_mask_poly_decode_host": "i:plppppiilplppp",
     "cvlm_mask_inter_sized": "i:plppiplppipilpps",
     "cvlm_debug_mask_inter_sized_host": "i:plppiplppipilpp",
+    "cvlm_coco_match": "i:pppiplppipppipipiipppppps",
+    "cvlm_debug_coco_match_host": "i:pppiplppipppipipiipppppp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -1215,6 +1217,52 @@ def mask_inter_sized_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims:
     _call("cvlm_debug_mask_inter_sized_host", a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa,
           b_bits.data_ptr(), b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words),
           inter.data_ptr(), status.data_ptr())
+
+
+def _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd, iou_thrs, area_rngs,
+                     dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status) -> Tuple[int, int, int, int, int, int]:
+    """Shape and dtype checks shared by `coco_match` and `coco_match_host` -> (E, N, ND, NG, T, A)."""
+    E, N, ND, NG = int(det_offsets.numel()) - 1, int(inter.numel()), int(det_area.numel()), int(gt_area.numel())
+    T, A = int(iou_thrs.numel()), int(area_rngs.shape[0])
+    i32, u8, f64 = torch.int32, torch.uint8, torch.float64
+    for t, dtype, shape in ((det_offsets, i32, (E + 1,)), (gt_offsets, i32, (E + 1,)), (pair_offsets, torch.int64, (E + 1,)), (inter, i32, (N,)),
+                            (det_area, i32, (ND,)), (score, torch.float32, (ND,)), (gt_area, i32, (NG,)), (gt_range_area, f64, (NG,)),
+                            (gt_crowd, u8, (NG,)), (iou_thrs, f64, (T,)), (area_rngs, f64, (A, 2)), (dt_order, i32, (ND,)),
+                            (dt_match, i32, (A, T, ND)), (dt_ignore, u8, (A, T, ND)), (gt_match, i32, (A, T, NG)), (gt_ignore, u8, (A, NG)),
+                            (status, i32, (1,))):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == det_offsets.device, (t.dtype, tuple(t.shape), shape)
+    return E, N, ND, NG, T, A
+
+
+def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor, det_area: torch.Tensor,
+               score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor, iou_thrs: torch.Tensor,
+               area_rngs: torch.Tensor, max_det: int, dt_order: torch.Tensor, dt_match: torch.Tensor, dt_ignore: torch.Tensor,
+               gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+    """The COCO matching of E groups of detections and annotations (include/cvlm.h: cvlm_coco_match): offsets int32 /
+    int32 / int64 [E + 1], inter int32 [N] in D_e x G_e blocks, det_area int32 and score f32 [sum D], gt_area int32, gt_range_area f64 and
+    gt_crowd uint8 [sum G], iou_thrs f64 [T], area_rngs f64 [A][2] -> dt_order int32 [sum D], dt_match int32 and dt_ignore uint8 [A][T][sum D]
+    in rank order, gt_match int32 [A][T][sum G], gt_ignore uint8 [A][sum G], status int32 [1] = 1 if a group was refused."""
+    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
+                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
+    _on_current_device(det_offsets)
+    p = lambda t: t.data_ptr() if t.numel() else None
+    _call("cvlm_coco_match", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area), p(score), ND,
+          p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det), p(dt_order),
+          p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+
+
+def coco_match_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
+                    det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor,
+                    iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, dt_order: torch.Tensor, dt_match: torch.Tensor,
+                    dt_ignore: torch.Tensor, gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+    """`coco_match` on HOST tensors without a device (cvlm_debug_coco_match_host: the same per-thread functions, run sequentially)."""
+    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
+                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
+    assert not det_offsets.is_cuda
+    p = lambda t: t.data_ptr() if t.numel() else None
+    _call("cvlm_debug_coco_match_host", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area),
+          p(score), ND, p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det),
+          p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

@@ -1,9 +1,9 @@
-"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §20): packed masks with areas, boxes and overlaps, connected
-components, holes, the edge band, packed edge maps, COCO run-length encoding, masks at each image's own size and their intersections
-with ground truth.  Three layers: the pure host checks of every argument (`*_request`) with the result types; `MaskUtilities`, the
-stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan of these outputs for one Cascade.infer_classes / decode call.
-`engine` imports every public name back: callers keep importing them from there.  Kernels are called as `hip.<name>(...)`, looked up
-at call time, so that a test can stand in for a launch."""
+"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §22): packed masks with areas, boxes and overlaps, connected
+components, holes, the edge band, packed edge maps, COCO run-length encoding, masks at each image's own size, their intersections
+with ground truth and COCO's matching of detections to annotations.  Three layers: the pure host checks of every argument
+(`*_request`) with the result types; `MaskUtilities`, the stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan of
+these outputs for one Cascade.infer_classes / decode call. `engine` imports every public name back: callers keep importing them from
+there.  Kernels are called as `hip.<name>(...)`, looked up at call time, so that a test can stand in for a launch."""
 from __future__ import annotations
 
 from dataclasses import InitVar, dataclass
@@ -495,6 +495,154 @@ def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, w
     return np.ascontiguousarray(np.stack([p, q], axis=1).astype(np.int32))
 
 
+MATCH_CAP = 1024                  # detections, and annotations, of one group (csrc/match_logic.h)
+MATCH_MAX_T, MATCH_MAX_A = 16, 8
+MATCH_IOU_THRS = tuple(np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True).tolist())     # COCO's ten
+MATCH_AREA_RNGS = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))             # all, small, medium, large
+
+
+@dataclass
+class MatchRequest:
+    """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
+    keys: list                      # E (category or None, image id), sorted by (category, image)
+    det_perm: np.ndarray            # (sum D,) int64: the caller's detection plane of each row of the detection table, group by group
+    gt_perm: np.ndarray             # (sum G,) int64: the same for the annotations
+    det_offsets: np.ndarray         # (E + 1,) int32 rows of the detection table
+    gt_offsets: np.ndarray          # (E + 1,) int32 rows of the annotation table
+    pair_offsets: np.ndarray        # (E + 1,) int64 into pairs
+    pairs: np.ndarray               # (N, 2) int32 (the caller's detection plane, annotation plane): group e's D_e x G_e block, detection-major
+    crowd: np.ndarray               # (sum G,) uint8 in table order
+    range_area: Optional[np.ndarray]    # (sum G,) float64 in table order, the annotation file's "area"; None: the planes' pixel areas
+    scores: Optional[np.ndarray]    # (sum D,) float32 in table order when the caller gave them on the host
+    iou_thrs: np.ndarray            # (T,) float64
+    area_rngs: np.ndarray           # (A, 2) float64
+    max_det: int
+
+
+def match_request(det_sizes, gt_sizes, *, det_image, gt_image, det_category=None, gt_category=None, iscrowd=None, gt_area=None,
+                  scores=None, iou_thrs=None, area_rngs=None, max_det=100, who: str = "coco_match") -> MatchRequest:
+    """Every check of Cascade.coco_match that the host can make, before anything is launched (ValueError) ->
+    MatchRequest.  det_sizes / gt_sizes: the (h, w) of each detection / annotation plane (either list may be empty).  det_image /
+    gt_image: one int image id per plane; det_category / gt_category: one int per plane, both or neither -- without them a group is an
+    image (pycocotools' useCats = 0).  iscrowd: None or one truth value per annotation; gt_area: None or one finite number >= 0 per
+    annotation; scores: None (they are on the device) or one number per detection, no NaN.  iou_thrs: 1 .. 16 numbers in (0, 1], default
+    COCO's ten; area_rngs: 1 .. 8 pairs lo <= hi, default all / small / medium / large; max_det: an int >= 1.  All planes of a group have
+    one size; a group has at most 1024 detections and 1024 annotations; all groups together at most 2^20 pairs."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    Pd, Pg = len(det_sizes), len(gt_sizes)
+
+    def ints(name, seq, P):
+        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
+            raise ValueError(f"{who}: {name} must hold one int per plane, {P} of them")
+        return np.asarray([int(v) for v in seq], dtype=np.int64)
+
+    def reals(name, seq, P, what):
+        try:
+            arr = np.asarray(seq.cpu() if isinstance(seq, torch.Tensor) else seq)
+        except Exception as e:
+            raise ValueError(f"{who}: {name} must hold {what}") from e
+        if arr.shape != (P,) or (arr.size and arr.dtype.kind not in "iufb"):
+            raise ValueError(f"{who}: {name} must hold {what}, {P} of them")
+        return arr
+
+    d_img, g_img = ints("det_image", det_image, Pd), ints("gt_image", gt_image, Pg)
+    if (det_category is None) != (gt_category is None):
+        raise ValueError(f"{who}: give both det_category= and gt_category=, or neither")
+    cats = det_category is not None
+    d_cat = ints("det_category", det_category, Pd) if cats else np.zeros(Pd, dtype=np.int64)
+    g_cat = ints("gt_category", gt_category, Pg) if cats else np.zeros(Pg, dtype=np.int64)
+    crowd = np.zeros(Pg, dtype=np.uint8) if iscrowd is None else (reals("iscrowd", iscrowd, Pg, "one truth value per annotation") != 0).astype(np.uint8)
+    ra = None
+    if gt_area is not None:
+        ra = reals("gt_area", gt_area, Pg, "one number per annotation").astype(np.float64)
+        if not bool(np.isfinite(ra).all()) or bool((ra < 0).any()):
+            raise ValueError(f"{who}: gt_area must be finite and >= 0")
+    sc = None
+    if scores is not None:
+        sc = reals("scores", scores, Pd, "one number per detection").astype(np.float32)
+        if bool(np.isnan(sc).any()):
+            raise ValueError(f"{who}: a score is NaN")
+    try:
+        thrs = np.asarray(MATCH_IOU_THRS if iou_thrs is None else iou_thrs, dtype=np.float64)
+        rngs = np.asarray(MATCH_AREA_RNGS if area_rngs is None else area_rngs, dtype=np.float64)
+    except Exception as e:
+        raise ValueError(f"{who}: iou_thrs and area_rngs must hold numbers") from e
+    if thrs.ndim != 1 or not 1 <= thrs.size <= MATCH_MAX_T or not bool(((thrs > 0) & (thrs <= 1)).all()):
+        raise ValueError(f"{who}: iou_thrs must be 1 .. {MATCH_MAX_T} numbers in (0, 1]")
+    if rngs.ndim != 2 or rngs.shape[1] != 2 or not 1 <= rngs.shape[0] <= MATCH_MAX_A or not bool((rngs[:, 0] <= rngs[:, 1]).all()):
+        raise ValueError(f"{who}: area_rngs must be 1 .. {MATCH_MAX_A} pairs (lo, hi) with lo <= hi")
+    if not is_int(max_det) or not 1 <= int(max_det) < 2 ** 31:
+        raise ValueError(f"{who}: max_det must be an int >= 1, got {max_det!r}")
+    rows = {}                                                         # (category, image) -> ([detection planes], [annotation planes])
+    for side, (cat, img) in enumerate(((d_cat, d_img), (g_cat, g_img))):
+        for p, key in enumerate(zip(cat.tolist(), img.tolist())):
+            rows.setdefault(key, ([], []))[side].append(p)
+    keys = sorted(rows)
+    D = [len(rows[k][0]) for k in keys]
+    G = [len(rows[k][1]) for k in keys]
+    for k, d, g in zip(keys, D, G):
+        if d > MATCH_CAP or g > MATCH_CAP:
+            raise ValueError(f"{who}: group {k} has {d} detections and {g} annotations, at most {MATCH_CAP} of each are taken")
+        sizes = {tuple(det_sizes[p]) for p in rows[k][0]} | {tuple(gt_sizes[q]) for q in rows[k][1]}
+        if len(sizes) > 1:
+            raise ValueError(f"{who}: the planes of group {k} have the sizes {sorted(sizes)}: one image has one size")
+    if not keys:
+        raise ValueError(f"{who}: no detection and no annotation")
+    n_pairs = int(sum(d * g for d, g in zip(D, G)))
+    if n_pairs > 1 << 20:
+        raise ValueError(f"{who}: the groups give {n_pairs} pairs, at most 2^20 are taken")
+    det_perm = np.asarray([p for k in keys for p in rows[k][0]], dtype=np.int64)
+    gt_perm = np.asarray([q for k in keys for q in rows[k][1]], dtype=np.int64)
+    blocks = [np.stack(np.meshgrid(rows[k][0], rows[k][1], indexing="ij"), axis=-1).reshape(-1, 2) for k in keys if rows[k][0] and rows[k][1]]
+    pairs = np.concatenate(blocks).astype(np.int32) if blocks else np.zeros((0, 2), dtype=np.int32)
+    offs = lambda counts, dt: np.concatenate([[0], np.cumsum(counts)]).astype(dt)
+    return MatchRequest(keys=[(k[0] if cats else None, k[1]) for k in keys], det_perm=det_perm, gt_perm=gt_perm, det_offsets=offs(D, np.int32),
+                        gt_offsets=offs(G, np.int32), pair_offsets=offs([d * g for d, g in zip(D, G)], np.int64),
+                        pairs=np.ascontiguousarray(pairs), crowd=crowd[gt_perm], range_area=None if ra is None else ra[gt_perm],
+                        scores=None if sc is None else sc[det_perm], iou_thrs=thrs, area_rngs=np.ascontiguousarray(rngs), max_det=int(max_det))
+
+
+@dataclass
+class CocoMatches:
+    """The COCO matching of detections and annotations (Cascade.coco_match; cvlm_coco_match), on the device.  Rows are
+    those of the request's tables: group e = request.keys[e] has the detection rows det_offsets[e] .. det_offsets[e + 1] - 1, row i is the
+    caller's plane det_perm[i]; likewise the annotations.  dt_match / dt_ignore are in RANK order inside each group."""
+    dt_order: torch.Tensor          # (sum D,) int32: rank r of group e holds the row of its detection
+    dt_match: torch.Tensor          # (A, T, sum D) int32: the annotation row the detection of that rank took, or -1
+    dt_ignore: torch.Tensor         # (A, T, sum D) uint8
+    gt_match: torch.Tensor          # (A, T, sum G) int32: the detection row that took the annotation, or -1
+    gt_ignore: torch.Tensor         # (A, sum G) uint8
+    score: torch.Tensor             # (sum D,) float32 in table (not rank) order
+    status: torch.Tensor            # (1,) int32, non-zero if the kernel refused a group
+    overlaps: Optional["SizedOverlaps"]     # the intersections behind it; None when no group has both detections and annotations
+    request: MatchRequest
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a group or a pair (synchronises).  The tables come from `match_request`, so a refused
+        group says that the library is broken; a refused pair is two planes whose tables do not fit."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("coco_match: cvlm_coco_match refused a group: offsets or a pair block that do not fit")
+        if self.overlaps is not None:
+            self.overlaps.check()
+
+    def to_host(self) -> dict:
+        """Everything cocoeval.accumulate needs, as numpy arrays, by ONE read of the device (synchronises): the five result tables under
+        their names, `score` in table order, `status`, and the request's `keys`, `det_offsets`, `gt_offsets`, `det_perm`, `gt_perm`,
+        `iou_thrs`, `area_rngs`, `max_det`."""
+        parts = [self.dt_order, self.dt_match, self.gt_match, self.score, self.status, self.dt_ignore, self.gt_ignore]
+        flat = torch.cat([t.contiguous().view(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        out, at = {}, 0
+        for name, t in zip(("dt_order", "dt_match", "gt_match", "score", "status", "dt_ignore", "gt_ignore"), parts):
+            n = t.numel() * t.element_size()
+            dt = {torch.int32: np.int32, torch.float32: np.float32, torch.uint8: np.uint8}[t.dtype]
+            out[name] = flat[at:at + n].view(dt).reshape(tuple(t.shape))
+            at += n
+        r = self.request
+        out.update(status=int(out["status"][0]), keys=list(r.keys), det_offsets=r.det_offsets, gt_offsets=r.gt_offsets, det_perm=r.det_perm,
+                   gt_perm=r.gt_perm, iou_thrs=r.iou_thrs, area_rngs=r.area_rngs, max_det=r.max_det)
+        return out
+
+
 def ground_truth_request(ground_truth, sreq, n: int, who: str = "decode"):
     """Every check of the ground_truth= argument of Cascade.infer_classes / decode, on the host, before anything is
     launched (ValueError) -> None when nothing is asked for, otherwise (gt, the image id of each of its planes).  ground_truth is (gt,
@@ -914,6 +1062,57 @@ class MaskUtilities:
         hip.mask_inter_sized(a.bits, a.offsets, a_dims, b.bits, b.offsets, b_dims, tab, max(a_words, b_words), inter, status)
         pick = lambda s, col: s.area.index_select(0, tab[:, col].long().clamp_(0, len(s.sizes) - 1))
         return SizedOverlaps(pairs=tab, inter=inter, area_a=pick(a, 0), area_b=pick(b, 1), status=status)
+
+
+    # ---- COCO matching on the device ---------------------------------------------------------------------------------------
+    def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,
+                   gt_category=None, iscrowd=None, gt_area=None, iou_thrs=None, area_rngs=None, max_det: int = 100) -> "CocoMatches":
+        """Detections against annotations as COCOeval.evaluateImg matches them -> CocoMatches (cvlm_coco_match), for every
+        (image, category) group, area range and IoU threshold at once; `cocoeval.accumulate` / `summarize` turn it into AP and AR.  dets
+        / gts: SizedMasks on this engine's device with areas, e.g. `sized` of infer_classes / decode and `rle_decode` /
+        `polygons_decode` of the annotations; None for a side without planes.  scores: one per plane of dets -- a float32 tensor on the
+        device, taken as it is (NaN ranks last), or a host sequence (NaN: ValueError).  The other arguments are `match_request`'s, which
+        checks all of them on the host before anything is launched (ValueError).  Then: `mask_inter_sized(pairs=...)` for the groups'
+        pair blocks (skipped when no group has both sides), gathers of the areas and scores into table order, one cvlm_coco_match call.
+        No workspace, no synchronisation: `CocoMatches.to_host()` does the one read."""
+        for name, s in (("dets", dets), ("gts", gts)):
+            if s is not None and (not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535):
+                raise ValueError(f"coco_match: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas, or None")
+        d_sizes, g_sizes = ([] if s is None else s.sizes for s in (dets, gts))
+        on_device = isinstance(scores, torch.Tensor) and scores.is_cuda
+        if on_device and (scores.dtype != torch.float32 or tuple(scores.shape) != (len(d_sizes),)):
+            raise ValueError(f"coco_match: scores on the device must be a float32 tensor ({len(d_sizes)},)")
+        req = match_request(d_sizes, g_sizes, det_image=det_image, gt_image=gt_image, det_category=det_category, gt_category=gt_category,
+                            iscrowd=iscrowd, gt_area=gt_area, scores=None if on_device else scores, iou_thrs=iou_thrs, area_rngs=area_rngs,
+                            max_det=max_det)
+        if not on_device and req.scores is None:
+            raise ValueError("coco_match: scores must hold one number per detection")
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ND, NG = int(req.det_perm.size), int(req.gt_perm.size)
+        A, T = int(req.area_rngs.shape[0]), int(req.iou_thrs.size)
+        overlaps = self.mask_inter_sized(dets, gts, pairs=req.pairs) if req.pairs.shape[0] else None
+        inter = overlaps.inter if overlaps is not None else torch.empty(0, dtype=torch.int32, device=dev)
+        if ND:
+            det_perm = up(req.det_perm)
+            det_area = dets.area.index_select(0, det_perm)
+            score = scores.detach().index_select(0, det_perm) if on_device else up(req.scores)
+        else:
+            det_area, score = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        if NG:
+            g_area = gts.area.index_select(0, up(req.gt_perm))
+            range_area = g_area.to(torch.float64) if req.range_area is None else up(req.range_area)
+        else:
+            g_area, range_area = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev)
+        out = CocoMatches(dt_order=torch.empty(ND, dtype=torch.int32, device=dev), dt_match=torch.empty(A, T, ND, dtype=torch.int32, device=dev),
+                          dt_ignore=torch.empty(A, T, ND, dtype=torch.uint8, device=dev),
+                          gt_match=torch.empty(A, T, NG, dtype=torch.int32, device=dev),
+                          gt_ignore=torch.empty(A, NG, dtype=torch.uint8, device=dev), score=score,
+                          status=torch.empty(1, dtype=torch.int32, device=dev), overlaps=overlaps, request=req)
+        hip.coco_match(up(req.det_offsets), up(req.gt_offsets), up(req.pair_offsets), inter, det_area.contiguous(), score.contiguous(),
+                       g_area.contiguous(), range_area.contiguous(), up(req.crowd), up(req.iou_thrs), up(req.area_rngs), req.max_det,
+                       out.dt_order, out.dt_match, out.dt_ignore, out.gt_match, out.gt_ignore, out.status)
+        return out
 
 
 COMPONENT_FIELDS = ("n_comp", "comps", "n_kept", "kept_bits", "kept_area", "kept_box")

@@ -831,6 +831,46 @@ int cvlm_debug_mask_inter_sized_host(const uint8_t* a_bits, int64_t a_bytes, con
                                      const uint8_t* b_bits, int64_t b_bytes, const int64_t* b_offsets, const int32_t* b_dims, int32_t Pb,
                                      const int32_t* pairs, int32_t N, int64_t max_words, int32_t* inter, int32_t* status);
 
+/* cvlm_coco_match: the greedy matching of COCOeval.evaluateImg, for E GROUPS -- one (image, category) pair each -- and
+ * every (area range, IoU threshold) instance at once.  All tensors are device memory.  Group e has the detections det_offsets[e] ..
+ * det_offsets[e + 1] - 1 and the annotations gt_offsets[e] .. gt_offsets[e + 1] - 1 of the tables below (int32 [E + 1] each), and its
+ * intersections are inter[pair_offsets[e] ..), D_e x G_e values, detection-major, in the caller's detection order (pair_offsets int64
+ * [E + 1]; inter int32 [N] as cvlm_mask_inter_sized writes it: -1 for a refused pair).  det_area int32 and score f32 [ND]; gt_area int32
+ * (pixels), gt_range_area f64 (the annotation file's "area") and gt_crowd uint8 [NG]; iou_thrs f64 [T]; area_rngs f64 [A][2] = (lo, hi).
+ *   IoU          (double)inter / (double)u, u = det_area against a crowd annotation, else det_area + gt_area - inter; 0 for inter = 0; -1,
+ *                which matches nothing, for inter < 0 and for u < 1.
+ *   gt_ignore    uint8 [A][NG] = crowd or gt_range_area < lo_a or gt_range_area > hi_a.
+ *   dt_order     int32 [ND]: rank r of group e (at det_offsets[e] + r) holds the row of its detection; score descending, equal scores in
+ *                the caller's order, NaN behind every number.  Only the first min(D_e, max_det) ranks are matched.
+ *   dt_match     int32 [A][T][ND] in RANK order: the row of the annotation the detection took, or -1.  Per instance the detections
+ *                choose in rank order: among the annotations not ignored and not yet taken the largest IoU >= min(t, 1 - 1e-10), on
+ *                ties the largest row; only if there is none, the same among the ignored ones, where a crowd annotation may be taken
+ *                again -- what the published loop over the annotations sorted ignore-last gives.
+ *   dt_ignore    uint8 [A][T][ND]: the taken annotation's gt_ignore; unmatched: det_area < lo_a or det_area > hi_a.
+ *   gt_match     int32 [A][T][NG] in the caller's order: the row of the (last) detection that took the annotation, or -1.
+ * Ranks >= max_det, and every row no accepted group covers, hold match -1, ignore 1 and order -1: the call writes every output first,
+ * so a launch sequence replays.  A group is REFUSED whole -- status[0] |= 1 (the call zeroes it first), nothing of its tables or block is
+ * read -- if its offsets run backwards or leave [0, ND] / [0, NG], if D_e or G_e exceeds 1024, or if its pair block is not exactly
+ * D_e * G_e long inside [0, N].  Groups whose rows overlap are the caller's error (their outputs are unspecified, nothing is
+ * written outside the tables).  Two launches: the fill, then one workgroup of 128 threads per group (30 KiB of LDS, no scratch); no
+ * workspace, no allocation, no synchronisation, no workgroup waits for another.
+ * CVLM_E_BADARG, before anything touches the device: a NULL offsets / iou_thrs / area_rngs / status; a NULL table or output whose
+ * count (N for inter; ND for det_area, score, dt_order, dt_match, dt_ignore; NG for gt_area, gt_range_area, gt_crowd, gt_match,
+ * gt_ignore) is not 0; an int32 / f32 pointer not 4-byte aligned, pair_offsets or an f64 pointer not 8-byte aligned; E outside [1, 2^20];
+ * N, ND or NG outside [0, 2^20]; T outside [1, 16]; A outside [1, 8]; max_det < 1. */
+int cvlm_coco_match(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E, const int32_t* inter,
+                    int64_t N, const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area, const double* gt_range_area,
+                    const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A,
+                    int32_t max_det, int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
+                    int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_coco_match on HOST memory, no stream -- the same per-thread functions (csrc/match_logic.h) run
+ * sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                               const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND,
+                               const int32_t* gt_area, const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG,
+                               const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det, int32_t* dt_order,
+                               int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
