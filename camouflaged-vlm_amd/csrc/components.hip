@@ -26,13 +26,8 @@ __host__ __device__ inline PlaneWs plane_ws(void* workspace, int64_t slot, int64
 // n_comp = 0 (it is the counter of the root lists), kept_area = 0, kept_box = -1 for all P planes
 __global__ __launch_bounds__(256) void cc_init_kernel(int* __restrict__ n_comp, int* __restrict__ kept_area, int* __restrict__ kept_box, int P) {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    n_comp[p] = 0;
-    if (kept_area) {
-        kept_area[p] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) kept_box[4 * p + k] = -1;
-    }
+    if (p < P) n_comp[p] = 0;
+    mb_init_planes(nullptr, kept_area, kept_box, P);
 }
 
 // pass 1: plane blockIdx.y of the round, one word per thread
@@ -128,18 +123,13 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 __global__ __launch_bounds__(256) void cc_select_kernel(int words, void* workspace, const int* __restrict__ n_comp, int M, int min_area,
                                                         int* __restrict__ comps, int* __restrict__ n_kept) {
     __shared__ uint64_t red[4];
-    __shared__ int cnt[4];
     const PlaneWs ws = plane_ws(workspace, blockIdx.x, (int64_t)words * 32);
     const int n = n_comp[blockIdx.x];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (n_kept) {
-        int c = 0;
-        for (int i = threadIdx.x; i < n; i += 256) c += ws.area[ws.list[i] >> 1] >= min_area ? 1 : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0) cnt[wave] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) n_kept[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+        int c[1] = {0};
+        for (int i = threadIdx.x; i < n; i += 256) c[0] += ws.area[ws.list[i] >> 1] >= min_area ? 1 : 0;
+        if (mb_block_sum(c)) n_kept[blockIdx.x] = c[0];
     }
     uint64_t prev = ~0ull;
     for (int m = 0; m < M; ++m) {
@@ -174,43 +164,15 @@ __global__ __launch_bounds__(256) void cc_keep_kernel(const uint32_t* __restrict
                                                       uint32_t* __restrict__ kept_bits, int* __restrict__ kept_area, int* __restrict__ kept_box) {
     const int wi = blockIdx.x * 256 + threadIdx.x;
     const PlaneWs ws = plane_ws(const_cast<void*>(workspace), blockIdx.y, (int64_t)words * 32);
-    unsigned cnt = 0, x0 = 0xffffffffu, y0 = 0xffffffffu;
-    int x1 = -1, y1 = -1;
+    mb_stats stats;
     if (wi < words) {
         const int64_t at = (int64_t)blockIdx.y * words + wi;
         const uint32_t w = cc_unpack(bits[at]);
         const uint32_t kept = w ? cc_keep_word(w, wi * 32, ws.parent, ws.area, min_area) : 0u;
         kept_bits[at] = cc_pack(kept);
-        if (kept) {
-            const int y = wi / wpr, xw = (wi - y * wpr) * 32;
-            cnt = __popc(kept);
-            x0 = xw + __builtin_ctz(kept); x1 = xw + 31 - __builtin_clz(kept);
-            y0 = y; y1 = y;
-        }
+        if (kept) mb_word(stats, kept, wi % wpr, wi / wpr);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
-        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-    }
-    __shared__ unsigned red[4][5];
-    if ((threadIdx.x & 63) == 0) {
-        unsigned* r = red[threadIdx.x >> 6];
-        r[0] = cnt; r[1] = x0; r[2] = y0; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned c = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        if (c) {
-            const int p = blockIdx.y;
-            atomicAdd(&kept_area[p], (int)c);
-            atomicMin((unsigned*)&kept_box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
-            atomicMin((unsigned*)&kept_box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
-            atomicMax(&kept_box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
-            atomicMax(&kept_box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
-        }
-    }
+    mb_block_commit(stats, kept_area, kept_box, blockIdx.y);
 }
 
 // ---- holes (cvlm_mask_holes): the passes above on the CLEAR pixels, at the dual connectivity -----------------------------
@@ -249,23 +211,18 @@ __global__ __launch_bounds__(256) void hl_flatten_kernel(const uint32_t* __restr
 __global__ __launch_bounds__(256) void hl_select_kernel(int words, int wpr, void* workspace, int* __restrict__ n_holes, int M, int fill_below,
                                                         int* __restrict__ holes, int* __restrict__ n_filled) {
     __shared__ uint64_t red[4];
-    __shared__ int cnt[4][2];
     const PlaneWs ws = plane_ws(workspace, blockIdx.x, (int64_t)words * 32);
     const int H = words / wpr, W = wpr * 32;
     const int n = n_holes[blockIdx.x];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int c = 0, f = 0;
+    int cf[2] = {0, 0};                                             // the holes, and those of them below fill_below
     for (int i = threadIdx.x; i < n; i += 256) {
         const int k = ws.list[i] >> 1;
-        if (cc_box_inside(ws.box[k], H, W)) { ++c; f += ws.area[k] < fill_below ? 1 : 0; }
+        if (cc_box_inside(ws.box[k], H, W)) { ++cf[0]; cf[1] += ws.area[k] < fill_below ? 1 : 0; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); f += __shfl_xor(f, o, 64); }
-    if (lane == 0) { cnt[wave][0] = c; cnt[wave][1] = f; }
-    __syncthreads();                                                // every thread has read n by now
-    if (threadIdx.x == 0) {
-        n_holes[blockIdx.x] = cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0];
-        if (n_filled) n_filled[blockIdx.x] = cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
+    if (mb_block_sum(cf)) {                                         // behind its barrier every thread has read n
+        n_holes[blockIdx.x] = cf[0];
+        if (n_filled) n_filled[blockIdx.x] = cf[1];
     }
     uint64_t prev = ~0ull;
     for (int m = 0; m < M; ++m) {
@@ -299,30 +256,21 @@ __global__ __launch_bounds__(256) void hl_fill_kernel(const uint32_t* __restrict
                                                       uint32_t* __restrict__ filled_bits, int* __restrict__ filled_area) {
     const int wi = blockIdx.x * 256 + threadIdx.x;
     const PlaneWs ws = plane_ws(const_cast<void*>(workspace), blockIdx.y, (int64_t)words * 32);
-    int cnt = 0;
+    int cnt[1] = {0};
     if (wi < words) {
         const int64_t at = (int64_t)blockIdx.y * words + wi;
         const uint32_t set = cc_unpack(bits[at]);
         const uint32_t filled = ~set ? set | cc_fill_word(~set, wi * 32, ws.parent, ws.area, ws.box, words / wpr, wpr * 32, fill_below) : set;
         filled_bits[at] = cc_pack(filled);
-        cnt = __popc(filled);
+        cnt[0] = __popc(filled);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    __shared__ int red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int c = red[0] + red[1] + red[2] + red[3];
-        if (c) atomicAdd(&filled_area[blockIdx.y], c);
-    }
+    if (mb_block_sum(cnt) && cnt[0]) atomicAdd(&filled_area[blockIdx.y], cnt[0]);
 }
 
 // what both hole entries refuse, workspace aside
 bool hl_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t fill_below,
                     const int32_t* n_holes, const int32_t* holes, const int32_t* n_filled, const uint32_t* filled_bits, const int32_t* filled_area) {
-    if (!bits || !n_holes || (((uintptr_t)bits) & 3) != 0 || (((uintptr_t)filled_bits) & 3) != 0) return true;
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if (!bits || !n_holes || mb_misaligned(4, bits, filled_bits) || mb_bad_planes(P, H, W)) return true;
     if ((connectivity != 4 && connectivity != 8) || M < 0 || M > CC_MAXM || (M > 0) != (holes != nullptr) || fill_below < 0) return true;
     const bool fill = fill_below > 0;
     return fill != (n_filled != nullptr) || fill != (filled_bits != nullptr) || fill != (filled_area != nullptr);
@@ -332,8 +280,7 @@ bool hl_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32
 bool cc_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t connectivity, int32_t M, int32_t min_area,
                     const int32_t* n_comp, const int32_t* comps, const int32_t* n_kept, const uint32_t* kept_bits, const int32_t* kept_area,
                     const int32_t* kept_box) {
-    if (!bits || !n_comp || (((uintptr_t)bits) & 3) != 0 || (((uintptr_t)kept_bits) & 3) != 0) return true;
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if (!bits || !n_comp || mb_misaligned(4, bits, kept_bits) || mb_bad_planes(P, H, W)) return true;
     if ((connectivity != 4 && connectivity != 8) || M < 0 || M > CC_MAXM || (M > 0) != (comps != nullptr) || min_area < 0) return true;
     const bool keep = min_area > 0;
     return keep != (n_kept != nullptr) || keep != (kept_bits != nullptr) || keep != (kept_area != nullptr) || keep != (kept_box != nullptr);
@@ -366,7 +313,7 @@ int host_label_plane(const uint32_t* src, int words, int wpr, int connectivity, 
 extern "C" {
 
 int64_t cvlm_mask_components_workspace_bytes(int32_t P, int32_t H, int32_t W) {
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return -1;
+    if (mb_bad_planes(P, H, W)) return -1;
     return plane_ws_bytes((int64_t)H * W) * P;
 }
 
@@ -375,11 +322,11 @@ int cvlm_mask_components(const uint32_t* bits, int32_t P, int32_t H, int32_t W, 
                          int32_t* kept_area, int32_t* kept_box, void* stream) {
     if (cc_bad_request(bits, P, H, W, connectivity, M, min_area, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)) return CVLM_E_BADARG;
     const int64_t HW = (int64_t)H * W;
-    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_ws_bytes(HW)) return CVLM_E_BADARG;
+    if (mb_bad_workspace(workspace, workspace_bytes, plane_ws_bytes(HW))) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int words = (int)(HW / 32), wpr = W / 32;
     const int gx = (words + 255) / 256;
-    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_ws_bytes(HW));   // planes per round
+    const int fit = mb_fit(P, workspace_bytes, plane_ws_bytes(HW));
     hipLaunchKernelGGL(cc_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_comp, (int*)kept_area, (int*)kept_box, (int)P);
     CVLM_CHECK_LAUNCH();
     for (int p0 = 0; p0 < P; p0 += fit) {
@@ -441,19 +388,15 @@ int cvlm_debug_mask_components_host(const uint32_t* bits, int32_t P, int32_t H, 
             prev = best;
         }
         if (min_area > 0) {
-            int a = 0, x0 = -1, y0 = -1, x1 = -1, y1 = -1;
+            mb_stats stats;
             for (int wi = 0; wi < words; ++wi) {
                 const uint32_t w = cc_unpack(src[wi]);
                 const uint32_t kept = w ? cc_keep_word(w, wi * 32, ws.parent, ws.area, min_area) : 0u;
                 kept_bits[(int64_t)p * words + wi] = cc_pack(kept);
-                if (!kept) continue;
-                const int y = wi / wpr, xw = (wi - y * wpr) * 32, lo = xw + __builtin_ctz(kept), hi = xw + 31 - __builtin_clz(kept);
-                a += __builtin_popcount(kept);
-                x0 = x0 < 0 ? lo : std::min(x0, lo); y0 = y0 < 0 ? y : y0;
-                x1 = std::max(x1, hi); y1 = y;
+                if (kept) mb_word(stats, kept, wi % wpr, wi / wpr);
             }
-            kept_area[p] = a;
-            kept_box[4 * p + 0] = x0; kept_box[4 * p + 1] = y0; kept_box[4 * p + 2] = x1; kept_box[4 * p + 3] = y1;
+            mb_init(kept_area, kept_box, p);
+            mb_store(stats, kept_area, kept_box, p);
         }
     }
     return 0;
@@ -466,11 +409,11 @@ int cvlm_mask_holes(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32
                     uint32_t* filled_bits, int32_t* filled_area, void* stream) {
     if (hl_bad_request(bits, P, H, W, connectivity, M, fill_below, n_holes, holes, n_filled, filled_bits, filled_area)) return CVLM_E_BADARG;
     const int64_t HW = (int64_t)H * W;
-    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_ws_bytes(HW)) return CVLM_E_BADARG;
+    if (mb_bad_workspace(workspace, workspace_bytes, plane_ws_bytes(HW))) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int words = (int)(HW / 32), wpr = W / 32;
     const int gx = (words + 255) / 256;
-    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_ws_bytes(HW));   // planes per round
+    const int fit = mb_fit(P, workspace_bytes, plane_ws_bytes(HW));
     hipLaunchKernelGGL(hl_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_holes, (int*)n_filled, (int*)filled_area, (int)P);
     CVLM_CHECK_LAUNCH();
     for (int p0 = 0; p0 < P; p0 += fit) {

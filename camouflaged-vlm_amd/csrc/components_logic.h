@@ -3,26 +3,19 @@
 // word on the CPU.  No HIP call, no allocation.  cvlm_mask_holes runs the same logic on the complement: see cc_fetch.
 //
 // A plane is H rows of W / 32 words; a word never straddles a row.  In memory a word is in numpy.packbits' order (what cvlm_mask_pack
-// stores); cc_unpack turns it into bit i = pixel i of the word, so that a horizontal RUN is a maximal group of consecutive set bits.
-// Every run is named by the plane index of its first pixel.  Two runs never start on adjacent pixels (inside a word a clear bit
+// stores); cc_unpack (maskbits.h) turns it into bit i = pixel i of the word, so that a horizontal RUN is a maximal group of consecutive
+// set bits.  Every run is named by the plane index of its first pixel.  Two runs never start on adjacent pixels (inside a word a clear bit
 // separates them; a word boundary separates an odd index from the next even one), so run start i owns slot i >> 1 of three arrays of
 // H * W / 2 entries: parent (union-find), area and box.  Invariant of the forest: parent[i >> 1] <= i, and equal exactly at a root, so
 // the root of a region is its lowest run start -- its lowest pixel index, the `seed` of the interface.
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define CC_HD __host__ __device__ __forceinline__
-#else
-#define CC_HD inline
-#endif
+#include "maskbits.h"
 
 struct cc_box { int x0, y0, x1, y1; };                            // inclusive; 16 bytes
 
-// ---- words ----------------------------------------------------------------------------------------------------------------------------
-CC_HD uint32_t cc_unpack(uint32_t stored) { return __builtin_bitreverse32(__builtin_bswap32(stored)); }
-CC_HD uint32_t cc_pack(uint32_t word) { return __builtin_bswap32(__builtin_bitreverse32(word)); }
-
+// ---- runs of a word ---------------------------------------------------------------------------------------------------------------------
 // bits [s, e) of a word, 0 <= s < e <= 32
 CC_HD uint32_t cc_span(int s, int e) { return (e >= 32 ? 0xffffffffu : (1u << e) - 1u) & ~((1u << s) - 1u); }
 // the run of `w` that holds set bit b: its first bit, and one past its last

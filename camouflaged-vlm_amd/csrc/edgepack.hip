@@ -58,7 +58,6 @@ __global__ __launch_bounds__(256) void ep_pack_kernel(const float* __restrict__ 
                                                       float threshold, int col_tiles, uint32_t* __restrict__ bits, int* __restrict__ area,
                                                       const uint32_t* __restrict__ with_bits, int* __restrict__ with_inter) {
     __shared__ float s_src[STAGE ? EP_LDS_FLOATS : 1];
-    __shared__ int red[4][2];
     const int tr = blockIdx.x / col_tiles, tc = blockIdx.x - tr * col_tiles;
     const int ox0 = tc * EP_TW, oy0 = tr * EP_TH;
     const int ox_last = min(ox0 + EP_TW, wout) - 1, oy_last = min(oy0 + EP_TH, hout) - 1;
@@ -101,34 +100,18 @@ __global__ __launch_bounds__(256) void ep_pack_kernel(const float* __restrict__ 
         ep_rows(src, win, 0, xa, xb, lx, sy, hin, threshold, oy0, oy_last, col_in, ox >> 5, wpr, bits + plane,
                 with_bits ? with_bits + plane : nullptr, n_set, n_with);
 
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_set += __shfl_xor(n_set, o, 64);
-        n_with += __shfl_xor(n_with, o, 64);
+    int n[2] = {n_set, n_with};
+    if (mb_block_sum(n)) {
+        if (n[0]) atomicAdd(&area[blockIdx.y], n[0]);                 // a workgroup that set nothing leaves the plane's sums alone
+        if (with_inter && n[1]) atomicAdd(&with_inter[blockIdx.y], n[1]);
     }
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6][0] = n_set;
-        red[threadIdx.x >> 6][1] = n_with;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int a = red[0][0] + red[1][0] + red[2][0] + red[3][0], w = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-        if (a) atomicAdd(&area[blockIdx.y], a);                       // a workgroup that set nothing leaves the plane's sums alone
-        if (with_inter && w) atomicAdd(&with_inter[blockIdx.y], w);
-    }
-}
-
-bool ep_ranges_meet(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + b_bytes && y < x + a_bytes;
 }
 
 // what both entries refuse
 bool ep_bad_request(const float* prob, int32_t P, int32_t hin, int32_t win, int32_t hout, int32_t wout, float threshold, const uint8_t* bits,
                     const int32_t* area, const uint8_t* with_bits, const int32_t* with_inter) {
-    if (!prob || !bits || !area || (((uintptr_t)bits | (uintptr_t)with_bits) & 3) != 0) return true;
-    if (P < 1 || P > 65535 || hin <= 0 || win <= 0 || hout <= 0 || wout <= 0 || wout % 32 != 0) return true;
-    if ((int64_t)hout * wout >= ((int64_t)1 << 31) || (int64_t)hin * win >= ((int64_t)1 << 31)) return true;
+    if (!prob || !bits || !area || mb_misaligned(4, bits, with_bits) || mb_bad_planes(P, hout, wout)) return true;
+    if (hin <= 0 || win <= 0 || (int64_t)hin * win >= ((int64_t)1 << 31)) return true;
     if (!(threshold > 0.0f && threshold < 1.0f)) return true;         // NaN and the infinities fail both comparisons
     if ((with_bits != nullptr) != (with_inter != nullptr)) return true;
     const uint64_t in_bytes = (uint64_t)P * ((uint64_t)hin * win * 4), plane_bytes = (uint64_t)P * ((uint64_t)hout * wout / 8);
@@ -136,9 +119,9 @@ bool ep_bad_request(const float* prob, int32_t P, int32_t hin, int32_t win, int3
     const void* outs[3] = {bits, area, with_inter};
     const uint64_t out_bytes[3] = {plane_bytes, sum_bytes, sum_bytes};
     for (int i = 0; i < 3; ++i) {
-        if (ep_ranges_meet(outs[i], out_bytes[i], prob, in_bytes) || ep_ranges_meet(outs[i], out_bytes[i], with_bits, plane_bytes)) return true;
+        if (mb_ranges_meet(outs[i], out_bytes[i], prob, in_bytes) || mb_ranges_meet(outs[i], out_bytes[i], with_bits, plane_bytes)) return true;
         for (int k = i + 1; k < 3; ++k)
-            if (ep_ranges_meet(outs[i], out_bytes[i], outs[k], out_bytes[k])) return true;
+            if (mb_ranges_meet(outs[i], out_bytes[i], outs[k], out_bytes[k])) return true;
     }
     return false;
 }

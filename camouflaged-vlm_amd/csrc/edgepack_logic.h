@@ -16,7 +16,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "components_logic.h"
+#include "maskbits.h"
 
 #define EP_HD CC_HD
 

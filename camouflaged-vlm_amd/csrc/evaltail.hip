@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "../../include/cvlm.h"
+#include "maskbits.h"
 
 namespace {
 
@@ -542,14 +543,9 @@ __global__ __launch_bounds__(64) void topk_kernel(const float* __restrict__ scor
 }
 
 // ---- packed masks, areas, boxes and overlaps of class hypotheses ------------------------------------------------------
-// area = 0, box = (-1, -1, -1, -1): the corners x0 / y0 are then lowered by UNSIGNED minima (0xffffffff is the largest unsigned and -1
-// as the int32 the caller reads: an empty plane needs no second pass), x1 / y1 raised by signed maxima.
+// area = 0, box = -1 (maskbits.h: the scheme of the areas and boxes)
 __global__ __launch_bounds__(256) void mask_pack_init_kernel(int* __restrict__ area, int* __restrict__ box, int P) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    area[p] = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
+    mb_init_planes(nullptr, area, box, P);
 }
 
 // logit > 0.0f on the bit pattern: sign clear, not zero, not above +inf's pattern (NaN) -- a denormal counts whatever the denormal mode
@@ -570,8 +566,7 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const float* __restrict_
     const unsigned groups = (unsigned)(HW >> 2);                      // < 2^29
     const unsigned span = gridDim.x * 256u;
     const unsigned rounds = (groups + span - 1) / span;
-    unsigned cnt = 0, x0 = 0xffffffffu, y0 = 0xffffffffu;
-    int x1 = -1, y1 = -1;
+    mb_stats stats;
     for (unsigned rd = 0; rd < rounds; ++rd) {
         const unsigned q = rd * span + blockIdx.x * 256u + threadIdx.x;
         const bool ok = q < groups;
@@ -585,44 +580,18 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const float* __restrict_
         word |= __shfl_xor(word, 1, 64);
         word |= __shfl_xor(word, 2, 64);
         word |= __shfl_xor(word, 4, 64);
-        if (ok && (threadIdx.x & 7) == 0) dst[q >> 3] = __builtin_bswap32(__brev(word));
+        if (ok && (threadIdx.x & 7) == 0) dst[q >> 3] = cc_pack(word);
         if (STATS && nib) {
             const unsigned i0 = 4u * q;                                // < 2^31
             unsigned y = i0 / (unsigned)W, x = i0 - y * (unsigned)W;
-            cnt += __popc(nib);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (nib >> j & 1) {
-                    x0 = min(x0, x); y0 = min(y0, y);
-                    x1 = max(x1, (int)x); y1 = max(y1, (int)y);
-                }
+                if (nib >> j & 1) mb_pixel(stats, (int)x, (int)y);
                 if (++x == (unsigned)W) { x = 0; ++y; }
             }
         }
     }
-    if (!STATS) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
-        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-    }
-    __shared__ unsigned red[4][5];
-    if ((threadIdx.x & 63) == 0) {
-        unsigned* r = red[threadIdx.x >> 6];
-        r[0] = cnt; r[1] = x0; r[2] = y0; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned c = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        if (c) {                                                      // a workgroup that found nothing leaves the plane's results alone
-            atomicAdd(&area[p], (int)c);
-            atomicMin((unsigned*)&box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
-            atomicMin((unsigned*)&box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
-            atomicMax(&box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
-            atomicMax(&box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
-        }
-    }
+    if (STATS) mb_block_commit(stats, area, box, p);
 }
 
 // inter[img][a][b] += popcount(row a AND row b) over the words [blockIdx.x * span, + span) for the 32 x 32 pairs of tile (ta, tb),
@@ -737,7 +706,7 @@ int cvlm_mask_joint_hist(const uint8_t* pre, const uint8_t* gt, int32_t N, int32
 }
 
 int cvlm_mask_pack(const float* logits, int32_t P, int64_t HW, int32_t W, uint8_t* bits, int32_t* area, int32_t* box, void* stream) {
-    if (!logits || !bits || (((uintptr_t)bits) & 3) != 0 || (area == nullptr) != (box == nullptr) || P < 1 || P > 65535 || HW <= 0 ||
+    if (!logits || !bits || mb_misaligned(4, bits) || (area == nullptr) != (box == nullptr) || P < 1 || P > 65535 || HW <= 0 ||
         HW >= ((int64_t)1 << 31) || HW % 32 != 0 || W <= 0 || HW % W != 0)
         return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;

@@ -24,14 +24,9 @@ constexpr int GD_SCAN = 1024;                                         // threads
 constexpr int GD_TW = 16, GD_TH = 128, GD_LD = GD_TW * 33;
 constexpr int GI_SPAN = 2048;                                         // words of a pair per workgroup and step of the intersection
 
-// status = 0; area = 0, box = -1 (cvlm_mask_pack's scheme: x0 / y0 lowered by unsigned minima, x1 / y1 raised by signed maxima)
+// status = 0; area = 0, box = -1
 __global__ __launch_bounds__(256) void gd_init_kernel(int* __restrict__ area, int* __restrict__ box, int P, int* __restrict__ status) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p == 0) status[0] = 0;
-    if (!area || p >= P) return;
-    area[p] = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
+    mb_init_planes(status, area, box, P);
 }
 
 // One workgroup per plane of the round, slot blockIdx.x of the zeroed workspace.  Every check of the plane, then its counts in slabs
@@ -133,7 +128,6 @@ __global__ __launch_bounds__(256) void gd_transpose_kernel(const int* __restrict
                                                            const uint32_t* __restrict__ ws, int64_t ws_stride, int* __restrict__ area,
                                                            int* __restrict__ box) {
     __shared__ uint32_t s_v[GD_TH / 32 * GD_LD];
-    __shared__ unsigned red[4][5];
     const int p = p0 + blockIdx.y;
     const int h = dims[2 * p], w = dims[2 * p + 1];
     const int64_t off = bit_offsets[p];
@@ -145,8 +139,7 @@ __global__ __launch_bounds__(256) void gd_transpose_kernel(const int* __restrict
     const int tiles = col_tiles * row_tiles;                          // <= 32 * 128
     const int64_t swords = gd_stream_words((int64_t)h * w);           // read only where good: then h w <= max_pixels
     uint32_t* dst = (uint32_t*)(bits + off);
-    unsigned cnt = 0, x0 = 0xffffffffu, y0m = 0xffffffffu;
-    int x1 = -1, y1 = -1;
+    mb_stats stats;
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int tr = t / col_tiles, tc = t - tr * col_tiles;
         const int c0 = tc * GD_TW, y0 = tr * GD_TH;
@@ -168,41 +161,18 @@ __global__ __launch_bounds__(256) void gd_transpose_kernel(const int* __restrict
             if (c >= wsr || r >= rows) continue;
             const uint32_t m = good ? gd_row_word(s_v + (r >> 5) * GD_LD + cl * 33, 1, c, w, r & 31) : 0u;
             dst[sz_word_of(y0 + r, 32 * c, wsr)] = cc_pack(m);
-            if (STATS && m) gd_word_stats(m, c, y0 + r, cnt, x0, y0m, x1, y1);
+            if (STATS && m) mb_word(stats, m, c, y0 + r);
         }
         if (good) __syncthreads();                                    // the next tile stages into the same words
     }
-    if (!STATS) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        x0 = min(x0, __shfl_xor(x0, o, 64)); y0m = min(y0m, __shfl_xor(y0m, o, 64));
-        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-    }
-    if (lane == 0) {
-        unsigned* r = red[wave];
-        r[0] = cnt; r[1] = x0; r[2] = y0m; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned n = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        if (n) {                                                      // a workgroup that found nothing leaves the plane's results alone
-            atomicAdd(&area[p], (int)n);
-            atomicMin((unsigned*)&box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
-            atomicMin((unsigned*)&box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
-            atomicMax(&box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
-            atomicMax(&box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
-        }
-    }
+    if (STATS) mb_block_commit(stats, area, box, p);
 }
 
 // The transposition on the host: the stream of a plane of h x w (NULL: a refused plane, zero words) -> its rows at dst, area and box
 // where they are asked for (initialised by the caller; an empty plane leaves them alone)
 void gd_rows_host(const uint32_t* stream, int64_t swords, int h, int w, uint32_t* dst, int32_t* area, int32_t* box) {
     const int wsr = sz_words_per_row(w);
-    unsigned cnt = 0, x0 = 0xffffffffu, y0m = 0xffffffffu;
-    int x1 = -1, y1 = -1;
+    mb_stats stats;
     uint32_t v[32];
     for (int c = 0; c < wsr; ++c)
         for (int y0 = 0; y0 < h; y0 += 32) {
@@ -211,22 +181,46 @@ void gd_rows_host(const uint32_t* stream, int64_t swords, int h, int w, uint32_t
             for (int r = 0; r < std::min(32, h - y0); ++r) {
                 const uint32_t m = stream ? gd_row_word(v, 1, c, w, r) : 0u;
                 dst[sz_word_of(y0 + r, 32 * c, wsr)] = cc_pack(m);
-                if (m) gd_word_stats(m, c, y0 + r, cnt, x0, y0m, x1, y1);
+                if (m) mb_word(stats, m, c, y0 + r);
             }
         }
-    if (area && cnt) {
-        area[0] = (int)cnt;
-        box[0] = (int)x0; box[1] = (int)y0m; box[2] = x1; box[3] = y1;
+    if (area) mb_store(stats, area, box, 0);
+}
+
+// The prefix pass on the host: the inclusive prefix XOR of the stream `cur` of `words` words, stored to `out` or (or_in) ORed into it.
+// out may be cur itself.
+void gd_prefix_host(const uint32_t* cur, int64_t words, uint32_t* out, bool or_in) {
+    uint32_t before = 0u;
+    for (int64_t k = 0; k < words; ++k) {
+        const uint32_t c = cur[k], m = gd_prefix_word(c, before);
+        out[k] = or_in ? out[k] | m : m;
+        before ^= (uint32_t)__builtin_popcount(c) & 1u;
     }
+}
+
+// The last launch of a round of n planes of either decoder, behind gd_prefix_kernel (and the polygons' layers): the streams in the
+// round's slots -> the rows of the planes p0 .. p0 + n - 1, with area and box where the call asks for them.
+int gd_rows_round(const int32_t* dims, const int64_t* bit_offsets, uint8_t* bits, int64_t bits_bytes, int p0, int n, int64_t max_pixels,
+                  const uint32_t* ws, int64_t ws_stride, int32_t* area, int32_t* box, hipStream_t st) {
+    // workgroups per plane: one per 16384 pixels of the largest plane the slot admits, about 8192 in all and at most 256; they walk
+    // their plane's tiles in strides
+    const int64_t by_work = (max_pixels + 16383) / 16384, want = (8192 + n - 1) / n;
+    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_work, want), 256));
+    if (area)
+        hipLaunchKernelGGL(gd_transpose_kernel<true>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0, ws,
+                           ws_stride, (int*)area, (int*)box);
+    else
+        hipLaunchKernelGGL(gd_transpose_kernel<false>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0, ws,
+                           ws_stride, (int*)nullptr, (int*)nullptr);
+    CVLM_CHECK_LAUNCH();
+    return 0;
 }
 
 // what both decode entries refuse
 bool gd_bad(const int32_t* counts, int64_t total, const int64_t* run_offsets, const int32_t* dims, const int64_t* bit_offsets, int32_t P,
             int64_t max_pixels, const uint8_t* bits, int64_t nbytes, const int32_t* area, const int32_t* box, const int32_t* status) {
     if (!counts || !run_offsets || !dims || !bit_offsets || !bits || !status || (area == nullptr) != (box == nullptr)) return true;
-    if (((((uintptr_t)counts) | ((uintptr_t)dims) | ((uintptr_t)bits) | ((uintptr_t)area) | ((uintptr_t)box) | ((uintptr_t)status)) & 3) != 0 ||
-        ((((uintptr_t)run_offsets) | ((uintptr_t)bit_offsets)) & 7) != 0)
-        return true;
+    if (mb_misaligned(4, counts, dims, bits, area, box, status) || mb_misaligned(8, run_offsets, bit_offsets)) return true;
     return P < 1 || P > 65535 || total < 1 || nbytes < 4 || max_pixels < 1 || max_pixels > GT_MAX_PIXELS;
 }
 
@@ -399,9 +393,7 @@ bool gp_bad(const double* xy, int64_t total, const int64_t* poly_offsets, const 
             const int64_t* bit_offsets, int32_t P, int32_t Q, int64_t max_pixels, const uint8_t* bits, int64_t nbytes, const int32_t* area,
             const int32_t* box, const int32_t* status) {
     if (!xy || !poly_offsets || !plane_polys || !dims || !bit_offsets || !bits || !status || (area == nullptr) != (box == nullptr)) return true;
-    if (((((uintptr_t)plane_polys) | ((uintptr_t)dims) | ((uintptr_t)bits) | ((uintptr_t)area) | ((uintptr_t)box) | ((uintptr_t)status)) & 3) != 0 ||
-        ((((uintptr_t)xy) | ((uintptr_t)poly_offsets) | ((uintptr_t)bit_offsets)) & 7) != 0)
-        return true;
+    if (mb_misaligned(4, plane_polys, dims, bits, area, box, status) || mb_misaligned(8, xy, poly_offsets, bit_offsets)) return true;
     if (P < 1 || P > 65535 || Q < 1 || (int64_t)Q > (int64_t)P * PL_MAX_POLYS) return true;
     return total < 1 || nbytes < 4 || max_pixels < 1 || max_pixels > GT_MAX_PIXELS;
 }
@@ -421,7 +413,6 @@ __global__ __launch_bounds__(256) void gi_inter_kernel(const uint8_t* __restrict
                                                        int64_t b_bytes, const int64_t* __restrict__ b_off, const int* __restrict__ b_dims,
                                                        int Pb, const int* __restrict__ pairs, int* __restrict__ inter,
                                                        int* __restrict__ status) {
-    __shared__ int red[4];
     const int i = blockIdx.x;
     const int a = pairs[2 * i], b = pairs[2 * i + 1];
     if (!gi_pair_ok(a, b, Pa, Pb, a_dims, a_off, a_bytes, b_dims, b_off, b_bytes)) {    // the same for every thread of the pair
@@ -432,22 +423,15 @@ __global__ __launch_bounds__(256) void gi_inter_kernel(const uint8_t* __restrict
     const int wsr = sz_words_per_row(w), words = h * wsr;             // <= 2^23
     const uint32_t* pa = (const uint32_t*)(a_bits + a_off[a]);
     const uint32_t* pb = (const uint32_t*)(b_bits + b_off[b]);
-    int n = 0;
+    int n[1] = {0};
     for (int s0 = blockIdx.y * GI_SPAN; s0 < words; s0 += gridDim.y * GI_SPAN) {
 #pragma unroll
         for (int k = 0; k < GI_SPAN / 256; ++k) {
             const int wi = s0 + k * 256 + threadIdx.x;
-            if (wi < words) n += gi_word(pa[wi], pb[wi], wi % wsr, w);
+            if (wi < words) n[0] += gi_word(pa[wi], pb[wi], wi % wsr, w);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int s = red[0] + red[1] + red[2] + red[3];
-        if (s) atomicAdd(&inter[i], s);
-    }
+    if (mb_block_sum(n) && n[0]) atomicAdd(&inter[i], n[0]);
 }
 
 // what both intersection entries refuse
@@ -455,9 +439,7 @@ bool gi_bad(const uint8_t* a_bits, int64_t a_bytes, const int64_t* a_off, const 
             int64_t b_bytes, const int64_t* b_off, const int32_t* b_dims, int32_t Pb, const int32_t* pairs, int32_t N, int64_t max_words,
             const int32_t* inter, const int32_t* status) {
     if (!a_bits || !a_off || !a_dims || !b_bits || !b_off || !b_dims || !pairs || !inter || !status) return true;
-    if (((((uintptr_t)a_bits) | ((uintptr_t)a_dims) | ((uintptr_t)b_bits) | ((uintptr_t)b_dims) | ((uintptr_t)pairs) | ((uintptr_t)inter) |
-          ((uintptr_t)status)) & 3) != 0 || ((((uintptr_t)a_off) | ((uintptr_t)b_off)) & 7) != 0)
-        return true;
+    if (mb_misaligned(4, a_bits, a_dims, b_bits, b_dims, pairs, inter, status) || mb_misaligned(8, a_off, b_off)) return true;
     if (Pa < 1 || Pa > 65535 || Pb < 1 || Pb > 65535 || N < 1 || N > (1 << 20) || a_bytes < 4 || b_bytes < 4) return true;
     return max_words < 1 || max_words > (int64_t)SZ_MAX_SIDE * (SZ_MAX_SIDE / 32);
 }
@@ -476,9 +458,9 @@ int cvlm_mask_rle_decode(const int32_t* counts, int64_t total, const int64_t* ru
                          void* workspace, int64_t workspace_bytes, void* stream) {
     if (gd_bad(counts, total, run_offsets, dims, bit_offsets, P, max_pixels, bits, bits_bytes, area, box, status)) return CVLM_E_BADARG;
     const int64_t plane_bytes = gd_plane_ws_bytes(max_pixels);
-    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_bytes) return CVLM_E_BADARG;
+    if (mb_bad_workspace(workspace, workspace_bytes, plane_bytes)) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_bytes);              // planes per round
+    const int fit = mb_fit(P, workspace_bytes, plane_bytes);
     const int64_t ws_stride = plane_bytes / 4;
     uint32_t* ws = (uint32_t*)workspace;
     hipLaunchKernelGGL(gd_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)area, (int*)box, (int)P, (int*)status);
@@ -492,17 +474,8 @@ int cvlm_mask_rle_decode(const int32_t* counts, int64_t total, const int64_t* ru
         CVLM_CHECK_LAUNCH();
         hipLaunchKernelGGL(gd_prefix_kernel, dim3(n), dim3(GD_SCAN), 0, st, (const int*)dims, p0, ws, ws_stride);
         CVLM_CHECK_LAUNCH();
-        // workgroups per plane: one per 16384 pixels of the largest plane the slot admits, about 8192 in all and at most 256; they walk
-        // their plane's tiles in strides
-        const int64_t by_work = (max_pixels + 16383) / 16384, want = (8192 + n - 1) / n;
-        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_work, want), 256));
-        if (area)
-            hipLaunchKernelGGL(gd_transpose_kernel<true>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
-                               (const uint32_t*)ws, ws_stride, (int*)area, (int*)box);
-        else
-            hipLaunchKernelGGL(gd_transpose_kernel<false>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
-                               (const uint32_t*)ws, ws_stride, (int*)nullptr, (int*)nullptr);
-        CVLM_CHECK_LAUNCH();
+        const int rc = gd_rows_round(dims, bit_offsets, bits, bits_bytes, p0, n, max_pixels, ws, ws_stride, area, box, st);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -515,10 +488,7 @@ int cvlm_debug_mask_rle_decode_host(const int32_t* counts, int64_t total, const 
     status[0] = 0;
     std::vector<uint32_t> stream;
     for (int p = 0; p < P; ++p) {
-        if (area) {
-            area[p] = 0;
-            for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
-        }
+        if (area) mb_init(area, box, p);
         const int h = dims[2 * p], w = dims[2 * p + 1];
         const int64_t off = run_offsets[p], end = run_offsets[p + 1], boff = bit_offsets[p];
         const bool table = sz_plane_ok(h, w, boff, bit_offsets[p + 1], bits_bytes);
@@ -537,14 +507,7 @@ int cvlm_debug_mask_rle_decode_host(const int32_t* counts, int64_t total, const 
                 if (k < end - off - 1 && gd_toggle(e, hw, word, bit)) stream[(size_t)word] ^= bit;
             }
             good = good && e == hw;
-            if (good) {
-                uint32_t before = 0u;
-                for (int64_t k = 0; k < swords; ++k) {
-                    const uint32_t v = stream[(size_t)k];
-                    stream[(size_t)k] = gd_prefix_word(v, before);
-                    before ^= (uint32_t)__builtin_popcount(v) & 1u;
-                }
-            }
+            if (good) gd_prefix_host(stream.data(), swords, stream.data(), false);
         }
         if (!good) status[0] |= 1;
         if (!table) continue;                                         // nothing of its slice is stored
@@ -564,9 +527,9 @@ int cvlm_mask_poly_decode(const double* xy, int64_t total, const int64_t* poly_o
                           int32_t* area, int32_t* box, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
     if (gp_bad(xy, total, poly_offsets, plane_polys, dims, bit_offsets, P, Q, max_pixels, bits, bits_bytes, area, box, status)) return CVLM_E_BADARG;
     const int64_t plane_bytes = gd_plane_ws_bytes(max_pixels);
-    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < 2 * plane_bytes) return CVLM_E_BADARG;
+    if (mb_bad_workspace(workspace, workspace_bytes, 2 * plane_bytes)) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    const int fit = (int)std::min<int64_t>(P, workspace_bytes / (2 * plane_bytes));       // planes per round
+    const int fit = mb_fit(P, workspace_bytes, 2 * plane_bytes);
     const int64_t ws_stride = plane_bytes / 4;
     uint32_t* ws = (uint32_t*)workspace;                                                 // the round's accumulators, then its second streams
     uint32_t* cur = ws + (int64_t)fit * ws_stride;
@@ -587,15 +550,8 @@ int cvlm_mask_poly_decode(const double* xy, int64_t total, const int64_t* poly_o
                                (const int*)dims, p0, ws, cur, ws_stride, (int*)status);
             CVLM_CHECK_LAUNCH();
         }
-        const int64_t by_work = (max_pixels + 16383) / 16384, want = (8192 + n - 1) / n;   // cvlm_mask_rle_decode's grid
-        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_work, want), 256));
-        if (area)
-            hipLaunchKernelGGL(gd_transpose_kernel<true>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
-                               (const uint32_t*)ws, ws_stride, (int*)area, (int*)box);
-        else
-            hipLaunchKernelGGL(gd_transpose_kernel<false>, dim3(gx, n), dim3(256), 0, st, (const int*)dims, bit_offsets, bits, bits_bytes, p0,
-                               (const uint32_t*)ws, ws_stride, (int*)nullptr, (int*)nullptr);
-        CVLM_CHECK_LAUNCH();
+        const int rc = gd_rows_round(dims, bit_offsets, bits, bits_bytes, p0, n, max_pixels, ws, ws_stride, area, box, st);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -608,10 +564,7 @@ int cvlm_debug_mask_poly_decode_host(const double* xy, int64_t total, const int6
     status[0] = 0;
     std::vector<uint32_t> acc, cur;
     for (int p = 0; p < P; ++p) {
-        if (area) {
-            area[p] = 0;
-            for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
-        }
+        if (area) mb_init(area, box, p);
         const int h = dims[2 * p], w = dims[2 * p + 1];
         const int q0 = plane_polys[p], q1 = plane_polys[p + 1];
         const int64_t boff = bit_offsets[p];
@@ -650,12 +603,7 @@ int cvlm_debug_mask_poly_decode_host(const double* xy, int64_t total, const int6
                         first = false;
                     }
                 }
-                uint32_t before = 0u;
-                for (int64_t i = 0; i < swords; ++i) {
-                    const uint32_t c = cur[(size_t)i];
-                    acc[(size_t)i] |= gd_prefix_word(c, before);
-                    before ^= (uint32_t)__builtin_popcount(c) & 1u;
-                }
+                gd_prefix_host(cur.data(), swords, acc.data(), true);
             }
         }
         if (!good) status[0] |= 1;

@@ -71,18 +71,6 @@ GT_HD uint32_t gd_row_word(const uint32_t* v, int stride, int c, int w, int r) {
     return rl_gather(v, stride, n < 32 ? n : 32, r);
 }
 
-// Area and box of a row's unpacked word m != 0 of word column c of row y, folded into running values (x0 / y0 lowered as unsigned
-// minima from 0xffffffff, x1 / y1 raised from -1: cvlm_mask_pack's scheme)
-GT_HD void gd_word_stats(uint32_t m, int c, int y, unsigned& cnt, unsigned& x0, unsigned& y0, int& x1, int& y1) {
-    cnt += (unsigned)__builtin_popcount(m);
-    const unsigned lo = (unsigned)(32 * c + __builtin_ctz(m));
-    const int hi = 32 * c + 31 - __builtin_clz(m);
-    x0 = lo < x0 ? lo : x0;
-    y0 = (unsigned)y < y0 ? (unsigned)y : y0;
-    x1 = hi > x1 ? hi : x1;
-    y1 = y > y1 ? y : y1;
-}
-
 // ---- intersections of pairs of sized planes --------------------------------------------------------------------------------------------
 // Pair (a, b) of planes of two tables: both indices in range, both planes pass §19's check against their own tensors, equal sizes.
 GT_HD bool gi_pair_ok(int a, int b, int Pa, int Pb, const int* a_dims, const int64_t* a_off, int64_t a_bytes, const int* b_dims,

@@ -112,10 +112,8 @@ bool mt_bad(const int32_t* det_off, const int32_t* gt_off, const int64_t* pair_o
     if (N > 0 && !inter) return true;
     if (ND > 0 && (!det_area || !score || !dt_order || !dt_match || !dt_ignore)) return true;
     if (NG > 0 && (!gt_area || !gt_range_area || !gt_crowd || !gt_match || !gt_ignore)) return true;
-    if (((((uintptr_t)det_off) | ((uintptr_t)gt_off) | ((uintptr_t)inter) | ((uintptr_t)det_area) | ((uintptr_t)score) | ((uintptr_t)gt_area) |
-          ((uintptr_t)dt_order) | ((uintptr_t)dt_match) | ((uintptr_t)gt_match) | ((uintptr_t)status)) & 3) != 0)
-        return true;
-    return ((((uintptr_t)pair_off) | ((uintptr_t)gt_range_area) | ((uintptr_t)iou_thrs) | ((uintptr_t)area_rngs)) & 7) != 0;
+    if (mb_misaligned(4, det_off, gt_off, inter, det_area, score, gt_area, dt_order, dt_match, gt_match, status)) return true;
+    return mb_misaligned(8, pair_off, gt_range_area, iou_thrs, area_rngs);
 }
 
 }  // namespace

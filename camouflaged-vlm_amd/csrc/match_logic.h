@@ -12,7 +12,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "components_logic.h"
+#include "maskbits.h"
 
 #define MT_HD CC_HD
 

@@ -36,7 +36,6 @@ __global__ __launch_bounds__(256) void mo_morph_kernel(const uint32_t* __restric
                                                        uint32_t* __restrict__ band_bits, int* __restrict__ band_area) {
     __shared__ __attribute__((aligned(16))) uint32_t s_hd[MO_ROWS * MO_TW];
     __shared__ __attribute__((aligned(16))) uint32_t s_he[MO_ROWS * MO_TW];
-    __shared__ int red[4][3];
     const int tr = blockIdx.x / col_tiles, tc = blockIdx.x - tr * col_tiles;
     const int64_t plane = (int64_t)blockIdx.y * H * wpr;             // in words; 64-bit: P * H * W / 32 passes 2^31 words at large P
     const uint32_t* src = bits + plane;
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(256) void mo_morph_kernel(const uint32_t* __restric
     __syncthreads();
 
     const int cl = threadIdx.x & 15, c = c0 + cl;
-    int n_dil = 0, n_ero = 0, n_band = 0;
+    int n[3] = {0, 0, 0};                                             // set pixels of the dilation, the erosion, the band
     if (c < wpr) {
         for (int y = y0 + (threadIdx.x >> 4); y < min(H, y0 + MO_TH); y += 16) {
             const int lo = max(0, y - r), hi = min(H - 1, y + r);     // inside [ya, yb)
@@ -92,45 +91,29 @@ __global__ __launch_bounds__(256) void mo_morph_kernel(const uint32_t* __restric
             if (dil_bits) dil_bits[out] = cc_pack(d);
             if (ero_bits) ero_bits[out] = cc_pack(e);
             if (band_bits) band_bits[out] = cc_pack(b);
-            n_dil += __popc(d); n_ero += __popc(e); n_band += __popc(b);
+            n[0] += __popc(d); n[1] += __popc(e); n[2] += __popc(b);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_dil += __shfl_xor(n_dil, o, 64); n_ero += __shfl_xor(n_ero, o, 64); n_band += __shfl_xor(n_band, o, 64);
+    if (mb_block_sum(n)) {
+        if (dil_area && n[0]) atomicAdd(&dil_area[blockIdx.y], n[0]);
+        if (ero_area && n[1]) atomicAdd(&ero_area[blockIdx.y], n[1]);
+        if (band_area && n[2]) atomicAdd(&band_area[blockIdx.y], n[2]);
     }
-    if ((threadIdx.x & 63) == 0) {
-        int* w = red[threadIdx.x >> 6];
-        w[0] = n_dil; w[1] = n_ero; w[2] = n_band;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int sd = red[0][0] + red[1][0] + red[2][0] + red[3][0], se = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-        const int sb = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-        if (dil_area && sd) atomicAdd(&dil_area[blockIdx.y], sd);
-        if (ero_area && se) atomicAdd(&ero_area[blockIdx.y], se);
-        if (band_area && sb) atomicAdd(&band_area[blockIdx.y], sb);
-    }
-}
-
-bool mo_ranges_meet(const void* a, const void* b, uint64_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + bytes && y < x + bytes;
 }
 
 // what both entries refuse
 bool mo_bad_request(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t radius, const uint32_t* dil_bits, const int32_t* dil_area,
                     const uint32_t* ero_bits, const int32_t* ero_area, const uint32_t* band_bits, const int32_t* band_area) {
-    if (!bits || (((uintptr_t)bits | (uintptr_t)dil_bits | (uintptr_t)ero_bits | (uintptr_t)band_bits) & 3) != 0) return true;
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if (!bits || mb_misaligned(4, bits, dil_bits, ero_bits, band_bits) || mb_bad_planes(P, H, W)) return true;
     if (radius < 1 || radius > MO_MAXR) return true;
     if ((dil_bits != nullptr) != (dil_area != nullptr) || (ero_bits != nullptr) != (ero_area != nullptr) ||
         (band_bits != nullptr) != (band_area != nullptr))
         return true;
     if (!dil_bits && !ero_bits && !band_bits) return true;
     const uint64_t bytes = (uint64_t)P * ((uint64_t)H * W / 8);       // the kernel reads halo rows: no output may lie on the input
-    return mo_ranges_meet(bits, dil_bits, bytes) || mo_ranges_meet(bits, ero_bits, bytes) || mo_ranges_meet(bits, band_bits, bytes) ||
-           mo_ranges_meet(dil_bits, ero_bits, bytes) || mo_ranges_meet(dil_bits, band_bits, bytes) || mo_ranges_meet(ero_bits, band_bits, bytes);
+    return mb_ranges_meet(bits, bytes, dil_bits, bytes) || mb_ranges_meet(bits, bytes, ero_bits, bytes) ||
+           mb_ranges_meet(bits, bytes, band_bits, bytes) || mb_ranges_meet(dil_bits, bytes, ero_bits, bytes) ||
+           mb_ranges_meet(dil_bits, bytes, band_bits, bytes) || mb_ranges_meet(ero_bits, bytes, band_bits, bytes);
 }
 
 }  // namespace

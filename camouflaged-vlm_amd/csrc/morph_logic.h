@@ -2,7 +2,7 @@
 // and for the sequential host entry cvlm_debug_mask_morph_host, which runs these same functions word by word on the CPU.  No HIP call,
 // no allocation.
 //
-// A plane is H rows of W / 32 words in numpy.packbits' order; cc_unpack (components_logic.h) turns a stored word into bit i = pixel i
+// A plane is H rows of W / 32 words in numpy.packbits' order; cc_unpack (maskbits.h) turns a stored word into bit i = pixel i
 // of the word, so that "x + 1" is "bit << 1" and the word to the LEFT of a word holds the pixels BELOW its bit 0.  The structuring
 // element is the (2r + 1)^2 square, 1 <= r <= 16, and it is separable: a horizontal pass inside each row (mo_hdilate / mo_herode, one
 // neighbour word each side always suffices) and a vertical pass over the rows max(0, y - r) .. min(H - 1, y + r) (mo_column).  Pixels
@@ -10,7 +10,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "components_logic.h"
+#include "maskbits.h"
 
 #define MO_HD CC_HD
 

@@ -32,26 +32,18 @@ __global__ __launch_bounds__(256) void rl_init_kernel(int* __restrict__ n_runs, 
 
 // n_runs[blockIdx.y] += the transitions of RL_COUNT_WORDS words of the plane
 __global__ __launch_bounds__(256) void rl_count_kernel(const uint32_t* __restrict__ bits, int H, int wpr, int Wt, int* __restrict__ n_runs) {
-    __shared__ int red[4];
     const int words = H * wpr;                                        // < 2^26
     const uint32_t* src = bits + (int64_t)blockIdx.y * words;         // 64-bit: P * H * W / 32 passes 2^31 words at large P
-    int n = 0;
+    int n[1] = {0};
 #pragma unroll
     for (int i = 0; i < RL_COUNT_WORDS / 256; ++i) {
         const int wi = blockIdx.x * RL_COUNT_WORDS + i * 256 + threadIdx.x;
         if (wi < words) {
             const int y = wi / wpr;
-            n += __popc(rl_transition(src, y, wi - y * wpr, H, wpr, Wt));
+            n[0] += __popc(rl_transition(src, y, wi - y * wpr, H, wpr, Wt));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int s = red[0] + red[1] + red[2] + red[3];
-        if (s) atomicAdd(&n_runs[blockIdx.y], s);
-    }
+    if (mb_block_sum(n) && n[0]) atomicAdd(&n_runs[blockIdx.y], n[0]);
 }
 
 // Tile blockIdx.x = (row tile) * col_tiles + (column tile) of plane blockIdx.y of the round.  stream: the round's workspace, planes
@@ -156,18 +148,17 @@ __global__ __launch_bounds__(256) void rl_emit_kernel(const uint32_t* __restrict
 
 // what every entry refuses; Wt: the true width, the last word of a row holds at least one of its columns
 bool rl_bad_planes(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt) {
-    if (!bits || (((uintptr_t)bits) & 3) != 0) return true;
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return true;
+    if (!bits || mb_misaligned(4, bits) || mb_bad_planes(P, H, W)) return true;
     return Wt > W || Wt <= W - 32;
 }
 
 bool rl_bad_emit(const int64_t* offsets, const int32_t* counts, int64_t total, const int32_t* status) {
     if (!offsets || !counts || !status || total < 1) return true;
-    return (((uintptr_t)offsets) & 7) != 0 || ((((uintptr_t)counts) | ((uintptr_t)status)) & 3) != 0;
+    return mb_misaligned(8, offsets) || mb_misaligned(4, counts, status);
 }
 
 int rl_count(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, void* stream) {
-    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
+    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || mb_misaligned(4, n_runs)) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int wpr = W / 32, words = H * wpr;                          // < 2^26: the grid fits
     hipLaunchKernelGGL(rl_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (int*)n_runs, (int)P, (int*)nullptr);
@@ -183,13 +174,13 @@ int rl_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, c
             int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
     if (rl_bad_planes(bits, P, H, W, Wt) || rl_bad_emit(offsets, counts, total, status)) return CVLM_E_BADARG;
     const int64_t plane_bytes = rl_plane_ws_bytes((int64_t)H * W);
-    if (!workspace || (((uintptr_t)workspace) & 15) != 0 || workspace_bytes < plane_bytes) return CVLM_E_BADARG;
+    if (mb_bad_workspace(workspace, workspace_bytes, plane_bytes)) return CVLM_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int wpr = W / 32, words = H * wpr;
     const int HW = H * Wt, swords = (int)(((int64_t)HW + 31) / 32);   // the stream: swords <= words, equal when Wt = W
     const int col_tiles = (wpr + RL_TW - 1) / RL_TW, row_tiles = (H + RL_TH - 1) / RL_TH;   // words < 2^26: the grids fit
     const bool aligned = H % 32 == 0;
-    const int fit = (int)std::min<int64_t>(P, workspace_bytes / plane_bytes);              // planes per round
+    const int fit = mb_fit(P, workspace_bytes, plane_bytes);
     const int64_t ws_stride = plane_bytes / 4;
     uint32_t* ws = (uint32_t*)workspace;
     hipLaunchKernelGGL(rl_init_kernel, dim3(1), dim3(256), 0, st, (int*)nullptr, 0, (int*)status);
@@ -220,7 +211,7 @@ int rl_emit(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, c
 // The same functions on host memory, plane by plane and word by word, through rle_logic.h.  counts == NULL: only n_runs.
 int rl_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, int32_t* n_runs, const int64_t* offsets, int32_t* counts,
             int64_t total, int32_t* status) {
-    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || (((uintptr_t)n_runs) & 3) != 0) return CVLM_E_BADARG;
+    if (rl_bad_planes(bits, P, H, W, Wt) || !n_runs || mb_misaligned(4, n_runs)) return CVLM_E_BADARG;
     if (counts && rl_bad_emit(offsets, counts, total, status)) return CVLM_E_BADARG;
     const int wpr = W / 32, words = H * wpr;
     const int HW = H * Wt, swords = (int)(((int64_t)HW + 31) / 32);
@@ -266,7 +257,7 @@ int rl_host(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int32_t Wt, i
 extern "C" {
 
 int64_t cvlm_mask_rle_workspace_bytes(int32_t P, int32_t H, int32_t W) {
-    if (P < 1 || P > 65535 || H <= 0 || W <= 0 || W % 32 != 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return CVLM_E_BADARG;
+    if (mb_bad_planes(P, H, W)) return CVLM_E_BADARG;
     return (int64_t)P * rl_plane_ws_bytes((int64_t)H * W);
 }
 

@@ -4,7 +4,7 @@
 //
 // A plane is H rows of wpr = W / 32 words in numpy.packbits' order, of which the columns below the true width Wt <= W are the image
 // (Wt = W for the planes of cvlm_mask_pack; the sized planes of cvlm_mask_pack_sized end inside their last word: DESIGN.md §19);
-// cc_unpack (components_logic.h) turns a stored word into bit i = pixel i of the word.  COCO's order is column-major: position j = x * H + y.  A TRANSITION is a position whose pixel differs from
+// cc_unpack (maskbits.h) turns a stored word into bit i = pixel i of the word.  COCO's order is column-major: position j = x * H + y.  A TRANSITION is a position whose pixel differs from
 // the pixel of position j - 1 (from 0 at j = 0); the counts of the encoding are the differences of consecutive transition positions.
 //   - rl_transition: the transition bits of one word of the row-major plane -- one XOR with the word of the row above; row 0 takes
 //     the last row of the previous column, which is the last row's word shifted up by one pixel with the word before it carrying in.
@@ -14,7 +14,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "components_logic.h"
+#include "maskbits.h"
 
 #define RL_HD CC_HD
 

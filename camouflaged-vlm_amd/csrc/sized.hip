@@ -10,15 +10,9 @@
 
 namespace {
 
-// status = 0; area = 0, box = (-1, -1, -1, -1): x0 / y0 are then lowered by UNSIGNED minima, x1 / y1 raised by signed maxima
-// (cvlm_mask_pack's scheme: an empty plane needs no second pass)
+// status = 0; area = 0, box = -1
 __global__ __launch_bounds__(256) void sized_init_kernel(int* __restrict__ area, int* __restrict__ box, int P, int* __restrict__ status) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p == 0) status[0] = 0;
-    if (!area || p >= P) return;
-    area[p] = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
+    mb_init_planes(status, area, box, P);
 }
 
 // Plane blockIdx.y.  A UNIT is 64 consecutive pixels of one output row -- two words; a row has ceil(ws / 2) of them.  Wave v of
@@ -44,8 +38,7 @@ __global__ __launch_bounds__(256) void sized_pack_kernel(const float* __restrict
     const float* src = logits + (int64_t)p * Hs * Ws;
     uint32_t* dst = (uint32_t*)(bits + off);
     const double sx = (double)Ws / (double)w, sy = (double)Hs / (double)h;
-    unsigned cnt = 0, x0 = 0xffffffffu, y0 = 0xffffffffu;
-    int x1 = -1, y1 = -1;
+    mb_stats stats;
     for (int u = blockIdx.x * 4 + wave; u < units; u += gridDim.x * 4) {
         const int y = u / upr, c = 2 * (u - y * upr);                 // c: the first of the unit's two words
         const int x = 32 * c + lane;
@@ -54,44 +47,16 @@ __global__ __launch_bounds__(256) void sized_pack_kernel(const float* __restrict
         const unsigned long long both = __ballot(on);
         const uint32_t mine = lane < 32 ? (uint32_t)both : (uint32_t)(both >> 32);
         if ((lane & 31) == 0 && c + (lane >> 5) < ws) dst[sz_word_of(y, x, ws)] = cc_pack(mine);
-        if (STATS && on) {
-            ++cnt;
-            x0 = min(x0, (unsigned)x); y0 = min(y0, (unsigned)y);
-            x1 = max(x1, x); y1 = max(y1, y);
-        }
+        if (STATS && on) mb_pixel(stats, x, y);
     }
-    if (!STATS) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
-        x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-    }
-    __shared__ unsigned red[4][5];
-    if (lane == 0) {
-        unsigned* r = red[wave];
-        r[0] = cnt; r[1] = x0; r[2] = y0; r[3] = (unsigned)x1; r[4] = (unsigned)y1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned n = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        if (n) {                                                      // a workgroup that found nothing leaves the plane's results alone
-            atomicAdd(&area[p], (int)n);
-            atomicMin((unsigned*)&box[4 * p + 0], min(min(red[0][1], red[1][1]), min(red[2][1], red[3][1])));
-            atomicMin((unsigned*)&box[4 * p + 1], min(min(red[0][2], red[1][2]), min(red[2][2], red[3][2])));
-            atomicMax(&box[4 * p + 2], max(max((int)red[0][3], (int)red[1][3]), max((int)red[2][3], (int)red[3][3])));
-            atomicMax(&box[4 * p + 3], max(max((int)red[0][4], (int)red[1][4]), max((int)red[2][4], (int)red[3][4])));
-        }
-    }
+    if (STATS) mb_block_commit(stats, area, box, p);
 }
 
 // what both entries refuse
 bool sized_bad(const float* logits, int32_t P, int32_t Hs, int32_t Ws, const int32_t* dims, const int64_t* offsets, int32_t level,
                const uint8_t* bits, int64_t nbytes, int64_t max_words, const int32_t* area, const int32_t* box, const int32_t* status) {
     if (!logits || !dims || !offsets || !bits || !status || (area == nullptr) != (box == nullptr)) return true;
-    if ((((uintptr_t)logits) & 3) != 0 || (((uintptr_t)bits) & 3) != 0 || (((uintptr_t)offsets) & 7) != 0 || (((uintptr_t)dims) & 3) != 0 ||
-        ((((uintptr_t)area) | ((uintptr_t)box) | ((uintptr_t)status)) & 3) != 0)
-        return true;
+    if (mb_misaligned(4, logits, bits, dims, area, box, status) || mb_misaligned(8, offsets)) return true;
     if (P < 1 || P > 65535 || Hs <= 0 || Ws <= 0 || (int64_t)Hs * Ws >= ((int64_t)1 << 31) || level < 1 || level > 255) return true;
     return nbytes < 4 || max_words < 1 || max_words > (int64_t)SZ_MAX_SIDE * (SZ_MAX_SIDE / 32);
 }
@@ -129,10 +94,7 @@ int cvlm_debug_mask_pack_sized_host(const float* logits, int32_t P, int32_t Hs, 
     if (sized_bad(logits, P, Hs, Ws, dims, offsets, level, bits, bits_bytes, max_words, area, box, status)) return CVLM_E_BADARG;
     status[0] = 0;
     for (int p = 0; p < P; ++p) {
-        if (area) {
-            area[p] = 0;
-            for (int k = 0; k < 4; ++k) box[4 * p + k] = -1;
-        }
+        if (area) mb_init(area, box, p);
         const int h = dims[2 * p], w = dims[2 * p + 1];
         const int64_t off = offsets[p], end = offsets[p + 1];
         if (!sz_plane_ok(h, w, off, end, bits_bytes)) { status[0] |= 1; continue; }
@@ -140,7 +102,7 @@ int cvlm_debug_mask_pack_sized_host(const float* logits, int32_t P, int32_t Hs, 
         const float* src = logits + (int64_t)p * Hs * Ws;
         uint32_t* dst = (uint32_t*)(bits + off);
         const double sx = (double)Ws / (double)w, sy = (double)Hs / (double)h;
-        int n = 0, x0 = w, y0 = h, x1 = -1, y1 = -1;
+        mb_stats stats;
         for (int y = 0; y < h; ++y) {
             const sz_axis ay = sz_axis_of(y, Hs, sy, false);
             for (int c = 0; c < ws; ++c) {
@@ -148,17 +110,12 @@ int cvlm_debug_mask_pack_sized_host(const float* logits, int32_t P, int32_t Hs, 
                 for (int x = 32 * c; x < std::min(w, 32 * c + 32); ++x) {
                     if (!sz_pixel(src, Ws, sz_axis_of(x, Ws, sx, true), ay, level)) continue;
                     word |= sz_bit_of(x);
-                    ++n;
-                    x0 = std::min(x0, x); y0 = std::min(y0, y);
-                    x1 = std::max(x1, x); y1 = std::max(y1, y);
+                    mb_pixel(stats, x, y);
                 }
                 dst[sz_word_of(y, 32 * c, ws)] = cc_pack(word);
             }
         }
-        if (area && n) {
-            area[p] = n;
-            box[4 * p + 0] = x0; box[4 * p + 1] = y0; box[4 * p + 2] = x1; box[4 * p + 3] = y1;
-        }
+        if (area) mb_store(stats, area, box, p);
     }
     return 0;
 }

@@ -2,7 +2,7 @@
 // kernel (sized.hip) and for the sequential host entry cvlm_debug_mask_pack_sized_host, which runs these same functions pixel by pixel
 // on the CPU.  No HIP call, no allocation.
 //
-// A sized plane is h rows of ws = ceil(w / 32) words in numpy.packbits' order (components_logic.h: cc_pack); the pad bits of a row,
+// A sized plane is h rows of ws = ceil(w / 32) words in numpy.packbits' order (maskbits.h: cc_pack); the pad bits of a row,
 // columns w .. 32 ws - 1, are 0.  bit(y, x) = (v(y, x) * 255.0f >= (float)level) with v the value of cvlm_mask_to_u8's resize -- cv::resize
 // (INTER_LINEAR) on the fp32 sigmoid of the logits:
 //   - sz_axis_of: the two taps and weights of one output coordinate -- the source coordinate formed in double and rounded to float;
@@ -15,7 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "components_logic.h"
+#include "maskbits.h"
 
 #define SZ_HD CC_HD
 

@@ -92,7 +92,8 @@ def test_sized_entries_refuse_bad_arguments_without_gpu():
     ok = dict(logits=p, P=2, Hs=8, Ws=8, dims=p + 4096, off=p + 8192, level=128, bits=p + 12288, nbytes=4096, words=64, area=p + 16384,
               box=p + 20480, status=p + 24576)
     bad = [dict(logits=None), dict(dims=None), dict(off=None), dict(bits=None), dict(status=None), dict(bits=p + 12290),
-           dict(off=p + 8196), dict(dims=p + 4098), dict(P=0), dict(P=-1), dict(P=65536), dict(Hs=0), dict(Ws=0), dict(Hs=-8),
+           dict(off=p + 8196), dict(dims=p + 4098), dict(logits=p + 1), dict(area=p + 16386), dict(box=p + 20481), dict(status=p + 24578),
+           dict(P=0), dict(P=-1), dict(P=65536), dict(Hs=0), dict(Ws=0), dict(Hs=-8),
            dict(Hs=2 ** 16, Ws=2 ** 15), dict(level=0), dict(level=256), dict(level=-1), dict(area=None), dict(box=None),
            dict(nbytes=0), dict(words=0)]
     for kw in bad:
