@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void joint_hist_kernel(const uint8_t* __restri
 // Exact Euclidean distance transform with the index of the nearest foreground pixel, resolved like scipy's
 // distance_transform_edt (checked on the CPU against scipy on random masks): nearest foreground row inside each column,
 // ties to the smaller row; then along the row the column minimising dx^2 + dy^2, ties to the smaller column.
-// Workspace per image: near_y i32 [h][w] | d2 i32 [h][w] | Et f64 [h][w].
+// Workspace: near_y i32 [N][h][w] | d2 i32 [N][h][w] | Et f64 [N][h][w] | the weight pass's partial sums (| lohi for the uint8 entry).
 constexpr int WFM_INF = 1 << 29;
 
 __device__ __forceinline__ double wfm_norm(int v, int lo, int hi) {      // prepare_data per level, same IEEE operations

@@ -14,6 +14,7 @@ import torch
 
 from oracle import metrics_oracle as M
 from camouflaged_vlm_amd import evaltail as E
+from ends_cases import cod_counts_numpy as _cod_counts_numpy, counts_numpy as _counts_numpy      # shared with the edge tests
 
 TOL = 1e-9        # float64 sums in a different order (counts x levels instead of pixels)
 
@@ -27,20 +28,6 @@ def gold(golden_dir):
 def _cases(gold):
     for i in range(len(gold["cases"])):
         yield i, gold[f"case{i}_pre"], gold[f"case{i}_gt"]
-
-
-def _counts_numpy(pre, gt):
-    """what cvlm_mask_joint_hist returns, built with numpy"""
-    h, w = gt.shape
-    g = gt > 128
-    ys, xs = np.nonzero(g)
-    stats = np.asarray([g.sum(), xs.sum(), ys.sum()], dtype=np.int64)
-    cx, cy = M.centroid(g)
-    yy, xx = np.mgrid[0:h, 0:w]
-    quad = (yy >= cy) * 2 + (xx >= cx)
-    hist = np.zeros((4, 2, 256), dtype=np.int64)
-    np.add.at(hist, (quad.ravel(), g.ravel().astype(np.int64), pre.ravel().astype(np.int64)), 1)
-    return stats, hist
 
 
 def _close(a, b, tag):
@@ -92,26 +79,6 @@ def test_counts_to_metrics_match_reference_metricer(gold):
             got = E.metrics_from_counts(stats, hist, *gt.shape, same_class=same)
             for k in got:
                 _close(np.asarray(got[k], dtype=np.float64).reshape(-1), _ref(gold, i, same, k), (i, same, k))
-
-
-def _cod_counts_numpy(p, g):
-    """what cod_counts returns for one image (without the weighted-F sums), built with numpy in the reference's float32 operations"""
-    h, w = g.shape
-    gt = g > 128
-    pred = (p * np.float32(255)) / 255
-    mn, mx = pred.min(), pred.max()
-    pn = (pred - mn) / (mx - mn) if mx != mn else pred
-    q = (pn * 255).astype(np.uint8)
-    stats, hist = _counts_numpy(q, g)
-    cx, cy = M.centroid(gt)
-    yy, xx = np.mgrid[0:h, 0:w]
-    quad = (yy >= cy) * 2 + (xx >= cx)
-    mom = np.zeros((4, 2, 2), dtype=np.float64)
-    for k in range(4):
-        for c in range(2):
-            v = pn[(quad == k) & (gt == bool(c))].astype(np.float64)
-            mom[k, c] = (v.sum(), (v * v).sum())
-    return stats, hist, mom, pn, gt
 
 
 def test_calc_cod_from_counts_matches_reference(gold):
