@@ -134,7 +134,8 @@ class SAM(nn.Module):
 
     def infer_classes(self, input, clip_image, clip_zero_mask, classes=None, topk=None, quality=False, vocab=None, masks="logits",
                       overlaps=False, components=None, min_area=0, connectivity=8, holes=None, fill_holes=0, band=None,
-                      edge_threshold=None, rle=None, sizes=None, sized_level=128, ground_truth=None):
+                      edge_threshold=None, rle=None, sizes=None, sized_level=128, ground_truth=None, label_maps=False, label_weights=None,
+                      overlap_threshold=0.8):
         """EXTENSION, not a reference method: K class hypotheses per image from one encoder pass -- for each, the mask logits,
         the edge map and stage 2 that `infer_test` + demo.py:116-122 give had CLIP pass 1 predicted that class (the reference's
         decoder runs K prompts per image in one call, mask_decoder_edge.py:150-158).  Exactly one of `topk` (the K largest
@@ -146,7 +147,8 @@ class SAM(nn.Module):
         them; sizes= / sized_level=: the masks at each image's own (h, w) -- what test_ovcos_maskdecoder_edge.py:116-130 resizes to -- as
         bits of the uint8 mask >= sized_level (`sized`, engine.SizedMasks), rle="sized": those as COCO RLE with each image's own "size";
         ground_truth=(gt, gt_image): the sized planes' intersections with the annotations of their image (`gt_overlaps`,
-        engine.SizedOverlaps, whose `iou()` is the COCO IoU).
+        engine.SizedOverlaps, whose `iou()` is the COCO IoU); label_maps=True / label_weights= / overlap_threshold=: one hypothesis per
+        pixel at each image's own size (`label_maps`, engine.LabelMaps).
         -> engine.ClassHypotheses (INTEGRATION.md, "K class hypotheses per image")."""
         H, W = input.shape[-2:]
         assert H == self.inp_size and W == self.inp_size, \
@@ -156,7 +158,8 @@ class SAM(nn.Module):
                                             vocab=self._vocab(vocab), masks=masks, overlaps=overlaps, components=components,
                                             min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
                                             edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level,
-                                            ground_truth=ground_truth)
+                                            ground_truth=ground_truth, label_maps=label_maps, label_weights=label_weights,
+                                            overlap_threshold=overlap_threshold)
 
     def pack_masks(self, logits):
         """EXTENSION, not a reference method: (bits, area, box) of (N, S, S) or (N, 1, S, S) f32 mask logits, e.g. `infer_test`'s:
@@ -192,6 +195,19 @@ class SAM(nn.Module):
         image's own size sizes[i] = (h, w): the bits of sigmoid -> cv2.resize -> * 255 (test_ovcos_maskdecoder_edge.py:103,116-130) >=
         level -> engine.SizedMasks (engine.Cascade.pack_masks_sized)."""
         return self.cascade().pack_masks_sized(logits, sizes, level=level)
+
+    def label_maps(self, logits, sizes, *, K, weights=None, level=128, overlap_threshold=0.8):
+        """EXTENSION, not a reference method: (B * K, S, S) or (B * K, 1, S, S) f32 mask logits of K hypotheses per image as one label
+        map per image at its own size sizes[b] = (h, w) -- per pixel the hypothesis with the largest weight * resized sigmoid mask, per
+        hypothesis the areas and the overlap test of Mask2Former's panoptic_inference -> engine.LabelMaps (engine.Cascade.label_maps)."""
+        return self.cascade().label_maps(logits, sizes, K=K, weights=weights, level=level, overlap_threshold=overlap_threshold)
+
+    def label_iou(self, pred, gt, *, num_classes, ignore_index=255, reduce_zero_label=False, totals=None):
+        """EXTENSION, not a reference method: the vendored mmseg's intersect_and_union (models/mmseg/core/evaluation/metrics.py:5-59) of a
+        label map against ground truth, summed on the device -> int64 (3, num_classes) totals for segeval.eval_metrics
+        (engine.Cascade.label_iou)."""
+        return self.cascade().label_iou(pred, gt, num_classes=num_classes, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label,
+                                        totals=totals)
 
     def mask_rle_sized(self, sized):
         """EXTENSION, not a reference method: COCO run-length encoding of an engine.SizedMasks, "size": [h, w] of each image
@@ -254,7 +270,7 @@ class SAM(nn.Module):
     def decode_classes(self, enc, **kw):
         """EXTENSION, not a reference method: K prompts per encoded image -- `classes=`, `topk=` or caller-supplied text rows
         `text=` (what sam_text_proj takes at :342-344), optionally for a subset `images=`, with `quality=` / `stage2=` / `masks=` /
-        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` / `sizes=` / `sized_level=` / `ground_truth=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
+        `overlaps=` / `components=` / `min_area=` / `connectivity=` / `holes=` / `fill_holes=` / `band=` / `edge_threshold=` / `rle=` / `sizes=` / `sized_level=` / `ground_truth=` / `label_maps=` / `label_weights=` / `overlap_threshold=` as engine.Cascade.decode documents them; `vocab=` decodes against another vocabulary than the one the images were encoded
         with.  No encoder launch.  -> engine.ClassHypotheses."""
         self._vocab(kw.get("vocab"))
         return self.cascade().decode(enc, **kw)

@@ -25,9 +25,9 @@ from .hip import ACT_ABS_POST, ACT_GELU, ACT_NONE, ACT_QUICKGELU, ACT_RELU, H2
 # the packed-mask family lives in maskpost.py; its public names stay importable from here
 from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIELDS, HOLE_FIELDS, HOLES_MAXM, MASK_MODES, MATCH_AREA_RNGS, MATCH_CAP,
                        MATCH_IOU_THRS, MORPH_MAXR, OVERLAP_MAXK, OVERLAP_MAXP, RLE_SIZED, RLE_SOURCES, RLE_WS_CAP, SIZED_MAX_SIDE, CocoMatches,
-                       EdgeBits, MaskComponents, MaskHoles, MaskMorph, MaskPost, MaskRle, MaskUtilities, MatchRequest, SizedMasks, SizedOverlaps,
+                       EdgeBits, LabelMaps, MaskComponents, MaskHoles, MaskMorph, MaskPost, MaskRle, MaskUtilities, MatchRequest, SizedMasks, SizedOverlaps,
                        _edge_threshold, compact_request, components_request, edge_request, ground_truth_request, holes_request, match_request,
-                       morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
+                       label_tables, labels_request, morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry
 
 
@@ -1457,11 +1457,15 @@ class ClassHypotheses:
     # sized planes with the annotations of their own image: a SizedOverlaps over all pairs (p = b * K + k, q) with gt_image[q] == b,
     # ordered by p, then q; `gt_overlaps.iou(iscrowd)` is the COCO IoU of each pair.
     gt_overlaps: InitVar[Optional["SizedOverlaps"]] = None
+    # label_maps=True (needs sizes=), otherwise None; a pseudo-field like `sized`.  One hypothesis per pixel at each image's
+    # own size: a LabelMaps, on the device -- per pixel the k with the largest label_weights[b, k] * value (the value behind the sized
+    # bits), per hypothesis Mask2Former's areas and overlap test; `label_maps.categories(classes)` is the semantic map.
+    label_maps: InitVar[Optional["LabelMaps"]] = None
 
     def __post_init__(self, iou, mask_bits, area, box, inter, n_comp, comps, n_kept, kept_bits, kept_area, kept_box,
                       n_holes, holes, n_filled, filled_bits, filled_area, band_bits, band_area, band_inter,
-                      edge_bits, edge_area, edge_band, edge_inter, rle, sized, gt_overlaps):
-        self.rle, self.sized, self.gt_overlaps = rle, sized, gt_overlaps
+                      edge_bits, edge_area, edge_band, edge_inter, rle, sized, gt_overlaps, label_maps):
+        self.rle, self.sized, self.gt_overlaps, self.label_maps = rle, sized, gt_overlaps, label_maps
         self.edge_bits, self.edge_area, self.edge_band, self.edge_inter = edge_bits, edge_area, edge_band, edge_inter
         self.band_bits, self.band_area, self.band_inter = band_bits, band_area, band_inter
         self.iou, self.mask_bits, self.area, self.box, self.inter = iou, mask_bits, area, box, inter
@@ -2016,7 +2020,8 @@ class Cascade(_Base, MaskUtilities):
                       masks: str = "logits", overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                       connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0,
                       band: Optional[int] = None, edge_threshold: Optional[float] = None,
-                      rle: Optional[str] = None, sizes=None, sized_level: int = 128, ground_truth=None) -> ClassHypotheses:
+                      rle: Optional[str] = None, sizes=None, sized_level: int = 128, ground_truth=None,
+                      label_maps: bool = False, label_weights=None, overlap_threshold: float = 0.8) -> ClassHypotheses:
         """K class hypotheses per image from ONE encoder pass: masks, edge maps and stage 2 for each.
         topk=K: the K largest CLIP pass-1 logits of each image, descending (ties to the lower class index; classes[:, 0] is
         pass 1's prediction).  classes=: int64 (B, K) class indices of the loaded test bank, repeats allowed.  Exactly one of
@@ -2038,7 +2043,8 @@ class Cascade(_Base, MaskUtilities):
         score against it -- up to 65536 classes, topk <= 64 above 1024.
         masks= / overlaps=, components= / min_area= / connectivity=, holes= / fill_holes=, band=, edge_threshold=, rle=, sizes= /
         sized_level= and ground_truth=: the packed outputs of each hypothesis's mask, one paragraph each under
-        `MaskPost`, the plan `decode` runs too; checked with the rest before any launch.  The defaults ask for none of them and make
+        `MaskPost`, the plan `decode` runs too; checked with the rest before any launch.  label_maps= / label_weights= /
+        overlap_threshold= (they need sizes=): `label_maps`, one hypothesis per pixel at each image's own size.  The defaults ask for none of them and make
         exactly the launches, allocations and synchronisations of a call without them; rle='s one read synchronises the host with the
         side stream."""
         B = int(inp.shape[0])
@@ -2046,7 +2052,8 @@ class Cascade(_Base, MaskUtilities):
         K, host_classes = self._class_request(B, classes, topk, vocab)
         post = MaskPost(who="infer_classes", n=B, K=K, side=self.g.inp_size, masks=masks, overlaps=overlaps, components=components,
                         min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
-                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth)
+                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth,
+                        label_maps=label_maps, label_weights=label_weights, overlap_threshold=overlap_threshold)
         out_name = self._begin(inp, clip_image, clip_mask)
         g, dev = self.g, self.device
         P, T, C = B * K, g.grid * g.grid, g.prompt_embed_dim
@@ -2125,7 +2132,8 @@ class Cascade(_Base, MaskUtilities):
                overlaps: bool = False, components: Optional[int] = None, min_area: int = 0,
                connectivity: int = 8, holes: Optional[int] = None, fill_holes: int = 0, band: Optional[int] = None,
                edge_threshold: Optional[float] = None, rle: Optional[str] = None, sizes=None,
-               sized_level: int = 128, ground_truth=None) -> ClassHypotheses:
+               sized_level: int = 128, ground_truth=None, label_maps: bool = False, label_weights=None,
+               overlap_threshold: float = 0.8) -> ClassHypotheses:
         """K prompts for each of n encoded images: what `infer_classes` does behind its encoder, on the images of `enc`.  Exactly one
         of classes= (int64 (n, K), as in `infer_classes`), topk= (ranks enc.pass1_logits, same tie and NaN rules) and text= (f32
         (n, K, D): caller-supplied text rows of the bank's width, fed to sam_text_proj where the bank's rows go -- the
@@ -2140,7 +2148,7 @@ class Cascade(_Base, MaskUtilities):
         vocab: the vocabulary to decode against, default the one `enc` was encoded with (enc.vocab).  Another one first re-scores pass 1
         from enc.pass1_features against it -- one head launch, no encoder launch, no CLIP forward --; the returned pass1_logits are
         the re-scored ones.
-        masks= .. ground_truth=: as in `infer_classes` (`MaskPost`, the same plan), checked with the rest.  With
+        masks= .. overlap_threshold=: as in `infer_classes` (`MaskPost`, the same plan), checked with the rest.  With
         stage2=False and masks="bits" the chunk's planes are only packed; rle='s one read synchronises the host with the caller's
         stream; sizes= holds one (h, w) per decoded row -- per entry of `images` --, and gt_image[q] of ground_truth= names a decoded
         row, not an image of `enc`."""
@@ -2156,7 +2164,8 @@ class Cascade(_Base, MaskUtilities):
                                                  text=text, images=images, rank_cap=RANK_CAP if vocab is None else RANK_CAP_WIDE)
         post = MaskPost(who="decode", n=len(images), K=K, side=self.g.inp_size, masks=masks, overlaps=overlaps, components=components,
                         min_area=min_area, connectivity=connectivity, holes=holes, fill_holes=fill_holes, band=band,
-                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth)
+                        edge_threshold=edge_threshold, rle=rle, sizes=sizes, sized_level=sized_level, ground_truth=ground_truth,
+                        label_maps=label_maps, label_weights=label_weights, overlap_threshold=overlap_threshold)
         self.flush()
         self._fold_guard_check()
         g, dev, B = self.g, self.device, enc.B

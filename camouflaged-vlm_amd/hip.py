@@ -89,6 +89,16 @@ _SIGNATURES = {
     "cvlm_debug_mask_inter_sized_host": "i:plppiplppipilpp",
     "cvlm_coco_match": "i:pppiplppipppipipiipppppps",
     "cvlm_debug_coco_match_host": "i:pppiplppipppipipiipppppp",
+    "cvlm_label_init": "i:ppplppiipps",
+    "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
+    "cvlm_label_finish": "i:iipppppllpppps",
+    "cvlm_label_lookup": "i:piippllpipps",
+    "cvlm_label_iou_hist": "i:ppiliiiips",
+    "cvlm_debug_label_init_host": "i:ppplppiipp",
+    "cvlm_debug_label_accumulate_host": "i:piiiiiipppipppllpp",
+    "cvlm_debug_label_finish_host": "i:iipppppllpppp",
+    "cvlm_debug_label_lookup_host": "i:piippllpipp",
+    "cvlm_debug_label_iou_hist_host": "i:ppiliiiip",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -1263,6 +1273,96 @@ def coco_match_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_of
     _call("cvlm_debug_coco_match_host", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area),
           p(score), ND, p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det),
           p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+
+
+# ---- label maps: the tensors below live on the device for the cvlm_label_* entries and on the host for `host=True` ----
+def _label_state(score, winner, segment, areas, segment_id, n_segments, status, B: int, K: int) -> int:
+    """Shape and dtype checks of the state and outputs of the label entries (score None: an entry that does not take it) -> n_pix."""
+    n_pix = winner.numel()
+    assert score is None or (score.dtype == torch.float32 and tuple(score.shape) == (n_pix,) and score.is_contiguous())
+    for t in (winner, segment):
+        assert t.dtype == torch.int16 and tuple(t.shape) == (n_pix,) and t.is_contiguous()
+    assert areas.dtype == torch.int32 and tuple(areas.shape) == (3, B * K) and areas.is_contiguous()
+    assert segment_id is None or (segment_id.dtype == torch.int32 and tuple(segment_id.shape) == (B * K,) and segment_id.is_contiguous())
+    assert n_segments is None or (n_segments.dtype == torch.int32 and tuple(n_segments.shape) == (B,) and n_segments.is_contiguous())
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == winner.device for t in (score, segment, areas, segment_id, n_segments, status))
+    return n_pix
+
+
+def _label_tables(dims, pix_offsets, B: int, like: torch.Tensor) -> None:
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (B, 2) and dims.is_contiguous() and dims.device == like.device
+    assert pix_offsets.dtype == torch.int64 and tuple(pix_offsets.shape) == (B + 1,) and pix_offsets.is_contiguous()
+    assert pix_offsets.device == like.device
+
+
+def _label_entry(name: str, host: bool, t: torch.Tensor) -> str:
+    assert t.is_cuda != host, "host=True runs on host tensors, the device entry on device tensors"
+    if host:
+        return "cvlm_debug_" + name[5:] + "_host"
+    _on_current_device(t)
+    return name
+
+
+def label_init(score, winner, segment, areas, segment_id, n_segments, status, B: int, K: int, host: bool = False) -> None:
+    """The fill of a label-map state (include/cvlm.h: cvlm_label_init): score f32 [n_pix] = 0, winner / segment int16 [n_pix] = -1,
+    areas int32 [3][B * K] = segment_id int32 [B * K] = n_segments int32 [B] = 0, status int32 [1] = 0."""
+    n_pix = _label_state(score, winner, segment, areas, segment_id, n_segments, status, B, K)
+    _call(_label_entry("cvlm_label_init", host, score), score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, areas.data_ptr(),
+          segment_id.data_ptr(), B, K, n_segments.data_ptr(), status.data_ptr())
+
+
+def label_accumulate(planes: torch.Tensor, p0: int, B: int, K: int, dims, pix_offsets, weights, level: int, score, winner, segment,
+                     max_pixels: int, areas, status, host: bool = False) -> None:
+    """planes f32 [n][Hs][Ws] = the planes p0 .. p0 + n - 1 of B * K, offered in increasing k to the pixels of their images
+    (cvlm_label_accumulate): dims int32 [B][2], pix_offsets int64 [B + 1] in pixels, weights f32 [B * K] or None."""
+    n, Hs, Ws = planes.shape
+    assert planes.dtype == torch.float32 and planes.is_contiguous() and isinstance(level, int)
+    n_pix = _label_state(score, winner, segment, areas, None, None, status, B, K)
+    _label_tables(dims, pix_offsets, B, score)
+    assert weights is None or (weights.dtype == torch.float32 and weights.numel() == B * K and weights.is_contiguous()
+                               and weights.device == score.device)
+    assert planes.device == score.device
+    _call(_label_entry("cvlm_label_accumulate", host, score), planes.data_ptr(), p0, p0 + n, Hs, Ws, B, K, dims.data_ptr(),
+          pix_offsets.data_ptr(), _p(weights), level, score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, int(max_pixels),
+          areas.data_ptr(), status.data_ptr())
+
+
+def label_finish(B: int, K: int, dims, pix_offsets, overlap_threshold: float, winner, segment, max_pixels: int, areas, segment_id,
+                 n_segments, status, host: bool = False) -> None:
+    """won_area, kept_area, kept / segment_id / n_segments and the final `segment` map from the state (cvlm_label_finish); the
+    threshold is handed over as one host double."""
+    n_pix = _label_state(None, winner, segment, areas, segment_id, n_segments, status, B, K)
+    _label_tables(dims, pix_offsets, B, winner)
+    thr = C.c_double(overlap_threshold)
+    _call(_label_entry("cvlm_label_finish", host, winner), B, K, dims.data_ptr(), pix_offsets.data_ptr(), C.addressof(thr), winner.data_ptr(),
+          segment.data_ptr(), n_pix, int(max_pixels), areas.data_ptr(), segment_id.data_ptr(), n_segments.data_ptr(), status.data_ptr())
+
+
+def label_lookup(map_: torch.Tensor, B: int, K: int, dims, pix_offsets, max_pixels: int, table: torch.Tensor, void: int, out: torch.Tensor,
+                 status: torch.Tensor, host: bool = False) -> None:
+    """out int32 [n_pix] = map < 0 ? void : table[b * K + map] for the pixels of every image (cvlm_label_lookup)."""
+    n_pix = map_.numel()
+    assert map_.dtype == torch.int16 and map_.dim() == 1 and map_.is_contiguous()
+    assert table.dtype == torch.int32 and table.numel() == B * K and table.is_contiguous()
+    assert out.dtype == torch.int32 and tuple(out.shape) == (n_pix,) and out.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    _label_tables(dims, pix_offsets, B, map_)
+    assert table.device == map_.device and out.device == map_.device and status.device == map_.device
+    _call(_label_entry("cvlm_label_lookup", host, map_), map_.data_ptr(), B, K, dims.data_ptr(), pix_offsets.data_ptr(), n_pix,
+          int(max_pixels), table.data_ptr(), int(void), out.data_ptr(), status.data_ptr())
+
+
+def label_iou_hist(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, ignore_index: int, reduce_zero_label: bool, zero_first: bool,
+                   totals: torch.Tensor, host: bool = False) -> None:
+    """totals int64 [3][C] += (area_intersect, area_pred_label, area_label) of pred int32 [n] against gt int32 or uint8 [n]
+    (cvlm_label_iou_hist: mmseg's intersect_and_union)."""
+    assert pred.dtype == torch.int32 and pred.dim() == 1 and pred.is_contiguous()
+    assert gt.dtype in (torch.int32, torch.uint8) and tuple(gt.shape) == tuple(pred.shape) and gt.is_contiguous()
+    assert totals.dtype == torch.int64 and tuple(totals.shape) == (3, num_classes) and totals.is_contiguous()
+    assert gt.device == pred.device and totals.device == pred.device
+    _call(_label_entry("cvlm_label_iou_hist", host, pred), pred.data_ptr(), gt.data_ptr(), int(gt.dtype == torch.uint8), pred.numel(),
+          num_classes, int(ignore_index), int(bool(reduce_zero_label)), int(bool(zero_first)), totals.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

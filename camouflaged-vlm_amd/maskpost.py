@@ -360,6 +360,150 @@ class SizedMasks:
                           level=levels.pop() if len(levels) == 1 else 0)
 
 
+LABELS_MAX_K = 16384              # hypotheses per image of a label map: a winner is an int16 (csrc/labels_logic.h: LB_MAX_K)
+LABELS_MAX_CLASSES = 65536        # classes of Cascade.label_iou (LB_MAX_C)
+
+
+def label_tables(sizes):
+    """Host tables of label maps for a list of per-image (h, w): dims int32 (B, 2), pixel offsets int64 (B + 1) -- image
+    b's map is its h * w entries, row pitch w, the images lie back to back -- and the largest image's pixel count."""
+    dims = np.asarray(sizes, dtype=np.int32).reshape(-1, 2)
+    pixels = dims[:, 0].astype(np.int64) * dims[:, 1].astype(np.int64)
+    offsets = np.zeros(dims.shape[0] + 1, dtype=np.int64)
+    np.cumsum(pixels, out=offsets[1:])
+    return dims, offsets, int(pixels.max())
+
+
+def labels_request(*, label_maps=False, sizes=None, weights=None, level=128, overlap_threshold=0.8, n: int, K: int, masks="bits",
+                   who: str = "decode"):
+    """Every check of the label_maps= / label_weights= / overlap_threshold= arguments of Cascade.infer_classes / decode and of
+    Cascade.label_maps, on the host, before anything is launched (ValueError) -> None when no label maps are asked
+    for, otherwise (weights, level, overlap_threshold): weights is None (every weight 1), a float32 numpy array (n * K,) to upload, or
+    the caller's device tensor.  Label maps live at the images' own sizes: they need sizes= (checked by `sized_request`) and packed
+    masks; K <= 16384; level an int in 1 .. 255; overlap_threshold a real in (0, 1]; weights one f32 per hypothesis -- a host
+    sequence of n * K reals or n rows of K, none of them NaN, or a float32 device tensor of shape (n, K) or (n * K,)."""
+    if not isinstance(label_maps, (bool, np.bool_)):
+        raise ValueError(f"{who}: label_maps must be a bool, got {label_maps!r}")
+    if not label_maps:
+        if weights is not None:
+            raise ValueError(f"{who}: label_weights= weighs the hypotheses of a label map: ask for label_maps=True")
+        return None
+    if sizes is None:
+        raise ValueError(f"{who}: label maps live at the images' own sizes: give sizes=")
+    if masks == "logits":
+        raise ValueError(f"{who}: label_maps=True goes with the packed masks: ask for masks='bits' or 'both'")
+    if not 1 <= K <= LABELS_MAX_K:
+        raise ValueError(f"{who}: a label map holds 1 .. {LABELS_MAX_K} hypotheses per image, got K = {K}")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not is_int(level) or not 1 <= int(level) <= 255:
+        raise ValueError(f"{who}: the level of a label map must be an int in [1, 255], got {level!r}")
+    is_real = isinstance(overlap_threshold, (int, float, np.integer, np.floating)) and not isinstance(overlap_threshold, (bool, np.bool_))
+    if not is_real or not 0.0 < float(overlap_threshold) <= 1.0:      # a NaN fails the comparison too
+        raise ValueError(f"{who}: overlap_threshold must be a real in (0, 1], got {overlap_threshold!r}")
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((n, K), (n * K,)):
+            raise ValueError(f"{who}: label weights on the device must be float32 of shape ({n}, {K}), got {weights.dtype} "
+                             f"{tuple(weights.shape)}")
+    elif weights is not None:
+        try:
+            host = np.asarray(weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: label weights must be reals, one per hypothesis") from None
+        if host.shape not in ((n, K), (n * K,)):
+            raise ValueError(f"{who}: label weights hold {host.shape} entries for {n} images of {K} hypotheses")
+        if np.isnan(host).any():
+            raise ValueError(f"{who}: a label weight is NaN: leave the hypothesis out with class -1 instead")
+        weights = np.ascontiguousarray(host.reshape(-1), dtype=np.float32)
+    return weights, int(level), float(overlap_threshold)
+
+
+@dataclass
+class LabelMaps:
+    """One hypothesis per pixel at each image's own size (Cascade.label_maps, label_maps=True of infer_classes / decode; DESIGN.md
+    §23): Mask2Former's panoptic_inference over the K hypotheses of each image.  Image b's maps are its h * w entries, row pitch w,
+    from entry pix_offsets[b] of the flat tensors on.  All tensors on the device; nothing here synchronises but `check` and `to_host`."""
+    score: torch.Tensor             # (pixels,) f32: the winner's s = weight * value
+    winner: torch.Tensor            # (pixels,) int16: the k with the largest s (ties: the smallest k), -1 where no hypothesis takes part
+    segment: torch.Tensor           # (pixels,) int16: k where winner = k, k's own sized bit is set and k is kept; else -1
+    areas: torch.Tensor             # (3, B * K) int32: orig_area (|bit_k|), won_area (|winner = k|), kept_area (|winner = k and bit_k|)
+    segment_id: torch.Tensor        # (B * K,) int32: 1, 2, ... over the kept hypotheses of an image in increasing k; 0 = not kept
+    n_segments: torch.Tensor        # (B,) int32
+    status: torch.Tensor            # (1,) int32: non-zero if a kernel refused an image
+    dims: torch.Tensor              # (B, 2) int32 (h, w)
+    pix_offsets: torch.Tensor       # (B + 1,) int64, in pixels
+    sizes: list                     # B (h, w) pairs, on the host
+    K: int
+    level: int = 128
+    overlap_threshold: float = 0.8
+
+    @property
+    def B(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def kept(self) -> torch.Tensor:
+        """(B, K) bool: the hypotheses that own a segment."""
+        return self.segment_id.view(self.B, self.K) > 0
+
+    def _range(self, b: int) -> Tuple[int, int]:
+        _, offsets, _ = label_tables(self.sizes)                      # from the sizes alone: no read of the device
+        return int(offsets[b]), int(offsets[b + 1])
+
+    def image_of(self, flat: torch.Tensor, b: int) -> torch.Tensor:
+        """Image b's (h, w) view of a flat per-pixel tensor of these maps -- `winner`, `segment`, or what `categories` returned."""
+        lo, hi = self._range(b)
+        return flat[lo:hi].view(*self.sizes[b])
+
+    def winner_of(self, b: int) -> torch.Tensor:
+        return self.image_of(self.winner, b)
+
+    def segment_of(self, b: int) -> torch.Tensor:
+        return self.image_of(self.segment, b)
+
+    def check(self) -> None:
+        """RuntimeError if a kernel refused an image (synchronises).  The tables come from the same sizes as the allocation, so this
+        says that the library is broken."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("label_maps: a cvlm_label_* kernel refused an image whose slice did not fit its size")
+
+    def _lookup(self, table: torch.Tensor, which: str, void: int) -> torch.Tensor:
+        if which not in ("winner", "segment"):
+            raise ValueError(f"LabelMaps: which must be 'winner' or 'segment', got {which!r}")
+        is_int = isinstance(void, (int, np.integer)) and not isinstance(void, (bool, np.bool_))
+        if not is_int or not -2 ** 31 <= int(void) < 2 ** 31:
+            raise ValueError(f"LabelMaps: void must be an int32 value, got {void!r}")
+        out = torch.empty(self.winner.numel(), dtype=torch.int32, device=self.winner.device)
+        _, _, max_pixels = label_tables(self.sizes)
+        hip.label_lookup(getattr(self, which), self.B, self.K, self.dims, self.pix_offsets, max_pixels, table, int(void), out, self.status)
+        return out
+
+    def categories(self, labels, which: str = "winner", void: int = 255) -> torch.Tensor:
+        """The maps as class maps: (pixels,) int32 = labels[b, k] where the map holds k, `void` where it holds -1 (cvlm_label_lookup).
+        labels: (B, K) integers, e.g. `classes` of the call -- which="winner": the semantic map (MaskFormer's semantic inference with
+        one class per query); which="segment": the panoptic category map.  `image_of(result, b)` is image b's (h, w) view."""
+        t = torch.as_tensor(labels)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or tuple(t.shape) not in ((self.B, self.K), (self.B * self.K,)):
+            raise ValueError(f"LabelMaps.categories: labels must be ({self.B}, {self.K}) integers, got {t.dtype} {tuple(t.shape)}")
+        table = t.to(device=self.winner.device, dtype=torch.int32).contiguous().view(-1)
+        return self._lookup(table, which, void)
+
+    def panoptic(self) -> torch.Tensor:
+        """The published `panoptic_seg`: (pixels,) int32 segment ids 1 .. n_segments[b], 0 where no segment holds the pixel."""
+        return self._lookup(self.segment_id, "segment", 0)
+
+    def to_host(self) -> dict:
+        """Everything as numpy arrays in one read-back (synchronises): winner / segment as lists of (h, w) int16 arrays, orig_area /
+        won_area / kept_area / segment_id (B, K) int32, kept (B, K) bool, n_segments (B,), status."""
+        self.check()
+        B, K = self.B, self.K
+        winner, segment = self.winner.cpu().numpy(), self.segment.cpu().numpy()
+        areas = self.areas.cpu().numpy().reshape(3, B, K)
+        ids = self.segment_id.cpu().numpy().reshape(B, K)
+        cut = lambda flat: [flat[slice(*self._range(b))].reshape(self.sizes[b]) for b in range(B)]
+        return dict(winner=cut(winner), segment=cut(segment), orig_area=areas[0], won_area=areas[1], kept_area=areas[2], segment_id=ids,
+                    kept=ids > 0, n_segments=self.n_segments.cpu().numpy(), status=int(self.status.cpu().item()))
+
+
 def rle_decode_request(rles, who: str = "rle_decode"):
     """Every check of a list of COCO run-length dicts {"size": [h, w], "counts": list | bytes | str}, on the host, before
     anything is launched (ValueError) -> (counts int32 (total,), run offsets int64 (P + 1,) in elements of counts, the P (h, w) pairs).
@@ -939,6 +1083,101 @@ class MaskUtilities:
         self._pack_sized(logits.detach().contiguous().view(N, Hs, Ws), out, dims, max_words, 0, N, 0)
         return out
 
+    # ---- label maps -------------------------------------------------------------------------------------------------
+    def _label_outputs(self, sizes, K: int, weights, level: int, overlap_threshold: float):
+        """The LabelMaps of K hypotheses per (h, w) of `sizes` with its two tables uploaded, the weights on the device (or None) and
+        the largest image's pixel count; cvlm_label_init has written the fill."""
+        dims, offsets, max_pixels = label_tables(sizes)
+        dev, B, n_pix = self.device, len(sizes), int(offsets[-1])
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        i16 = lambda: torch.empty(n_pix, dtype=torch.int16, device=dev)
+        out = LabelMaps(score=torch.empty(n_pix, dtype=torch.float32, device=dev), winner=i16(), segment=i16(), areas=i32(3, B * K),
+                        segment_id=i32(B * K), n_segments=i32(B), status=i32(1), dims=torch.from_numpy(dims).to(dev),
+                        pix_offsets=torch.from_numpy(offsets).to(dev), sizes=[tuple(s) for s in sizes], K=K, level=level,
+                        overlap_threshold=overlap_threshold)
+        if isinstance(weights, np.ndarray):
+            weights = torch.from_numpy(weights).to(dev)
+        elif weights is not None:
+            weights = weights.detach().contiguous().view(-1)
+        hip.label_init(out.score, out.winner, out.segment, out.areas, out.segment_id, out.n_segments, out.status, B, K)
+        return out, weights, max_pixels
+
+    @staticmethod
+    def _label_accumulate(planes: torch.Tensor, out: "LabelMaps", weights, max_pixels: int, p0: int, p1: int) -> None:
+        """cvlm_label_accumulate of the p1 - p0 full-resolution planes p0 .. p1 - 1: one launch, whatever images they belong to."""
+        hip.label_accumulate(planes[:p1 - p0], p0, out.B, out.K, out.dims, out.pix_offsets, weights, out.level, out.score, out.winner,
+                             out.segment, max_pixels, out.areas, out.status)
+
+    @staticmethod
+    def _label_finish(out: "LabelMaps", max_pixels: int) -> None:
+        hip.label_finish(out.B, out.K, out.dims, out.pix_offsets, out.overlap_threshold, out.winner, out.segment, max_pixels,
+                         out.areas, out.segment_id, out.n_segments, out.status)
+
+    def label_maps(self, logits: torch.Tensor, sizes, *, K: int, weights=None, level: int = 128, overlap_threshold: float = 0.8) -> "LabelMaps":
+        """One label map per image from (B * K, Hs, Ws) or (B * K, 1, Hs, Ws) f32 mask logits on this engine's device, plane b * K + k the
+        k-th hypothesis of image b, at the B sizes (h, w) of `sizes` -> LabelMaps (cvlm_label_init / accumulate / finish).
+        Per pixel the hypothesis with the largest weight * value wins, the value being the reference's resized sigmoid mask as
+        `pack_masks_sized` forms it (ties: the smallest k; a NaN plane never wins); per hypothesis Mask2Former's areas and overlap test
+        decide which own a segment.  weights: one per hypothesis -- the score that ranks them is the caller's: a softmax of pass-1
+        logits at the hypothesis's class, a predicted quality --, None for 1.  Five launches on the caller's stream, the tables
+        uploaded before them; no workspace, no synchronisation.  ValueError before anything is launched for anything else."""
+        N, Hs, Ws = self._f32_planes("label_maps", "logits", logits, "H, W")
+        is_int = isinstance(K, (int, np.integer)) and not isinstance(K, (bool, np.bool_))
+        if not is_int or K < 1 or N % K != 0:
+            raise ValueError(f"label_maps: {N} planes are no whole number of images of K = {K!r} hypotheses")
+        B = N // int(K)
+        if not 1 <= B <= 65535 or Hs < 1 or Ws < 1 or Hs * Ws >= 2 ** 31:
+            raise ValueError(f"label_maps: {B} images of planes of {Hs} x {Ws}: 1 .. 65535 images of fewer than 2^31 pixels")
+        sreq = sized_request(sizes=sizes, sized_level=level, n=B, who="label_maps")
+        lreq = labels_request(label_maps=True, sizes=sizes, weights=weights, level=level, overlap_threshold=overlap_threshold, n=B, K=int(K),
+                              who="label_maps")
+        weights, level, overlap_threshold = lreq
+        if not logits.is_cuda or (isinstance(weights, torch.Tensor) and weights.device != logits.device):
+            raise ValueError("label_maps: logits (and weights given as a device tensor) must be on this engine's device")
+        out, weights, max_pixels = self._label_outputs(sreq[0], int(K), weights, level, overlap_threshold)
+        self._label_accumulate(logits.detach().contiguous().view(N, Hs, Ws), out, weights, max_pixels, 0, N)
+        self._label_finish(out, max_pixels)
+        return out
+
+    def label_iou(self, pred, gt, *, num_classes: int, ignore_index: int = 255, reduce_zero_label: bool = False, totals=None) -> torch.Tensor:
+        """mmseg's intersect_and_union of a predicted label map against ground truth, summed on the device (cvlm_label_iou_hist, DESIGN.md
+        §23) -> totals int64 (3, num_classes) = (area_intersect, area_pred_label, area_label), which `segeval.eval_metrics` turns into
+        aAcc, Acc and IoU / Dice.  pred: integers of any shape, e.g. `LabelMaps.categories(classes)`; gt: as many integers, uint8 or
+        int32; both on this engine's device, or host arrays that are uploaded.  The kernel reads int32: any other integer type is
+        converted, and its values must lie in the int32 range -- a host array is checked (ValueError), a device tensor is the caller's
+        contract (a check would synchronise; a value outside the range wraps).  totals: the result
+        of an earlier call, accumulated into -- a dataset's batches sum on the device; None starts from zero.  A value outside
+        [0, num_classes - 1] is counted nowhere (np.histogram would count the value num_classes in the last class); `label_map` is the
+        caller's: remap before upload.  No synchronisation.  ValueError before anything is launched for anything else."""
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        if not is_int(num_classes) or not 1 <= int(num_classes) <= LABELS_MAX_CLASSES:
+            raise ValueError(f"label_iou: num_classes must be an int in [1, {LABELS_MAX_CLASSES}], got {num_classes!r}")
+        if not is_int(ignore_index) or not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+            raise ValueError(f"label_iou: ignore_index must be an int32 value, got {ignore_index!r}")
+        if not isinstance(reduce_zero_label, (bool, np.bool_)):
+            raise ValueError(f"label_iou: reduce_zero_label must be a bool, got {reduce_zero_label!r}")
+        maps = []
+        for name, m in (("pred", pred), ("gt", gt)):
+            t = torch.as_tensor(m) if isinstance(m, (torch.Tensor, np.ndarray)) else None
+            if t is None or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.numel() < 1:
+                raise ValueError(f"label_iou: {name} must be a non-empty integer tensor or array, got {type(m).__name__}")
+            keep = name == "gt" and t.dtype == torch.uint8
+            if not t.is_cuda and t.dtype not in (torch.int32, torch.uint8, torch.int16, torch.int8) and \
+                    (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+                raise ValueError(f"label_iou: {name} holds a value outside the int32 range")
+            maps.append(t.detach().to(device=self.device, dtype=torch.uint8 if keep else torch.int32).contiguous().view(-1))
+        if maps[0].numel() != maps[1].numel():
+            raise ValueError(f"label_iou: pred holds {maps[0].numel()} pixels, gt {maps[1].numel()}")
+        C_ = int(num_classes)
+        fresh = totals is None
+        if fresh:
+            totals = torch.empty(3, C_, dtype=torch.int64, device=self.device)
+        elif not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (3, C_) or \
+                totals.device != maps[0].device or not totals.is_contiguous():
+            raise ValueError(f"label_iou: totals must be what an earlier call with num_classes = {C_} returned")
+        hip.label_iou_hist(maps[0], maps[1], C_, int(ignore_index), bool(reduce_zero_label), fresh, totals)
+        return totals
+
     def mask_rle_sized(self, sized: "SizedMasks") -> "MaskRle":
         """COCO run-length encoding of sized planes -> MaskRle whose `to_coco()` writes each plane's own "size": [h, w],
         what an evaluator holds against an annotation of the original image.  One cvlm_mask_rle_count_w call per run of consecutive
@@ -1173,13 +1412,19 @@ class MaskPost:
     a SizedOverlaps with the intersection of every hypothesis's sized plane with every annotation of its own image -- pairs
     (b * K + k, q) ordered by the plane, then q --, by one cvlm_mask_inter_sized call behind the last chunk; `gt_overlaps.iou(iscrowd)`
     is the COCO IoU.  Nothing is matched or chosen.
+    label_maps=True / label_weights= / overlap_threshold= (`labels_request`; needs sizes=): adds `label_maps`, a
+    LabelMaps with one hypothesis per pixel of each image at its own size -- Mask2Former's panoptic_inference at the level sized_level,
+    the weights (B, K) being the caller's scores.  cvlm_label_init with the other allocations, the weights uploaded before the first
+    chunk, one cvlm_label_accumulate per chunk right behind cvlm_mask_pack_sized on the chunk's planes while they sit in the workspace,
+    cvlm_label_finish behind the last chunk: about 8 bytes per image pixel, no (B, K, S, S) tensor, no synchronisation.
     Each option is independent of the others: without it the call makes exactly the launches, allocations and synchronisations it
     makes with the others alone, and every other field keeps its bits."""
     FIELDS = ("masks", "edges", "mask_bits", "area", "box", "inter") + COMPONENT_FIELDS + HOLE_FIELDS + BAND_FIELDS + EDGE_FIELDS + \
-        ("rle", "sized", "gt_overlaps")
+        ("rle", "sized", "gt_overlaps", "label_maps")
 
     def __init__(self, *, who: str, n: int, K: int, side: int, masks="logits", overlaps=False, components=None, min_area=0, connectivity=8,
-                 holes=None, fill_holes=0, band=None, edge_threshold=None, rle=None, sizes=None, sized_level=128, ground_truth=None):
+                 holes=None, fill_holes=0, band=None, edge_threshold=None, rle=None, sizes=None, sized_level=128, ground_truth=None,
+                 label_maps=False, label_weights=None, overlap_threshold=0.8):
         self.n, self.K, self.side = n, K, side
         self.want_logits, self.want_bits, self.want_inter = compact_request(masks=masks, overlaps=overlaps, n=n, K=K, who=who)
         self.want_comps, self.comps_m, self.min_area, self.connectivity = components_request(
@@ -1194,6 +1439,9 @@ class MaskPost:
         self.sizes, self.sized_level = (None, None) if sreq is None else sreq
         greq = ground_truth_request(ground_truth, sreq, n, who=who)
         self.gt, self.gt_image = (None, None) if greq is None else greq
+        self.labels_req = labels_request(label_maps=label_maps, sizes=sizes, weights=label_weights, level=sized_level,
+                                         overlap_threshold=overlap_threshold, n=n, K=K, masks=masks, who=who)
+        self.label_weights_in = label_weights if isinstance(label_weights, torch.Tensor) and label_weights.is_cuda else None
         for f in self.FIELDS:
             setattr(self, f, None)
 
@@ -1227,6 +1475,8 @@ class MaskPost:
             self.edge_inter = i32(n, K, K) if self.want_edge_inter else None
         if self.sizes is not None:
             self.sized, self.sized_dims, self.sized_max_words = eng._sized_outputs(self.sizes, self.sized_level, K, -(-n * K // chunk))
+        if self.labels_req is not None:
+            self.label_maps, self.label_weights, self.label_max_pixels = eng._label_outputs(self.sizes, K, *self.labels_req)
 
     def chunk_planes(self, p0: int, p1: int):
         """Where the full-resolution planes of the prompts p0 <= p < p1 go: the result's tensors, or with masks="bits" the workspace
@@ -1247,6 +1497,8 @@ class MaskPost:
             hip.mask_pack(planes, bits, rows(self.area, 0), rows(self.box, 1))
         if self.sized is not None:
             eng._pack_sized(planes, self.sized, self.sized_dims, self.sized_max_words, p0, p1, call)
+        if self.label_maps is not None:
+            eng._label_accumulate(planes, self.label_maps, self.label_weights, self.label_max_pixels, p0, p1)
         if self.want_band:
             hip.mask_morph(bits, S, S, self.band_radius, band_bits=rows(self.band_bits, 1), band_area=rows(self.band_area, 0))
         if self.want_edges:
@@ -1282,10 +1534,12 @@ class MaskPost:
         if self.gt is not None:
             self.gt_overlaps = eng.mask_inter_sized(self.sized, self.gt, a_image=[b for b in range(self.n) for _ in range(self.K)],
                                                     b_image=self.gt_image)
+        if self.label_maps is not None:
+            eng._label_finish(self.label_maps, self.label_max_pixels)
 
     def outputs(self) -> tuple:
         """Every tensor of the result but `masks` and `edges`, in the order of FIELDS: what the caller's stream must wait for."""
-        out = [getattr(self, f) for f in self.FIELDS[2:-3]]
+        out = [getattr(self, f) for f in self.FIELDS[2:-4]]
         if self.rle is not None:
             out += [self.rle.counts, self.rle.offsets, self.rle.n_runs, self.rle.status]
         if self.sized is not None:
@@ -1293,11 +1547,15 @@ class MaskPost:
         if self.gt_overlaps is not None:
             o = self.gt_overlaps
             out += [o.pairs, o.inter, o.area_a, o.area_b, o.status]
+        if self.label_maps is not None:
+            m = self.label_maps
+            out += [m.score, m.winner, m.segment, m.areas, m.segment_id, m.n_segments, m.status, m.dims, m.pix_offsets]
         return tuple(t for t in out if t is not None)
 
     def inputs(self) -> tuple:
-        """The caller's tensors this plan reads on the decoding stream: the ground truth's."""
-        return () if self.gt is None else (self.gt.bits, self.gt.offsets, self.gt.area)
+        """The caller's tensors this plan reads on the decoding stream: the ground truth's and label weights given on the device."""
+        ins = () if self.gt is None else (self.gt.bits, self.gt.offsets, self.gt.area)
+        return ins if self.label_weights_in is None else ins + (self.label_weights_in,)
 
     def fields(self) -> dict:
         """The results as keywords of ClassHypotheses(...)."""

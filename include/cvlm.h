@@ -871,6 +871,79 @@ int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_off
                                const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det, int32_t* dt_order,
                                int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status);
 
+/* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
+ * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
+ * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
+ * overlap_threshold`) restated on the device, and mmseg's intersect_and_union (models/mmseg/core/evaluation/metrics.py:5-59) for a
+ * label map against ground truth.
+ * Planes and tables.  B images of K hypotheses each, B in [1, 65535], K in [1, 16384]; plane p = b * K + k is an f32 plane Hs x Ws of
+ * mask logits.  dims int32 [B][2] = (h, w) of each IMAGE, 1 <= h, w <= 16384; pix_offsets int64 [B + 1] in PIXELS: image b's maps are
+ * its h * w entries, row pitch w, from entry pix_offsets[b] on; n_pix is the length of the maps in pixels.  v_p(y, x) is the value
+ * cvlm_mask_pack_sized forms (csrc/sized_logic.h, called) and bit_p(y, x) = (v * 255.0f >= (float)level) its bit, to the last bit: the
+ * published `>= 0.5` at the project's level rule (0.5 itself would be level 127.5).
+ * State and outputs, 8 bytes per pixel in all: score f32 [n_pix], the best s so far; winner int16 [n_pix], -1 = none; segment int16
+ * [n_pix].  areas int32 [3][B * K] = orig_area (|bit_k|, the published original_area), won_area (|winner = k|, mask_area), kept_area
+ * (|winner = k and bit_k|); segment_id int32 [B * K]; n_segments int32 [B]; status int32 [1].
+ * cvlm_label_init writes the fill -- score 0, winner and segment -1, areas, segment_id and n_segments 0, status 0 -- so that a
+ * sequence init, accumulate ..., finish can be replayed into used outputs.
+ * cvlm_label_accumulate offers the planes p0 <= p < p1 (logits points at plane p0: a chunk, which may begin and end inside an
+ * image) to the pixels of the images they belong to, in increasing k: s = w_p * v_p, one fp32 product, weights f32 [B * K] or NULL
+ * for 1.0f.  A hypothesis takes part at a pixel iff neither w_p nor v_p is NaN; the first to take part is taken, a later one iff its s
+ * is strictly larger -- so on equal s the smallest k wins, +0 and -0 are equal, and a pixel where none takes part stays -1.  Behind
+ * the call segment holds the winner where the winner's own bit is set, else -1, and orig_area[p] has been summed.  One launch, grid
+ * (workgroups, images the chunk touches); a wave takes 64 consecutive pixels of one row, a lane forms its axis tables once and walks
+ * the planes with the running best in registers: a pixel's state is read and written once per call (and per 1024 planes), no
+ * atomics on it, no order between workgroups.  The result does not depend on how the planes are cut into calls, provided the calls
+ * come in increasing plane order on one stream.  max_pixels: the largest h * w, which sizes the grid (a smaller value costs time).
+ * cvlm_label_finish, once behind the last accumulate: three launches -- won_area and kept_area counted from the maps (lanes of a wave
+ * that hold the same k issue one atomic); per image, kept[k] = won_area > 0 and orig_area > 0 and kept_area > 0 and not
+ * ((double)won_area / (double)orig_area < overlap_threshold), segment_id = 1, 2, ... over the kept k in increasing k (the published
+ * current_segment_id; 0 = not kept) and n_segments; then segment keeps k only where k is kept.  overlap_threshold points at ONE double
+ * in HOST memory, read before the launches (published default 0.8).
+ * cvlm_label_lookup: out int32 [n_pix]; out[pix] = map[pix] < 0 ? void_value : table[b * K + map[pix]], table int32 [B * K] -- class
+ * labels over winner: the semantic map; over segment: the panoptic categories; segment_id over segment with void 0: panoptic_seg.
+ * Before anything of an image is read or stored every kernel checks 1 <= h, w <= 16384, 0 <= pix_offsets[b], pix_offsets[b + 1] -
+ * pix_offsets[b] == h * w and pix_offsets[b + 1] <= n_pix; an image that fails is skipped whole, keeps the fill and ORs 1 into status[0]
+ * (only cvlm_label_init clears it).  No workspace, no allocation, no synchronisation, 64-bit offsets.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (weights may be NULL); an f32 / int32 pointer not 4-byte, an
+ * int16 pointer not 2-byte, pix_offsets not 8-byte aligned; B or K outside their ranges; n_pix < 1; max_pixels outside [1, 2^28]; Hs or
+ * Ws <= 0, Hs * Ws >= 2^31; level outside [1, 255]; p0 < 0, p1 <= p0 or p1 > B * K; overlap_threshold NaN, <= 0 or > 1. */
+int cvlm_label_init(float* score, int16_t* winner, int16_t* segment, int64_t n_pix, int32_t* areas, int32_t* segment_id, int32_t B,
+                    int32_t K, int32_t* n_segments, int32_t* status, void* stream);
+int cvlm_label_accumulate(const float* logits, int32_t p0, int32_t p1, int32_t Hs, int32_t Ws, int32_t B, int32_t K, const int32_t* dims,
+                          const int64_t* pix_offsets, const float* weights, int32_t level, float* score, int16_t* winner,
+                          int16_t* segment, int64_t n_pix, int64_t max_pixels, int32_t* areas, int32_t* status, void* stream);
+int cvlm_label_finish(int32_t B, int32_t K, const int32_t* dims, const int64_t* pix_offsets, const double* overlap_threshold,
+                      const int16_t* winner, int16_t* segment, int64_t n_pix, int64_t max_pixels, int32_t* areas, int32_t* segment_id,
+                      int32_t* n_segments, int32_t* status, void* stream);
+int cvlm_label_lookup(const int16_t* map, int32_t B, int32_t K, const int32_t* dims, const int64_t* pix_offsets, int64_t n_pix,
+                      int64_t max_pixels, const int32_t* table, int32_t void_value, int32_t* out, int32_t* status, void* stream);
+/* cvlm_label_iou_hist: intersect_and_union (metrics.py:41-56) summed into totals int64 [3][C] = area_intersect (pred = gt = c),
+ * area_pred_label, area_label; the union is their sum minus the intersection.  pred int32 [n]; gt int32 [n], or uint8 [n] with gt_is_u8
+ * = 1.  With reduce_zero_label gt goes 0 -> 255, then - 1, then 254 -> 255; pixels with gt == ignore_index are dropped.  One deviation:
+ * np.histogram(bins = arange(C + 1)) closes its last bin and counts the value C in class C - 1; here a value outside [0, C - 1] is
+ * counted nowhere.  totals is ACCUMULATED into, so a dataset's batches sum on the device; zero_first != 0 clears it first (one more
+ * launch).  C <= 4096: counters in the workgroup's LDS (12 C bytes), flushed as 64-bit atomics; above, wave-aggregated 64-bit atomics
+ * on totals.  CVLM_E_BADARG, before anything touches the device: a NULL pointer, pred (or an int32 gt) not 4-byte, totals not 8-byte
+ * aligned, n < 1, C outside [1, 65536], gt_is_u8 outside {0, 1}. */
+int cvlm_label_iou_hist(const int32_t* pred, const void* gt, int32_t gt_is_u8, int64_t n, int32_t C, int32_t ignore_index,
+                        int32_t reduce_zero_label, int32_t zero_first, int64_t* totals, void* stream);
+/* Outside the ABI contract: the cvlm_label_* entries on HOST memory, no stream -- the same per-thread functions (csrc/labels_logic.h)
+ * run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_label_init_host(float* score, int16_t* winner, int16_t* segment, int64_t n_pix, int32_t* areas, int32_t* segment_id,
+                               int32_t B, int32_t K, int32_t* n_segments, int32_t* status);
+int cvlm_debug_label_accumulate_host(const float* logits, int32_t p0, int32_t p1, int32_t Hs, int32_t Ws, int32_t B, int32_t K,
+                                     const int32_t* dims, const int64_t* pix_offsets, const float* weights, int32_t level, float* score,
+                                     int16_t* winner, int16_t* segment, int64_t n_pix, int64_t max_pixels, int32_t* areas,
+                                     int32_t* status);
+int cvlm_debug_label_finish_host(int32_t B, int32_t K, const int32_t* dims, const int64_t* pix_offsets, const double* overlap_threshold,
+                                 const int16_t* winner, int16_t* segment, int64_t n_pix, int64_t max_pixels, int32_t* areas,
+                                 int32_t* segment_id, int32_t* n_segments, int32_t* status);
+int cvlm_debug_label_lookup_host(const int16_t* map, int32_t B, int32_t K, const int32_t* dims, const int64_t* pix_offsets, int64_t n_pix,
+                                 int64_t max_pixels, const int32_t* table, int32_t void_value, int32_t* out, int32_t* status);
+int cvlm_debug_label_iou_hist_host(const int32_t* pred, const void* gt, int32_t gt_is_u8, int64_t n, int32_t C, int32_t ignore_index,
+                                   int32_t reduce_zero_label, int32_t zero_first, int64_t* totals);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
