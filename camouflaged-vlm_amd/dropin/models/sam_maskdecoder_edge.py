@@ -209,6 +209,17 @@ class SAM(nn.Module):
         return self.cascade().label_iou(pred, gt, num_classes=num_classes, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label,
                                         totals=totals)
 
+    def panoptic_remap(self, raw, sizes, segments, *, rgb=False):
+        """EXTENSION, not a reference method: a panoptic ground truth -- id maps, or the RGB pixels the reference's visualizer reads through
+        panopticapi's rgb2id (models/utils/visualizer.py:606-611) -- as dense slot indices with its slot tables ->
+        engine.PanopticGroundTruth (engine.Cascade.panoptic_remap)."""
+        return self.cascade().panoptic_remap(raw, sizes, segments, rgb=rgb)
+
+    def panoptic_quality(self, pred, pred_cat, gt, gt_cat, gt_crowd, sizes, *, num_classes, totals=None):
+        """EXTENSION, not a reference method: panopticapi's pq_compute of a predicted panoptic map against ground truth, summed on the
+        device -> engine.PanopticTotals for segeval.pq_average (engine.Cascade.panoptic_quality)."""
+        return self.cascade().panoptic_quality(pred, pred_cat, gt, gt_cat, gt_crowd, sizes, num_classes=num_classes, totals=totals)
+
     def mask_rle_sized(self, sized):
         """EXTENSION, not a reference method: COCO run-length encoding of an engine.SizedMasks, "size": [h, w] of each image
         -> engine.MaskRle (engine.Cascade.mask_rle_sized)."""

@@ -99,6 +99,15 @@ _SIGNATURES = {
     "cvlm_debug_label_finish_host": "i:iipppppllpppp",
     "cvlm_debug_label_lookup_host": "i:piippllpipp",
     "cvlm_debug_label_iou_hist_host": "i:ppiliiiip",
+    "cvlm_pan_remap": "i:piippllppplppps",
+    "cvlm_pan_pair_hist": "i:ppiiippllipps",
+    "cvlm_pan_match": "i:piiipppippppps",
+    "cvlm_pan_accumulate": "i:iiipppppiipps",
+    "cvlm_debug_pan_lds_cells": "i:",
+    "cvlm_debug_pan_remap_host": "i:piippllppplppp",
+    "cvlm_debug_pan_pair_hist_host": "i:ppiiippllipp",
+    "cvlm_debug_pan_match_host": "i:piiipppippppp",
+    "cvlm_debug_pan_accumulate_host": "i:iiipppppiipp",
     "cvlm_mask_wfm": "i:ppiiipppps",
     "cvlm_prob_quantise": "i:piiippps",
     "cvlm_prob_moments": "i:ppiiipppps",
@@ -1363,6 +1372,72 @@ def label_iou_hist(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, ignor
     assert gt.device == pred.device and totals.device == pred.device
     _call(_label_entry("cvlm_label_iou_hist", host, pred), pred.data_ptr(), gt.data_ptr(), int(gt.dtype == torch.uint8), pred.numel(),
           num_classes, int(ignore_index), int(bool(reduce_zero_label)), int(bool(zero_first)), totals.data_ptr())
+
+
+# ---- panoptic quality: device tensors for the cvlm_pan_* entries, host tensors for `host=True` ------------------------------
+def pan_lds_cells() -> int:
+    """The G * S up to which cvlm_pan_pair_hist keeps an image's table in LDS (csrc/panoptic_logic.h: pn_lds_cells)."""
+    return int(load().cvlm_debug_pan_lds_cells())
+
+
+def _pan_tensor(t: torch.Tensor, shape, like: torch.Tensor, dtype=torch.int32) -> None:
+    assert t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == like.device
+
+
+def pan_remap(raw: torch.Tensor, B: int, dims, pix_offsets, max_pixels: int, keys, vals, table_offsets, out, unknown, status,
+              host: bool = False) -> None:
+    """out int32 [n_pix] = the dense index of each pixel's raw id -- raw uint8 [n_pix][3] (rgb2id) or int32 [n_pix] -- looked up in image
+    b's slice table_offsets[b] .. table_offsets[b + 1] of keys (ascending) / vals; unknown int32 [B] = the pixels whose non-zero id the
+    table does not hold (cvlm_pan_remap)."""
+    rgb = raw.dtype == torch.uint8
+    n_pix = out.numel()
+    assert raw.is_contiguous() and (tuple(raw.shape) == (n_pix, 3) if rgb else (raw.dtype == torch.int32 and tuple(raw.shape) == (n_pix,)))
+    _label_tables(dims, pix_offsets, B, raw)
+    n_keys = keys.numel()
+    _pan_tensor(keys, (n_keys,), raw), _pan_tensor(vals, (n_keys,), raw), _pan_tensor(table_offsets, (B + 1,), raw, torch.int64)
+    _pan_tensor(out, (n_pix,), raw), _pan_tensor(unknown, (B,), raw)
+    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == raw.device
+    _call(_label_entry("cvlm_pan_remap", host, raw), raw.data_ptr(), int(rgb), B, dims.data_ptr(), pix_offsets.data_ptr(), n_pix,
+          int(max_pixels), keys.data_ptr(), vals.data_ptr(), table_offsets.data_ptr(), n_keys, out.data_ptr(), unknown.data_ptr(),
+          status.data_ptr())
+
+
+def pan_pair_hist(pred, gt, B: int, G: int, S: int, dims, pix_offsets, max_pixels: int, zero_first: bool, inter, status,
+                  host: bool = False) -> None:
+    """inter int32 [B][G][S] += the pixels of image b with gt = g and pred = s, both int32 [n_pix] (cvlm_pan_pair_hist)."""
+    n_pix = pred.numel()
+    assert pred.dtype == torch.int32 and pred.dim() == 1 and pred.is_contiguous()
+    _pan_tensor(gt, (n_pix,), pred), _pan_tensor(inter, (B, G, S), pred)
+    _label_tables(dims, pix_offsets, B, pred)
+    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == pred.device
+    _call(_label_entry("cvlm_pan_pair_hist", host, pred), pred.data_ptr(), gt.data_ptr(), B, G, S, dims.data_ptr(), pix_offsets.data_ptr(),
+          n_pix, int(max_pixels), int(bool(zero_first)), inter.data_ptr(), status.data_ptr())
+
+
+def pan_match(inter, pred_cat, gt_cat, gt_crowd, num_classes: int, pred_match, pred_iou, gt_match, pred_area, gt_area,
+              host: bool = False) -> None:
+    """Steps 2 to 4 of DESIGN.md §24 per image from inter int32 [B][G][S], pred_cat int32 [B][S], gt_cat int32 [B][G] and gt_crowd uint8
+    [B][G] -> pred_match / pred_area int32 [B][S], pred_iou f64 [B][S], gt_match / gt_area int32 [B][G] (cvlm_pan_match)."""
+    assert inter.dtype == torch.int32 and inter.dim() == 3 and inter.is_contiguous()
+    B, G, S = inter.shape
+    _pan_tensor(pred_cat, (B, S), inter), _pan_tensor(gt_cat, (B, G), inter), _pan_tensor(gt_crowd, (B, G), inter, torch.uint8)
+    _pan_tensor(pred_match, (B, S), inter), _pan_tensor(pred_area, (B, S), inter), _pan_tensor(pred_iou, (B, S), inter, torch.float64)
+    _pan_tensor(gt_match, (B, G), inter), _pan_tensor(gt_area, (B, G), inter)
+    _call(_label_entry("cvlm_pan_match", host, inter), inter.data_ptr(), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(),
+          gt_crowd.data_ptr(), int(num_classes), pred_match.data_ptr(), pred_iou.data_ptr(), gt_match.data_ptr(), pred_area.data_ptr(),
+          gt_area.data_ptr())
+
+
+def pan_accumulate(pred_cat, gt_cat, pred_match, pred_iou, gt_match, num_classes: int, zero_first: bool, counts, iou_sum,
+                   host: bool = False) -> None:
+    """counts int64 [3][C] (tp, fp, fn) and iou_sum f64 [C] += what cvlm_pan_match stored for a batch (cvlm_pan_accumulate)."""
+    B, S = pred_cat.shape
+    G = gt_cat.shape[1]
+    _pan_tensor(pred_cat, (B, S), pred_cat), _pan_tensor(gt_cat, (B, G), pred_cat), _pan_tensor(pred_match, (B, S), pred_cat)
+    _pan_tensor(pred_iou, (B, S), pred_cat, torch.float64), _pan_tensor(gt_match, (B, G), pred_cat)
+    _pan_tensor(counts, (3, num_classes), pred_cat, torch.int64), _pan_tensor(iou_sum, (num_classes,), pred_cat, torch.float64)
+    _call(_label_entry("cvlm_pan_accumulate", host, pred_cat), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(), pred_match.data_ptr(),
+          pred_iou.data_ptr(), gt_match.data_ptr(), int(num_classes), int(bool(zero_first)), counts.data_ptr(), iou_sum.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:

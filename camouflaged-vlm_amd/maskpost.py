@@ -491,6 +491,20 @@ class LabelMaps:
         """The published `panoptic_seg`: (pixels,) int32 segment ids 1 .. n_segments[b], 0 where no segment holds the pixel."""
         return self._lookup(self.segment_id, "segment", 0)
 
+    def pq_inputs(self, labels) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The panoptic map in the form Cascade.panoptic_quality scores -> (pred, pred_cat), no synchronisation: pred
+        (pixels,) int32 = k + 1 where `segment` holds k, 0 (void) elsewhere (cvlm_label_lookup); pred_cat (B, K + 1) int32 on the device
+        = labels[b, k] in slot k + 1, -1 in slot 0.  labels: (B, K) integers, e.g. `classes` of the call.  So S = K + 1; a hypothesis
+        that was not kept owns no pixel, and a slot without a pixel is skipped by the matching."""
+        t = torch.as_tensor(labels)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or tuple(t.shape) not in ((self.B, self.K), (self.B * self.K,)):
+            raise ValueError(f"LabelMaps.pq_inputs: labels must be ({self.B}, {self.K}) integers, got {t.dtype} {tuple(t.shape)}")
+        dev = self.winner.device
+        slots = torch.arange(1, self.K + 1, dtype=torch.int32, device=dev).repeat(self.B)
+        pred_cat = torch.full((self.B, self.K + 1), -1, dtype=torch.int32, device=dev)
+        pred_cat[:, 1:] = t.to(device=dev, dtype=torch.int32).view(self.B, self.K)
+        return self._lookup(slots, "segment", 0), pred_cat
+
     def to_host(self) -> dict:
         """Everything as numpy arrays in one read-back (synchronises): winner / segment as lists of (h, w) int16 arrays, orig_area /
         won_area / kept_area / segment_id (B, K) int32, kept (B, K) bool, n_segments (B,), status."""
@@ -502,6 +516,151 @@ class LabelMaps:
         cut = lambda flat: [flat[slice(*self._range(b))].reshape(self.sizes[b]) for b in range(B)]
         return dict(winner=cut(winner), segment=cut(segment), orig_area=areas[0], won_area=areas[1], kept_area=areas[2], segment_id=ids,
                     kept=ids > 0, n_segments=self.n_segments.cpu().numpy(), status=int(self.status.cpu().item()))
+
+
+PQ_MAX_CELLS = 1 << 24            # G * S of Cascade.panoptic_quality (csrc/panoptic_logic.h: PN_MAX_CELLS)
+
+
+def _pq_table(who: str, name: str, table, B: int, dtype):
+    """One slot table of pq_request: a device tensor is the caller's contract beyond shape and dtype (a look would synchronise); anything
+    else becomes a numpy array (B, slots) of `dtype`."""
+    if isinstance(table, torch.Tensor) and table.is_cuda:
+        want = torch.int32 if dtype is np.int32 else torch.uint8
+        if table.dtype != want or table.dim() != 2 or table.shape[0] != B or table.shape[1] < 1:
+            raise ValueError(f"{who}: {name} on the device must be {want} of shape ({B}, slots), got {table.dtype} {tuple(table.shape)}")
+        return table
+    try:
+        host = np.asarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} must be integers of shape ({B}, slots)") from None
+    if host.dtype == object or not (np.issubdtype(host.dtype, np.integer) or host.dtype == np.bool_) or host.ndim != 2 \
+            or host.shape[0] != B or host.shape[1] < 1:
+        raise ValueError(f"{who}: {name} must be integers of shape ({B}, slots), got {host.dtype} {host.shape}")
+    if dtype is np.int32 and host.dtype == np.bool_:
+        raise ValueError(f"{who}: {name} must be integers, got bool")
+    return host
+
+
+def pq_request(pred_cat, gt_cat, gt_crowd, sizes, *, num_classes, n_pred: int, n_gt: int, who: str = "panoptic_quality"):
+    """Every check of the arguments of Cascade.panoptic_quality, on the host, before anything is launched (ValueError)
+    -> (the B (h, w) pairs, pred_cat, gt_cat, gt_crowd, G, S): a table is an int32 / uint8 numpy array to upload, or the caller's device
+    tensor.  num_classes an int in [1, 65536]; sizes as `sized_request` has them, and n_pred = n_gt = their pixels; pred_cat (B, S)
+    and gt_cat (B, G) integers in [-1, num_classes) with -1 in slot 0, which is void; gt_crowd (B, G) of 0 / 1; G * S <= 2^24.  A host
+    table is checked value by value; of a device tensor only shape and dtype are (the kernels read a category outside [0,
+    num_classes) as "slot unused")."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not is_int(num_classes) or not 1 <= int(num_classes) <= LABELS_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be an int in [1, {LABELS_MAX_CLASSES}], got {num_classes!r}")
+    if sizes is None:
+        raise ValueError(f"{who}: the maps lie image by image at the images' own sizes: give sizes")
+    sizes, _ = sized_request(sizes=sizes, n=len(sizes) if hasattr(sizes, "__len__") else 0, who=who)
+    B = len(sizes)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"{who}: a call scores 1 .. 65535 images, got {B}")
+    pixels = sum(h * w for h, w in sizes)
+    if n_pred != n_gt:
+        raise ValueError(f"{who}: pred holds {n_pred} pixels, gt {n_gt}")
+    if n_pred != pixels:
+        raise ValueError(f"{who}: the maps hold {n_pred} pixels, sizes {pixels}")
+    pred_cat = _pq_table(who, "pred_cat", pred_cat, B, np.int32)
+    gt_cat = _pq_table(who, "gt_cat", gt_cat, B, np.int32)
+    gt_crowd = _pq_table(who, "gt_crowd", gt_crowd, B, np.uint8)
+    S, G = int(pred_cat.shape[1]), int(gt_cat.shape[1])
+    if tuple(gt_crowd.shape) != (B, G):
+        raise ValueError(f"{who}: gt_crowd must have gt_cat's shape ({B}, {G}), got {tuple(gt_crowd.shape)}")
+    if G * S > PQ_MAX_CELLS:
+        raise ValueError(f"{who}: {G} ground-truth slots x {S} predicted slots: the pair table holds at most 2^24 cells")
+    for name, t in (("pred_cat", pred_cat), ("gt_cat", gt_cat)):
+        if isinstance(t, torch.Tensor):
+            continue
+        if int(t.min()) < -1 or int(t.max()) >= int(num_classes):
+            raise ValueError(f"{who}: {name} holds a category outside [-1, {int(num_classes)})")
+        if (t[:, 0] != -1).any():
+            raise ValueError(f"{who}: slot 0 of {name} is void and must be -1")
+    if not isinstance(gt_crowd, torch.Tensor) and gt_crowd.dtype != np.bool_ and (int(gt_crowd.min()) < 0 or int(gt_crowd.max()) > 1):
+        raise ValueError(f"{who}: gt_crowd holds a value that is neither 0 nor 1")
+    as_np = lambda t, dt: t if isinstance(t, torch.Tensor) else np.ascontiguousarray(t, dtype=dt)
+    return sizes, as_np(pred_cat, np.int32), as_np(gt_cat, np.int32), as_np(gt_crowd, np.uint8), G, S
+
+
+def pq_segments_request(segments, B: int, *, num_classes=None, who: str = "panoptic_remap"):
+    """The per-image `segments_info` of Cascade.panoptic_remap -- per image a list of (id, category, iscrowd) in annotation order -- as the
+    kernels' tables (ValueError otherwise) -> (keys int32, vals int32, table_offsets int64 (B + 1,), gt_cat int32 (B, G), gt_crowd uint8
+    (B, G)): keys ascending per image, vals the 1-based position in the annotation, G = the largest count + 1.  An id is an int in [1,
+    2^24) (0 is void), unique within its image; a category an int >= 0 (below num_classes where that is given)."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if isinstance(segments, (str, bytes)) or not hasattr(segments, "__len__") or len(segments) != B:
+        raise ValueError(f"{who}: segments must hold one list of (id, category, iscrowd) per image, {B} in all")
+    G = max([len(s) for s in segments] + [0]) + 1
+    keys, vals, offsets = [], [], [0]
+    gt_cat, gt_crowd = np.full((B, G), -1, np.int32), np.zeros((B, G), np.uint8)
+    for b, segs in enumerate(segments):
+        ids = []
+        for i, seg in enumerate(segs):
+            if isinstance(seg, (str, bytes)) or not hasattr(seg, "__len__") or len(seg) != 3:
+                raise ValueError(f"{who}: a segment is (id, category, iscrowd), got {seg!r}")
+            sid, cat, crowd = seg
+            if not is_int(sid) or not 1 <= int(sid) < 2 ** 24:
+                raise ValueError(f"{who}: a segment id must be an int in [1, 2^24), got {sid!r}")
+            if not is_int(cat) or int(cat) < 0 or (num_classes is not None and int(cat) >= int(num_classes)):
+                raise ValueError(f"{who}: a segment's category must be an int >= 0 and below num_classes, got {cat!r}")
+            if crowd not in (0, 1, False, True):
+                raise ValueError(f"{who}: iscrowd must be 0 or 1, got {crowd!r}")
+            ids.append(int(sid))
+            gt_cat[b, i + 1], gt_crowd[b, i + 1] = int(cat), int(crowd)
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"{who}: image {b} lists a segment id twice")
+        order = np.argsort(np.asarray(ids, np.int64), kind="stable")
+        keys += [ids[i] for i in order]
+        vals += [int(i) + 1 for i in order]
+        offsets.append(len(keys))
+    return (np.asarray(keys or [0], np.int32), np.asarray(vals or [0], np.int32), np.asarray(offsets, np.int64), gt_cat, gt_crowd)
+
+
+@dataclass
+class PanopticGroundTruth:
+    """What Cascade.panoptic_remap returns: a ground-truth id map as dense slot indices with the slot tables
+    Cascade.panoptic_quality takes.  Tensors on the device; nothing here synchronises but `check`."""
+    gt: torch.Tensor                # (pixels,) int32: 1 + the position of the pixel's segment in its image's annotation, 0 = void
+    unknown: torch.Tensor           # (B,) int32: pixels whose non-zero raw id the annotation does not list (they became void)
+    gt_cat: np.ndarray              # (B, G) int32: category per slot, -1 = unused, slot 0 void
+    gt_crowd: np.ndarray            # (B, G) uint8: iscrowd per slot
+    status: torch.Tensor            # (1,) int32: non-zero if the kernel refused an image
+    sizes: list
+
+    def check(self) -> None:
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("panoptic_remap: cvlm_pan_remap refused an image whose slice did not fit its size")
+
+
+@dataclass
+class PanopticTotals:
+    """What Cascade.panoptic_quality returns: a dataset's sums, into which further calls accumulate (`totals=`), and the
+    per-image matching of the last call.  All tensors on the device; nothing here synchronises but `check` and `to_host`."""
+    counts: torch.Tensor            # (3, C) int64: tp, fp, fn per category
+    iou_sum: torch.Tensor           # (C,) f64: the sum of the true positives' IoU per category
+    status: torch.Tensor            # (1,) int32: 1 = a kernel refused an image, 2 = a map held an index outside its slot table
+    inter: torch.Tensor             # (B, G, S) int32: the last call's pair counts
+    pred_match: torch.Tensor        # (B, S) int32: the matched g, 0 = unused / no pixel / void, -1 = false positive, -2 = ignored
+    pred_iou: torch.Tensor          # (B, S) f64
+    gt_match: torch.Tensor          # (B, G) int32: the matched s, 0 = unused / void, -1 = false negative, -2 = crowd
+    pred_area: torch.Tensor         # (B, S) int32
+    gt_area: torch.Tensor           # (B, G) int32
+    num_classes: int
+
+    def check(self) -> None:
+        """RuntimeError if a kernel refused an image or met an index outside its table, in any call summed so far (synchronises)."""
+        s = int(self.status.cpu().item())
+        if s & 1:
+            raise RuntimeError("panoptic_quality: a cvlm_pan_* kernel refused an image whose slice did not fit its size")
+        if s & 2:
+            raise RuntimeError("panoptic_quality: a map holds a segment index outside its slot table; such pixels were counted nowhere")
+
+    def to_host(self) -> dict:
+        """Everything as numpy arrays in one read-back (synchronises); `segeval.pq_average(counts, iou_sum)` gives PQ, SQ and RQ."""
+        self.check()
+        names = ("counts", "iou_sum", "inter", "pred_match", "pred_iou", "gt_match", "pred_area", "gt_area")
+        return dict({n: getattr(self, n).cpu().numpy() for n in names}, status=0)
 
 
 def rle_decode_request(rles, who: str = "rle_decode"):
@@ -1177,6 +1336,83 @@ class MaskUtilities:
             raise ValueError(f"label_iou: totals must be what an earlier call with num_classes = {C_} returned")
         hip.label_iou_hist(maps[0], maps[1], C_, int(ignore_index), bool(reduce_zero_label), fresh, totals)
         return totals
+
+    # ---- panoptic quality ----------------------------------------------------------------------------------------------
+    def _pq_map(self, who: str, name: str, m, rgb: bool = False) -> torch.Tensor:
+        """A flat map of a panoptic call on this engine's device: int32 (pixels,), or uint8 (pixels, 3) for an RGB id image.  A list holds
+        one array per image and is laid back to back."""
+        if isinstance(m, (list, tuple)) and m and all(isinstance(a, (torch.Tensor, np.ndarray)) for a in m):
+            parts = [torch.as_tensor(a) for a in m]
+            m = torch.cat([a.reshape(-1, 3) if rgb else a.reshape(-1) for a in parts])
+        t = torch.as_tensor(m) if isinstance(m, (torch.Tensor, np.ndarray)) else None
+        if t is None or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.numel() < 1:
+            raise ValueError(f"{who}: {name} must be a non-empty integer tensor or array, got {type(m).__name__}")
+        if rgb:
+            if t.dtype != torch.uint8 or t.shape[-1] != 3:
+                raise ValueError(f"{who}: with rgb=True {name} must be uint8 with a last axis of 3, got {t.dtype} {tuple(t.shape)}")
+            return t.detach().to(device=self.device).contiguous().view(-1, 3)
+        if not t.is_cuda and t.dtype not in (torch.int32, torch.uint8, torch.int16, torch.int8) and \
+                (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+            raise ValueError(f"{who}: {name} holds a value outside the int32 range")
+        return t.detach().to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+
+    def panoptic_remap(self, raw, sizes, segments, *, rgb: bool = False) -> "PanopticGroundTruth":
+        """A panoptic ground truth as cvlm_pan_pair_hist reads it (cvlm_pan_remap) -> PanopticGroundTruth: `gt`, the dense
+        slot index of every pixel, `unknown` (B,), and the slot tables `gt_cat` / `gt_crowd` for panoptic_quality.  raw: the images' id
+        maps back to back at the B sizes (h, w) of `sizes`, or a list of one array per image -- integers (the ids), or with rgb=True the
+        uint8 (h, w, 3) pixels of COCO's panoptic PNGs (id = R + 256 G + 65536 B).  segments: per image its annotation's segments_info
+        as (id, category, iscrowd) triples, in annotation order: slot i + 1 is the i-th.  Id 0 is void; an id the annotation does not
+        list becomes void and is counted in `unknown`.  No synchronisation.  ValueError before anything is launched."""
+        if not isinstance(rgb, (bool, np.bool_)):
+            raise ValueError(f"panoptic_remap: rgb must be a bool, got {rgb!r}")
+        if sizes is None:
+            raise ValueError("panoptic_remap: the maps lie image by image at the images' own sizes: give sizes")
+        sizes, _ = sized_request(sizes=sizes, n=len(sizes) if hasattr(sizes, "__len__") else 0, who="panoptic_remap")
+        B = len(sizes)
+        if not 1 <= B <= 65535:
+            raise ValueError(f"panoptic_remap: a call takes 1 .. 65535 images, got {B}")
+        keys, vals, offsets, gt_cat, gt_crowd = pq_segments_request(segments, B)
+        t = self._pq_map("panoptic_remap", "raw", raw, bool(rgb))
+        dims, pix_offsets, max_pixels = label_tables(sizes)
+        if t.shape[0] != int(pix_offsets[-1]):
+            raise ValueError(f"panoptic_remap: raw holds {t.shape[0]} pixels, sizes {int(pix_offsets[-1])}")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        out = PanopticGroundTruth(gt=torch.empty(t.shape[0], dtype=torch.int32, device=self.device),
+                                  unknown=torch.empty(B, dtype=torch.int32, device=self.device), gt_cat=gt_cat, gt_crowd=gt_crowd,
+                                  status=torch.zeros(1, dtype=torch.int32, device=self.device), sizes=sizes)
+        hip.pan_remap(t, B, up(dims), up(pix_offsets), max_pixels, up(keys), up(vals), up(offsets), out.gt, out.unknown, out.status)
+        return out
+
+    def panoptic_quality(self, pred, pred_cat, gt, gt_cat, gt_crowd, sizes, *, num_classes: int, totals=None) -> "PanopticTotals":
+        """Panoptic quality's sums of a predicted panoptic map against ground truth, on the device (cvlm_pan_pair_hist / match /
+        accumulate) -> PanopticTotals, whose `counts` and `iou_sum` `segeval.pq_average` turns into PQ, SQ and RQ.  pred,
+        gt: dense segment indices, 0 = void, back to back at the B sizes of `sizes` (or a list of one array per image) -- e.g.
+        `LabelMaps.pq_inputs(classes)` and `panoptic_remap(...).gt`; pred_cat (B, S), gt_cat (B, G): a slot's category in [0,
+        num_classes) or -1, slot 0 = -1; gt_crowd (B, G): iscrowd.  totals: the result of an earlier call, accumulated into -- a dataset's
+        batches sum on the device, and `status` with them; None starts from zero.  The per-image tensors are the last call's.  One
+        (B, G, S) int32 table is allocated per call.  No synchronisation.  ValueError (`pq_request`) before anything is launched."""
+        maps = [self._pq_map("panoptic_quality", n, m) for n, m in (("pred", pred), ("gt", gt))]
+        sizes, pred_cat, gt_cat, gt_crowd, G, S = pq_request(pred_cat, gt_cat, gt_crowd, sizes, num_classes=num_classes,
+                                                             n_pred=maps[0].numel(), n_gt=maps[1].numel())
+        C_ = int(num_classes)
+        if totals is not None and not (isinstance(totals, PanopticTotals) and totals.num_classes == C_ and totals.counts.device == maps[0].device):
+            raise ValueError(f"panoptic_quality: totals must be what an earlier call with num_classes = {C_} returned")
+        B = len(sizes)
+        dev = self.device
+        up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        pred_cat, gt_cat, gt_crowd = up(pred_cat).contiguous(), up(gt_cat).contiguous(), up(gt_crowd).contiguous()
+        dims, pix_offsets, max_pixels = label_tables(sizes)
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        fresh = totals is None
+        out = PanopticTotals(counts=torch.empty(3, C_, dtype=torch.int64, device=dev) if fresh else totals.counts,
+                             iou_sum=torch.empty(C_, dtype=torch.float64, device=dev) if fresh else totals.iou_sum,
+                             status=torch.zeros(1, dtype=torch.int32, device=dev) if fresh else totals.status,
+                             inter=i32(B, G, S), pred_match=i32(B, S), pred_iou=torch.empty(B, S, dtype=torch.float64, device=dev),
+                             gt_match=i32(B, G), pred_area=i32(B, S), gt_area=i32(B, G), num_classes=C_)
+        hip.pan_pair_hist(maps[0], maps[1], B, G, S, up(dims), up(pix_offsets), max_pixels, True, out.inter, out.status)
+        hip.pan_match(out.inter, pred_cat, gt_cat, gt_crowd, C_, out.pred_match, out.pred_iou, out.gt_match, out.pred_area, out.gt_area)
+        hip.pan_accumulate(pred_cat, gt_cat, out.pred_match, out.pred_iou, out.gt_match, C_, fresh, out.counts, out.iou_sum)
+        return out
 
     def mask_rle_sized(self, sized: "SizedMasks") -> "MaskRle":
         """COCO run-length encoding of sized planes -> MaskRle whose `to_coco()` writes each plane's own "size": [h, w],

@@ -944,6 +944,65 @@ int cvlm_debug_label_lookup_host(const int16_t* map, int32_t B, int32_t K, const
 int cvlm_debug_label_iou_hist_host(const int32_t* pred, const void* gt, int32_t gt_is_u8, int64_t n, int32_t C, int32_t ignore_index,
                                    int32_t reduce_zero_label, int32_t zero_first, int64_t* totals);
 
+/* Panoptic quality: panopticapi.evaluation.pq_compute (Kirillov et al., "Panoptic Segmentation") restated for the flat
+ * maps of the label family -- dims, pix_offsets, n_pix and max_pixels are exactly those of cvlm_label_*, and so is what every pixel
+ * kernel checks of an image before it touches it: an image that fails is skipped whole and ORs 1 into status[0].
+ * Maps and tables.  pred int32 [n_pix]: dense predicted segment index in [0, S), 0 = void; gt int32 [n_pix]: dense ground-truth
+ * segment index in [0, G), 0 = void.  pred_cat int32 [B][S] and gt_cat int32 [B][G]: the category in [0, C) of a slot, anything else
+ * (-1 by convention) = slot unused; slot 0 is void and never read as a segment.  gt_crowd uint8 [B][G]: iscrowd.
+ * cvlm_pan_remap: raw ids to dense indices.  raw is uint8 [n_pix][3] with raw_is_rgb = 1 (id = R + 256 G + 65536 B, panopticapi's
+ * rgb2id) or int32 [n_pix] with 0.  Image b's table is keys[table_offsets[b] .. table_offsets[b + 1]), int32 ascending, with vals the
+ * dense index of each key; n_keys is the length of keys and vals.  out[pix] = 0 for id 0, vals[i] for id = keys[i], and 0 for an id the
+ * table does not hold; the pixels of the last kind are counted into unknown int32 [B], which the call clears first (two launches).  A
+ * table slice outside [0, n_keys] or not ascending in its offsets skips the image and ORs 1 as well.
+ * cvlm_pan_pair_hist: inter int32 [B][G][S] += the number of pixels of image b with gt = g and pred = s; zero_first != 0 clears inter
+ * first (one more launch).  Grid (workgroups, B); a wave takes 64 consecutive pixels of one row, counts the lanes that hold the same
+ * cell by ballot and popcount and keeps the count of its current cell in registers until it meets another.  G * S <=
+ * cvlm_debug_pan_lds_cells(): the table in the workgroup's LDS (4 G S bytes, dynamic), flushed as one atomic per non-zero cell; above:
+ * the wave's counts as global atomics.  A pixel whose gt is outside [0, G) or whose pred is outside [0, S) is counted nowhere and ORs
+ * 2 into status[0].  status is only ORed into: the caller clears it.
+ * cvlm_pan_match: per image, one workgroup, no atomics.  pred_area[s] = sum_g inter[g][s], gt_area[g] = sum_s inter[g][s].  A pair g >=
+ * 1, s >= 1 with both categories in [0, C) and equal, gt_crowd[g] == 0 and inter[g][s] > 0 has union = pred_area[s] + gt_area[g] -
+ * inter[g][s] - inter[0][s] and iou = (double)inter / (double)union; iou > 0.5 makes it a true positive (unique, so no order is
+ * involved).  pred_match int32 [B][S]: the matched g, 0 = slot unused, without a pixel or void, -1 = false positive, -2 = ignored (more
+ * than half of it -- strictly -- on void and on its category's crowd segment, the LAST crowd slot of that category); pred_iou f64 [B][S]:
+ * the IoU of a matched s, else 0.  gt_match int32 [B][G]: the matched s, 0 = unused or void, -1 = false negative (also with gt_area 0),
+ * -2 = crowd (never a false negative, never matched).  pred_area int32 [B][S], gt_area int32 [B][G].
+ * cvlm_pan_accumulate: counts int64 [3][C] (tp, fp, fn) and iou_sum f64 [C] += the image results; zero_first != 0 starts from zero.  One
+ * lane per category; iou_sum[c] is added in increasing b and within an image in increasing g, so a run is reproducible to the last
+ * bit.  It adds what it is given: calling it twice for one cvlm_pan_match counts that batch twice.
+ * No workspace, no allocation, no synchronisation, 64-bit offsets.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer; an int32 pointer not 4-byte, an int64 / f64 pointer not 8-byte
+ * aligned (an RGB raw has no alignment); B outside [1, 65535]; G or S < 1 or G * S > 2^24; C outside [1, 65536]; n_pix < 1; n_keys < 1;
+ * max_pixels outside [1, 2^28]; raw_is_rgb outside {0, 1}; an output range that shares a byte with an input or another output. */
+int cvlm_pan_remap(const void* raw, int32_t raw_is_rgb, int32_t B, const int32_t* dims, const int64_t* pix_offsets, int64_t n_pix,
+                   int64_t max_pixels, const int32_t* keys, const int32_t* vals, const int64_t* table_offsets, int64_t n_keys, int32_t* out,
+                   int32_t* unknown, int32_t* status, void* stream);
+int cvlm_pan_pair_hist(const int32_t* pred, const int32_t* gt, int32_t B, int32_t G, int32_t S, const int32_t* dims,
+                       const int64_t* pix_offsets, int64_t n_pix, int64_t max_pixels, int32_t zero_first, int32_t* inter, int32_t* status,
+                       void* stream);
+int cvlm_pan_match(const int32_t* inter, int32_t B, int32_t G, int32_t S, const int32_t* pred_cat, const int32_t* gt_cat,
+                   const uint8_t* gt_crowd, int32_t C, int32_t* pred_match, double* pred_iou, int32_t* gt_match, int32_t* pred_area,
+                   int32_t* gt_area, void* stream);
+int cvlm_pan_accumulate(int32_t B, int32_t G, int32_t S, const int32_t* pred_cat, const int32_t* gt_cat, const int32_t* pred_match,
+                        const double* pred_iou, const int32_t* gt_match, int32_t C, int32_t zero_first, int64_t* counts, double* iou_sum,
+                        void* stream);
+/* Outside the ABI contract: the cells up to which cvlm_pan_pair_hist keeps its table in LDS, and the cvlm_pan_* entries on HOST memory,
+ * no stream -- the same per-thread functions (csrc/panoptic_logic.h) run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_pan_lds_cells(void);
+int cvlm_debug_pan_remap_host(const void* raw, int32_t raw_is_rgb, int32_t B, const int32_t* dims, const int64_t* pix_offsets, int64_t n_pix,
+                              int64_t max_pixels, const int32_t* keys, const int32_t* vals, const int64_t* table_offsets, int64_t n_keys,
+                              int32_t* out, int32_t* unknown, int32_t* status);
+int cvlm_debug_pan_pair_hist_host(const int32_t* pred, const int32_t* gt, int32_t B, int32_t G, int32_t S, const int32_t* dims,
+                                  const int64_t* pix_offsets, int64_t n_pix, int64_t max_pixels, int32_t zero_first, int32_t* inter,
+                                  int32_t* status);
+int cvlm_debug_pan_match_host(const int32_t* inter, int32_t B, int32_t G, int32_t S, const int32_t* pred_cat, const int32_t* gt_cat,
+                              const uint8_t* gt_crowd, int32_t C, int32_t* pred_match, double* pred_iou, int32_t* gt_match,
+                              int32_t* pred_area, int32_t* gt_area);
+int cvlm_debug_pan_accumulate_host(int32_t B, int32_t G, int32_t S, const int32_t* pred_cat, const int32_t* gt_cat,
+                                   const int32_t* pred_match, const double* pred_iou, const int32_t* gt_match, int32_t C,
+                                   int32_t zero_first, int64_t* counts, double* iou_sum);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
