@@ -32,6 +32,9 @@ __global__ __launch_bounds__(256) void mt_init_kernel(int* __restrict__ dt_order
     if (i < (int64_t)A * NG) gt_ignore[i] = 1;
 }
 
+// BOUNDARY: step (3) divides twice per pair -- the mask's integers and the boundary's (inter_b, det_area_b, gt_area_b)
+// -- and keeps the minimum; the false form never reads the three tables.
+template <bool BOUNDARY>
 __global__ __launch_bounds__(MT_THREADS) void mt_match_kernel(const int* __restrict__ det_off, const int* __restrict__ gt_off,
                                                               const int64_t* __restrict__ pair_off, const int* __restrict__ inter, int64_t N,
                                                               const int* __restrict__ det_area, const float* __restrict__ score, int ND,
@@ -40,7 +43,9 @@ __global__ __launch_bounds__(MT_THREADS) void mt_match_kernel(const int* __restr
                                                               int T, const double* __restrict__ area_rngs, int A, int max_det,
                                                               int* __restrict__ dt_order, int* __restrict__ dt_match,
                                                               uint8_t* __restrict__ dt_ignore, int* __restrict__ gt_match,
-                                                              uint8_t* __restrict__ gt_ignore, int* __restrict__ status) {
+                                                              uint8_t* __restrict__ gt_ignore, int* __restrict__ status,
+                                                              const int* __restrict__ inter_b, const int* __restrict__ det_area_b,
+                                                              const int* __restrict__ gt_area_b) {
     __shared__ double row[MT_CAP];                              // the scores (as floats) until the order stands, then one IoU row
     __shared__ uint32_t taken[(MT_CAP / 32) * MT_THREADS];      // word-major: word k of instance i at [k * MT_THREADS + i]
     __shared__ int order[MT_CAP];
@@ -80,7 +85,14 @@ __global__ __launch_bounds__(MT_THREADS) void mt_match_kernel(const int* __restr
         const int d = order[r];
         const int ad = det_area[q.d0 + d];
         const int* block = inter + q.p0 + (int64_t)d * q.G;
-        for (int g = tid; g < q.G; g += MT_THREADS) row[g] = mt_iou(block[g], ad, gt_area[q.g0 + g], crowd[g] != 0);
+        if constexpr (BOUNDARY) {
+            const int adb = det_area_b[q.d0 + d];
+            const int* block_b = inter_b + q.p0 + (int64_t)d * q.G;
+            for (int g = tid; g < q.G; g += MT_THREADS)
+                row[g] = mt_iou_min(block[g], ad, gt_area[q.g0 + g], block_b[g], adb, gt_area_b[q.g0 + g], crowd[g] != 0);
+        } else {
+            for (int g = tid; g < q.G; g += MT_THREADS) row[g] = mt_iou(block[g], ad, gt_area[q.g0 + g], crowd[g] != 0);
+        }
         __syncthreads();
         if (active) {
             const int m = mt_pick(row, q.G, ign, crowd, a, thr, taken + tid, MT_THREADS);
@@ -116,40 +128,38 @@ bool mt_bad(const int32_t* det_off, const int32_t* gt_off, const int64_t* pair_o
     return mb_misaligned(8, pair_off, gt_range_area, iou_thrs, area_rngs);
 }
 
-}  // namespace
+// what the boundary entries refuse on top of it: each of the three tables NULL where its count is not 0, or off 4 bytes
+bool mt_bad_boundary(const int32_t* inter_b, int64_t N, const int32_t* det_area_b, int32_t ND, const int32_t* gt_area_b, int32_t NG) {
+    if ((N > 0 && !inter_b) || (ND > 0 && !det_area_b) || (NG > 0 && !gt_area_b)) return true;
+    return mb_misaligned(4, inter_b, det_area_b, gt_area_b);
+}
 
-extern "C" {
-
-int cvlm_coco_match(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E, const int32_t* inter,
-                    int64_t N, const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area, const double* gt_range_area,
-                    const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A,
-                    int32_t max_det, int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
-                    int32_t* status, void* stream) {
-    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
-               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status))
-        return CVLM_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
+// the two launches of both device entries
+template <bool BOUNDARY>
+int mt_launch(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E, const int32_t* inter, int64_t N,
+              const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area, const double* gt_range_area,
+              const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det,
+              int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status,
+              const int32_t* inter_b, const int32_t* det_area_b, const int32_t* gt_area_b, hipStream_t st) {
     const int AT = A * T;
     const int64_t cells = std::max<int64_t>(1, (int64_t)AT * std::max(ND, NG));             // <= 2^27
     hipLaunchKernelGGL(mt_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (int*)dt_order, (int*)dt_match, dt_ignore,
                        (int*)gt_match, gt_ignore, (int)ND, (int)NG, (int)A, AT, (int*)status);
     CVLM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mt_match_kernel, dim3(E), dim3(MT_THREADS), 0, st, (const int*)det_offsets, (const int*)gt_offsets, pair_offsets,
-                       (const int*)inter, N, (const int*)det_area, score, (int)ND, (const int*)gt_area, gt_range_area, gt_crowd, (int)NG,
-                       iou_thrs, (int)T, area_rngs, (int)A, (int)max_det, (int*)dt_order, (int*)dt_match, dt_ignore, (int*)gt_match,
-                       gt_ignore, (int*)status);
+    hipLaunchKernelGGL(mt_match_kernel<BOUNDARY>, dim3(E), dim3(MT_THREADS), 0, st, (const int*)det_offsets, (const int*)gt_offsets,
+                       pair_offsets, (const int*)inter, N, (const int*)det_area, score, (int)ND, (const int*)gt_area, gt_range_area, gt_crowd,
+                       (int)NG, iou_thrs, (int)T, area_rngs, (int)A, (int)max_det, (int*)dt_order, (int*)dt_match, dt_ignore, (int*)gt_match,
+                       gt_ignore, (int*)status, (const int*)inter_b, (const int*)det_area_b, (const int*)gt_area_b);
     CVLM_CHECK_LAUNCH();
     return 0;
 }
 
-int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
-                               const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND,
-                               const int32_t* gt_area, const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG,
-                               const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det, int32_t* dt_order,
-                               int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status) {
-    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
-               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status))
-        return CVLM_E_BADARG;
+// the sequential form of both host entries
+int mt_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E, const int32_t* inter, int64_t N,
+            const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area, const double* gt_range_area,
+            const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det,
+            int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status, bool boundary,
+            const int32_t* inter_b, const int32_t* det_area_b, const int32_t* gt_area_b) {
     const int AT = A * T;
     status[0] = 0;
     for (int i = 0; i < ND; ++i) dt_order[i] = -1;
@@ -189,8 +199,12 @@ int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_off
         for (int r = 0; r < R; ++r) {
             const int d = order[(size_t)r];
             const int ad = det_area[q.d0 + d];
-            for (int g = 0; g < q.G; ++g)
-                row[(size_t)g] = mt_iou(inter[q.p0 + (int64_t)d * q.G + g], ad, gt_area[q.g0 + g], crowd[(size_t)g] != 0);
+            for (int g = 0; g < q.G; ++g) {
+                const int64_t at = q.p0 + (int64_t)d * q.G + g;
+                const bool c = crowd[(size_t)g] != 0;
+                row[(size_t)g] = boundary ? mt_iou_min(inter[at], ad, gt_area[q.g0 + g], inter_b[at], det_area_b[q.d0 + d], gt_area_b[q.g0 + g], c)
+                                          : mt_iou(inter[at], ad, gt_area[q.g0 + g], c);
+            }
             for (int inst = 0; inst < AT; ++inst) {
                 const int a = inst / T, t = inst % T;
                 const int m = mt_pick(row.data(), q.G, ign.data(), crowd.data(), a, mt_threshold(iou_thrs[t]), taken.data() + inst, AT);
@@ -209,6 +223,65 @@ int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_off
         }
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvlm_coco_match(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E, const int32_t* inter,
+                    int64_t N, const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area, const double* gt_range_area,
+                    const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A,
+                    int32_t max_det, int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
+                    int32_t* status, void* stream) {
+    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status))
+        return CVLM_E_BADARG;
+    return mt_launch<false>(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG,
+                            iou_thrs, T, area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status, nullptr, nullptr,
+                            nullptr, (hipStream_t)stream);
+}
+
+int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                               const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND,
+                               const int32_t* gt_area, const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG,
+                               const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det, int32_t* dt_order,
+                               int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status) {
+    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status))
+        return CVLM_E_BADARG;
+    return mt_host(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+                   area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status, false, nullptr, nullptr, nullptr);
+}
+
+// The boundary matching: the same two launches, the matching kernel in its form that divides twice per pair
+int cvlm_coco_match_boundary(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                             const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area,
+                             const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T,
+                             const double* area_rngs, int32_t A, int32_t max_det, const int32_t* inter_b, const int32_t* det_area_b,
+                             const int32_t* gt_area_b, int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match,
+                             uint8_t* gt_ignore, int32_t* status, void* stream) {
+    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status) ||
+        mt_bad_boundary(inter_b, N, det_area_b, ND, gt_area_b, NG))
+        return CVLM_E_BADARG;
+    return mt_launch<true>(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG,
+                           iou_thrs, T, area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status, inter_b, det_area_b,
+                           gt_area_b, (hipStream_t)stream);
+}
+
+int cvlm_debug_coco_match_boundary_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                                        const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND,
+                                        const int32_t* gt_area, const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG,
+                                        const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det,
+                                        const int32_t* inter_b, const int32_t* det_area_b, const int32_t* gt_area_b, int32_t* dt_order,
+                                        int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status) {
+    if (mt_bad(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+               area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status) ||
+        mt_bad_boundary(inter_b, N, det_area_b, ND, gt_area_b, NG))
+        return CVLM_E_BADARG;
+    return mt_host(det_offsets, gt_offsets, pair_offsets, E, inter, N, det_area, score, ND, gt_area, gt_range_area, gt_crowd, NG, iou_thrs, T,
+                   area_rngs, A, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status, true, inter_b, det_area_b, gt_area_b);
 }
 
 }  // extern "C"

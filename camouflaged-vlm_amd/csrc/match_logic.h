@@ -7,6 +7,7 @@
 //   - mt_group_ok:    what is checked before anything of a group is read or stored;
 //   - mt_precedes:    the order of two detections: score descending, NaN last, equal scores in the caller's order;
 //   - mt_iou:         rleIou's quotient from integers, one correctly rounded double division;
+//   - mt_iou_min:     the smaller of the mask's and the boundary's IoU of a pair, two such divisions;
 //   - mt_ignore_mask: bit a of an annotation's byte = it is ignored in area range a;
 //   - mt_pick:        the annotation one detection takes in one (area range, threshold) instance, or -1.
 #pragma once
@@ -53,6 +54,13 @@ MT_HD double mt_iou(int inter, int area_d, int area_g, bool crowd) {
     const int64_t u = crowd ? (int64_t)area_d : (int64_t)area_d + area_g - inter;
     if (u < 1) return -1.0;
     return (double)inter / (double)u;
+}
+
+// What the boundary matching compares with a threshold (boundary_iou_api's COCOeval, iouType = "boundary"): min(mask IoU, boundary
+// IoU), each mt_iou of its own integers under the same crowd flag.  -1 on either side stays -1: no other value is negative.
+MT_HD double mt_iou_min(int inter, int area_d, int area_g, int inter_b, int area_d_b, int area_g_b, bool crowd) {
+    const double m = mt_iou(inter, area_d, area_g, crowd), b = mt_iou(inter_b, area_d_b, area_g_b, crowd);
+    return b < m ? b : m;
 }
 
 // Bit a set: the annotation is ignored in area range a (rngs[2 a], rngs[2 a + 1])

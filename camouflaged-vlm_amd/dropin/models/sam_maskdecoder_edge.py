@@ -243,13 +243,18 @@ class SAM(nn.Module):
         return self.cascade().mask_inter_sized(a, b, pairs=pairs, a_image=a_image, b_image=b_image)
 
     def coco_match(self, dets, gts, *, scores, det_image, gt_image, det_category=None, gt_category=None, iscrowd=None, gt_area=None,
-                   iou_thrs=None, area_rngs=None, max_det=100):
+                   iou_thrs=None, area_rngs=None, max_det=100, boundary=None):
         """EXTENSION, not a reference method: detections against annotations as pycocotools' COCOeval.evaluateImg matches them, for
         every (image, category) group, area range and IoU threshold -> engine.CocoMatches, from which cocoeval.accumulate / summarize
-        give AP and AR (engine.Cascade.coco_match)."""
+        give AP and AR (engine.Cascade.coco_match); boundary=0.02 matches on min(mask IoU, boundary IoU): Boundary AP and AR."""
         return self.cascade().coco_match(dets, gts, scores=scores, det_image=det_image, gt_image=gt_image, det_category=det_category,
                                          gt_category=gt_category, iscrowd=iscrowd, gt_area=gt_area, iou_thrs=iou_thrs, area_rngs=area_rngs,
-                                         max_det=max_det)
+                                         max_det=max_det, boundary=boundary)
+
+    def mask_boundary_sized(self, sized, *, dilation_ratio=0.02, radius=None):
+        """EXTENSION, not a reference method: the boundary of each plane of an engine.SizedMasks as boundary_iou_api's mask_to_boundary
+        forms it -> engine.SizedMasks (engine.Cascade.mask_boundary_sized)."""
+        return self.cascade().mask_boundary_sized(sized, dilation_ratio=dilation_ratio, radius=radius)
 
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --

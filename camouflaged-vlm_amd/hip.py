@@ -89,6 +89,10 @@ _SIGNATURES = {
     "cvlm_debug_mask_inter_sized_host": "i:plppiplppipilpp",
     "cvlm_coco_match": "i:pppiplppipppipipiipppppps",
     "cvlm_debug_coco_match_host": "i:pppiplppipppipipiipppppp",
+    "cvlm_mask_boundary_sized": "i:plpppilpppps",
+    "cvlm_debug_mask_boundary_sized_host": "i:plpppilpppp",
+    "cvlm_coco_match_boundary": "i:pppiplppipppipipiippppppppps",
+    "cvlm_debug_coco_match_boundary_host": "i:pppiplppipppipipiippppppppp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1282,6 +1286,84 @@ def coco_match_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_of
     _call("cvlm_debug_coco_match_host", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area),
           p(score), ND, p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det),
           p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+
+
+# ---- Boundary IoU ---------------------------------------------------------------------------------------------------------
+def _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status) -> int:
+    """Shape and dtype checks shared by `mask_boundary_sized` and `mask_boundary_sized_host` -> P."""
+    P = int(dims.shape[0])
+    for t in (bits, out_bits, workspace):
+        assert t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous() and t.numel() == bits.numel()
+    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert radius.dtype == torch.int32 and tuple(radius.shape) == (P,) and radius.is_contiguous()
+    assert out_area is None or (out_area.dtype == torch.int32 and tuple(out_area.shape) == (P,) and out_area.is_contiguous())
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == bits.device for t in (offsets, dims, radius, workspace, out_bits, out_area, status))
+    return P
+
+
+def mask_boundary_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, radius: torch.Tensor, max_words: int,
+                        workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """The boundary of each sized plane at its own radius (include/cvlm.h: cvlm_mask_boundary_sized): bits flat uint8,
+    byte offsets int64 [P + 1], dims int32 [P][2], radius int32 [P] in 1 .. 16384 -> out_bits (the same layout, X & ~erode(X, radius) with
+    the outside of the plane clear), out_area int32 [P] or None, status int32 [1] = 1 if a plane was refused.  workspace: uint8, as
+    many bytes as bits.  max_words: the largest h * ceil(w / 32) of the call."""
+    P = _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status)
+    _on_current_device(bits)
+    _call("cvlm_mask_boundary_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
+          int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
+
+
+def mask_boundary_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, radius: torch.Tensor, max_words: int,
+                             workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """`mask_boundary_sized` on HOST tensors without a device (cvlm_debug_mask_boundary_sized_host: the kernels' per-thread functions
+    run sequentially)."""
+    P = _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_boundary_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
+          int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
+
+
+def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,
+                         gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore, gt_match,
+                         gt_ignore, status) -> None:
+    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
+                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
+    for t, n in ((inter_b, N), (det_area_b, ND), (gt_area_b, NG)):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (n,) and t.is_contiguous() and t.device == det_offsets.device
+    if host:
+        assert not det_offsets.is_cuda
+    else:
+        _on_current_device(det_offsets)
+    p = lambda t: t.data_ptr() if t.numel() else None
+    _call(name, det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area), p(score), ND,
+          p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det), p(inter_b),
+          p(det_area_b), p(gt_area_b), p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+
+
+def coco_match_boundary(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
+                        det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor,
+                        iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, inter_b: torch.Tensor, det_area_b: torch.Tensor,
+                        gt_area_b: torch.Tensor, dt_order: torch.Tensor, dt_match: torch.Tensor, dt_ignore: torch.Tensor,
+                        gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+    """`coco_match` with the IoU of a pair replaced by min(mask IoU, boundary IoU) (include/cvlm.h: cvlm_coco_match_boundary; DESIGN.md
+    §25): inter_b int32 [N], det_area_b int32 [sum D] and gt_area_b int32 [sum G] are the boundaries' intersections and areas, in the
+    order of inter, det_area and gt_area."""
+    _coco_match_boundary("cvlm_coco_match_boundary", False, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area,
+                         gt_range_area, gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore,
+                         gt_match, gt_ignore, status)
+
+
+def coco_match_boundary_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
+                             det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor,
+                             gt_crowd: torch.Tensor, iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, inter_b: torch.Tensor,
+                             det_area_b: torch.Tensor, gt_area_b: torch.Tensor, dt_order: torch.Tensor, dt_match: torch.Tensor,
+                             dt_ignore: torch.Tensor, gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+    """`coco_match_boundary` on HOST tensors without a device (cvlm_debug_coco_match_boundary_host)."""
+    _coco_match_boundary("cvlm_debug_coco_match_boundary_host", True, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area,
+                         gt_range_area, gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore,
+                         gt_match, gt_ignore, status)
 
 
 # ---- label maps (DESIGN.md §23): the tensors below live on the device for the cvlm_label_* entries and on the host for `host=True` ----

@@ -804,6 +804,43 @@ MATCH_IOU_THRS = tuple(np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 
 MATCH_AREA_RNGS = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))             # all, small, medium, large
 
 
+BOUNDARY_MAX_RADIUS = 16384       # the radius of a boundary (csrc/boundary_logic.h: BD_MAX_RADIUS)
+BOUNDARY_RATIO = 0.02             # boundary_iou_api's dilation_ratio: the radius is this share of the image's diagonal
+
+
+def boundary_radius(h: int, w: int, ratio: float = BOUNDARY_RATIO) -> int:
+    """The radius of the boundary of an h x w image, exactly as boundary_iou_api's mask_to_boundary forms it: float64,
+    Python's round (half to even), at least 1.  (480, 640) -> 16, (1024, 1024) -> 29, (100, 75) -> 2: the product is exactly 2.5."""
+    return max(1, int(round(ratio * np.sqrt(h ** 2 + w ** 2))))
+
+
+def boundary_request(sizes, *, dilation_ratio=BOUNDARY_RATIO, radius=None, who: str = "mask_boundary_sized") -> np.ndarray:
+    """Every check of the dilation_ratio= / radius= arguments of Cascade.mask_boundary_sized and of boundary= of Cascade.coco_match
+    (DESIGN.md §25), on the host, before anything is launched (ValueError) -> the radius of each plane of `sizes`, int32 (P,).
+    dilation_ratio: a finite real > 0 (no bool), the share of each plane's own diagonal (`boundary_radius`); a plane whose radius would
+    exceed 16384 is refused.  radius: instead of it, one int in [1, 16384] for all planes or one per plane (no bools); together with a
+    dilation_ratio other than the default it is a contradiction."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    is_real = isinstance(dilation_ratio, (int, float, np.integer, np.floating)) and not isinstance(dilation_ratio, (bool, np.bool_))
+    if not is_real or not np.isfinite(float(dilation_ratio)) or not float(dilation_ratio) > 0.0:
+        raise ValueError(f"{who}: the dilation ratio must be a finite real > 0, got {dilation_ratio!r}")
+    P = len(sizes)
+    if radius is None:
+        out = [boundary_radius(int(h), int(w), float(dilation_ratio)) for h, w in sizes]
+        if any(d > BOUNDARY_MAX_RADIUS for d in out):
+            raise ValueError(f"{who}: a dilation ratio of {dilation_ratio!r} gives a radius above {BOUNDARY_MAX_RADIUS}")
+        return np.asarray(out, dtype=np.int32).reshape(P)
+    if float(dilation_ratio) != BOUNDARY_RATIO:
+        raise ValueError(f"{who}: give either radius= or a dilation ratio, not both")
+    if is_int(radius):
+        radius = [radius] * P
+    if isinstance(radius, (str, bytes)) or not hasattr(radius, "__len__") or len(radius) != P or not all(is_int(v) for v in radius):
+        raise ValueError(f"{who}: radius must be an int or hold one int per plane, {P} of them")
+    if not all(1 <= int(v) <= BOUNDARY_MAX_RADIUS for v in radius):
+        raise ValueError(f"{who}: a radius must lie in [1, {BOUNDARY_MAX_RADIUS}]")
+    return np.asarray([int(v) for v in radius], dtype=np.int32).reshape(P)
+
+
 @dataclass
 class MatchRequest:
     """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
@@ -919,14 +956,16 @@ class CocoMatches:
     status: torch.Tensor            # (1,) int32, non-zero if the kernel refused a group
     overlaps: Optional["SizedOverlaps"]     # the intersections behind it; None when no group has both detections and annotations
     request: MatchRequest
+    boundary_overlaps: Optional["SizedOverlaps"] = None     # coco_match(boundary=...): the intersections of the boundaries
 
     def check(self) -> None:
         """RuntimeError if the kernel refused a group or a pair (synchronises).  The tables come from `match_request`, so a refused
         group says that the library is broken; a refused pair is two planes whose tables do not fit."""
         if int(self.status.item()) != 0:
             raise RuntimeError("coco_match: cvlm_coco_match refused a group: offsets or a pair block that do not fit")
-        if self.overlaps is not None:
-            self.overlaps.check()
+        for overlaps in (self.overlaps, self.boundary_overlaps):
+            if overlaps is not None:
+                overlaps.check()
 
     def to_host(self) -> dict:
         """Everything cocoeval.accumulate needs, as numpy arrays, by ONE read of the device (synchronises): the five result tables under
@@ -1539,9 +1578,34 @@ class MaskUtilities:
         return SizedOverlaps(pairs=tab, inter=inter, area_a=pick(a, 0), area_b=pick(b, 1), status=status)
 
 
+    # ---- Boundary IoU ---------------------------------------------------------------------------------------------------
+    def mask_boundary_sized(self, sized: "SizedMasks", *, dilation_ratio=BOUNDARY_RATIO, radius=None) -> "SizedMasks":
+        """The boundary of each sized plane -> SizedMasks of the same sizes, offsets and level (cvlm_mask_boundary_sized):
+        boundary_iou_api's mask_to_boundary -- the mask without its erosion by a square of radius d, pixels outside the image read as
+        clear, d = `boundary_radius` of the plane's own (h, w) or radius= --, at a cost that does not grow with d.  `boundary_request`
+        checks the arguments on the host before anything is launched (ValueError).  `area` is the boundary's pixel count and `box` a
+        clone of the input's (the box of a non-empty boundary is its mask's) when the input has them, both None when it has not;
+        `status` is the kernel's.  The result feeds `mask_inter_sized`, `mask_rle_sized` and `SizedMasks.concat` as it is: the Boundary
+        IoU of pairs is `mask_inter_sized(boundary(a), boundary(b), ...).iou()`.  One upload of the radius table and of the size
+        table, a workspace as large as the planes from torch.empty, no synchronisation."""
+        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda or not 1 <= len(sized.sizes) <= 65535:
+            raise ValueError("mask_boundary_sized: sized must be a SizedMasks of 1 .. 65535 planes on the device")
+        radii = boundary_request(sized.sizes, dilation_ratio=dilation_ratio, radius=radius)
+        dev = sized.bits.device
+        dims, _, max_words = sized_tables(sized.sizes)
+        stats = sized.area is not None
+        out = SizedMasks(bits=torch.empty_like(sized.bits), offsets=sized.offsets,
+                         area=torch.empty(len(sized.sizes), dtype=torch.int32, device=dev) if stats else None,
+                         box=sized.box.clone() if stats else None, status=torch.empty(1, dtype=torch.int32, device=dev),
+                         sizes=[tuple(z) for z in sized.sizes], level=sized.level)
+        hip.mask_boundary_sized(sized.bits, sized.offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(radii).to(dev), max_words,
+                                torch.empty_like(sized.bits), out.bits, out.area, out.status)
+        return out
+
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,
-                   gt_category=None, iscrowd=None, gt_area=None, iou_thrs=None, area_rngs=None, max_det: int = 100) -> "CocoMatches":
+                   gt_category=None, iscrowd=None, gt_area=None, iou_thrs=None, area_rngs=None, max_det: int = 100,
+                   boundary=None) -> "CocoMatches":
         """Detections against annotations as COCOeval.evaluateImg matches them -> CocoMatches (cvlm_coco_match), for every
         (image, category) group, area range and IoU threshold at once; `cocoeval.accumulate` / `summarize` turn it into AP and AR.  dets
         / gts: SizedMasks on this engine's device with areas, e.g. `sized` of infer_classes / decode and `rle_decode` /
@@ -1549,7 +1613,13 @@ class MaskUtilities:
         device, taken as it is (NaN ranks last), or a host sequence (NaN: ValueError).  The other arguments are `match_request`'s, which
         checks all of them on the host before anything is launched (ValueError).  Then: `mask_inter_sized(pairs=...)` for the groups'
         pair blocks (skipped when no group has both sides), gathers of the areas and scores into table order, one cvlm_coco_match call.
-        No workspace, no synchronisation: `CocoMatches.to_host()` does the one read."""
+        No workspace, no synchronisation: `CocoMatches.to_host()` does the one read.
+        boundary=ratio (None: exactly the launches and allocations above): the matching compares min(mask IoU, boundary
+        IoU) with the thresholds, as boundary_iou_api's COCOeval with iouType = "boundary" does -- `accumulate` / `summarize` over the
+        result are Boundary AP and AR.  ratio is `boundary_request`'s dilation ratio, 0.02 in the published evaluators.  Added, in this
+        order: `mask_boundary_sized` of dets and of gts, a second `mask_inter_sized(pairs=...)` on the boundaries (kept as
+        `boundary_overlaps`), the gathers of the boundaries' areas, and cvlm_coco_match_boundary in place of cvlm_coco_match.  The area
+        ranges keep using the masks' areas and gt_area."""
         for name, s in (("dets", dets), ("gts", gts)):
             if s is not None and (not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535):
                 raise ValueError(f"coco_match: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas, or None")
@@ -1562,6 +1632,10 @@ class MaskUtilities:
                             max_det=max_det)
         if not on_device and req.scores is None:
             raise ValueError("coco_match: scores must hold one number per detection")
+        if boundary is not None:
+            for s in (dets, gts):
+                if s is not None:
+                    boundary_request(s.sizes, dilation_ratio=boundary, who="coco_match")
         dev = self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         ND, NG = int(req.det_perm.size), int(req.gt_perm.size)
@@ -1584,9 +1658,22 @@ class MaskUtilities:
                           gt_match=torch.empty(A, T, NG, dtype=torch.int32, device=dev),
                           gt_ignore=torch.empty(A, NG, dtype=torch.uint8, device=dev), score=score,
                           status=torch.empty(1, dtype=torch.int32, device=dev), overlaps=overlaps, request=req)
-        hip.coco_match(up(req.det_offsets), up(req.gt_offsets), up(req.pair_offsets), inter, det_area.contiguous(), score.contiguous(),
-                       g_area.contiguous(), range_area.contiguous(), up(req.crowd), up(req.iou_thrs), up(req.area_rngs), req.max_det,
-                       out.dt_order, out.dt_match, out.dt_ignore, out.gt_match, out.gt_ignore, out.status)
+        if boundary is None:
+            hip.coco_match(up(req.det_offsets), up(req.gt_offsets), up(req.pair_offsets), inter, det_area.contiguous(), score.contiguous(),
+                           g_area.contiguous(), range_area.contiguous(), up(req.crowd), up(req.iou_thrs), up(req.area_rngs), req.max_det,
+                           out.dt_order, out.dt_match, out.dt_ignore, out.gt_match, out.gt_ignore, out.status)
+            return out
+        none = torch.empty(0, dtype=torch.int32, device=dev)
+        det_b = None if dets is None else self.mask_boundary_sized(dets, dilation_ratio=boundary)
+        gt_b = None if gts is None else det_b if gts is dets else self.mask_boundary_sized(gts, dilation_ratio=boundary)
+        out.boundary_overlaps = self.mask_inter_sized(det_b, gt_b, pairs=req.pairs) if req.pairs.shape[0] else None
+        inter_b = out.boundary_overlaps.inter if out.boundary_overlaps is not None else none
+        det_area_b = det_b.area.index_select(0, det_perm) if ND else none
+        gt_area_b = gt_b.area.index_select(0, up(req.gt_perm)) if NG else none
+        hip.coco_match_boundary(up(req.det_offsets), up(req.gt_offsets), up(req.pair_offsets), inter, det_area.contiguous(),
+                                score.contiguous(), g_area.contiguous(), range_area.contiguous(), up(req.crowd), up(req.iou_thrs),
+                                up(req.area_rngs), req.max_det, inter_b, det_area_b.contiguous(), gt_area_b.contiguous(), out.dt_order,
+                                out.dt_match, out.dt_ignore, out.gt_match, out.gt_ignore, out.status)
         return out
 
 

@@ -871,6 +871,66 @@ int cvlm_debug_coco_match_host(const int32_t* det_offsets, const int32_t* gt_off
                                const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det, int32_t* dt_order,
                                int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status);
 
+/* Boundary IoU and Boundary AP (Cheng et al., "Boundary IoU", CVPR 2021; boundary_iou_api's mask_to_boundary and its
+ * COCOeval with iouType = "boundary").
+ * cvlm_mask_boundary_sized: the boundary of each of P sized planes, as a sized plane of the same layout.  bits / n_bytes / offsets int64
+ * [P + 1] in bytes / dims int32 [P][2] as cvlm_mask_pack_sized's; radius int32 [P], 1 .. 16384, the plane's own d -- on the host
+ * max(1, int(round(0.02 * sqrt(h^2 + w^2)))) in float64 with round-half-to-even; all device memory.  With X the plane,
+ *   ero(y, x)  = AND of X over |y' - y| <= d, |x' - x| <= d, a pixel OUTSIDE the plane read as CLEAR;
+ *   boundary   = X & ~ero
+ * which is cv2.copyMakeBorder(X, 1, 1, 1, 1, BORDER_CONSTANT, 0), cv2.erode(., ones((3, 3)), iterations = d) and the crop.  So ero is
+ * inside X; a pixel nearer than d to the plane's border is never in ero (a mask cut by the border has a boundary there); 2 d + 1 >
+ * min(h, w) gives boundary = X; an empty plane gives an empty boundary; the box of a non-empty boundary is the box of its mask.
+ * Pixels at columns >= w read as clear whatever the input's pad bits hold, and the output's pad bits are 0.  out_bits: n_bytes bytes,
+ * the same offsets; out_area int32 [P], the boundary's popcount, may be NULL; status int32 [1].  The Boundary IoU of two planes is the
+ * IoU of their boundaries: cvlm_mask_inter_sized on two outputs of this entry.
+ * A plane is REFUSED whole -- status[0] |= 1 (the call zeroes it first), out_area 0, nothing of it read -- if it fails
+ * cvlm_mask_pack_sized's check of (h, w, offsets[p], offsets[p + 1], n_bytes) or if its radius lies outside [1, 16384]; its output
+ * bytes [offsets[p], offsets[p + 1]) are zeroed if that range is whole words inside [0, n_bytes) and forwards, and left alone
+ * otherwise.  No table content makes a kernel read or store outside bits, out_bits or the workspace.
+ * The cost does not grow with d.  Three launches: the init launch (out_area, status); a row pass, a wave per row: chunks of 64 pixels
+ * as 64-bit masks, the run of set pixels ending at / starting at each pixel from a count of leading / trailing zeros plus one carried
+ * integer per direction, a pixel survives iff both runs reach d + 1 -- into the workspace; a column pass, a wave per 64 pixel columns
+ * and SEGMENT of max(4 d, 128) rows (rounded up to 32): lane i counts the consecutive surviving rows of its column, one ballot of
+ * "count >= 2 d + 1" is the eroded row y - d, X & ~ero leaves as whole words; a segment starts its counts 2 d rows early; popcounts
+ * reach memory as at most one integer atomic per workgroup and plane.  Whole-word stores only, no atomics on planes, 64-bit offsets,
+ * no thread waits for another workgroup.  max_words: the largest h * ceil(w / 32) of the call, which sizes the grid (a smaller value
+ * costs time, not correctness).
+ * workspace: caller-owned, n_bytes bytes, contents need no initialisation.  No allocation, no synchronisation, no pointer kept; every
+ * output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (out_area may be NULL); bits / dims / radius / workspace / out_bits
+ * / out_area / status not 4-byte aligned, offsets not 8-byte aligned; P outside [1, 65535]; n_bytes < 4; max_words outside [1,
+ * 16384 * 512]; out_bits or the workspace sharing a byte with bits, or with each other (n_bytes bytes each). */
+int cvlm_mask_boundary_sized(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* radius,
+                             int32_t P, int64_t max_words, void* workspace, uint8_t* out_bits, int32_t* out_area, int32_t* status,
+                             void* stream);
+/* Outside the ABI contract: cvlm_mask_boundary_sized on HOST memory, no stream -- the same per-thread functions
+ * (csrc/boundary_logic.h) run sequentially on the CPU, with the kernel's segments.  Same outputs, same refusals. */
+int cvlm_debug_mask_boundary_sized_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims,
+                                        const int32_t* radius, int32_t P, int64_t max_words, void* workspace, uint8_t* out_bits,
+                                        int32_t* out_area, int32_t* status);
+/* cvlm_coco_match_boundary: cvlm_coco_match with the IoU of a pair replaced by min(mask IoU, boundary IoU) -- what boundary_iou_api's
+ * COCOeval compares with a threshold.  inter_b int32 [N]: the intersections of the BOUNDARIES, in inter's order (-1: refused);
+ * det_area_b int32 [ND] and gt_area_b int32 [NG]: the boundaries' areas, in table order.  Both IoUs are cvlm_coco_match's quotient of
+ * their own integers under the same crowd flag, one correctly rounded double division each; -1 on either side stays -1.  The area
+ * ranges keep using det_area and gt_range_area -- the mask's area and the annotation file's "area" --, as the published evaluator
+ * does.  Everything else, the outputs, the refusals and the launches, is cvlm_coco_match's: the matching kernel in a second
+ * instantiation.  CVLM_E_BADARG as there, and for inter_b / det_area_b / gt_area_b NULL where N / ND / NG is not 0 or not 4-byte
+ * aligned. */
+int cvlm_coco_match_boundary(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                             const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND, const int32_t* gt_area,
+                             const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG, const double* iou_thrs, int32_t T,
+                             const double* area_rngs, int32_t A, int32_t max_det, const int32_t* inter_b, const int32_t* det_area_b,
+                             const int32_t* gt_area_b, int32_t* dt_order, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match,
+                             uint8_t* gt_ignore, int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_coco_match_boundary on HOST memory, no stream.  Same outputs, same refusals. */
+int cvlm_debug_coco_match_boundary_host(const int32_t* det_offsets, const int32_t* gt_offsets, const int64_t* pair_offsets, int32_t E,
+                                        const int32_t* inter, int64_t N, const int32_t* det_area, const float* score, int32_t ND,
+                                        const int32_t* gt_area, const double* gt_range_area, const uint8_t* gt_crowd, int32_t NG,
+                                        const double* iou_thrs, int32_t T, const double* area_rngs, int32_t A, int32_t max_det,
+                                        const int32_t* inter_b, const int32_t* det_area_b, const int32_t* gt_area_b, int32_t* dt_order,
+                                        int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status);
+
 /* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
  * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
  * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
