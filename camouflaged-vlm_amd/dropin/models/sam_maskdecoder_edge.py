@@ -256,6 +256,12 @@ class SAM(nn.Module):
         forms it -> engine.SizedMasks (engine.Cascade.mask_boundary_sized)."""
         return self.cascade().mask_boundary_sized(sized, dilation_ratio=dilation_ratio, radius=radius)
 
+    def mask_contours_sized(self, sized, *, connectivity=8):
+        """EXTENSION, not a reference method: the outline of each plane of an engine.SizedMasks as closed polygons along the pixel
+        edges -- what the reference's GenericMask.mask_to_polygons (models/utils/visualizer.py:125) gets from cv2.findContours on the
+        host -> engine.MaskContours, whose `to_coco()` gives the polygon lists (engine.Cascade.mask_contours_sized)."""
+        return self.cascade().mask_contours_sized(sized, connectivity=connectivity)
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads

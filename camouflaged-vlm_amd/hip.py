@@ -93,6 +93,10 @@ _SIGNATURES = {
     "cvlm_debug_mask_boundary_sized_host": "i:plpppilpppp",
     "cvlm_coco_match_boundary": "i:pppiplppipppipipiippppppppps",
     "cvlm_debug_coco_match_boundary_host": "i:pppiplppipppipipiippppppppp",
+    "cvlm_mask_contour_workspace_bytes": "l:ill",
+    "cvlm_mask_contour_count": "i:plppiilpps",
+    "cvlm_mask_contour_emit": "i:plppiilplppplppls",
+    "cvlm_debug_mask_contour_host": "i:plppiippppplp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1323,6 +1327,84 @@ def mask_boundary_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: to
     assert not bits.is_cuda
     _call("cvlm_debug_mask_boundary_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
           int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
+
+
+# ---- Contours: COCO polygons out ------------------------------------------------------------------------------------------
+def _contour_planes(bits, offsets, dims) -> int:
+    """Shape and dtype checks of the planes of the contour entries -> P."""
+    P = int(dims.shape[0])
+    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
+    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
+    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
+    assert offsets.device == bits.device and dims.device == bits.device
+    return P
+
+
+def _contour_outputs(P, dev, vertex_offsets, xy, ring_start, n_rings, status) -> int:
+    """Shape and dtype checks of the outputs of the contour emit -> total."""
+    total = int(xy.shape[0])
+    assert vertex_offsets.dtype == torch.int64 and tuple(vertex_offsets.shape) == (P + 1,) and vertex_offsets.is_contiguous()
+    assert xy.dtype == torch.int16 and tuple(xy.shape) == (total, 2) and xy.is_contiguous()
+    assert ring_start.dtype == torch.uint8 and tuple(ring_start.shape) == (total,) and ring_start.is_contiguous()
+    assert n_rings.dtype == torch.int32 and tuple(n_rings.shape) == (P, 2) and n_rings.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == dev for t in (vertex_offsets, xy, ring_start, n_rings, status))
+    return total
+
+
+def mask_contour_workspace_bytes(P: int, round_vertices: int, max_words: int) -> int:
+    """Bytes of workspace of one `mask_contour_emit` call on P planes that hold round_vertices vertices together (host arithmetic)."""
+    need = int(load().cvlm_mask_contour_workspace_bytes(int(P), int(round_vertices), int(max_words)))
+    if need < 0:
+        raise RuntimeError(f"cvlm_mask_contour_workspace_bytes failed with code {need}")
+    return need
+
+
+def mask_contour_count(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, connectivity: int, max_words: int,
+                       n_vertices: torch.Tensor, status: torch.Tensor) -> None:
+    """Vertices of the crack contour of each sized plane (include/cvlm.h: cvlm_mask_contour_count): bits flat uint8, byte
+    offsets int64 [P + 1], dims int32 [P][2] -> n_vertices int32 [P], status int32 [1] = 1 if a plane was refused."""
+    P = _contour_planes(bits, offsets, dims)
+    assert n_vertices.dtype == torch.int32 and tuple(n_vertices.shape) == (P,) and n_vertices.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1 and n_vertices.device == bits.device and status.device == bits.device
+    _on_current_device(bits)
+    _call("cvlm_mask_contour_count", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity), int(max_words),
+          n_vertices.data_ptr(), status.data_ptr())
+
+
+def mask_contour_emit(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, connectivity: int, max_words: int,
+                      vertex_offsets: torch.Tensor, round_vertices: int, xy: torch.Tensor, ring_start: torch.Tensor, n_rings: torch.Tensor,
+                      status: torch.Tensor, workspace: torch.Tensor) -> None:
+    """The rings of each sized plane (include/cvlm.h: cvlm_mask_contour_emit).  offsets / dims / vertex_offsets / n_rings
+    may be views of longer tables -- one round of planes of a larger call --; xy int16 [total][2] and ring_start uint8 [total] are whole
+    and vertex_offsets absolute.  round_vertices: at least the vertices of these planes."""
+    P = _contour_planes(bits, offsets, dims)
+    total = _contour_outputs(P, bits.device, vertex_offsets, xy, ring_start, n_rings, status)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
+    _on_current_device(bits)
+    p = lambda t: t.data_ptr() if t.numel() else None
+    _call("cvlm_mask_contour_emit", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity), int(max_words),
+          vertex_offsets.data_ptr(), int(round_vertices), p(xy), p(ring_start), n_rings.data_ptr(), total, status.data_ptr(),
+          workspace.data_ptr(), workspace.numel())
+
+
+def mask_contour_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, connectivity: int, n_vertices: torch.Tensor,
+                      status: torch.Tensor, vertex_offsets: Optional[torch.Tensor] = None, xy: Optional[torch.Tensor] = None,
+                      ring_start: Optional[torch.Tensor] = None, n_rings: Optional[torch.Tensor] = None) -> None:
+    """`mask_contour_count` (vertex_offsets None) or count and emit on HOST tensors without a device (cvlm_debug_mask_contour_host: the
+    kernels' maps and successors, the rings followed sequentially)."""
+    P = _contour_planes(bits, offsets, dims)
+    assert not bits.is_cuda
+    assert n_vertices.dtype == torch.int32 and tuple(n_vertices.shape) == (P,) and n_vertices.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    if vertex_offsets is None:
+        _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
+              n_vertices.data_ptr(), None, None, None, None, 0, status.data_ptr())
+        return
+    total = _contour_outputs(P, bits.device, vertex_offsets, xy, ring_start, n_rings, status)
+    p = lambda t: t.data_ptr() if t.numel() else None
+    _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
+          n_vertices.data_ptr(), vertex_offsets.data_ptr(), p(xy), p(ring_start), n_rings.data_ptr(), total, status.data_ptr())
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

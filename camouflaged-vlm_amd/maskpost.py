@@ -841,6 +841,103 @@ def boundary_request(sizes, *, dilation_ratio=BOUNDARY_RATIO, radius=None, who: 
     return np.asarray([int(v) for v in radius], dtype=np.int32).reshape(P)
 
 
+CONTOUR_MAX_VERTS = 1 << 22       # vertices of one plane's contour (csrc/contour_logic.h: CT_MAX_VERTS)
+
+
+def contour_request(sizes, *, connectivity=8, who: str = "mask_contours_sized"):
+    """Every check of the arguments of Cascade.mask_contours_sized, on the host, before anything is launched
+    (ValueError) -> (the (h, w) pairs as ints, the connectivity).  sizes: 1 .. 65535 pairs of ints in [1, 16384], no bools;
+    connectivity: the int 4 or 8, no bool -- how the foreground hangs together where two pixels touch at a corner."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not is_int(connectivity) or int(connectivity) not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be the int 4 or 8, got {connectivity!r}")
+    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
+        raise ValueError(f"{who}: sizes must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
+    if not 1 <= len(sizes) <= 65535:
+        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(sizes)}")
+    out = []
+    for pair in sizes:
+        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+            raise ValueError(f"{who}: sizes must hold (h, w) pairs, got {pair!r}")
+        h, w = pair
+        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+            raise ValueError(f"{who}: a size must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
+        out.append((int(h), int(w)))
+    return out, int(connectivity)
+
+
+def contour_rounds(n_vertices, max_words: int, cap: int, need) -> list:
+    """The rounds of Cascade.mask_contours_sized: consecutive planes [a, b) taken while need(b - a, their vertices, max_words) stays
+    within `cap` bytes, one plane at least -> [(a, b, vertices, bytes)].  Pure host arithmetic; `need` is
+    hip.mask_contour_workspace_bytes."""
+    out, a, P = [], 0, len(n_vertices)
+    while a < P:
+        b, rv = a + 1, int(n_vertices[a])
+        while b < P and need(b + 1 - a, rv + int(n_vertices[b]), max_words) <= cap:
+            rv += int(n_vertices[b])
+            b += 1
+        out.append((a, b, rv, need(b - a, rv, max_words)))
+        a = b
+    return out
+
+
+@dataclass
+class MaskContours:
+    """Crack contours of P sized planes (Cascade.mask_contours_sized), on the device: the boundary between set and clear
+    pixels as closed rings of lattice points -- pixel (y, x) is the square [x, x + 1] x [y, y + 1] --, foreground on the right, one
+    vertex per turn.  Plane p's vertices are xy[vertex_offsets[p] : vertex_offsets[p + 1]], ring after ring; a ring starts at its vertex
+    with the smallest (y, x) and a plane's rings are ordered by their starts.  An outer ring's first edge heads east and its signed
+    area is positive; a hole's heads south and its area is negative; the areas of a plane sum to its popcount."""
+    xy: torch.Tensor                # (total, 2) int16 (x, y)
+    ring_start: torch.Tensor        # (total,) uint8, 1 on the first vertex of each ring
+    vertex_offsets: torch.Tensor    # (P + 1,) int64
+    n_vertices: torch.Tensor        # (P,) int32
+    n_rings: torch.Tensor           # (P, 2) int32 (outer rings, holes)
+    sizes: list                     # P (h, w) pairs, on the host
+    connectivity: int
+    status: torch.Tensor            # int32 on the device, non-zero if a plane was refused
+
+    def check(self) -> None:
+        """RuntimeError if a plane was refused (synchronises): a plane of more than 2^22 vertices, or bits that were written between
+        the count and the emit."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError(f"mask_contours_sized: a plane was refused: more than {CONTOUR_MAX_VERTS} vertices, or were the bits written "
+                               "while the call ran?")
+
+    def rings(self) -> torch.Tensor:
+        """Ring r of the call is xy[rings[r] : rings[r + 1]] -> (R + 1,) int64 on the device (synchronises: R is data)."""
+        first = torch.nonzero(self.ring_start, as_tuple=False).reshape(-1)
+        return torch.cat([first, torch.full((1,), int(self.xy.shape[0]), dtype=torch.int64, device=first.device)])
+
+    def _host_rings(self):
+        """-> per plane the list of its rings as int64 arrays (n, 2); one copy of each of the three tensors."""
+        self.check()
+        xy, start = self.xy.cpu().numpy().astype(np.int64), self.ring_start.cpu().numpy()
+        vo = self.vertex_offsets.cpu().numpy()
+        out = []
+        for p in range(vo.size - 1):
+            a, b = int(vo[p]), int(vo[p + 1])
+            cuts = a + np.flatnonzero(start[a:b])
+            out.append([xy[c:d] for c, d in zip(cuts, list(cuts[1:]) + [b])])
+        return out
+
+    def to_coco(self, holes: bool = True) -> list:
+        """On the host: one {"size": [h, w], "polygons": [[x0, y0, x1, y1, ...], ...]} per plane, a ring per polygon -- the list
+        `polygons_request` takes and the reference's GenericMask holds as `polygons`.  holes=False drops the rings whose first edge
+        heads south.  With holes, `polygons_decode` of each ring as a plane of its own, XORed, is the mask; the OR of one annotation
+        fills the holes.  Synchronises."""
+        out = []
+        for (h, w), rings in zip(self.sizes, self._host_rings()):
+            keep = [r for r in rings if holes or r[1, 0] != r[0, 0]]
+            out.append({"size": [int(h), int(w)], "polygons": [r.reshape(-1).tolist() for r in keep]})
+        return out
+
+    def signed_areas(self) -> list:
+        """On the host: per plane the float64 array of its rings' signed areas 1/2 sum(x_k y_k+1 - x_k+1 y_k).  Synchronises."""
+        area = lambda r: 0.5 * float((r[:, 0] * np.roll(r[:, 1], -1) - np.roll(r[:, 0], -1) * r[:, 1]).sum())
+        return [np.asarray([area(r) for r in rings], dtype=np.float64) for rings in self._host_rings()]
+
+
 @dataclass
 class MatchRequest:
     """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
@@ -1601,6 +1698,39 @@ class MaskUtilities:
         hip.mask_boundary_sized(sized.bits, sized.offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(radii).to(dev), max_words,
                                 torch.empty_like(sized.bits), out.bits, out.area, out.status)
         return out
+
+    # ---- Contours: COCO polygons out ---------------------------------------------------------------------------------------
+    def mask_contours_sized(self, sized: "SizedMasks", *, connectivity=8) -> "MaskContours":
+        """The crack contour of each sized plane -> MaskContours (cvlm_mask_contour_count / cvlm_mask_contour_emit), whose
+        `to_coco()` is the polygon list of an iscrowd = 0 annotation and of the reference's GenericMask.  `contour_request` checks the
+        arguments on the host before anything is launched (ValueError).  The count, one torch.cumsum, ONE read of n_vertices (the
+        call's only synchronisation), then the host cuts the planes into rounds whose workspace stays within RLE_WS_CAP -- a plane
+        that needs more on its own is a round of its own -- and one emit call per round goes through the grow-only workspace
+        "cls_rle".  The status words are folded into one on the device.  Launches on the caller's stream."""
+        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
+            raise ValueError("mask_contours_sized: sized must be a SizedMasks on the device")
+        sizes, connectivity = contour_request(sized.sizes, connectivity=connectivity)
+        P, dev = len(sizes), sized.bits.device
+        dims, _, max_words = sized_tables(sizes)
+        dims = torch.from_numpy(dims).to(dev)
+        n_vertices = torch.empty(P, dtype=torch.int32, device=dev)
+        count_status = torch.empty(1, dtype=torch.int32, device=dev)
+        hip.mask_contour_count(sized.bits, sized.offsets, dims, connectivity, max_words, n_vertices, count_status)
+        offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_vertices, 0, dtype=torch.int64, out=offsets[1:])
+        counted = n_vertices.cpu().numpy()                           # the one synchronisation
+        total = int(counted.astype(np.int64).sum())
+        rounds = contour_rounds(counted, max_words, RLE_WS_CAP, hip.mask_contour_workspace_bytes)
+        xy = torch.empty(total, 2, dtype=torch.int16, device=dev)
+        ring_start = torch.empty(total, dtype=torch.uint8, device=dev)
+        n_rings = torch.empty(P, 2, dtype=torch.int32, device=dev)
+        status = torch.empty(len(rounds), dtype=torch.int32, device=dev)
+        ws = self.ws.scratch("cls_rle", max(r[3] for r in rounds))
+        for i, (a, b, rv, need) in enumerate(rounds):
+            hip.mask_contour_emit(sized.bits, sized.offsets[a:b + 1], dims[a:b], connectivity, max_words, offsets[a:b + 1], rv, xy, ring_start,
+                                  n_rings[a:b], status[i:i + 1], ws[:need])
+        return MaskContours(xy=xy, ring_start=ring_start, vertex_offsets=offsets, n_vertices=n_vertices, n_rings=n_rings, sizes=sizes,
+                            connectivity=connectivity, status=torch.maximum(torch.amax(status, 0, keepdim=True), count_status))
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

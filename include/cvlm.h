@@ -931,6 +931,55 @@ int cvlm_debug_coco_match_boundary_host(const int32_t* det_offsets, const int32_
                                         const int32_t* inter_b, const int32_t* det_area_b, const int32_t* gt_area_b, int32_t* dt_order,
                                         int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, int32_t* status);
 
+/* Contours of sized planes: COCO polygons out.  The CRACK contour of a plane is the boundary between its set and its
+ * clear pixels, a pixel outside the plane and a pad bit read as clear.  Pixel (y, x) is the square [x, x + 1] x [y, y + 1]; every side
+ * of a set pixel whose neighbour across it is clear is a unit edge directed with the foreground on its right (top side east, right
+ * side south, bottom side west, left side north).  Where a lattice point has two incoming edges -- its four pixels are a diagonal pair
+ * -- connectivity 8 follows the edge of the diagonal pixel (a left turn) and connectivity 4 the edge of the same pixel (a right turn);
+ * the edges then fall into disjoint rings.  Straight runs are merged: a VERTEX is a lattice point where the ring turns, a ring has an
+ * even number of them, 4 at least.  A ring starts at its vertex with the smallest (y, x) and follows the edges; the rings of a plane
+ * are ordered by their start.  A ring with positive area 1/2 sum(x_k y_k+1 - x_k+1 y_k) is an outer ring (its first edge heads east),
+ * one with negative area a hole (its first edge heads south); the areas of a plane's rings sum to its popcount, and each ring taken
+ * as one polygon by cvlm_mask_poly_decode, the results XORed, gives the plane back bit for bit.
+ * Planes: bits / n_bytes / offsets int64 [P + 1] in bytes / dims int32 [P][2] as cvlm_mask_pack_sized's; max_words: the largest
+ * h * ceil(w / 32) of the call (it sizes grids and the maps of the workspace); all device memory.
+ * cvlm_mask_contour_count: n_vertices int32 [P], the vertices of each plane; status int32 [1].  Three launches (init, count -- a
+ * thread per lattice word on the words of two pixel rows and the carry bit of the neighbouring word, at most one integer atomic per
+ * workgroup and plane --, cap).
+ * cvlm_mask_contour_emit: the rings of the P planes of the call.  vertex_offsets int64 [P + 1]: plane p's vertices go to the entries
+ * [vertex_offsets[p], vertex_offsets[p + 1]) of xy int16 [total][2] = (x, y) and ring_start uint8 [total] (1 on the first vertex of
+ * each ring); the slice's length is the count the plane must have.  n_rings int32 [P][2] = (outer rings, holes).  A caller may pass
+ * a sub-range of a longer table as offsets + p0, dims + 2 p0, vertex_offsets + p0, n_rings + 2 p0 with the absolute xy, ring_start and
+ * total: rounds under a workspace cap are calls.  round_vertices >= vertex_offsets[P] - vertex_offsets[0].  Six launches: init, the
+ * corner maps, a workgroup scan per plane, the successors (a vertical partner is found by walking the plane's column: at most h
+ * steps), pointer doubling in one workgroup per plane (at most 24 rounds, ended by a workgroup-uniform flag), the placement.  One
+ * 32-bit store per vertex; every store's slot is checked against the slice first; 64-bit offsets; no thread waits for another workgroup.
+ * A plane is REFUSED -- status[0] |= 1 (each call zeroes it first), n_vertices 0 / n_rings (0, 0), its slice, where that is inside
+ * [0, total], zeroed, nothing of it read -- if it fails cvlm_mask_pack_sized's check of (h, w, offsets[p], offsets[p + 1], n_bytes), if
+ * it has more than 2^22 vertices, or, in the emit, if its slice is not 0 <= v0 <= v1 <= total, lies before vertex_offsets[0] or ends
+ * beyond round_vertices behind it, if (h + 1) (w / 32 + 1) > 2 max_words + 2, or if it does not have exactly v1 - v0 vertices (the
+ * bits were written between the two calls).  No table content makes a kernel read or store outside bits, the outputs or the workspace.
+ * workspace: caller-owned, 16-byte aligned, cvlm_mask_contour_workspace_bytes(P, round_vertices, max_words) bytes = 4 P (rounded) +
+ * 20 P (2 max_words + 2) + 28 round_vertices; contents need no initialisation.  No allocation, no synchronisation, no pointer kept; every
+ * output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (xy and ring_start may be NULL when total is 0); bits / dims /
+ * n_vertices / xy / n_rings / status not 4-byte aligned, offsets / vertex_offsets not 8-byte aligned, the workspace not 16-byte aligned;
+ * P outside [1, 65535]; n_bytes < 4; max_words outside [1, 16384 * 512]; connectivity not 4 or 8; total < 0; round_vertices outside
+ * [0, 2^22 P]; a workspace below cvlm_mask_contour_workspace_bytes; an output or the workspace sharing a byte with bits or with another
+ * output. */
+int64_t cvlm_mask_contour_workspace_bytes(int32_t P, int64_t round_vertices, int64_t max_words);
+int cvlm_mask_contour_count(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t P, int32_t connectivity,
+                            int64_t max_words, int32_t* n_vertices, int32_t* status, void* stream);
+int cvlm_mask_contour_emit(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t P, int32_t connectivity,
+                           int64_t max_words, const int64_t* vertex_offsets, int64_t round_vertices, int16_t* xy, uint8_t* ring_start,
+                           int32_t* n_rings, int64_t total, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* Outside the ABI contract: both on HOST memory, no stream, no workspace -- the maps and successors of csrc/contour_logic.h, the rings
+ * by following the successors sequentially.  vertex_offsets == NULL: only n_vertices and status.  Same outputs, same refusals (the two
+ * that concern the workspace aside). */
+int cvlm_debug_mask_contour_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t P,
+                                 int32_t connectivity, int32_t* n_vertices, const int64_t* vertex_offsets, int16_t* xy, uint8_t* ring_start,
+                                 int32_t* n_rings, int64_t total, int32_t* status);
+
 /* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
  * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
  * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
