@@ -262,6 +262,17 @@ class SAM(nn.Module):
         host -> engine.MaskContours, whose `to_coco()` gives the polygon lists (engine.Cascade.mask_contours_sized)."""
         return self.cascade().mask_contours_sized(sized, connectivity=connectivity)
 
+    def mask_distance_sized(self, sized, *, reach=None):
+        """EXTENSION, not a reference method: the exact squared Euclidean distance map of each plane of an engine.SizedMasks
+        -> engine.MaskDistances (engine.Cascade.mask_distance_sized)."""
+        return self.cascade().mask_distance_sized(sized, reach=reach)
+
+    def mask_surface_distances(self, a, b, *, pairs=None, tolerance=0.008, surface="boundary", reach=None):
+        """EXTENSION, not a reference method: how far the contours of pairs of planes of two engine.SizedMasks lie apart
+        -> engine.SurfaceTotals, from which surfeval.surface_metrics gives the Hausdorff distance, ASSD, NSD and the boundary
+        F-measure (engine.Cascade.mask_surface_distances)."""
+        return self.cascade().mask_surface_distances(a, b, pairs=pairs, tolerance=tolerance, surface=surface, reach=reach)
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads

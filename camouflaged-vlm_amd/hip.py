@@ -97,6 +97,12 @@ _SIGNATURES = {
     "cvlm_mask_contour_count": "i:plppiilpps",
     "cvlm_mask_contour_emit": "i:plppiilplppplppls",
     "cvlm_debug_mask_contour_host": "i:plppiippppplp",
+    "cvlm_mask_distance_workspace_bytes": "l:il",
+    "cvlm_mask_distance_sized": "i:plpppilplplpps",
+    "cvlm_debug_mask_distance_sized_host": "i:plpppilplplpp",
+    "cvlm_mask_surface_workspace_bytes": "l:l",
+    "cvlm_mask_surface_totals": "i:plppipplpiplpilplppppppps",
+    "cvlm_debug_mask_surface_totals_host": "i:plppipplpiplpilplppppppp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1405,6 +1411,108 @@ def mask_contour_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Ten
     p = lambda t: t.data_ptr() if t.numel() else None
     _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
           n_vertices.data_ptr(), vertex_offsets.data_ptr(), p(xy), p(ring_start), n_rings.data_ptr(), total, status.data_ptr())
+
+
+# ---- Distance maps and surface totals --------------------------------------------------------------------------------------
+DT_FAR = 0x7fffffff               # D2 of a pixel with no set pixel within reach (csrc/distance_logic.h)
+
+
+def mask_distance_workspace_bytes(P: int, max_pixels: int) -> int:
+    """Bytes of workspace that hold `mask_distance_sized` on P planes of at most max_pixels pixels lying back to back (host arithmetic)."""
+    need = int(load().cvlm_mask_distance_workspace_bytes(int(P), int(max_pixels)))
+    if need < 0:
+        raise RuntimeError(f"cvlm_mask_distance_workspace_bytes failed with code {need}")
+    return need
+
+
+def mask_surface_workspace_bytes(N: int) -> int:
+    """Bytes of workspace of one `mask_surface_totals` call on N pairs (host arithmetic)."""
+    need = int(load().cvlm_mask_surface_workspace_bytes(int(N)))
+    if need < 0:
+        raise RuntimeError(f"cvlm_mask_surface_workspace_bytes failed with code {need}")
+    return need
+
+
+def _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status) -> int:
+    """Shape and dtype checks shared by `mask_distance_sized` and `mask_distance_sized_host` -> P."""
+    P = _contour_planes(bits, offsets, dims)
+    assert reach.dtype == torch.int32 and tuple(reach.shape) == (P,) and reach.is_contiguous()
+    assert pix_offsets.dtype == torch.int64 and tuple(pix_offsets.shape) == (P + 1,) and pix_offsets.is_contiguous()
+    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
+    assert out_d2.dtype == torch.int32 and out_d2.dim() == 1 and out_d2.is_contiguous() and out_d2.numel() >= 1
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == bits.device for t in (reach, pix_offsets, workspace, out_d2, status))
+    return P
+
+
+def mask_distance_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, reach: torch.Tensor, max_words: int,
+                        pix_offsets: torch.Tensor, workspace: torch.Tensor, out_d2: torch.Tensor, status: torch.Tensor) -> None:
+    """The squared distance map of each sized plane (include/cvlm.h: cvlm_mask_distance_sized): bits flat uint8, byte
+    offsets int64 [P + 1], dims int32 [P][2], reach int32 [P] in 0 .. 23170 (0: unlimited) -> out_d2 int32 [n_pix], plane p's h * w
+    values at pix_offsets[p] (int64 [P + 1], in pixels), DT_FAR where no set pixel is within reach; status int32 [1] = 1 if a plane was
+    refused.  workspace: uint8, 2 bytes per entry of out_d2 rounded up to 16.  max_words: the largest h * ceil(w / 32) of the call."""
+    P = _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status)
+    _on_current_device(bits)
+    _call("cvlm_mask_distance_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), reach.data_ptr(), P, int(max_words),
+          pix_offsets.data_ptr(), out_d2.numel(), workspace.data_ptr(), workspace.numel(), out_d2.data_ptr(), status.data_ptr())
+
+
+def mask_distance_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, reach: torch.Tensor, max_words: int,
+                             pix_offsets: torch.Tensor, workspace: torch.Tensor, out_d2: torch.Tensor, status: torch.Tensor) -> None:
+    """`mask_distance_sized` on HOST tensors without a device (cvlm_debug_mask_distance_sized_host: the kernels' per-thread functions
+    run sequentially)."""
+    P = _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_distance_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), reach.data_ptr(), P,
+          int(max_words), pix_offsets.data_ptr(), out_d2.numel(), workspace.data_ptr(), workspace.numel(), out_d2.data_ptr(), status.data_ptr())
+
+
+def _surface_totals(name: str, a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n, far, within,
+                    max_d2, sum_d2, sum_d, status) -> None:
+    Pa = _contour_planes(a_bits, a_offsets, a_dims)
+    Pb = int(b_dims.shape[0])
+    N, T = int(pairs.shape[0]), int(radii.shape[-1])
+    dev = a_bits.device
+    assert b_d2.dtype == torch.int32 and b_d2.dim() == 1 and b_d2.is_contiguous()
+    assert b_pix_offsets.dtype == torch.int64 and tuple(b_pix_offsets.shape) == (Pb + 1,) and b_pix_offsets.is_contiguous()
+    assert b_dims.dtype == torch.int32 and tuple(b_dims.shape) == (Pb, 2) and b_dims.is_contiguous()
+    assert pairs.dtype == torch.int32 and tuple(pairs.shape) == (N, 2) and pairs.is_contiguous()
+    assert radii.dtype == torch.int32 and tuple(radii.shape) == (N, T) and radii.is_contiguous()
+    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
+    for t in (n, far, max_d2):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (N,) and t.is_contiguous()
+    assert within.dtype == torch.int32 and tuple(within.shape) == (N, T) and within.is_contiguous()
+    assert sum_d2.dtype == torch.int64 and tuple(sum_d2.shape) == (N,) and sum_d2.is_contiguous()
+    assert sum_d.dtype == torch.float64 and tuple(sum_d.shape) == (N,) and sum_d.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == dev for t in (b_d2, b_pix_offsets, b_dims, pairs, radii, workspace, n, far, within, max_d2, sum_d2, sum_d, status))
+    _call(name, a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa, b_d2.data_ptr(), b_pix_offsets.data_ptr(),
+          b_d2.numel(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, radii.data_ptr(), T, int(max_words), workspace.data_ptr(),
+          workspace.numel(), n.data_ptr(), far.data_ptr(), within.data_ptr(), max_d2.data_ptr(), sum_d2.data_ptr(), sum_d.data_ptr(),
+          status.data_ptr())
+
+
+def mask_surface_totals(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_d2: torch.Tensor, b_pix_offsets: torch.Tensor,
+                        b_dims: torch.Tensor, pairs: torch.Tensor, radii: torch.Tensor, max_words: int, workspace: torch.Tensor,
+                        n: torch.Tensor, far: torch.Tensor, within: torch.Tensor, max_d2: torch.Tensor, sum_d2: torch.Tensor,
+                        sum_d: torch.Tensor, status: torch.Tensor) -> None:
+    """Directed surface totals of pairs (include/cvlm.h: cvlm_mask_surface_totals): over the set pixels of plane
+    pairs[i, 0] of A (sized planes) against map pairs[i, 1] of B (`mask_distance_sized`'s out_d2, pix_offsets and dims) -> n, far, max_d2
+    int32 [N], within int32 [N][T] at radii int32 [N][T], sum_d2 int64 [N], sum_d float64 [N]; status int32 [1] = 1 if a pair was refused
+    (-1 in its integers).  workspace: uint8, `mask_surface_workspace_bytes(N)`."""
+    _on_current_device(a_bits)
+    _surface_totals("cvlm_mask_surface_totals", a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n,
+                    far, within, max_d2, sum_d2, sum_d, status)
+
+
+def mask_surface_totals_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_d2: torch.Tensor,
+                             b_pix_offsets: torch.Tensor, b_dims: torch.Tensor, pairs: torch.Tensor, radii: torch.Tensor, max_words: int,
+                             workspace: torch.Tensor, n: torch.Tensor, far: torch.Tensor, within: torch.Tensor, max_d2: torch.Tensor,
+                             sum_d2: torch.Tensor, sum_d: torch.Tensor, status: torch.Tensor) -> None:
+    """`mask_surface_totals` on HOST tensors without a device (cvlm_debug_mask_surface_totals_host)."""
+    assert not a_bits.is_cuda
+    _surface_totals("cvlm_debug_mask_surface_totals_host", a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words,
+                    workspace, n, far, within, max_d2, sum_d2, sum_d, status)
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

@@ -938,6 +938,204 @@ class MaskContours:
         return [np.asarray([area(r) for r in rings], dtype=np.float64) for rings in self._host_rings()]
 
 
+DISTANCE_FAR = 0x7fffffff        # D2 of a pixel with no set pixel within reach (csrc/distance_logic.h: DT_FAR)
+DISTANCE_MAX_REACH = 23170        # a reach and a tolerance radius: 0 .. 23170, 23170^2 < 2^31 (DT_MAX_REACH)
+SURFACE_MAX_T = 8                 # tolerances of one Cascade.mask_surface_distances call (DT_MAX_T)
+SURFACE_RATIO = 0.008             # the tolerance of the published boundary F-measure: this share of the image's diagonal
+SURFACE_MAX_PAIRS = 1 << 24
+
+
+def surface_tolerance(h: int, w: int, ratio: float = SURFACE_RATIO) -> int:
+    """The tolerance radius of an h x w image, in float64: ceil(ratio * diagonal) for a ratio below 1 -- the published
+    boundary F-measure's bound_th -- and ceil(ratio) for a ratio that is a pixel count already.  (480, 640) -> 7, (1024, 1024) -> 12,
+    (1, 1) -> 1."""
+    return int(np.ceil(ratio * np.sqrt(h ** 2 + w ** 2))) if ratio < 1 else int(np.ceil(ratio))
+
+
+def _plane_sizes(sizes, who: str, name: str = "sizes") -> list:
+    """1 .. 65535 (h, w) pairs of ints in [1, 16384], no bools -> the pairs as ints (ValueError otherwise)."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
+        raise ValueError(f"{who}: {name} must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
+    if not 1 <= len(sizes) <= 65535:
+        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(sizes)}")
+    out = []
+    for pair in sizes:
+        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+            raise ValueError(f"{who}: {name} must hold (h, w) pairs, got {pair!r}")
+        h, w = pair
+        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+            raise ValueError(f"{who}: a size must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
+        out.append((int(h), int(w)))
+    return out
+
+
+def _reaches(reach, P: int, who: str) -> np.ndarray:
+    """reach= as one int in [0, 23170] for all planes or one per plane, None for 0 (unlimited), no bools -> int32 (P,)."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if reach is None:
+        reach = 0
+    if is_int(reach):
+        reach = [reach] * P
+    if isinstance(reach, (str, bytes)) or not hasattr(reach, "__len__") or len(reach) != P or not all(is_int(v) for v in reach):
+        raise ValueError(f"{who}: reach must be None, an int or hold one int per plane, {P} of them")
+    if not all(0 <= int(v) <= DISTANCE_MAX_REACH for v in reach):
+        raise ValueError(f"{who}: a reach must lie in [0, {DISTANCE_MAX_REACH}]")
+    return np.asarray([int(v) for v in reach], dtype=np.int32).reshape(P)
+
+
+def distance_request(sizes, *, reach=None, who: str = "mask_distance_sized"):
+    """Every check of the arguments of Cascade.mask_distance_sized, on the host, before anything is launched
+    (ValueError) -> (the (h, w) pairs as ints, the reach of each plane as int32 (P,)).  sizes: 1 .. 65535 pairs of ints in [1, 16384];
+    reach: None or 0 for an unlimited search, or an int in [1, 23170] -- for all planes or one per plane -- beyond which a pixel is
+    far; no bools."""
+    sizes = _plane_sizes(sizes, who)
+    return sizes, _reaches(reach, len(sizes), who)
+
+
+@dataclass
+class SurfaceRequest:
+    """What `surface_request` hands to Cascade.mask_surface_distances: host tables."""
+    a_sizes: list
+    b_sizes: list
+    pairs: np.ndarray               # (N, 2) int32 (plane of a, plane of b)
+    radii: np.ndarray               # (N, T) int32, the tolerance radii of each pair
+    reach_a: np.ndarray             # (Pa,) int32, the reach of each plane of a's map (read by the pixels of b)
+    reach_b: np.ndarray             # (Pb,) int32
+
+
+def surface_request(a_sizes, b_sizes, *, pairs=None, tolerance=SURFACE_RATIO, reach=None, who: str = "mask_surface_distances") -> SurfaceRequest:
+    """Every check of the arguments of Cascade.mask_surface_distances, on the host, before anything is launched
+    (ValueError).  a_sizes / b_sizes: 1 .. 65535 pairs of ints in [1, 16384] each.  pairs: (N, 2) ints (plane of a, plane of b), in
+    range and of equal sizes, 1 <= N <= 2^24; None: plane p of a against plane p of b.  tolerance: one tolerance or 1 .. 8 of them,
+    each an int in [0, 23170] -- pixels -- or a real in (0, 1) -- a share of the pair's diagonal, `surface_tolerance` --; no bools.
+    reach: None -- unlimited --, an int in [0, 23170] for every plane, or "tolerance": each plane's reach is the largest radius of the
+    pairs that name it (1 at least), the cheap path when only NSD and F are wanted."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    is_real = lambda v: isinstance(v, (float, np.floating))
+    a_sizes, b_sizes = _plane_sizes(a_sizes, who, "a's sizes"), _plane_sizes(b_sizes, who, "b's sizes")
+    Pa, Pb = len(a_sizes), len(b_sizes)
+    if pairs is None:
+        if Pa != Pb:
+            raise ValueError(f"{who}: without pairs= both sides need as many planes, got {Pa} and {Pb}")
+        arr = np.stack([np.arange(Pa), np.arange(Pa)], axis=1)
+    else:
+        if isinstance(pairs, (str, bytes)) or isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+            raise ValueError(f"{who}: pairs must be (N, 2) ints on the host")
+        try:
+            arr = np.asarray(pairs)
+        except Exception as e:
+            raise ValueError(f"{who}: pairs must be (N, 2) ints") from e
+        if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype.kind not in "iu" or not 1 <= arr.shape[0] <= SURFACE_MAX_PAIRS:
+            raise ValueError(f"{who}: pairs must be (N, 2) ints, 1 <= N <= 2^24")
+        if bool((arr < 0).any()) or bool((arr[:, 0] >= Pa).any()) or bool((arr[:, 1] >= Pb).any()):
+            raise ValueError(f"{who}: a pair names a plane outside [0, {Pa}) x [0, {Pb})")
+    arr = np.ascontiguousarray(arr.astype(np.int32))
+    dims_a, dims_b = np.asarray(a_sizes, dtype=np.int64)[arr[:, 0]], np.asarray(b_sizes, dtype=np.int64)[arr[:, 1]]
+    if bool((dims_a != dims_b).any()):
+        i = int(np.nonzero((dims_a != dims_b).any(axis=1))[0][0])
+        raise ValueError(f"{who}: pair {i} holds planes of different sizes, {tuple(dims_a[i])} and {tuple(dims_b[i])}")
+    tols = [tolerance] if is_int(tolerance) or is_real(tolerance) else tolerance
+    if isinstance(tols, (str, bytes, bool, np.bool_)) or not hasattr(tols, "__len__") or not 1 <= len(tols) <= SURFACE_MAX_T:
+        raise ValueError(f"{who}: tolerance must be one tolerance or 1 .. {SURFACE_MAX_T} of them, got {tolerance!r}")
+    radii = np.empty((arr.shape[0], len(tols)), dtype=np.int32)
+    for k, t in enumerate(tols):
+        if is_int(t) and 0 <= int(t) <= DISTANCE_MAX_REACH:
+            radii[:, k] = int(t)
+        elif is_real(t) and 0.0 < float(t) < 1.0:
+            radii[:, k] = [surface_tolerance(int(h), int(w), float(t)) for h, w in dims_a]
+        else:
+            raise ValueError(f"{who}: a tolerance must be an int in [0, {DISTANCE_MAX_REACH}] or a ratio in (0, 1), got {t!r}")
+    if isinstance(reach, str) and reach == "tolerance":
+        top = radii.max(axis=1)
+        reach_a, reach_b = np.ones(Pa, dtype=np.int32), np.ones(Pb, dtype=np.int32)
+        np.maximum.at(reach_a, arr[:, 0], top)
+        np.maximum.at(reach_b, arr[:, 1], top)
+    elif reach is None or is_int(reach):
+        reach_a, reach_b = _reaches(reach, Pa, who), _reaches(reach, Pb, who)
+    else:
+        raise ValueError(f"{who}: reach must be None, an int in [0, {DISTANCE_MAX_REACH}] or 'tolerance', got {reach!r}")
+    return SurfaceRequest(a_sizes=a_sizes, b_sizes=b_sizes, pairs=arr, radii=radii, reach_a=reach_a, reach_b=reach_b)
+
+
+def surface_rounds(pairs: np.ndarray, a_sizes, b_sizes, cap: int) -> list:
+    """The rounds of Cascade.mask_surface_distances: consecutive pairs [i0, i1) taken while the maps of the planes they name -- 6 bytes
+    per pixel: 4 of the map, 2 of the distance entry's workspace -- stay within `cap` bytes on either side, one pair at least ->
+    [(i0, i1, the planes of a they name, the planes of b, bytes)], the planes sorted.  Pure host arithmetic."""
+    px_a = [6 * h * w for h, w in a_sizes]
+    px_b = [6 * h * w for h, w in b_sizes]
+    out, i0, N = [], 0, len(pairs)
+    while i0 < N:
+        ua, ub, na, nb, i1 = set(), set(), 0, 0, i0
+        while i1 < N:
+            p, q = int(pairs[i1, 0]), int(pairs[i1, 1])
+            ma, mb = na + (0 if p in ua else px_a[p]), nb + (0 if q in ub else px_b[q])
+            if i1 > i0 and max(ma, mb) > cap:
+                break
+            ua.add(p)
+            ub.add(q)
+            na, nb, i1 = ma, mb, i1 + 1
+        out.append((i0, i1, sorted(ua), sorted(ub), max(na, nb)))
+        i0 = i1
+    return out
+
+
+@dataclass
+class MaskDistances:
+    """Squared distance maps of P sized planes (Cascade.mask_distance_sized), on the device: d2[pix_offsets[p] + y * w + x]
+    is the squared distance, between pixel centres, from pixel (y, x) of plane p to the plane's nearest set pixel -- exact, 0 on a set
+    pixel, DISTANCE_FAR where none lies within the plane's reach (everywhere on an empty plane)."""
+    d2: torch.Tensor                # (total pixels,) int32
+    pix_offsets: torch.Tensor       # (P + 1,) int64, in pixels
+    sizes: list                     # P (h, w) pairs, on the host
+    reach: np.ndarray               # (P,) int32 on the host, 0: unlimited
+    status: torch.Tensor            # (1,) int32 on the device, non-zero if a plane was refused
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
+        says that the input's offsets do not belong to its sizes."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("mask_distance_sized: cvlm_mask_distance_sized refused a plane whose slice did not fit its size")
+
+    def plane(self, p: int) -> torch.Tensor:
+        """Plane p's map as an int32 view (h, w) of `d2`, from the sizes alone: no read of the device."""
+        h, w = self.sizes[p]
+        _, off, _ = label_tables(self.sizes)
+        return self.d2[int(off[p]):int(off[p + 1])].view(h, w)
+
+    def distance(self, p: int) -> torch.Tensor:
+        """Plane p's distances in pixels, float32 (h, w) on the device: the square root, inf where the map is far."""
+        m = self.plane(p)
+        return torch.where(m == DISTANCE_FAR, torch.full_like(m, float("inf"), dtype=torch.float32), m.to(torch.float32).sqrt())
+
+
+SURFACE_TABLES = ("n", "far", "within", "max_d2", "sum_d2", "sum_d")
+
+
+@dataclass
+class SurfaceTotals:
+    """Directed surface totals of N pairs in both directions (Cascade.mask_surface_distances), on the device.  `ab`: the
+    surface pixels of a's plane against the distance map of b's -- prediction against truth --, `ba` the reverse; each a dict of
+    n, far, max_d2 int32 (N,), within int32 (N, T), sum_d2 int64 (N,), sum_d float64 (N,).  `surfeval.surface_metrics(to_host())` turns
+    them into the Hausdorff distance, ASSD, NSD and the boundary F-measure."""
+    pairs: torch.Tensor             # (N, 2) int32
+    radii: torch.Tensor             # (N, T) int32, the tolerance radii of each pair
+    ab: dict
+    ba: dict
+    status: torch.Tensor            # (1,) int32, non-zero if a plane or a pair was refused
+
+    def check(self) -> None:
+        """RuntimeError if a kernel refused a plane or a pair (synchronises)."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("mask_surface_distances: a plane or a pair was refused: do the offsets of the inputs belong to their sizes?")
+
+    def to_host(self) -> dict:
+        """Everything as numpy arrays: pairs, radii, status and the two dicts ab / ba (synchronises)."""
+        host = lambda d: {k: d[k].cpu().numpy() for k in SURFACE_TABLES}
+        return dict(pairs=self.pairs.cpu().numpy(), radii=self.radii.cpu().numpy(), ab=host(self.ab), ba=host(self.ba),
+                    status=int(self.status.item()))
+
+
 @dataclass
 class MatchRequest:
     """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
@@ -1731,6 +1929,111 @@ class MaskUtilities:
                                   n_rings[a:b], status[i:i + 1], ws[:need])
         return MaskContours(xy=xy, ring_start=ring_start, vertex_offsets=offsets, n_vertices=n_vertices, n_rings=n_rings, sizes=sizes,
                             connectivity=connectivity, status=torch.maximum(torch.amax(status, 0, keepdim=True), count_status))
+
+    # ---- Distance maps and surface distances ----------------------------------------------------------------------------------
+    @staticmethod
+    def _distance(bits, offsets, sizes, reach, out_d2, ws, status) -> None:
+        """One cvlm_mask_distance_sized call on planes that lie back to back, into out_d2 in label_tables' layout."""
+        dev = bits.device
+        dims, _, max_words = sized_tables(sizes)
+        _, pix, _ = label_tables(sizes)
+        hip.mask_distance_sized(bits, offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(np.ascontiguousarray(reach)).to(dev), max_words,
+                                torch.from_numpy(pix).to(dev), ws, out_d2, status)
+
+    def mask_distance_sized(self, sized: "SizedMasks", *, reach=None) -> "MaskDistances":
+        """The squared Euclidean distance map of each sized plane -> MaskDistances (cvlm_mask_distance_sized): for every
+        pixel the exact squared distance to the plane's nearest set pixel, DISTANCE_FAR where none is within reach.  reach: None for an
+        unlimited search; an int, or one per plane, in [1, 23170] keeps D2 <= reach^2 exact, makes everything else far and bounds every
+        pixel's work by O(reach).  `distance_request` checks the arguments on the host before anything is launched (ValueError).
+        Memory: 4 bytes per pixel of result and 2 bytes per pixel of the grow-only workspace "cls_rle".  One upload of the three small
+        tables, three launches on the caller's stream, no synchronisation."""
+        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
+            raise ValueError("mask_distance_sized: sized must be a SizedMasks on the device")
+        sizes, reaches = distance_request(sized.sizes, reach=reach)
+        dev = sized.bits.device
+        _, pix, _ = label_tables(sizes)
+        n_pix = int(pix[-1])
+        out = MaskDistances(d2=torch.empty(n_pix, dtype=torch.int32, device=dev), pix_offsets=torch.from_numpy(pix).to(dev), sizes=sizes,
+                            reach=reaches, status=torch.empty(1, dtype=torch.int32, device=dev))
+        ws = self.ws.scratch("cls_rle", (2 * n_pix + 15) // 16 * 16)
+        self._distance(sized.bits, sized.offsets, sizes, reaches, out.d2, ws, out.status)
+        return out
+
+    @staticmethod
+    def _take_planes(sized: "SizedMasks", planes: list):
+        """(bits, offsets, sizes) of the named planes lying back to back: the input's own tensors where all are named in order, a
+        gather of their byte ranges otherwise (the ranges come from the sizes: no read of the device)."""
+        if planes == list(range(len(sized.sizes))):
+            return sized.bits, sized.offsets, list(sized.sizes)
+        _, off, _ = sized_tables(sized.sizes)
+        sizes = [sized.sizes[p] for p in planes]
+        bits = torch.cat([sized.bits[int(off[p]):int(off[p + 1])] for p in planes])
+        return bits, torch.from_numpy(sized_tables(sizes)[1]).to(bits.device), sizes
+
+    def mask_surface_distances(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, tolerance=SURFACE_RATIO, surface="boundary",
+                               reach=None) -> "SurfaceTotals":
+        """How far the contours of pairs of planes lie apart -> SurfaceTotals (cvlm_mask_distance_sized + cvlm_mask_surface_totals, DESIGN.md
+        §27), from which `surfeval.surface_metrics` gives the Hausdorff distance, the average symmetric surface distance, the normalised
+        surface Dice and the boundary F-measure.  a: predictions, b: annotations (they may be the same object); pairs: (N, 2) (plane of
+        a, plane of b), None for plane p against plane p; tolerance: one or up to 8, ints in pixels or ratios of each pair's diagonal
+        (`surface_tolerance`; 0.008 is the published boundary F-measure's); reach: None -- unlimited, what Hausdorff and ASSD need -- or
+        "tolerance", which bounds every search by the pair's largest radius and leaves NSD and F exact; `surface_request` checks all of
+        it on the host before anything is launched (ValueError).
+        surface="boundary": the surface of a mask is `mask_boundary_sized(radius=1)` -- a set pixel with a clear or outside pixel among
+        its eight neighbours; this is §25's boundary, NOT the published measure's own seg2bmap --; surface=None takes the planes as given:
+        edge maps, which are contours already.
+        The call never holds all maps: the host cuts the pairs into rounds whose maps stay within RLE_WS_CAP (6 bytes per pixel of the
+        planes a round names; one pair at least), and per round and direction runs the distance entry on the planes the round names and
+        then the totals entry, through the grow-only workspace "cls_rle", on the caller's stream.  A plane named by many pairs is
+        transformed once per round it appears in.  No synchronisation: `SurfaceTotals.to_host()` does the one read."""
+        for name, s in (("a", a), ("b", b)):
+            if not isinstance(s, SizedMasks) or not s.bits.is_cuda:
+                raise ValueError(f"mask_surface_distances: {name} must be a SizedMasks on the device")
+        if surface is not None and not (isinstance(surface, str) and surface == "boundary"):
+            raise ValueError(f"mask_surface_distances: surface must be 'boundary' or None, got {surface!r}")
+        req = surface_request(a.sizes, b.sizes, pairs=pairs, tolerance=tolerance, reach=reach)
+        dev = a.bits.device
+        N, T = req.radii.shape
+        rounds = surface_rounds(req.pairs, req.a_sizes, req.b_sizes, RLE_WS_CAP)
+        if surface is not None:
+            sa = self.mask_boundary_sized(a, radius=1)
+            sb = sa if b is a else self.mask_boundary_sized(b, radius=1)
+        else:
+            sa, sb = a, b
+        table = lambda: dict(n=torch.empty(N, dtype=torch.int32, device=dev), far=torch.empty(N, dtype=torch.int32, device=dev),
+                             within=torch.empty(N, T, dtype=torch.int32, device=dev), max_d2=torch.empty(N, dtype=torch.int32, device=dev),
+                             sum_d2=torch.empty(N, dtype=torch.int64, device=dev), sum_d=torch.empty(N, dtype=torch.float64, device=dev))
+        out = SurfaceTotals(pairs=torch.from_numpy(req.pairs).to(dev), radii=torch.from_numpy(req.radii).to(dev), ab=table(), ba=table(),
+                            status=None)
+        status = torch.empty(len(rounds), 4, dtype=torch.int32, device=dev)
+        r16 = lambda v: (v + 15) // 16 * 16
+        need = lambda px, n: r16(4 * px) + r16(2 * px) + hip.mask_surface_workspace_bytes(n)
+        pixels = lambda sizes, planes: sum(sizes[p][0] * sizes[p][1] for p in planes)
+        ws = self.ws.scratch("cls_rle", max(need(max(pixels(req.a_sizes, ua), pixels(req.b_sizes, ub)), i1 - i0) for i0, i1, ua, ub, _ in rounds))
+        dims_of = {id(s): torch.from_numpy(sized_tables(s.sizes)[0]).to(dev) for s in (sa, sb)}
+        words_of = {id(s): sized_tables(s.sizes)[2] for s in (sa, sb)}
+        for r, (i0, i1, ua, ub, _) in enumerate(rounds):
+            # direction 0, "ab": the pixels of a's surfaces against the maps of the b planes of the round; direction 1 the reverse
+            for way, (pix_src, map_src, named, reaches, col, tab) in enumerate(((sa, sb, ub, req.reach_b, 1, out.ab),
+                                                                               (sb, sa, ua, req.reach_a, 0, out.ba))):
+                bits, offsets, sizes = self._take_planes(map_src, named)
+                _, pix, _ = label_tables(sizes)
+                px = int(pix[-1])
+                d2 = ws[:4 * px].view(torch.int32)
+                f = ws[r16(4 * px):r16(4 * px) + r16(2 * px)]
+                part = ws[r16(4 * px) + r16(2 * px):need(px, i1 - i0)]
+                self._distance(bits, offsets, sizes, reaches[named], d2, f, status[r, 2 * way:2 * way + 1])
+                local = np.searchsorted(named, req.pairs[i0:i1, col]).astype(np.int32)
+                pr = np.ascontiguousarray(np.stack([req.pairs[i0:i1, 1 - col], local], axis=1))
+                hip.mask_surface_totals(pix_src.bits, pix_src.offsets, dims_of[id(pix_src)], d2, torch.from_numpy(pix).to(dev),
+                                        torch.from_numpy(sized_tables(sizes)[0]).to(dev), torch.from_numpy(pr).to(dev), out.radii[i0:i1],
+                                        words_of[id(pix_src)], part, tab["n"][i0:i1], tab["far"][i0:i1], tab["within"][i0:i1],
+                                        tab["max_d2"][i0:i1], tab["sum_d2"][i0:i1], tab["sum_d"][i0:i1], status[r, 2 * way + 1:2 * way + 2])
+        out.status = torch.amax(status.reshape(-1), 0, keepdim=True)
+        if surface is not None:                                       # the boundaries' own refusals are the call's as well
+            for s in {id(sa): sa, id(sb): sb}.values():
+                out.status = torch.maximum(out.status, s.status.reshape(-1)[:1].ne(0).to(torch.int32))
+        return out
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

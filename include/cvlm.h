@@ -980,6 +980,87 @@ int cvlm_debug_mask_contour_host(const uint8_t* bits, int64_t n_bytes, const int
                                  int32_t connectivity, int32_t* n_vertices, const int64_t* vertex_offsets, int16_t* xy, uint8_t* ring_start,
                                  int32_t* n_rings, int64_t total, int32_t* status);
 
+/* Distance maps of sized planes and directed surface totals: the Hausdorff distance, the average symmetric surface
+ * distance, the normalised surface Dice and the boundary F-measure of two planes are functions of one thing -- for every set pixel of
+ * plane A the distance to the nearest set pixel of plane B.  Everything is exact in integers.
+ * cvlm_mask_distance_sized: the squared Euclidean distance map of each of P sized planes.  bits / n_bytes / offsets int64 [P + 1] in
+ * bytes / dims int32 [P][2] as cvlm_mask_pack_sized's; pixels at columns >= w and everything outside the plane read as clear whatever
+ * the pad bits hold.  With X the plane,
+ *   D2(y, x) = min over the set pixels (y', x') of X of (y - y')^2 + (x - x')^2, between pixel centres,
+ * an int32, 0 on a set pixel, at most 2 * 16383^2 = 536 805 378.  DT_FAR = 0x7fffffff where no set pixel is within reach: every pixel
+ * of an empty plane.  reach int32 [P], 0 .. 23170 (23170^2 < 2^31): 0 is unlimited; R >= 1 gives D2 if D2 <= R^2 and DT_FAR
+ * otherwise, exact up to R, and no pixel then does more than O(R) work.  Only distances leave, never the nearest pixel's index: ties
+ * need no rule.  out_d2 int32 [n_pix], flat and ragged: plane p's h * w values, row-major, no pad, at the entries [pix_offsets[p],
+ * pix_offsets[p + 1]) -- pix_offsets int64 [P + 1] in pixels, the tables of cvlm_label_init's maps; status int32 [1].  All device memory.
+ * A plane is REFUSED whole -- status[0] |= 1 (the call zeroes it first), nothing of it read -- if it fails cvlm_mask_pack_sized's check
+ * of (h, w, offsets[p], offsets[p + 1], n_bytes), if its reach lies outside [0, 23170], or if its pixel slice is not exactly h * w
+ * entries inside [0, n_pix); its slice is filled with DT_FAR where 0 <= pix_offsets[p] <= pix_offsets[p + 1] <= n_pix and left alone
+ * otherwise.  No table content makes a kernel read or store outside bits, out_d2 or the workspace.
+ * Three launches: the init launch (status); a row pass, a wave per row: chunks of 64 pixels as 64-bit masks, each pixel's distance to
+ * the nearest set pixel of its row from a count of leading / trailing zeros plus one carried integer per direction, the smaller of the
+ * two as a uint16 (0xFFFF: none within reach) into the workspace -- no pixel costs O(distance) there; a column pass, a thread per pixel
+ * with the lanes of a wave on consecutive x: D2 = min over y' of (y - y')^2 + f(y', x)^2 searched outwards from k = 0 over the rows y - k
+ * and y + k until k^2 >= the best so far, k > reach or both rows have left the plane, the best kept in 64 bits until it is stored:
+ * O(min(D, reach)) reads per pixel, each one coalesced row segment per wave.  Whole-element stores only, no atomics on maps, 64-bit
+ * offsets, no thread waits for another workgroup.  max_words: the largest h * ceil(w / 32) of the call, which sizes the grid (a smaller
+ * value costs time, not correctness).
+ * workspace: caller-owned, 16-byte aligned, 2 bytes per pixel in the layout of out_d2 -- 2 n_pix bytes rounded up to 16, which
+ * cvlm_mask_distance_workspace_bytes(P, max_pixels) = 2 P max_pixels (rounded up to 16; -1 for P outside [1, 65535] or max_pixels
+ * outside [1, 16384^2]) bounds for P planes of at most max_pixels pixels that lie back to back; contents need no initialisation.  No
+ * allocation, no synchronisation, no pointer kept; every output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer; bits / dims / reach / out_d2 / status not 4-byte aligned, offsets /
+ * pix_offsets not 8-byte aligned, the workspace not 16-byte aligned; P outside [1, 65535]; n_bytes < 4; n_pix < 1; max_words outside
+ * [1, 16384 * 512]; out_d2, status or the workspace sharing a byte with an input or with each other.  CVLM_E_WORKSPACE: ws_bytes below
+ * 2 n_pix rounded up to 16. */
+int64_t cvlm_mask_distance_workspace_bytes(int32_t P, int64_t max_pixels);
+int cvlm_mask_distance_sized(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* reach,
+                             int32_t P, int64_t max_words, const int64_t* pix_offsets, int64_t n_pix, void* workspace, int64_t ws_bytes,
+                             int32_t* out_d2, int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_mask_distance_sized on HOST memory, no stream -- the same per-thread functions
+ * (csrc/distance_logic.h) run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_distance_sized_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims,
+                                        const int32_t* reach, int32_t P, int64_t max_words, const int64_t* pix_offsets, int64_t n_pix,
+                                        void* workspace, int64_t ws_bytes, int32_t* out_d2, int32_t* status);
+/* cvlm_mask_surface_totals: the DIRECTED surface totals of N pairs.  pairs int32 [N][2] = (plane ia of A, map ib of B); A: a_bits /
+ * a_bytes / a_offsets int64 [Pa + 1] / a_dims int32 [Pa][2], sized planes; B: b_d2 int32 [b_n_pix] / b_pix_offsets int64 [Pb + 1] /
+ * b_dims int32 [Pb][2], the output of cvlm_mask_distance_sized; radii int32 [N][T], 1 <= T <= 8, each in [0, 23170], per pair because
+ * a tolerance depends on the image's size -- the device squares them in 64 bits.  Over the set pixels of A (pad bits read as clear)
+ * with D2 their entry of B's map:
+ *   n        int32 [N]     the popcount of A;
+ *   far      int32 [N]     the pixels of A whose D2 is DT_FAR;
+ *   within   int32 [N][T]  the pixels of A with D2 <= r_k^2: exactly those inside B dilated by the disc {dx^2 + dy^2 <= r_k^2};
+ *   max_d2   int32 [N]     the largest D2 over the pixels that are not far, -1 when there are none;
+ *   sum_d2   int64 [N]     the sum of D2 over the pixels that are not far;
+ *   sum_d    float64 [N]   the sum of sqrt(D2), each square root correctly rounded, over the pixels that are not far.
+ * sum_d is deterministic -- the same call twice gives the same bit pattern: every workgroup of a pair adds its threads' shares in a
+ * fixed order into one partial of the workspace and a finalise kernel adds a pair's partials in order; there is no float atomic.
+ * A pair is REFUSED -- status[0] |= 1 (the call zeroes it first), -1 in every integer, 0.0 in sum_d, nothing of it read -- if an index
+ * lies outside [0, Pa) x [0, Pb), if A's plane fails cvlm_mask_pack_sized's check, if the two sizes differ, if B's slice is not
+ * exactly h * w entries inside [0, b_n_pix), or if one of its radii lies outside [0, 23170].
+ * Three launches: init (every output and status); the totals, a thread per word of A -- popcount, then a walk over the set bits
+ * against B's map --, the sums per workgroup, at most one integer atomic per integer output, workgroup and pair (max_d2's is a max);
+ * the finalise.  64-bit offsets, no thread waits for another workgroup.  max_words: the largest h * ceil(w / 32) of A's planes.
+ * workspace: caller-owned, 16-byte aligned, cvlm_mask_surface_workspace_bytes(N) bytes = 8 N g (rounded up to 16) with g = the
+ * workgroups of a pair, min(256, ceil(4096 / N)); -1 for N outside [1, 2^24]; contents need no initialisation.  No allocation, no
+ * synchronisation, no pointer kept; every output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer; an int32 table or a_bits not 4-byte aligned, an int64 or float64
+ * table not 8-byte aligned, the workspace not 16-byte aligned; Pa or Pb outside [1, 65535]; N outside [1, 2^24]; T outside [1, 8];
+ * a_bytes < 4; b_n_pix < 1; max_words outside [1, 16384 * 512]; an output or the workspace sharing a byte with an input or with
+ * another output.  CVLM_E_WORKSPACE: ws_bytes below cvlm_mask_surface_workspace_bytes(N). */
+int64_t cvlm_mask_surface_workspace_bytes(int64_t N);
+int cvlm_mask_surface_totals(const uint8_t* a_bits, int64_t a_bytes, const int64_t* a_offsets, const int32_t* a_dims, int32_t Pa,
+                             const int32_t* b_d2, const int64_t* b_pix_offsets, int64_t b_n_pix, const int32_t* b_dims, int32_t Pb,
+                             const int32_t* pairs, int64_t N, const int32_t* radii, int32_t T, int64_t max_words, void* workspace,
+                             int64_t ws_bytes, int32_t* n, int32_t* far, int32_t* within, int32_t* max_d2, int64_t* sum_d2, double* sum_d,
+                             int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_mask_surface_totals on HOST memory, no stream -- the same per-pixel function, pair by pair and word
+ * by word, sum_d added in that order.  Same outputs (sum_d up to the order of its additions), same refusals. */
+int cvlm_debug_mask_surface_totals_host(const uint8_t* a_bits, int64_t a_bytes, const int64_t* a_offsets, const int32_t* a_dims, int32_t Pa,
+                                        const int32_t* b_d2, const int64_t* b_pix_offsets, int64_t b_n_pix, const int32_t* b_dims, int32_t Pb,
+                                        const int32_t* pairs, int64_t N, const int32_t* radii, int32_t T, int64_t max_words, void* workspace,
+                                        int64_t ws_bytes, int32_t* n, int32_t* far, int32_t* within, int32_t* max_d2, int64_t* sum_d2,
+                                        double* sum_d, int32_t* status);
+
 /* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
  * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
  * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
