@@ -273,6 +273,16 @@ class SAM(nn.Module):
         F-measure (engine.Cascade.mask_surface_distances)."""
         return self.cascade().mask_surface_distances(a, b, pairs=pairs, tolerance=tolerance, surface=surface, reach=reach)
 
+    def mask_thin_sized(self, sized, *, max_iter=None, path="auto", steps=64):
+        """EXTENSION, not a reference method: each plane of an engine.SizedMasks thinned to its centre lines (Guo & Hall; bwmorph's
+        'thin') -> engine.MaskThin (engine.Cascade.mask_thin_sized)."""
+        return self.cascade().mask_thin_sized(sized, max_iter=max_iter, path=path, steps=steps)
+
+    def mask_cldice(self, a, b, *, pairs=None, a_image=None, b_image=None):
+        """EXTENSION, not a reference method: the counts of centre-line Dice of pairs of planes of two engine.SizedMasks
+        -> engine.ClDiceTotals, from which surfeval.cldice gives Tprec, Tsens and clDice (engine.Cascade.mask_cldice)."""
+        return self.cascade().mask_cldice(a, b, pairs=pairs, a_image=a_image, b_image=b_image)
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads

@@ -103,6 +103,10 @@ _SIGNATURES = {
     "cvlm_mask_surface_workspace_bytes": "l:l",
     "cvlm_mask_surface_totals": "i:plppipplpiplpilplppppppps",
     "cvlm_debug_mask_surface_totals_host": "i:plppipplpiplpilplppppppp",
+    "cvlm_mask_thin_workspace_bytes": "l:lii",
+    "cvlm_mask_thin_resident": "i:ii",
+    "cvlm_mask_thin_sized": "i:plpppiliiplpppppps",
+    "cvlm_debug_mask_thin_sized_host": "i:plpppiliiplpppppp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1513,6 +1517,68 @@ def mask_surface_totals_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_di
     assert not a_bits.is_cuda
     _surface_totals("cvlm_debug_mask_surface_totals_host", a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words,
                     workspace, n, far, within, max_d2, sum_d2, sum_d, status)
+
+
+# ---- Thinning: skeletons, thin edges, clDice ----------------------------------------------------------------------------------
+THIN_MAX_ITER = 1 << 30           # max_iter of a plane: 0 (no limit) .. 2^30 (csrc/thin_logic.h: TH_MAX_ITER)
+THIN_MAX_STEPS = 1024             # iterations the stepping path launches in one call (TH_MAX_STEPS)
+
+
+def mask_thin_workspace_bytes(n_bytes: int, P: int, steps: int) -> int:
+    """Bytes of workspace of one `mask_thin_sized` call on P planes of n_bytes bytes in all with `steps` stepped iterations (host
+    arithmetic): the stepped state plus the flags."""
+    need = int(load().cvlm_mask_thin_workspace_bytes(int(n_bytes), int(P), int(steps)))
+    if need < 0:
+        raise RuntimeError(f"cvlm_mask_thin_workspace_bytes failed with code {need}")
+    return need
+
+
+def mask_thin_resident(h: int, w: int) -> bool:
+    """Whether an h x w plane, with its clear border, fits the resident kernel's LDS budget (host arithmetic: cvlm_mask_thin_resident)."""
+    return bool(load().cvlm_mask_thin_resident(int(h), int(w)))
+
+
+def _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status) -> int:
+    """Shape and dtype checks shared by `mask_thin_sized` and `mask_thin_sized_host` -> P."""
+    P = _contour_planes(bits, offsets, dims)
+    assert out_bits.dtype == torch.uint8 and out_bits.dim() == 1 and out_bits.is_contiguous() and out_bits.numel() == bits.numel()
+    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
+    for t in (max_iter, out_iters, out_done):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (P,) and t.is_contiguous()
+    assert (out_area is None) == (out_box is None)
+    assert out_area is None or (out_area.dtype == torch.int32 and tuple(out_area.shape) == (P,) and out_area.is_contiguous())
+    assert out_box is None or (out_box.dtype == torch.int32 and tuple(out_box.shape) == (P, 4) and out_box.is_contiguous())
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t is None or t.device == bits.device for t in (max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status))
+    return P
+
+
+def mask_thin_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_iter: torch.Tensor, max_words: int, mode: int,
+                    steps: int, workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor],
+                    out_box: Optional[torch.Tensor], out_iters: torch.Tensor, out_done: torch.Tensor, status: torch.Tensor) -> None:
+    """Each sized plane thinned by Guo & Hall's rule (include/cvlm.h: cvlm_mask_thin_sized): bits flat uint8, byte offsets
+    int64 [P + 1], dims int32 [P][2], max_iter int32 [P] in 0 .. 2^30 (0: to the fixed point) -> out_bits (the same layout), out_area
+    int32 [P] and out_box int32 [P][4] or both None, out_iters int32 [P] (the iterations that cleared a pixel), out_done int32 [P] (0:
+    `steps` ran out), status int32 [1] = 1 if a plane was refused.  mode 0: planes that fit the resident kernel's LDS are thinned there,
+    the others in `steps` stepped iterations; mode 1: every plane is stepped.  workspace: uint8, `mask_thin_workspace_bytes`.
+    max_words: the largest h * ceil(w / 32) of the call."""
+    P = _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status)
+    _on_current_device(bits)
+    _call("cvlm_mask_thin_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P, int(max_words),
+          int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box), out_iters.data_ptr(),
+          out_done.data_ptr(), status.data_ptr())
+
+
+def mask_thin_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_iter: torch.Tensor, max_words: int, mode: int,
+                         steps: int, workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor],
+                         out_box: Optional[torch.Tensor], out_iters: torch.Tensor, out_done: torch.Tensor, status: torch.Tensor) -> None:
+    """`mask_thin_sized` on HOST tensors without a device (cvlm_debug_mask_thin_sized_host: the same word function run sequentially,
+    every plane to its fixed point or its max_iter)."""
+    P = _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_thin_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P,
+          int(max_words), int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box),
+          out_iters.data_ptr(), out_done.data_ptr(), status.data_ptr())
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

@@ -1136,6 +1136,77 @@ class SurfaceTotals:
                     status=int(self.status.item()))
 
 
+THIN_MAX_ITER = 1 << 30           # max_iter of a thinning: 1 .. 2^30, None for none (csrc/thin_logic.h: TH_MAX_ITER)
+THIN_MAX_STEPS = 1024             # iterations of one round of the stepping path (TH_MAX_STEPS)
+THIN_PATHS = ("auto", "steps")
+
+
+def thin_request(sizes, *, max_iter=None, path="auto", steps=64, who: str = "mask_thin_sized"):
+    """Every check of the arguments of Cascade.mask_thin_sized, on the host, before anything is launched (ValueError)
+    -> (the (h, w) pairs as ints, max_iter of each plane as int32 (P,) with 0 for no limit, the entry's mode, steps).  sizes: 1 .. 65535
+    pairs of ints in [1, 16384]; max_iter: None -- thin to the fixed point --, an int in [1, 2^30] for all planes or one such per
+    plane; path: "auto" -- a plane that fits the resident kernel's LDS is thinned there, the others in rounds of `steps` stepped
+    iterations -- or "steps": every plane is stepped; steps: an int in [1, 1024]; no bools."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    sizes = _plane_sizes(sizes, who)
+    P = len(sizes)
+    if max_iter is None:
+        limits = np.zeros(P, dtype=np.int32)
+    else:
+        seq = [max_iter] * P if is_int(max_iter) else max_iter
+        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
+            raise ValueError(f"{who}: max_iter must be None, an int or hold one int per plane, {P} of them")
+        if not all(1 <= int(v) <= THIN_MAX_ITER for v in seq):
+            raise ValueError(f"{who}: a max_iter must lie in [1, 2^30]")
+        limits = np.asarray([int(v) for v in seq], dtype=np.int32).reshape(P)
+    if not isinstance(path, str) or path not in THIN_PATHS:
+        raise ValueError(f"{who}: path must be 'auto' or 'steps', got {path!r}")
+    if not is_int(steps) or not 1 <= int(steps) <= THIN_MAX_STEPS:
+        raise ValueError(f"{who}: steps must be an int in [1, {THIN_MAX_STEPS}], got {steps!r}")
+    return sizes, limits, THIN_PATHS.index(path), int(steps)
+
+
+@dataclass
+class MaskThin:
+    """Sized planes thinned by Guo & Hall's rule (Cascade.mask_thin_sized), on the device."""
+    masks: "SizedMasks"             # the thinned planes: the input's sizes, offsets and level, an area and a box of their own
+    iters: torch.Tensor             # (P,) int32: the iterations that cleared at least one pixel
+    done: torch.Tensor              # (P,) int32: 1 -- the plane reached its fixed point or its max_iter (every plane of a call that returned)
+    status: torch.Tensor            # (1,) int32, non-zero if a plane was refused
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
+        says that the input's offsets do not belong to its sizes."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("mask_thin_sized: cvlm_mask_thin_sized refused a plane whose slice did not fit its size")
+
+
+CLDICE_TABLES = ("skel_a", "skel_a_in_b", "skel_b", "skel_b_in_a")
+
+
+@dataclass
+class ClDiceTotals:
+    """The four counts of centre-line Dice for N pairs (Cascade.mask_cldice), on the device, int32 (N,) each: with S_X
+    the plane thinned to its fixed point, skel_a = |S_A|, skel_a_in_b = |S_A & B|, skel_b = |S_B|, skel_b_in_a = |S_B & A|; a pair of
+    two different sizes has -1 in both intersections.  `surfeval.cldice(to_host())` turns them into Tprec, Tsens and clDice."""
+    pairs: torch.Tensor             # (N, 2) int32 (plane of a, plane of b)
+    skel_a: torch.Tensor
+    skel_a_in_b: torch.Tensor
+    skel_b: torch.Tensor
+    skel_b_in_a: torch.Tensor
+    status: torch.Tensor            # (1,) int32, non-zero if a plane or a pair was refused
+
+    def check(self) -> None:
+        """RuntimeError if a kernel refused a plane or a pair (synchronises)."""
+        if int(self.status.item()) != 0:
+            raise RuntimeError("mask_cldice: a plane or a pair was refused: two sizes that differ, or offsets that do not belong to the sizes")
+
+    def to_host(self) -> dict:
+        """Everything as numpy arrays: pairs, the four counts and status (synchronises)."""
+        out = {k: getattr(self, k).cpu().numpy() for k in CLDICE_TABLES}
+        return dict(out, pairs=self.pairs.cpu().numpy(), status=int(self.status.item()))
+
+
 @dataclass
 class MatchRequest:
     """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
@@ -2034,6 +2105,92 @@ class MaskUtilities:
             for s in {id(sa): sa, id(sb): sb}.values():
                 out.status = torch.maximum(out.status, s.status.reshape(-1)[:1].ne(0).to(torch.int32))
         return out
+
+    # ---- Thinning: skeletons, thin edges, clDice -------------------------------------------------------------------------------
+    def _thin(self, bits, offsets, sizes, limits, mode, steps, out_bits, area, box, iters, done, status) -> None:
+        """One cvlm_mask_thin_sized call on planes that lie back to back, through the grow-only workspace "cls_rle"."""
+        dev = bits.device
+        dims, _, max_words = sized_tables(sizes)
+        ws = self.ws.scratch("cls_rle", hip.mask_thin_workspace_bytes(int(bits.numel()), len(sizes), steps))
+        hip.mask_thin_sized(bits, offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(np.ascontiguousarray(limits)).to(dev), max_words,
+                            mode, steps, ws, out_bits, area, box, iters, done, status)
+
+    def mask_thin_sized(self, sized: "SizedMasks", *, max_iter=None, path="auto", steps=64) -> "MaskThin":
+        """Each sized plane reduced to its centre lines -> MaskThin (cvlm_mask_thin_sized): Guo & Hall's thinning -- MATLAB's
+        bwmorph(X, 'thin', n), scikit-image's thin(X, max_num_iter) --, to the fixed point or for max_iter iterations.  The result is a
+        subset of the input with as many 8-connected components; `MaskThin.masks` is a SizedMasks of the same sizes, offsets and level
+        with an area and a box of its own, and feeds `mask_inter_sized`, `mask_rle_sized`, `mask_distance_sized` and their kin as it is.
+        `thin_request` checks the arguments on the host before anything is launched (ValueError).
+        path="auto": a plane that fits the resident kernel's LDS (`hip.mask_thin_resident`: 1024 x 1024 does) is thinned to its end by
+        one workgroup; where every plane is resident the call is one upload of the two small tables and one entry call, without a
+        synchronisation.  The other planes -- every plane under path="steps" -- are stepped in rounds of `steps` iterations: each round is
+        followed by ONE read of done (and status), then the next round runs on the planes that are not yet done, gathered back to back,
+        their output as the input and their max_iter less the iterations spent -- exact, because the state of the rule is the bits alone.
+        Workspace: the grow-only "cls_rle", as many bytes as the planes of a round plus 4 * steps per plane."""
+        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
+            raise ValueError("mask_thin_sized: sized must be a SizedMasks on the device")
+        sizes, limits, mode, steps = thin_request(sized.sizes, max_iter=max_iter, path=path, steps=steps)
+        P, dev = len(sizes), sized.bits.device
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        out = MaskThin(masks=SizedMasks(bits=torch.empty_like(sized.bits), offsets=sized.offsets, area=i32(P), box=i32(P, 4), status=i32(1),
+                                        sizes=sizes, level=sized.level), iters=i32(P), done=i32(P), status=None)
+        out.status = out.masks.status
+        fits = hip.load().cvlm_mask_thin_resident                      # host arithmetic, no launch
+        left = [p for p, (h, w) in enumerate(sizes) if mode == 1 or not fits(h, w)]
+        self._thin(sized.bits, sized.offsets, sizes, limits, mode, steps if left else 0, out.masks.bits, out.masks.area, out.masks.box,
+                   out.iters, out.done, out.status)
+        _, off, _ = sized_tables(sizes)
+        spent = 0
+        while left:
+            flags = torch.cat([out.done, out.status]).cpu().numpy()   # the round's one read
+            spent += steps
+            left = [p for p in left if flags[p] == 0]
+            if flags[P] != 0 or not left:                             # a refused plane is never done: check() reports it
+                break
+            idx = torch.tensor(left, dtype=torch.int64, device=dev)
+            part = [sizes[p] for p in left]
+            bits = torch.cat([out.masks.bits[int(off[p]):int(off[p + 1])] for p in left])
+            rest = np.where(limits[left] == 0, 0, limits[left] - spent).astype(np.int32)      # > 0 where limited: the plane is not done
+            r_bits, r_area, r_box, r_iters, r_done, r_status = torch.empty_like(bits), i32(len(left)), i32(len(left), 4), i32(len(left)), \
+                i32(len(left)), i32(1)
+            self._thin(bits, torch.from_numpy(sized_tables(part)[1]).to(dev), part, rest, mode, steps, r_bits, r_area, r_box, r_iters, r_done,
+                       r_status)
+            at = 0
+            for p in left:
+                n = int(off[p + 1] - off[p])
+                out.masks.bits[int(off[p]):int(off[p + 1])] = r_bits[at:at + n]
+                at += n
+            out.masks.area[idx] = r_area
+            out.masks.box[idx] = r_box
+            out.iters[idx] += r_iters
+            out.done[idx] = r_done
+            out.status |= r_status
+        return out
+
+    def mask_cldice(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, a_image=None, b_image=None) -> "ClDiceTotals":
+        """The counts of centre-line Dice (clDice, Shit et al., CVPR 2021) of pairs of sized planes -> ClDiceTotals, from
+        which `surfeval.cldice` gives Tprec = |S_A & B| / |S_A|, Tsens = |S_B & A| / |S_B| and their harmonic mean: the overlap that
+        notices a missing limb.  a: predictions, b: annotations (they may be the same object); pairs= or a_image= / b_image= as
+        `mask_inter_sized` takes them, on the host (`pairs_request` checks them before anything is launched, ValueError); none of the
+        three: plane p against plane p.  Both sides are thinned once, to their fixed points (`mask_thin_sized`), then two `mask_inter_sized`
+        calls count the skeletons inside the other side's masks, the second with the pair columns swapped.  No synchronisation beyond
+        `mask_thin_sized`'s: none where every plane is resident."""
+        for name, s in (("a", a), ("b", b)):
+            if not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535:
+                raise ValueError(f"mask_cldice: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas")
+        if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+            raise ValueError("mask_cldice: pairs must be (N, 2) ints on the host")
+        if pairs is None and a_image is None and b_image is None:     # plane p against plane p
+            if len(a.sizes) != len(b.sizes):
+                raise ValueError(f"mask_cldice: without pairs= or image ids both sides need as many planes, got {len(a.sizes)} and {len(b.sizes)}")
+            pairs = np.stack([np.arange(len(a.sizes))] * 2, axis=1)
+        table = pairs_request(a.sizes, b.sizes, pairs=pairs, a_image=a_image, b_image=b_image, who="mask_cldice")
+        ta = self.mask_thin_sized(a)
+        tb = ta if b is a else self.mask_thin_sized(b)
+        ab = self.mask_inter_sized(ta.masks, b, pairs=table)
+        ba = self.mask_inter_sized(tb.masks, a, pairs=np.ascontiguousarray(table[:, ::-1]))
+        status = torch.maximum(torch.maximum(ta.status, tb.status), torch.maximum(ab.status, ba.status)).ne(0).to(torch.int32)
+        return ClDiceTotals(pairs=ab.pairs, skel_a=ab.area_a, skel_a_in_b=ab.inter, skel_b=ba.area_a, skel_b_in_a=ba.inter, status=status)
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

@@ -43,3 +43,21 @@ def surface_metrics(totals_host: dict) -> dict:
     for k, v in out.items():
         out[k] = np.where(refused if v.ndim == 1 else refused[:, None], np.nan, v)
     return out
+
+
+def cldice(totals_host: dict) -> dict:
+    """Centre-line Dice (clDice, Shit et al., CVPR 2021) from what `ClDiceTotals.to_host()` returns -- for N pairs
+    skel_a = |S_A|, skel_a_in_b = |S_A & B|, skel_b = |S_B|, skel_b_in_a = |S_B & A| with S_X the thinned X -- in float64 -> per-pair
+    arrays tprec = skel_a_in_b / skel_a, tsens = skel_b_in_a / skel_b and cldice = 2 tprec tsens / (tprec + tsens).  A non-empty mask
+    never has an empty skeleton, so the skeleton counts say which side is empty: both empty give cldice = tprec = tsens = 1; exactly
+    one empty gives cldice = 0 (the empty side's own ratio 1, the other's 0, as the boundary F-measure has it); tprec + tsens = 0
+    gives 0.  A refused pair (an intersection of -1: two sizes that differ) gives NaN everywhere."""
+    sa, sb = np.asarray(totals_host["skel_a"], dtype=np.float64), np.asarray(totals_host["skel_b"], dtype=np.float64)
+    ia, ib = np.asarray(totals_host["skel_a_in_b"], dtype=np.float64), np.asarray(totals_host["skel_b_in_a"], dtype=np.float64)
+    refused = (ia < 0) | (ib < 0) | (sa < 0) | (sb < 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tp = np.where(sa == 0, 1.0, np.where(sb == 0, 0.0, ia / sa))
+        ts = np.where(sb == 0, 1.0, np.where(sa == 0, 0.0, ib / sb))
+        cl = np.where(tp + ts == 0, 0.0, 2 * tp * ts / (tp + ts))
+    cl = np.where((sa == 0) & (sb == 0), 1.0, np.where((sa == 0) | (sb == 0), 0.0, cl))
+    return {k: np.where(refused, np.nan, v) for k, v in dict(tprec=tp, tsens=ts, cldice=cl).items()}

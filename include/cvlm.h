@@ -1061,6 +1061,62 @@ int cvlm_debug_mask_surface_totals_host(const uint8_t* a_bits, int64_t a_bytes, 
                                         int64_t ws_bytes, int32_t* n, int32_t* far, int32_t* within, int32_t* max_d2, int64_t* sum_d2,
                                         double* sum_d, int32_t* status);
 
+/* Thinning of sized planes: a plane reduced to its centre lines -- MATLAB's bwmorph(X, 'thin', n) and scikit-image's
+ * morphology.thin(X, max_num_iter) (Guo & Hall 1989 as stated in Lam, Lee & Suen 1992), the step the published edge protocols run
+ * before they match edge maps, and the skeletons of centre-line Dice (Shit et al., CVPR 2021).  All integers, exact.
+ * cvlm_mask_thin_sized: bits / n_bytes / offsets int64 [P + 1] in bytes / dims int32 [P][2] as cvlm_mask_pack_sized's; pixels at columns
+ * >= w and everything outside the plane read as clear whatever the pad bits hold.  With the neighbours of p = (y, x) counter-clockwise
+ * from east, rows growing downwards -- x1 = (y, x+1), x2 = (y-1, x+1), x3 = (y-1, x), x4 = (y-1, x-1), x5 = (y, x-1), x6 = (y+1, x-1),
+ * x7 = (y+1, x), x8 = (y+1, x+1), x9 = x1 --
+ *   G1   X_H(p) = 1, X_H = the sum over i = 1 .. 4 of b_i, b_i = 1 iff x(2i-1) = 0 and (x(2i) = 1 or x(2i+1) = 1);
+ *   G2   2 <= min(n1, n2) <= 3, n1 = the sum over k = 1 .. 4 of (x(2k-1) | x(2k)), n2 = the sum of (x(2k) | x(2k+1));
+ *   G3   (x2 | x3 | !x8) & x1 = 0;     G3'  (x6 | x7 | !x4) & x5 = 0;
+ * subiteration 1 clears, at once, every set pixel with G1 & G2 & G3, subiteration 2 does the same on the result with G1 & G2 & G3'; an
+ * ITERATION is 1 then 2; iterations repeat until one clears nothing or max_iter[p] of them have run -- max_iter int32 [P], 0: no limit,
+ * 1 .. 2^30.  The state is the bits alone and an iteration starts with subiteration 1, so thinning the output of m iterations further
+ * equals thinning the input in one go.
+ * out_bits: n_bytes bytes in the layout of bits, pad bits clear; out_area int32 [P] / out_box int32 [P][4] inclusive (x0, y0, x1, y1),
+ * -1 for an empty plane: both or both NULL; out_iters int32 [P]: the iterations that cleared at least one pixel (a fixed point gives
+ * 0); out_done int32 [P]: 1 when the plane reached its fixed point or its max_iter, 0 when `steps` ran out first; status int32 [1].
+ * All device memory.
+ * mode 0: a plane that is RESIDENT -- cvlm_mask_thin_resident(h, w) = 1: with a clear border of one row and one word column all round
+ * it fits the resident kernel's LDS budget, (h + 2)(ceil(w / 32) + 2) * 4 <= 155 648 bytes (1024 x 1024: 139 536) -- is thinned to its
+ * end by one workgroup of up to 1024 threads in LDS and is always done; every other plane takes the stepping path.  mode 1: every
+ * plane takes the stepping path.  steps, 0 .. 1024: the iterations the stepping path launches in this call, 2 steps launches of a
+ * thread per word, subiteration 1 from out_bits (the first from bits) into the workspace and subiteration 2 back, so that out_bits
+ * holds the state after every whole iteration; one integer atomic per workgroup into the plane's flag of that iteration; a plane
+ * whose previous iteration cleared nothing, or whose max_iter is spent, costs a later launch one flag read per workgroup.  A plane
+ * with out_done = 0 is continued by a call with out_bits as the input (and max_iter less the iterations spent).
+ * A plane is REFUSED whole -- status[0] |= 1 (the call zeroes it first), nothing of it read, area 0, box -1, iters 0, done 0 -- if it
+ * fails cvlm_mask_pack_sized's check of (h, w, offsets[p], offsets[p + 1], n_bytes) or if its max_iter lies outside [0, 2^30]; its slice
+ * of out_bits is zeroed where it is whole words inside [0, n_bytes) and left alone otherwise.  Under steps = 0 a plane that is not
+ * resident is refused as well.  No table content makes a kernel read or store outside bits, out_bits or the workspace.
+ * max_words: the largest h * ceil(w / 32) of the call; it sizes the grids and the resident kernel's LDS (a plane of M words needs at
+ * most 3 M + 6 words with its border) -- a value below the truth sends planes that would be resident to the stepping path, consistently
+ * in every kernel, and costs time, not correctness.
+ * workspace: caller-owned, 16-byte aligned, cvlm_mask_thin_workspace_bytes(n_bytes, P, steps) = n_bytes rounded up to 16 (the stepped
+ * state, in the layout of bits) + 4 P steps rounded up to 16 (the flags); -1 for n_bytes < 4, P outside [1, 65535] or steps outside
+ * [0, 1024]; contents need no initialisation.  Whole-element stores, 64-bit offsets, no thread waits for another workgroup, no
+ * allocation, no synchronisation, no pointer kept; every output is initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (out_area and out_box both NULL is allowed, one of them is not);
+ * bits / dims / max_iter / an output not 4-byte aligned, offsets not 8-byte aligned, the workspace not 16-byte aligned; P outside
+ * [1, 65535]; n_bytes < 4; max_words outside [1, 16384 * 512]; mode outside [0, 1]; steps outside [0, 1024]; steps = 0 where the host
+ * can tell that a plane needs the stepping path -- under mode 1, and where max_words words cannot be resident in any shape --; an
+ * output or the workspace sharing a byte with an input or with another output.  CVLM_E_WORKSPACE: ws_bytes below
+ * cvlm_mask_thin_workspace_bytes(n_bytes, P, steps). */
+int64_t cvlm_mask_thin_workspace_bytes(int64_t n_bytes, int32_t P, int32_t steps);
+int cvlm_mask_thin_resident(int32_t h, int32_t w);
+int cvlm_mask_thin_sized(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* max_iter, int32_t P,
+                         int64_t max_words, int32_t mode, int32_t steps, void* workspace, int64_t ws_bytes, uint8_t* out_bits,
+                         int32_t* out_area, int32_t* out_box, int32_t* out_iters, int32_t* out_done, int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_mask_thin_sized on HOST memory, no stream -- the same word function (csrc/thin_logic.h) run
+ * sequentially on the CPU, every plane to its fixed point or its max_iter whatever mode and steps say (they are checked as above).  Same
+ * outputs, same refusals; every plane that is not refused is done. */
+int cvlm_debug_mask_thin_sized_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* max_iter,
+                                    int32_t P, int64_t max_words, int32_t mode, int32_t steps, void* workspace, int64_t ws_bytes,
+                                    uint8_t* out_bits, int32_t* out_area, int32_t* out_box, int32_t* out_iters, int32_t* out_done,
+                                    int32_t* status);
+
 /* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
  * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
  * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
