@@ -283,6 +283,19 @@ class SAM(nn.Module):
         -> engine.ClDiceTotals, from which surfeval.cldice gives Tprec, Tsens and clDice (engine.Cascade.mask_cldice)."""
         return self.cascade().mask_cldice(a, b, pairs=pairs, a_image=a_image, b_image=b_image)
 
+    def mask_regions_sized(self, sized, *, regions=8, min_area=0, connectivity=8):
+        """EXTENSION, not a reference method: each plane of an engine.SizedMasks split into its connected regions, the `regions` largest
+        as sized planes of their own -- what scipy.ndimage.label and a loop over its labels give on the host -> engine.MaskRegions,
+        whose `compact()` keeps the real regions (engine.Cascade.mask_regions_sized)."""
+        return self.cascade().mask_regions_sized(sized, regions=regions, min_area=min_area, connectivity=connectivity)
+
+    def classify_regions(self, regions, plane_of, mask_logits, clip_image, *, image_of=None, vocab=None):
+        """EXTENSION, not a reference method: demo.py:117-122 per region -- the alpha of the mask a region came from, gated by the
+        region's own pixels, through the Alpha-CLIP tower against that mask's image -> engine.RegionClasses
+        (engine.Cascade.classify_regions)."""
+        return self.cascade().classify_regions(regions, plane_of, mask_logits.float().contiguous(), clip_image.float().contiguous(),
+                                               image_of=image_of, vocab=self._vocab(vocab))
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads

@@ -32,6 +32,7 @@ from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIE
                        DISTANCE_FAR, DISTANCE_MAX_REACH, SURFACE_MAX_T, SURFACE_RATIO, MaskDistances, SurfaceRequest, SurfaceTotals, distance_request,
                        surface_request, surface_rounds, surface_tolerance,
                        THIN_MAX_ITER, THIN_MAX_STEPS, ClDiceTotals, MaskThin, thin_request,
+                       REGIONS_MAXM, MaskRegions, RegionClasses, instances_to_coco, regions_request,
                        PQ_MAX_CELLS, PanopticGroundTruth, PanopticTotals, pq_request, pq_segments_request,
                        label_tables, labels_request, morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry
@@ -2224,6 +2225,71 @@ class Cascade(_Base, MaskUtilities):
     def stage2(self, mask_logits: torch.Tensor, clip_image: torch.Tensor, vocab: Optional[Vocabulary] = None):
         """demo.py:117-122: alpha = resize(sigmoid(mask)) -> clip_model(image, alpha)."""
         return self.clip.forward(clip_image, self._alpha(mask_logits, "alpha2"), vocab=self._vocab_of(vocab))
+
+    def classify_regions(self, regions: SizedMasks, plane_of, mask_logits: torch.Tensor, clip_image: torch.Tensor, *, image_of=None,
+                         vocab: Optional[Vocabulary] = None) -> RegionClasses:
+        """Stage 2 per region -> RegionClasses: region q, a sized plane of `regions` (`MaskRegions.compact()`'s), is
+        scored with the alpha of the mask it came from gated by its own pixels -- alpha_q = resize(sigmoid(mask_logits[plane_of[q]]))
+        * resize(bits of q) (cvlm_region_alpha) -- against the image of that mask.  plane_of: Q ints on the host, the plane of
+        mask_logits (P, 1, S, S) each region came from; image_of: P ints on the host, the image of clip_image (B, 3, R, R) of each
+        plane, by default the identity, required when P != B.  The whole alphas are formed once (`_alpha`), then the regions go in
+        chunks of `class_chunk()`: one cvlm_region_alpha and ONE CLIP forward per chunk over the gathered images.  vocab: as
+        `stage2`.  Q = 0 returns empty tensors without a launch; malformed arguments raise ValueError before anything is queued.
+        Runs on the caller's stream, without a synchronisation."""
+        who = "classify_regions"
+        if not isinstance(regions, SizedMasks) or (len(regions.sizes) > 0 and not regions.bits.is_cuda):
+            raise ValueError(f"{who}: regions must be a SizedMasks on the device")
+        S, R = self.g.inp_size, self.c.image_resolution
+        if not isinstance(mask_logits, torch.Tensor) or mask_logits.dtype != torch.float32 or not mask_logits.is_cuda \
+                or mask_logits.dim() not in (3, 4) or (mask_logits.dim() == 4 and mask_logits.shape[1] != 1) \
+                or tuple(mask_logits.shape[-2:]) != (S, S) or int(mask_logits.shape[0]) < 1:
+            raise ValueError(f"{who}: mask_logits must be a float32 tensor (P, 1, {S}, {S}) on the device")
+        if not isinstance(clip_image, torch.Tensor) or clip_image.dtype != torch.float32 or not clip_image.is_cuda \
+                or clip_image.dim() != 4 or tuple(clip_image.shape[1:]) != (3, R, R) or int(clip_image.shape[0]) < 1:
+            raise ValueError(f"{who}: clip_image must be a float32 tensor (B, 3, {R}, {R}) on the device")
+        P, B, Q = int(mask_logits.shape[0]), int(clip_image.shape[0]), len(regions.sizes)
+
+        def ints(name, seq, n, bound):
+            if isinstance(seq, torch.Tensor):
+                if seq.is_cuda:
+                    raise ValueError(f"{who}: {name} must be on the host")
+                seq = seq.numpy()
+            arr = np.asarray(seq)
+            if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer) and arr.size:
+                raise ValueError(f"{who}: {name} must hold ints")
+            if arr.shape != (n,):
+                raise ValueError(f"{who}: {name} must hold {n} ints, got shape {arr.shape}")
+            arr = arr.astype(np.int64)
+            if arr.size and (arr.min() < 0 or arr.max() >= bound):
+                raise ValueError(f"{who}: a value of {name} outside [0, {bound})")
+            return arr
+
+        if image_of is None:
+            if P != B:
+                raise ValueError(f"{who}: {P} planes and {B} images: give image_of=")
+            image_of = np.arange(P)
+        image_of = ints("image_of", image_of, P, B)
+        plane_of = ints("plane_of", plane_of, Q, P)
+        vocab = self._vocab_of(vocab)
+        n_cls, dev = int(self._bank(vocab).shape[0]), self.device
+        if Q == 0:
+            return RegionClasses(logits=torch.empty(0, n_cls, device=dev), pred=torch.empty(0, dtype=torch.int64, device=dev),
+                                 status=torch.zeros(1, dtype=torch.int32).to(dev))
+        chunk = self.class_chunk()
+        alpha = self._alpha(mask_logits.detach().contiguous(), "alpha2")
+        dims = torch.from_numpy(sized_tables(regions.sizes)[0]).to(dev)
+        src = torch.from_numpy(plane_of.astype(np.int32)).to(dev)
+        image = torch.from_numpy(image_of[plane_of]).to(dev)
+        logits, pred = torch.empty(Q, n_cls, device=dev), torch.empty(Q, dtype=torch.int64, device=dev)
+        status = torch.empty(-(-Q // chunk), dtype=torch.int32, device=dev)
+        for i, q0 in enumerate(range(0, Q, chunk)):
+            q1 = min(Q, q0 + chunk)
+            a = self.ws.f32("region_alpha", q1 - q0, 1, R, R)
+            hip.region_alpha(regions.bits, regions.offsets[q0:q1 + 1], dims[q0:q1], alpha, src[q0:q1], a, status[i:i + 1])
+            _, _, pr, lg = self.clip.forward(clip_image.index_select(0, image[q0:q1]), a, vocab=vocab)
+            logits[q0:q1].copy_(lg)
+            pred[q0:q1].copy_(pr)
+        return RegionClasses(logits=logits, pred=pred, status=status)
 
     def cascade(self, inp, clip_image, clip_mask, pipelined: bool = False, vocab: Optional[Vocabulary] = None):
         """Stage 1 + stage 2.  With the side stream enabled only the SAM encoder runs on the caller's stream; CLIP pass

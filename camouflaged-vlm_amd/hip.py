@@ -107,6 +107,11 @@ _SIGNATURES = {
     "cvlm_mask_thin_resident": "i:ii",
     "cvlm_mask_thin_sized": "i:plpppiliiplpppppps",
     "cvlm_debug_mask_thin_sized_host": "i:plpppiliiplpppppp",
+    "cvlm_mask_regions_workspace_bytes": "l:lil",
+    "cvlm_mask_regions_sized": "i:plppiliiiplpppps",
+    "cvlm_debug_mask_regions_sized_host": "i:plppiliiipppp",
+    "cvlm_region_alpha": "i:plppipiippps",
+    "cvlm_debug_region_alpha_host": "i:plppipiippp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1579,6 +1584,91 @@ def mask_thin_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.
     _call("cvlm_debug_mask_thin_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P,
           int(max_words), int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box),
           out_iters.data_ptr(), out_done.data_ptr(), status.data_ptr())
+
+
+# ---- Instances: regions of sized planes, the alpha of a region -----------------------------------------------------------------
+REGIONS_MAXM = 64                 # rows of the table, and planes a plane is split into (csrc/regions_logic.h: RG_MAXM)
+
+
+def mask_regions_workspace_bytes(n_bytes: int, P: int, max_words: int) -> int:
+    """Bytes of workspace that keep all P planes of one `mask_regions_sized` call in flight (112 per byte of bits, host arithmetic);
+    `mask_regions_workspace_bytes(4 * max_words, 1, max_words)`, the largest plane's alone, is the least the entry takes."""
+    need = int(load().cvlm_mask_regions_workspace_bytes(int(n_bytes), int(P), int(max_words)))
+    if need < 0:
+        raise RuntimeError(f"cvlm_mask_regions_workspace_bytes failed with code {need}")
+    return need
+
+
+def _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status) -> Tuple[int, int]:
+    """Shape and dtype checks shared by `mask_regions_sized` and `mask_regions_sized_host` -> (P, M)."""
+    P = _contour_planes(bits, offsets, dims)
+    assert regions.dtype == torch.int32 and regions.dim() == 3 and regions.is_contiguous()
+    M = int(regions.shape[1])
+    assert tuple(regions.shape) == (P, M, 6)
+    assert n_regions.dtype == torch.int32 and tuple(n_regions.shape) == (P,) and n_regions.is_contiguous()
+    assert out_bits.dtype == torch.uint8 and out_bits.dim() == 1 and out_bits.is_contiguous() and out_bits.numel() == M * bits.numel()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == bits.device for t in (n_regions, regions, out_bits, status))
+    return P, M
+
+
+def mask_regions_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_words: int, connectivity: int, min_area: int,
+                       workspace: torch.Tensor, n_regions: torch.Tensor, regions: torch.Tensor, out_bits: torch.Tensor,
+                       status: torch.Tensor) -> None:
+    """Each sized plane split into its connected regions (include/cvlm.h: cvlm_mask_regions_sized): bits flat uint8, byte
+    offsets int64 [P + 1], dims int32 [P][2] -> n_regions int32 [P] (the regions of at least max(min_area, 1) pixels), regions int32
+    [P][M][6] = (area, x0, y0, x1, y1, seed) of the M largest, out_bits uint8 [M * bits.numel()]: plane (p, m) at byte M * offsets[p] +
+    m * (offsets[p + 1] - offsets[p]); status int32 [1] = 1 if a plane was refused.  workspace: uint8, at least the largest plane's
+    `mask_regions_workspace_bytes`; less than all planes' makes the entry walk them in rounds.  max_words: the largest h * ceil(w / 32)."""
+    P, _ = _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status)
+    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
+    _on_current_device(bits)
+    _call("cvlm_mask_regions_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(max_words), int(connectivity),
+          int(regions.shape[1]), int(min_area), workspace.data_ptr(), workspace.numel(), n_regions.data_ptr(), regions.data_ptr(),
+          out_bits.data_ptr(), status.data_ptr())
+
+
+def mask_regions_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_words: int, connectivity: int, min_area: int,
+                            n_regions: torch.Tensor, regions: torch.Tensor, out_bits: torch.Tensor, status: torch.Tensor) -> None:
+    """`mask_regions_sized` on HOST tensors without a device or a workspace (cvlm_debug_mask_regions_sized_host)."""
+    P, _ = _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_mask_regions_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(max_words),
+          int(connectivity), int(regions.shape[1]), int(min_area), n_regions.data_ptr(), regions.data_ptr(), out_bits.data_ptr(),
+          status.data_ptr())
+
+
+def _region_alpha_args(bits, offsets, dims, alpha, src, out, status) -> Tuple[int, int, int]:
+    """Shape and dtype checks shared by `region_alpha` and `region_alpha_host` -> (Q, N, R)."""
+    Q = _contour_planes(bits, offsets, dims)
+    assert alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.dim() in (3, 4) and alpha.shape[-1] == alpha.shape[-2]
+    N, R = int(alpha.shape[0]), int(alpha.shape[-1])
+    assert alpha.numel() == N * R * R
+    assert src.dtype == torch.int32 and tuple(src.shape) == (Q,) and src.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Q * R * R
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert all(t.device == bits.device for t in (alpha, src, out, status))
+    return Q, N, R
+
+
+def region_alpha(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, alpha: torch.Tensor, src: torch.Tensor, out: torch.Tensor,
+                 status: torch.Tensor) -> None:
+    """The stage-2 alpha of Q regions (include/cvlm.h: cvlm_region_alpha): out[q] = alpha[src[q]] * the bits of sized plane
+    q resized to R x R by `bilinear`'s arithmetic.  alpha f32 [N][R][R] or [N][1][R][R], src int32 [Q] in [0, N), out f32 of Q * R * R
+    values; status int32 [1] = 1 if a plane or a src was refused (its out is 0)."""
+    Q, N, R = _region_alpha_args(bits, offsets, dims, alpha, src, out, status)
+    _on_current_device(bits)
+    _call("cvlm_region_alpha", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R, src.data_ptr(),
+          out.data_ptr(), status.data_ptr())
+
+
+def region_alpha_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, alpha: torch.Tensor, src: torch.Tensor, out: torch.Tensor,
+                      status: torch.Tensor) -> None:
+    """`region_alpha` on HOST tensors without a device (cvlm_debug_region_alpha_host)."""
+    Q, N, R = _region_alpha_args(bits, offsets, dims, alpha, src, out, status)
+    assert not bits.is_cuda
+    _call("cvlm_debug_region_alpha_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R,
+          src.data_ptr(), out.data_ptr(), status.data_ptr())
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

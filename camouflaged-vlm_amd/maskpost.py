@@ -1207,6 +1207,106 @@ class ClDiceTotals:
         return dict(out, pairs=self.pairs.cpu().numpy(), status=int(self.status.item()))
 
 
+REGIONS_MAXM = 64                 # regions a plane is split into at most (csrc/regions_logic.h: RG_MAXM)
+
+
+def regions_request(sizes, *, regions=8, min_area=0, connectivity=8, who: str = "mask_regions_sized"):
+    """Every check of the arguments of Cascade.mask_regions_sized, on the host, before anything is launched (ValueError)
+    -> (the (h, w) pairs as ints, M, min_area, connectivity).  sizes: 1 .. 65535 pairs of ints in [1, 16384]; regions: an int in
+    [1, 64], the slots each plane is split into; min_area: an int in [0, 2^31), regions below it are neither counted nor kept (0 and 1
+    keep every region); connectivity: 4 or 8; no bools."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    sizes = _plane_sizes(sizes, who)
+    if not is_int(regions) or not 1 <= int(regions) <= REGIONS_MAXM:
+        raise ValueError(f"{who}: regions must be an int in [1, {REGIONS_MAXM}], got {regions!r}")
+    if not is_int(min_area) or not 0 <= int(min_area) < 2 ** 31:
+        raise ValueError(f"{who}: min_area must be an int in [0, 2^31), got {min_area!r}")
+    if not is_int(connectivity) or int(connectivity) not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
+    return sizes, int(regions), int(min_area), int(connectivity)
+
+
+@dataclass
+class MaskRegions:
+    """Sized planes split into their connected regions (Cascade.mask_regions_sized), on the device.  Plane p of the
+    source has the M slots p * M .. p * M + M - 1 of `masks`, each of plane p's size: slot m holds exactly the pixels of row m of
+    `table[p]`, and is an all-zero plane past min(n_regions[p], M)."""
+    n_regions: torch.Tensor         # (P,) int32: the regions of at least max(min_area, 1) pixels -- the full count, not capped at M
+    table: torch.Tensor             # (P, M, 6) int32 (area, x0, y0, x1, y1, seed), descending area, ties to the lower seed; filler (0, -1 ...)
+    masks: "SizedMasks"             # P * M planes in slot order; area and box are the table's columns, the level the source's
+    M: int
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a plane (synchronises).  The tables come from the same sizes as the allocation, so this
+        says that the input's offsets do not belong to its sizes."""
+        if bool(self.masks.status.ne(0).any().item()):
+            raise RuntimeError("mask_regions_sized: cvlm_mask_regions_sized refused a plane whose slice did not fit its size")
+
+    def compact(self):
+        """-> (SizedMasks of the real regions only, plane_of, rank): region q of the result is row rank[q] of table[plane_of[q]], in
+        slot order; plane_of and rank are host int64 arrays.  The ONE read of the device this feature makes: n_regions and the status,
+        together (synchronises; RuntimeError as `check` for a refused plane).  The real slots of a plane lie back to back, so the
+        result is one slice of bits, areas and boxes per plane, concatenated on the device -- the style of SizedMasks.concat."""
+        P, M, src = int(self.n_regions.shape[0]), self.M, self.masks
+        host = torch.cat([self.n_regions.reshape(-1), src.status.reshape(-1).ne(0).any().to(torch.int32).reshape(1)]).cpu().numpy()
+        if host[P] != 0:
+            raise RuntimeError("mask_regions_sized: cvlm_mask_regions_sized refused a plane whose slice did not fit its size")
+        real = np.minimum(host[:P].astype(np.int64), M)
+        plane_of = np.repeat(np.arange(P, dtype=np.int64), real)
+        rank = np.concatenate([np.arange(r, dtype=np.int64) for r in real]) if P else np.zeros(0, np.int64)
+        _, off, _ = sized_tables(src.sizes)                           # of the P * M slots, from the sizes alone
+        keep = [p for p in range(P) if real[p] > 0]
+        cat = lambda parts, empty: torch.cat(parts) if parts else empty
+        bits = cat([src.bits[int(off[p * M]):int(off[p * M + real[p]])] for p in keep], src.bits[:0])
+        area = cat([src.area[p * M:p * M + int(real[p])] for p in keep], src.area[:0])
+        box = cat([src.box[p * M:p * M + int(real[p])] for p in keep], src.box[:0])
+        sizes = [src.sizes[p * M] for p in plane_of]
+        offsets = np.zeros(1, np.int64) if not sizes else sized_tables(sizes)[1]
+        out = SizedMasks(bits=bits, offsets=torch.from_numpy(offsets).to(src.bits.device), area=area, box=box, status=src.status, sizes=sizes,
+                         level=src.level)
+        return out, plane_of, rank
+
+
+@dataclass
+class RegionClasses:
+    """The classes of Q regions (Cascade.classify_regions), on the device."""
+    logits: torch.Tensor            # (Q, n_cls) f32
+    pred: torch.Tensor              # (Q,) int64 = argmax of logits
+    status: torch.Tensor            # int32, one word per chunk: non-zero if cvlm_region_alpha refused a plane or a plane index
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused a region (synchronises)."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("classify_regions: cvlm_region_alpha refused a region whose slice did not fit its size")
+
+
+def instances_to_coco(rle: "MaskRle", image_ids, category_ids, scores, boxes=None) -> list:
+    """COCO result dicts of N instances, on the host, in pure Python: [{"image_id", "category_id", "segmentation", "score"}, ...] with
+    `rle.to_coco()`'s rows as segmentations (rle: a MaskRle, or such rows already) -- what COCO.loadRes takes.  image_ids,
+    category_ids, scores: one value per instance, sequences or tensors; boxes: optional inclusive (x0, y0, x1, y1) rows, the boxes of
+    SizedMasks, written as COCO's "bbox": [x, y, width, height].  ValueError where the lengths differ."""
+    rows = rle.to_coco() if isinstance(rle, MaskRle) else list(rle)
+    cols = {}
+    for name, v in (("image_ids", image_ids), ("category_ids", category_ids), ("scores", scores), ("boxes", boxes)):
+        if v is None and name == "boxes":
+            continue
+        v = v.tolist() if hasattr(v, "tolist") else list(v)
+        if len(v) != len(rows):
+            raise ValueError(f"instances_to_coco: {name} holds {len(v)} values for {len(rows)} instances")
+        cols[name] = v
+    out = []
+    for i, seg in enumerate(rows):
+        d = {"image_id": int(cols["image_ids"][i]), "category_id": int(cols["category_ids"][i]), "segmentation": seg,
+             "score": float(cols["scores"][i])}
+        if boxes is not None:
+            if len(cols["boxes"][i]) != 4:
+                raise ValueError(f"instances_to_coco: a box is (x0, y0, x1, y1), got {cols['boxes'][i]!r}")
+            x0, y0, x1, y1 = (int(c) for c in cols["boxes"][i])
+            d["bbox"] = [x0, y0, x1 - x0 + 1, y1 - y0 + 1]
+        out.append(d)
+    return out
+
+
 @dataclass
 class MatchRequest:
     """What `match_request` returns: the groups of a COCO matching and the tables cvlm_coco_match takes, on the host."""
@@ -2191,6 +2291,33 @@ class MaskUtilities:
         ba = self.mask_inter_sized(tb.masks, a, pairs=np.ascontiguousarray(table[:, ::-1]))
         status = torch.maximum(torch.maximum(ta.status, tb.status), torch.maximum(ab.status, ba.status)).ne(0).to(torch.int32)
         return ClDiceTotals(pairs=ab.pairs, skel_a=ab.area_a, skel_a_in_b=ab.inter, skel_b=ba.area_a, skel_b_in_a=ba.inter, status=status)
+
+    # ---- Instances: the regions of sized planes as planes of their own ---------------------------------------------------------
+    def mask_regions_sized(self, sized: "SizedMasks", *, regions: int = 8, min_area: int = 0, connectivity: int = 8) -> "MaskRegions":
+        """Each sized plane split into its connected regions -> MaskRegions (cvlm_mask_regions_sized): the number of
+        regions of at least max(min_area, 1) pixels, the `regions` largest with their boxes and seeds, and each of those as a sized
+        plane of its own, of the source plane's size -- `MaskRegions.masks` feeds `mask_rle_sized`, `mask_contours_sized`, `coco_match`
+        and their kin as it is, `MaskRegions.compact()` drops the empty slots.  `regions_request` checks the arguments on the host
+        before anything is launched (ValueError).  One upload of the two small tables and one entry call on the caller's stream,
+        without a synchronisation; the grow-only workspace "cls_comp" holds every plane in flight up to COMPONENTS_WS_CAP (and never
+        less than the largest plane), beyond it the entry walks the planes in rounds."""
+        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
+            raise ValueError("mask_regions_sized: sized must be a SizedMasks on the device")
+        sizes, M, min_area, connectivity = regions_request(sized.sizes, regions=regions, min_area=min_area, connectivity=connectivity)
+        P, dev = len(sizes), sized.bits.device
+        dims, _, max_words = sized_tables(sizes)
+        slots = [z for z in sizes for _ in range(M)]
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        n_regions, table, status = i32(P), i32(P, M, 6), i32(1)
+        out_bits = torch.empty(M * int(sized.bits.numel()), dtype=torch.uint8, device=dev)
+        n_bytes = int(sized.bits.numel())
+        least = hip.mask_regions_workspace_bytes(4 * max_words, 1, max_words)
+        want = min(hip.mask_regions_workspace_bytes(n_bytes, P, max_words), max(COMPONENTS_WS_CAP, least))
+        hip.mask_regions_sized(sized.bits, sized.offsets, torch.from_numpy(dims).to(dev), max_words, connectivity, min_area,
+                               self.ws.scratch("cls_comp", want), n_regions, table, out_bits, status)
+        masks = SizedMasks(bits=out_bits, offsets=torch.from_numpy(sized_tables(slots)[1]).to(dev), area=table[..., 0].reshape(P * M),
+                           box=table[..., 1:5].reshape(P * M, 4), status=status, sizes=slots, level=sized.level)
+        return MaskRegions(n_regions=n_regions, table=table, masks=masks, M=M)
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

@@ -1117,6 +1117,52 @@ int cvlm_debug_mask_thin_sized_host(const uint8_t* bits, int64_t n_bytes, const 
                                     uint8_t* out_bits, int32_t* out_area, int32_t* out_box, int32_t* out_iters, int32_t* out_done,
                                     int32_t* status);
 
+/* Instances of sized planes: every plane split into its connected regions, the M largest as sized planes of their own,
+ * and the stage-2 alpha of one region.  Added under ABI 12: entries are added, none is changed.
+ * cvlm_mask_regions_sized: bits / n_bytes / offsets int64 [P + 1] in bytes / dims int32 [P][2] as cvlm_mask_pack_sized's, P in
+ * [1, 65535], planes of any mix of sizes in one call.  A plane is labelled as h rows of ceil(w / 32) words by cvlm_mask_components'
+ * rule (connectivity 4 or 8): regions never join across a row end or across planes, and a set pad bit of the input is ignored.
+ * n_regions int32 [P]: the regions of at least max(min_area, 1) pixels -- the full count, not capped at M.  regions int32 [P][M][6]:
+ * the M largest of them as (area, x0, y0, x1, y1, seed), descending area, ties to the lower seed = y * w + x of the region's first
+ * pixel in raster order; rows past the count are the filler (0, -1, -1, -1, -1, -1).  out_bits: M * n_bytes bytes, P * M planes: plane
+ * (p, m) has the size of plane p, lies at byte M * offsets[p] + m * (offsets[p + 1] - offsets[p]) -- the layout of the same sizes with
+ * each repeated M times -- and holds exactly the pixels of row m; a slot past min(n_regions, M) is all zero; pad bits are 0.  status
+ * int32 [1]: 1 if a plane was refused -- it fails cvlm_mask_pack_sized's check of (h, w, offsets[p], offsets[p + 1], n_bytes) or has
+ * more than max_words words; its count is 0, its rows are filler, and its M slices are zeroed where [offsets[p], offsets[p + 1]) is
+ * whole words inside [0, n_bytes) and left alone otherwise.  All device memory.  Every output is initialised by the call, so a launch
+ * sequence replays.  Words are stored whole: no atomics on out_bits (while the call runs, plane (p, 0) holds the cleaned input).
+ * M in [1, 64]; min_area >= 0; max_words: the largest h * ceil(w / 32) of the call, it sizes the grids and the workspace slots.
+ * workspace: caller-owned, 16-byte aligned, 448 bytes per word of a plane.  cvlm_mask_regions_workspace_bytes(n_bytes, P, max_words) =
+ * 112 * n_bytes keeps every plane in flight; the minimum is that of the largest plane alone, 448 * max_words =
+ * cvlm_mask_regions_workspace_bytes(4 * max_words, 1, max_words).  With less than everything the launcher walks the planes in rounds
+ * of floor(ws_bytes / (448 * max_words)) on the one stream.  No allocation, no synchronisation, no cooperative launch; no thread
+ * waits for another workgroup; no table content makes a kernel read or store outside bits, out_bits or the workspace.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer; bits / dims / an output not 4-byte aligned, offsets not 8-byte
+ * aligned; P outside [1, 65535]; n_bytes < 4; max_words outside [1, 16384 * 512]; M outside [1, 64]; connectivity not 4 or 8;
+ * min_area < 0; an output sharing a byte with an input or another output; the workspace NULL, not 16-byte aligned, below the
+ * minimum, or sharing a byte with bits or out_bits.  cvlm_mask_regions_workspace_bytes: CVLM_E_BADARG for sizes out of these ranges. */
+int64_t cvlm_mask_regions_workspace_bytes(int64_t n_bytes, int32_t P, int64_t max_words);
+int cvlm_mask_regions_sized(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t P, int64_t max_words,
+                            int32_t connectivity, int32_t M, int32_t min_area, void* workspace, int64_t ws_bytes, int32_t* n_regions,
+                            int32_t* regions, uint8_t* out_bits, int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_mask_regions_sized on HOST memory, no stream, no workspace -- the same per-thread functions
+ * (csrc/components_logic.h, csrc/regions_logic.h) run sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_regions_sized_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t P,
+                                       int64_t max_words, int32_t connectivity, int32_t M, int32_t min_area, int32_t* n_regions, int32_t* regions,
+                                       uint8_t* out_bits, int32_t* status);
+/* cvlm_region_alpha: the stage-2 alpha of one region.  Q sized planes (the same tables), Q in [1, 2^24]; alpha f32 [N][R][R], the
+ * whole-mask alphas; src int32 [Q] in [0, N) -> out f32 [Q][R][R], out[q] = alpha[src[q]] * gate_q, one fp32 product.  gate_q is the
+ * plane's bits as 0 / 1 resized to R x R by cvlm_bilinear's two-tap align_corners=False arithmetic (float32 coordinates, clamped
+ * below at 0), four bit reads per output pixel, no f32 copy of the plane; the blend is not contracted, so host and device agree to
+ * the bit.  A plane of size (R, R) has weights 1 and 0: the gate is the bit itself, and a full plane reproduces alpha bit for bit.
+ * status int32 [1]: 1 if a plane fails cvlm_mask_pack_sized's check or its src lies outside [0, N); out[q] is then 0.  CVLM_E_BADARG:
+ * a NULL or misaligned pointer, Q outside [1, 2^24], N < 1, R outside [1, 16384], n_bytes < 4. */
+int cvlm_region_alpha(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t Q, const float* alpha, int32_t N,
+                      int32_t R, const int32_t* src, float* out, int32_t* status, void* stream);
+/* Outside the ABI contract: cvlm_region_alpha on HOST memory, no stream. */
+int cvlm_debug_region_alpha_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, int32_t Q, const float* alpha,
+                                 int32_t N, int32_t R, const int32_t* src, float* out, int32_t* status);
+
 /* Label maps: one hypothesis per pixel at the image's own size, Mask2Former's panoptic_inference
  * (mask2former/maskformer_model.py: `cur_prob_masks = cur_scores.view(-1, 1, 1) * cur_masks`, `cur_mask_ids = cur_prob_masks.argmax(0)`,
  * then per query `mask_area`, `original_area`, `mask = (cur_mask_ids == k) & (cur_masks[k] >= 0.5)` and `mask_area / original_area <
