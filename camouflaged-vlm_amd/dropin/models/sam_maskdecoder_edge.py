@@ -296,6 +296,13 @@ class SAM(nn.Module):
         return self.cascade().classify_regions(regions, plane_of, mask_logits.float().contiguous(), clip_image.float().contiguous(),
                                                image_of=image_of, vocab=self._vocab(vocab))
 
+    def mask_nms_sized(self, instances, *, scores, image, category=None, iou=0.5, measure="iou", method="greedy", sigma=2.0):
+        """EXTENSION, not a reference method: non-maximum suppression of instance masks across the class hypotheses of each image --
+        greedy, or SOLOv2's Matrix NMS -- on an engine.SizedMasks with areas and boxes -> engine.MaskNms, whose `select(instances)`
+        keeps the survivors (engine.Cascade.mask_nms_sized)."""
+        return self.cascade().mask_nms_sized(instances, scores=scores, image=image, category=category, iou=iou, measure=measure,
+                                             method=method, sigma=sigma)
+
     def mask_rle(self, bits, H, W):
         """EXTENSION, not a reference method: COCO run-length encoding of (N, H * W / 8) uint8 packed masks, e.g. `pack_masks`' bits --
         the "COCO-style RLE" dict the reference's GenericMask takes (models/utils/visualizer.py:72-101) and pycocotools reads

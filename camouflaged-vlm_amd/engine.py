@@ -33,6 +33,7 @@ from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIE
                        surface_request, surface_rounds, surface_tolerance,
                        THIN_MAX_ITER, THIN_MAX_STEPS, ClDiceTotals, MaskThin, thin_request,
                        REGIONS_MAXM, MaskRegions, RegionClasses, instances_to_coco, regions_request,
+                       NMS_MAX_PAIRS, MaskNms, NmsRequest, nms_request,
                        PQ_MAX_CELLS, PanopticGroundTruth, PanopticTotals, pq_request, pq_segments_request,
                        label_tables, labels_request, morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry

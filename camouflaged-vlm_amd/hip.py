@@ -112,6 +112,10 @@ _SIGNATURES = {
     "cvlm_debug_mask_regions_sized_host": "i:plppiliiipppp",
     "cvlm_region_alpha": "i:plppipiippps",
     "cvlm_debug_region_alpha_host": "i:plppipiippp",
+    "cvlm_mask_nms_inter": "i:plppppipppilpps",
+    "cvlm_debug_mask_nms_inter_host": "i:plppppipppilpp",
+    "cvlm_mask_nms": "i:pppiplpppiiippppppps",
+    "cvlm_debug_mask_nms_host": "i:pppiplpppiiippppppp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1669,6 +1673,56 @@ def region_alpha_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Ten
     assert not bits.is_cuda
     _call("cvlm_debug_region_alpha_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R,
           src.data_ptr(), out.data_ptr(), status.data_ptr())
+
+
+NMS_MEASURES = {"iou": 0, "min": 1}               # csrc/nms_logic.h: NM_IOU, NM_MIN
+NMS_METHODS = {"greedy": 0, "linear": 1, "gaussian": 2}
+
+
+def mask_nms_inter(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, area: torch.Tensor, box: torch.Tensor,
+                   group_offsets: torch.Tensor, member: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor, status: torch.Tensor,
+                   host: bool = False) -> None:
+    """Intersections of the pairs of each group of sized planes, inside the two boxes alone (include/cvlm.h: cvlm_mask_nms_inter; DESIGN.md
+    §30): the sized table of Q planes with area int32 [Q] and box int32 [Q][4], group_offsets int32 [G + 1] into member int32 [Q],
+    pair_offsets int64 [G + 1] -> inter int32 [N], group g's triangle at pair_offsets[g], -1 for a refused pair; status int32 [1]: bit 0
+    a pair, bit 1 a group was refused.  host=True: the same on HOST tensors without a device (cvlm_debug_mask_nms_inter_host)."""
+    Q = _contour_planes(bits, offsets, dims)
+    G, N = int(group_offsets.numel()) - 1, int(inter.numel())
+    i32 = torch.int32
+    for t, dtype, shape in ((area, i32, (Q,)), (box, i32, (Q, 4)), (group_offsets, i32, (G + 1,)), (member, i32, (Q,)),
+                            (pair_offsets, torch.int64, (G + 1,)), (inter, i32, (N,)), (status, i32, (1,))):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == bits.device, (t.dtype, tuple(t.shape), shape)
+    if host:
+        assert not bits.is_cuda
+    else:
+        _on_current_device(bits)
+    _call("cvlm_debug_mask_nms_inter_host" if host else "cvlm_mask_nms_inter", bits.data_ptr(), bits.numel(), offsets.data_ptr(),
+          dims.data_ptr(), area.data_ptr(), box.data_ptr(), Q, group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G, N,
+          inter.data_ptr() if N else None, status.data_ptr())
+
+
+def mask_nms(group_offsets: torch.Tensor, member: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor, area: torch.Tensor,
+             score: torch.Tensor, category: Optional[torch.Tensor], measure: int, method: int, thr: float, sigma: float, order: torch.Tensor,
+             keep: torch.Tensor, by: torch.Tensor, decay: torch.Tensor, n_keep: torch.Tensor, status: torch.Tensor, host: bool = False) -> None:
+    """Greedy or Matrix NMS of the groups of `mask_nms_inter` (include/cvlm.h: cvlm_mask_nms): area int32, score f32 and
+    category int32 (or None) [Q]; measure NMS_MEASURES, method NMS_METHODS; thr and sigma go as doubles -> order int32, keep uint8, by
+    int32 and decay f32 [Q], n_keep int32 [G], status int32 [1]: bit 1 a group was refused.  host=True: the same on HOST tensors without
+    a device (cvlm_debug_mask_nms_host)."""
+    G, N, Q = int(group_offsets.numel()) - 1, int(inter.numel()), int(area.numel())
+    i32 = torch.int32
+    for t, dtype, shape in ((group_offsets, i32, (G + 1,)), (member, i32, (Q,)), (pair_offsets, torch.int64, (G + 1,)), (inter, i32, (N,)),
+                            (area, i32, (Q,)), (score, torch.float32, (Q,)), (order, i32, (Q,)), (keep, torch.uint8, (Q,)), (by, i32, (Q,)),
+                            (decay, torch.float32, (Q,)), (n_keep, i32, (G,)), (status, i32, (1,))) + \
+            (() if category is None else ((category, i32, (Q,)),)):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == area.device, (t.dtype, tuple(t.shape), shape)
+    if host:
+        assert not area.is_cuda
+    else:
+        _on_current_device(area)
+    params = (C.c_double * 2)(float(thr), float(sigma))               # host memory: the entry reads it before it returns
+    _call("cvlm_debug_mask_nms_host" if host else "cvlm_mask_nms", group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G,
+          inter.data_ptr() if N else None, N, area.data_ptr(), score.data_ptr(), _p(category), Q, int(measure), int(method),
+          C.addressof(params), order.data_ptr(), keep.data_ptr(), by.data_ptr(), decay.data_ptr(), n_keep.data_ptr(), status.data_ptr())
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

@@ -1408,6 +1408,124 @@ def match_request(det_sizes, gt_sizes, *, det_image, gt_image, det_category=None
                         scores=None if sc is None else sc[det_perm], iou_thrs=thrs, area_rngs=np.ascontiguousarray(rngs), max_det=int(max_det))
 
 
+NMS_MAX_PAIRS = 1 << 22           # pairs of one call (csrc/nms_logic.h: NM_MAX_PAIRS)
+
+
+@dataclass
+class NmsRequest:
+    """What `nms_request` returns: the groups of a mask NMS and the tables cvlm_mask_nms_inter / cvlm_mask_nms take, on
+    the host."""
+    keys: list                      # G image ids, sorted
+    member: np.ndarray              # (Q,) int32: the caller's instance of each row of the group table, group by group, in the caller's order
+    group_offsets: np.ndarray       # (G + 1,) int32 rows of member
+    pair_offsets: np.ndarray        # (G + 1,) int64 into the intersections: group g's D (D - 1) / 2 pairs (i, j), i < j
+    thr: float
+    measure: int                    # hip.NMS_MEASURES
+    method: int                     # hip.NMS_METHODS
+    sigma: float
+
+    @property
+    def n_pairs(self) -> int:
+        return int(self.pair_offsets[-1])
+
+
+def nms_request(sizes, *, image, iou=0.5, measure="iou", method="greedy", sigma=2.0, who: str = "mask_nms_sized") -> NmsRequest:
+    """Every check of Cascade.mask_nms_sized that the host can make, before anything is launched (ValueError) ->
+    NmsRequest.  sizes: the (h, w) of each instance plane, 1 .. 65535 of them; image: one int image id per instance -- a group is an
+    image, its instances in the caller's order.  iou: the threshold, a number in [0, 1] (an instance is suppressed by a measure strictly
+    above it); measure: "iou" or "min" (intersection over the smaller area); method: "greedy", "linear" or "gaussian" (Matrix NMS);
+    sigma: a finite number > 0, the gaussian's.  All planes of a group have one size; a group has at most 1024 instances; all groups
+    together at most 2^22 pairs.  No bools."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    is_real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    sizes = _plane_sizes(sizes, who)
+    Q = len(sizes)
+    if isinstance(image, (str, bytes)) or not hasattr(image, "__len__") or len(image) != Q or not all(is_int(v) for v in image):
+        raise ValueError(f"{who}: image must hold one int per instance, {Q} of them")
+    if not is_real(iou) or not 0.0 <= float(iou) <= 1.0:
+        raise ValueError(f"{who}: iou must be a number in [0, 1], got {iou!r}")
+    if not isinstance(measure, str) or measure not in hip.NMS_MEASURES:
+        raise ValueError(f"{who}: measure must be one of {sorted(hip.NMS_MEASURES)}, got {measure!r}")
+    if not isinstance(method, str) or method not in hip.NMS_METHODS:
+        raise ValueError(f"{who}: method must be one of {sorted(hip.NMS_METHODS)}, got {method!r}")
+    if not is_real(sigma) or not np.isfinite(float(sigma)) or not float(sigma) > 0.0:
+        raise ValueError(f"{who}: sigma must be a finite number > 0, got {sigma!r}")
+    rows = {}
+    for q, img in enumerate(image):
+        rows.setdefault(int(img), []).append(q)
+    keys = sorted(rows)
+    for k in keys:
+        if len(rows[k]) > MATCH_CAP:
+            raise ValueError(f"{who}: image {k} has {len(rows[k])} instances, at most {MATCH_CAP} are taken")
+        group_sizes = {sizes[q] for q in rows[k]}
+        if len(group_sizes) > 1:
+            raise ValueError(f"{who}: the instances of image {k} have the sizes {sorted(group_sizes)}: one image has one size")
+    D = [len(rows[k]) for k in keys]
+    n_pairs = int(sum(d * (d - 1) // 2 for d in D))
+    if n_pairs > NMS_MAX_PAIRS:
+        raise ValueError(f"{who}: the groups give {n_pairs} pairs, at most 2^22 are taken")
+    offs = lambda counts, dt: np.concatenate([[0], np.cumsum(counts)]).astype(dt)
+    return NmsRequest(keys=keys, member=np.asarray([q for k in keys for q in rows[k]], dtype=np.int32), group_offsets=offs(D, np.int32),
+                      pair_offsets=offs([d * (d - 1) // 2 for d in D], np.int64), thr=float(iou), measure=hip.NMS_MEASURES[measure],
+                      method=hip.NMS_METHODS[method], sigma=float(sigma))
+
+
+@dataclass
+class MaskNms:
+    """The NMS of instances across the hypotheses of each image (Cascade.mask_nms_sized; cvlm_mask_nms), on the device.
+    Rows are the caller's instances.  Greedy: `keep` is the answer.  Matrix NMS ("linear", "gaussian"): every instance with pixels is
+    kept and `rescored(scores)` = scores * decay is what the caller thresholds."""
+    keep: torch.Tensor              # (Q,) uint8
+    by: torch.Tensor                # (Q,) int32: the instance that suppressed this one, -1 if none
+    decay: torch.Tensor             # (Q,) f32: greedy 1 / 0, Matrix NMS the decay coefficient
+    order: torch.Tensor             # (Q,) int32: group g's instances by rank at request.group_offsets[g] ..
+    n_keep: torch.Tensor            # (G,) int32, the groups in request.keys' order
+    inter: torch.Tensor             # (N,) int32: the triangles of cvlm_mask_nms_inter, -1 for a refused pair
+    status: torch.Tensor            # (2,) int32: cvlm_mask_nms_inter's and cvlm_mask_nms's -- bit 0 a pair, bit 1 a group was refused
+    request: Optional[NmsRequest] = None
+
+    def check(self) -> None:
+        """RuntimeError if a kernel refused a pair or a group (synchronises).  The tables come from the same sizes as the instances, so
+        this says that the instances' offsets or boxes do not belong to their sizes."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("mask_nms_sized: cvlm_mask_nms_inter or cvlm_mask_nms refused a pair or a group: a slice that does not fit "
+                               "its size, or a box outside its plane")
+
+    def rescored(self, scores) -> torch.Tensor:
+        """scores * decay -> f32 (Q,) on the device of `decay`: Matrix NMS' new scores (greedy: the kept ones, 0 elsewhere)."""
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores, dtype=np.float32))
+        if tuple(s.shape) != tuple(self.decay.shape):
+            raise ValueError(f"MaskNms.rescored: scores must hold one number per instance, {int(self.decay.numel())} of them")
+        return s.detach().to(device=self.decay.device, dtype=torch.float32) * self.decay
+
+    def select(self, instances: "SizedMasks"):
+        """-> (SizedMasks of the kept instances in the caller's order, their rows as a host int64 array).  The ONE read of the device
+        this feature makes: keep and status, in one tensor (synchronises; RuntimeError as `check`).  Kept neighbours lie back to back,
+        so the result is one slice of bits per run of kept rows, by byte ranges from the sizes alone -- the style of
+        MaskRegions.compact."""
+        Q = int(self.keep.numel())
+        if not isinstance(instances, SizedMasks) or len(instances.sizes) != Q or instances.area is None:
+            raise ValueError(f"MaskNms.select: instances must be the SizedMasks of the call, {Q} planes with areas")
+        host = torch.cat([self.status.reshape(-1).view(torch.uint8), self.keep.reshape(-1)]).cpu().numpy()
+        n_status = 4 * int(self.status.numel())
+        if host[:n_status].any():
+            raise RuntimeError("mask_nms_sized: cvlm_mask_nms_inter or cvlm_mask_nms refused a pair or a group: a slice that does not fit "
+                               "its size, or a box outside its plane")
+        idx = np.flatnonzero(host[n_status:]).astype(np.int64)
+        _, off, _ = sized_tables(instances.sizes) if Q else (None, np.zeros(1, np.int64), 0)
+        starts = [int(q) for k, q in enumerate(idx) if k == 0 or idx[k - 1] != q - 1]
+        ends = [int(q) + 1 for k, q in enumerate(idx) if k + 1 == idx.size or idx[k + 1] != q + 1]
+        cat = lambda parts, empty: torch.cat(parts) if parts else empty
+        bits = cat([instances.bits[int(off[a]):int(off[b])] for a, b in zip(starts, ends)], instances.bits[:0])
+        area = cat([instances.area[a:b] for a, b in zip(starts, ends)], instances.area[:0])
+        box = cat([instances.box[a:b] for a, b in zip(starts, ends)], instances.box[:0])
+        sizes = [instances.sizes[int(q)] for q in idx]
+        offsets = np.zeros(1, np.int64) if not sizes else sized_tables(sizes)[1]
+        out = SizedMasks(bits=bits, offsets=torch.from_numpy(offsets).to(instances.bits.device), area=area, box=box,
+                         status=instances.status, sizes=sizes, level=instances.level)
+        return out, idx
+
+
 @dataclass
 class CocoMatches:
     """The COCO matching of detections and annotations (Cascade.coco_match; cvlm_coco_match), on the device.  Rows are
@@ -2318,6 +2436,63 @@ class MaskUtilities:
         masks = SizedMasks(bits=out_bits, offsets=torch.from_numpy(sized_tables(slots)[1]).to(dev), area=table[..., 0].reshape(P * M),
                            box=table[..., 1:5].reshape(P * M, 4), status=status, sizes=slots, level=sized.level)
         return MaskRegions(n_regions=n_regions, table=table, masks=masks, M=M)
+
+    # ---- Mask NMS across the hypotheses of each image ------------------------------------------------------------------------
+    def mask_nms_sized(self, instances: "SizedMasks", *, scores, image, category=None, iou=0.5, measure: str = "iou", method: str = "greedy",
+                       sigma: float = 2.0) -> "MaskNms":
+        """The duplicate instances of each image dropped or decayed -> MaskNms (cvlm_mask_nms_inter + cvlm_mask_nms).
+        instances: a SizedMasks on this engine's device with areas and boxes, e.g. `MaskRegions.compact()`'s.  scores: one per instance,
+        a float32 tensor on the device taken as it is (NaN ranks last), or a host sequence.  category: None (class-agnostic), or one int
+        per instance -- an integer tensor on the device, e.g. `RegionClasses.pred`, or a host sequence -- and only instances of one
+        category suppress each other.  image and the other arguments are `nms_request`'s, which checks them on the host before anything
+        is launched (ValueError).  One upload of the three tables and the sizes, the two entry calls on the caller's stream, no workspace, no
+        synchronisation: `MaskNms.select(instances)` does the one read.  No instance: empty tensors, nothing launched."""
+        if not isinstance(instances, SizedMasks) or instances.area is None or instances.box is None:
+            raise ValueError("mask_nms_sized: instances must be a SizedMasks with areas and boxes")
+        dev, Q = instances.bits.device, len(instances.sizes)
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+        if Q == 0:
+            if len(image) != 0 or len(scores) != 0 or (category is not None and len(category) != 0):
+                raise ValueError("mask_nms_sized: scores, image and category must hold one value per instance, 0 of them")
+            return MaskNms(keep=e(0, torch.uint8), by=e(0, torch.int32), decay=e(0, torch.float32), order=e(0, torch.int32),
+                           n_keep=e(0, torch.int32), inter=e(0, torch.int32), status=torch.zeros(2, dtype=torch.int32, device=dev))
+        if not instances.bits.is_cuda:
+            raise ValueError("mask_nms_sized: instances must be on the device")
+        req = nms_request(instances.sizes, image=image, iou=iou, measure=measure, method=method, sigma=sigma)
+
+        def column(name, v, dtype, kinds):
+            if isinstance(v, torch.Tensor) and v.is_cuda:
+                ok = v.dtype == torch.float32 if dtype == torch.float32 else v.dtype in (torch.int32, torch.int64, torch.int16, torch.uint8)
+                if not ok or tuple(v.shape) != (Q,):
+                    raise ValueError(f"mask_nms_sized: {name} on the device must be a {'float32' if dtype == torch.float32 else 'integer'} tensor ({Q},)")
+                return v.detach().to(dtype).contiguous()
+            try:
+                arr = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+            except Exception as err:
+                raise ValueError(f"mask_nms_sized: {name} must hold one number per instance") from err
+            if arr.shape != (Q,) or arr.dtype.kind not in kinds:
+                raise ValueError(f"mask_nms_sized: {name} must hold one number per instance, {Q} of them")
+            return torch.from_numpy(np.ascontiguousarray(arr.astype(np.float32 if dtype == torch.float32 else np.int32))).to(dev)
+
+        score = column("scores", scores, torch.float32, "iuf")
+        cat = None if category is None else column("category", category, torch.int32, "iu")
+        G = len(req.keys)
+        dims = np.ascontiguousarray(sized_tables(instances.sizes)[0])
+        tables = np.concatenate([req.pair_offsets.view(np.uint8), req.group_offsets.view(np.uint8), req.member.view(np.uint8),
+                                 dims.reshape(-1).view(np.uint8)])
+        tables = torch.from_numpy(tables).to(dev)                     # the one upload: the int64 table first, so every view is aligned
+        pair_offsets = tables[:8 * (G + 1)].view(torch.int64)
+        group_offsets = tables[8 * (G + 1):12 * (G + 1)].view(torch.int32)
+        member = tables[12 * (G + 1):12 * (G + 1) + 4 * Q].view(torch.int32)
+        dims = tables[12 * (G + 1) + 4 * Q:].view(torch.int32).view(Q, 2)
+        status = e(2, torch.int32)
+        out = MaskNms(keep=e(Q, torch.uint8), by=e(Q, torch.int32), decay=e(Q, torch.float32), order=e(Q, torch.int32),
+                      n_keep=e(G, torch.int32), inter=e(req.n_pairs, torch.int32), status=status, request=req)
+        hip.mask_nms_inter(instances.bits, instances.offsets, dims, instances.area.contiguous(), instances.box.contiguous(), group_offsets,
+                           member, pair_offsets, out.inter, status[0:1])
+        hip.mask_nms(group_offsets, member, pair_offsets, out.inter, instances.area.contiguous(), score, cat, req.measure, req.method,
+                     req.thr, req.sigma, out.order, out.keep, out.by, out.decay, out.n_keep, status[1:2])
+        return out
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

@@ -1295,6 +1295,57 @@ int cvlm_debug_pan_accumulate_host(int32_t B, int32_t G, int32_t S, const int32_
                                    const int32_t* pred_match, const double* pred_iou, const int32_t* gt_match, int32_t C,
                                    int32_t zero_first, int64_t* counts, double* iou_sum);
 
+/* Mask NMS: the duplicate instances of an image -- one object found under several class hypotheses -- dropped (greedy)
+ * or decayed (Matrix NMS; Wang et al., SOLOv2, §3.3), without a read of the device.  Instances are the Q planes of a sized table (bits /
+ * n_bytes / offsets int64 [Q + 1] in bytes / dims int32 [Q][2] = (h, w)) with area int32 [Q] and box int32 [Q][4] inclusive (x0, y0, x1,
+ * y1), all -1 = the empty box: what every producer of sized planes writes.  A GROUP is the instances of one image: group_offsets int32
+ * [G + 1] into member int32 [Q] (Q' = group_offsets[G] <= Q entries are used), member[group_offsets[g] ..] the rows of group g in the
+ * caller's order, D_g <= 1024 of them.  Group g's pairs lie at pair_offsets[g] (int64 [G + 1]) of inter int32 [N]: the D (D - 1) / 2
+ * pairs (i, j), i < j in member order, pair (i, j) at i D - i (i + 1) / 2 + (j - i - 1).  The caller's groups name every row, and own
+ * every place of inter, at most once.
+ * cvlm_mask_nms_inter: inter[pair] = the set pixels of A AND B inside the intersection of the two boxes -- rows max(y0) .. min(y1),
+ * columns max(x0) .. min(x1), the first and last word masked to those columns; with true boxes the whole intersection, whatever the pad
+ * bits hold.  0 without a read of either plane where the boxes do not meet, a box is the empty box or an area is below 1.  A pair is
+ * refused (inter = -1, status[0] |= 1) if a plane fails cvlm_mask_pack_sized's slice check, the two (h, w) differ, or a box that is not
+ * the empty box has x0 > x1, y0 > y1 or leaves [0, w) x [0, h).  A group is refused whole (status[0] |= 2, nothing of its block stored) if
+ * its offsets run backwards or leave [0, Q], D_g > 1024, a member lies outside [0, Q), or its pair block is not exactly the triangle
+ * inside [0, N].  Places of inter that no accepted group owns hold -1.  An init launch plus one launch, one wave per pair striding over
+ * the window's words: integer sums, no atomic on inter, the same bytes whatever the schedule.
+ * cvlm_mask_nms: per group, the instances ranked as cvlm_coco_match ranks detections (score f32 [Q] descending, equal scores in member
+ * order, NaN behind every number); order int32 [Q]: order[group_offsets[g] + r] = the row of rank r.  m(i, j), in double: measure 0 =
+ * inter / (a_i + a_j - inter), measure 1 = inter / min(a_i, a_j); 0 for inter = 0, -1 for inter < 0 or a denominator below 1; with
+ * category int32 [Q] (NULL: class-agnostic) 0 for a pair of different categories.  params: HOST memory, two doubles (thr, sigma), read
+ * before the call returns.
+ *   method 0, greedy: in rank order an instance not suppressed and of area >= 1 is kept and suppresses every later-ranked instance of
+ *     its group with m > thr (strictly); a suppressed instance suppresses nothing.  keep uint8 [Q]; by int32 [Q] the row of the
+ *     suppressor, -1 if none (an empty instance: keep 0, by -1); decay f32 [Q] = keep; n_keep int32 [G].
+ *   method 1 / 2, Matrix NMS linear / gaussian: c_i = max of m(k, i) over the k ranked above i (0 without one), a negative m taken as 0
+ *     throughout; decay_j = the minimum over the i ranked above j of (1 - m_ij) / (1 - c_i) -- 1 where 1 - c_i == 0 -- or of
+ *     exp(-sigma (m_ij^2 - c_i^2)); 1 without an i.  Computed in double, stored as f32; keep = (area >= 1), by = -1.
+ * Rows that no accepted group names: keep 0, by -1, decay 0; order -1 at places no accepted group owns.  A refused group (as above):
+ * status[0] |= 2.  The fill launch, then one workgroup per group; no workgroup waits for another.
+ * No workspace, no allocation, no synchronisation, 64-bit offsets.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (category may be NULL; inter may be NULL when N == 0); an int32 /
+ * f32 pointer not 4-byte, an int64 / f64 pointer not 8-byte aligned; Q or G outside [1, 2^20]; N outside [0, 2^22]; n_bytes < 4; measure
+ * not 0 / 1; method not 0 / 1 / 2; thr outside [0, 1] or NaN; for method 2 a sigma that is not finite or <= 0; an output range that shares
+ * a byte with an input or another output. */
+int cvlm_mask_nms_inter(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* area,
+                        const int32_t* box, int32_t Q, const int32_t* group_offsets, const int32_t* member, const int64_t* pair_offsets,
+                        int32_t G, int64_t N, int32_t* inter, int32_t* status, void* stream);
+int cvlm_mask_nms(const int32_t* group_offsets, const int32_t* member, const int64_t* pair_offsets, int32_t G, const int32_t* inter, int64_t N,
+                  const int32_t* area, const float* score, const int32_t* category, int32_t Q, int32_t measure, int32_t method,
+                  const double* params, int32_t* order, uint8_t* keep, int32_t* by, float* decay, int32_t* n_keep, int32_t* status,
+                  void* stream);
+/* Outside the ABI contract: the two entries on HOST memory, no stream -- the same per-thread functions (csrc/nms_logic.h) run
+ * sequentially on the CPU.  Same outputs, same refusals. */
+int cvlm_debug_mask_nms_inter_host(const uint8_t* bits, int64_t n_bytes, const int64_t* offsets, const int32_t* dims, const int32_t* area,
+                                   const int32_t* box, int32_t Q, const int32_t* group_offsets, const int32_t* member,
+                                   const int64_t* pair_offsets, int32_t G, int64_t N, int32_t* inter, int32_t* status);
+int cvlm_debug_mask_nms_host(const int32_t* group_offsets, const int32_t* member, const int64_t* pair_offsets, int32_t G, const int32_t* inter,
+                             int64_t N, const int32_t* area, const float* score, const int32_t* category, int32_t Q, int32_t measure,
+                             int32_t method, const double* params, int32_t* order, uint8_t* keep, int32_t* by, float* decay, int32_t* n_keep,
+                             int32_t* status);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
