@@ -8,7 +8,8 @@ cvlm_gemm with split = 1) on each of the four instantiations csrc/gemm_plan.h ke
 
 at shapes on the tile and ring edges.  tests/test_gemm_split1_cpu.py plans every case (no GPU) and checks that it reaches the kernel it
 names; tests/test_gemm_split1_gpu.py runs them against fp64.  `launch` builds the operands and the keyword arguments of hip.gemm of a
-case on any device, so both files look at the same launch."""
+case on any device, so both files look at the same launch; tests/gemm_split3_cases.py builds the split-3 launches with it too (both
+planes real, images, a workspace, guard rows)."""
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Tuple
@@ -110,14 +111,19 @@ def operand(hip, x, device, true_lo=False):
     return hip.H2(t.to(device))
 
 
-def launch(case: Case, hip, device, true_lo=False) -> SimpleNamespace:
-    """The operands, prefilled outputs and hip.gemm keyword arguments of a case: A, W (h2, lo planes NaN), M, N, K, kw, and `host`, the
-    f32 tensors they were packed from plus whatever else the reference needs.  Outputs are prefilled with NaN (7.0: the half planes of
-    the head-major cases)."""
+def launch(case, hip, device, true_lo=False, *, split=1, guard=0, w_il=False, a_il=False, out_il=False, workspace=None) -> SimpleNamespace:
+    """The operands, prefilled outputs and hip.gemm keyword arguments of a case: A, W (h2; split 1: lo planes NaN unless true_lo; split 3:
+    both planes real), M, N, K, kw, and `host`, the f32 tensors they were packed from plus whatever else the reference needs.  Outputs
+    are prefilled with NaN (7.0: the half planes of the head-major cases).
+
+    guard: rows allocated and prefilled behind row M of every output and of the row-statistics pieces; `guards` lists them (they must
+    still hold the prefill after the launch).  w_il / a_il: the weight's interleaved image is passed / the activation travels as its
+    128-byte-row image (`A` is an H2IL, `planar_A` the planes).  out_il: the h2 output (and the in-place h2 residual) is an image
+    `out_img` of `out_cols` columns; `out_h2` is None then.  workspace: passed on."""
     f = case.form
     nan = float("nan")
     host = SimpleNamespace()
-    kw = dict(split=1)
+    kw = dict(split=split)
     if f in ("product", "plain", "ln_fold", "h2_residual"):
         M, N, K = case.shape
         a, w = rnd(M, K, seed=101), rnd(N, K, seed=102, scale=K ** -0.5)
@@ -129,8 +135,8 @@ def launch(case: Case, hip, device, true_lo=False) -> SimpleNamespace:
         M, N, K = Bn * H * Wd, 4 * Cout, Cin
         a, w = rnd(M, K, seed=105), rnd(N, K, seed=106, scale=K ** -0.5)       # weight rows (dy, dx, co)
     elif f == "head_major":
-        S, hd = case.shape
-        Bn, Hh, K = 2, 2, 64
+        S, hd = case.shape[:2]                                                 # (S, hd) or (S, hd, K, Bn, heads)
+        K, Bn, Hh = tuple(case.shape[2:]) + (64, 2, 2)[len(case.shape) - 2:]
         M, N = Bn * S, 3 * Hh * hd
         a, w = rnd(M, K, seed=107), rnd(N, K, seed=108, scale=K ** -0.5)
     elif f == "conv":
@@ -140,38 +146,69 @@ def launch(case: Case, hip, device, true_lo=False) -> SimpleNamespace:
     else:
         raise ValueError(f)
     host.a, host.w = a, w
+    true_lo = true_lo or split == 3
     A, W = operand(hip, a, device, true_lo), operand(hip, w, device, true_lo)
-    out_f32 = out_h2 = None
+    planar_A = A
+    if w_il or a_il:
+        kw.update(w_il=hip.interleave_planes(W))
+    if a_il:
+        A = hip.H2IL.from_planes(A)
+    if workspace is not None:
+        kw.update(workspace=workspace)
+    guards = []
+
+    def rows_of(full, rows, axis=0):
+        """the first `rows` rows of `full` (a view with the same base address: what the launch is given); the rest are guard rows"""
+        if full.shape[axis] > rows:
+            guards.append(full.narrow(axis, rows, full.shape[axis] - rows))
+        return full.narrow(axis, 0, rows)
+
+    def new_f32(rows, cols):
+        return rows_of(torch.full((rows + guard, cols), nan, device=device), rows)
+
+    def new_h2(cols, fill=nan):
+        return hip.H2(rows_of(torch.full((2, M + guard, cols), fill, dtype=torch.float16, device=device), M, axis=1))
+
+    out_cols = N + 64 - N % 32                                                 # image width: a multiple of 32, wider than N
+    out_f32 = out_h2 = out_img = None
     if f == "product":
-        out_f32 = torch.full((M, N), nan, device=device)
+        out_f32 = new_f32(M, N)
         kw.update(out_f32=out_f32)
     elif f == "plain":
         dldo, dldr, dldoh = LAYOUTS[case.layout]
         ldo, ldoh = N + dldo, N + dldoh
         ldr = N + dldr if dldr is not None else N + 1 + N % 2
         host.bias, host.res = rnd(N, seed=111), rnd(M, ldr, seed=112)
-        out_f32 = torch.full((M, ldo), nan, device=device)
-        out_h2 = hip.H2(torch.full((2, M, ldoh), nan, dtype=torch.float16, device=device))
-        kw.update(bias=host.bias.to(device), residual=host.res.to(device), ldr=ldr, out_f32=out_f32, ldo=ldo, out_h2=out_h2, ldoh=ldoh,
+        out_f32 = new_f32(M, ldo)
+        if out_il:
+            out_img = hip.H2IL(rows_of(torch.full((M + guard, 2 * out_cols), nan, dtype=torch.float16, device=device), M))
+            kw.update(out_h2=out_img)
+        else:
+            out_h2 = new_h2(ldoh)
+            kw.update(out_h2=out_h2, ldoh=ldoh)
+        kw.update(bias=host.bias.to(device), residual=host.res.to(device), ldr=ldr, out_f32=out_f32, ldo=ldo,
                   act=case.act, alpha=ALPHA, out_scale=OUT_SCALE)
     elif f == "batched":
         host.res = rnd(Bz, M, N, seed=113)
-        out_f32 = torch.full((Bz, M, N), nan, device=device)
+        out_f32 = new_f32(Bz * M, N).view(Bz, M, N)
         kw.update(residual=host.res.to(device), out_f32=out_f32, act=ACT_ABS_POST, alpha=-1.0, batch=Bz, stride_a=0, stride_w=N * K,
                   stride_r=M * N, stride_o=M * N)
     elif f == "pixel_shuffle":
         host.bias = rnd(Cout, seed=114)
-        out_f32 = torch.full((Bn, 2 * H, 2 * Wd, Cout), nan, device=device)
+        out_f32 = new_f32(Bn * 2 * H * 2 * Wd, Cout).view(Bn, 2 * H, 2 * Wd, Cout)
         kw.update(bias=host.bias.repeat(4).to(device), out_f32=out_f32, pixel_shuffle=(H, Wd, 2 * Cout))
     elif f == "head_major":
         host.bias = rnd(N, seed=115)
-        out_h2 = hip.H2(torch.full((2, M, N), 7.0, dtype=torch.float16, device=device))
+        out_h2 = new_h2(N, 7.0)
         kw.update(bias=host.bias.to(device), out_h2=out_h2, head_major=(S, Hh, hd), head_major_nolo=case.nolo)
     elif f == "ln_fold":
         host.bias, host.colsum = rnd(N, seed=116), rnd(N, seed=117)
         host.stats = torch.stack([0.5 + rnd(M, seed=118).abs(), 0.3 * rnd(M, seed=119)], 1).contiguous()   # (rstd, mu * rstd)
-        out_h2 = hip.H2(torch.full((2, M, N), nan, dtype=torch.float16, device=device))
-        kw.update(bias=host.bias.to(device), out_h2=out_h2, act=case.act, alpha=ALPHA, out_scale=OUT_SCALE,
+        if out_il:
+            out_img = hip.H2IL(rows_of(torch.full((M + guard, 2 * out_cols), nan, dtype=torch.float16, device=device), M))
+        else:
+            out_h2 = new_h2(N)
+        kw.update(bias=host.bias.to(device), out_h2=out_img if out_il else out_h2, act=case.act, alpha=ALPHA, out_scale=OUT_SCALE,
                   ln_fold=(host.stats.to(device), host.colsum.to(device)))
     elif f == "h2_residual":
         host.bias = rnd(N, seed=120)
@@ -179,11 +216,21 @@ def launch(case: Case, hip, device, true_lo=False) -> SimpleNamespace:
         x_old[:, 3] *= 1e3                                                     # massive channels, like real ViT residual streams
         x_old[:, N // 2] *= 300.0
         host.x_old = hip.H2.pack(x_old * XS)                                   # both planes real: this form reads the residual's lo plane
-        out_h2 = hip.H2(host.x_old.t.clone().to(device))                       # in place: the output is the residual
-        stats = torch.full((hip.stats_pieces(N), M, 2), nan, device=device)
-        kw.update(bias=host.bias.to(device), out_h2=out_h2, residual_h2=(out_h2, 1.0 / XS), out_scale=XS, row_stats=stats, alpha=ALPHA)
+        pieces = hip.stats_pieces(N)
+        stats = new_f32(pieces * M, 2).view(pieces, M, 2)
+        if out_il:                                                             # in place: the output image is the residual image
+            pl = torch.full((2, M + guard, out_cols), nan, dtype=torch.float16, device=device)
+            pl[:, :M, :N] = host.x_old.t.to(device)
+            out_img = hip.H2IL(rows_of(hip.interleave_planes(hip.H2(pl)), M))
+            kw.update(out_h2=out_img, residual_h2=(out_img, 1.0 / XS))
+        else:
+            out_h2 = new_h2(N)
+            out_h2.t.copy_(host.x_old.t)                                       # in place: the output is the residual
+            kw.update(out_h2=out_h2, residual_h2=(out_h2, 1.0 / XS))
+        kw.update(bias=host.bias.to(device), out_scale=XS, row_stats=stats, alpha=ALPHA)
     elif f == "conv":
         host.bias, host.res = rnd(N, seed=122), rnd(M, N, seed=123)
-        out_f32 = torch.full((M, N), nan, device=device)
+        out_f32 = new_f32(M, N)
         kw.update(bias=host.bias.to(device), residual=host.res.to(device), out_f32=out_f32, conv3x3=(H, Wd, Cc))
-    return SimpleNamespace(case=case, A=A, W=W, M=M, N=N, K=K, kw=kw, host=host, out_f32=out_f32, out_h2=out_h2)
+    return SimpleNamespace(case=case, A=A, planar_A=planar_A, W=W, M=M, N=N, K=K, kw=kw, host=host, out_f32=out_f32, out_h2=out_h2,
+                           out_img=out_img, out_cols=out_cols, guards=guards)

@@ -530,11 +530,12 @@ def test_gemm_persistent_equals_plain(hip, form, monkeypatch):
         assert torch.equal(outs["0"][1], outs["1"][1]) and bool(torch.isfinite(outs["0"][1]).all())
 
 
-@pytest.mark.parametrize("M,N,K", [(9296, 1024, 256), (9296 - 100, 1024, 4096), (6000, 768, 128)])
+@pytest.mark.parametrize("M,N,K", [(9296, 1024, 256), (9296 - 100, 1024, 4096), (6000, 768, 128), (4104, 2056, 512)])
 def test_gemm_192_row_tiles_equal_256_row_tiles(hip, monkeypatch, M, N, K):
     """Grids under one round of 256^2 tiles (CLIP out_proj / c_proj of the fused 16-image forward) run on 192 x 256 tiles
     (CVLM_GEMM_T192, h2-residual form): same K order, so outputs and piece statistics are bit-identical to the 256-row tiling,
-    ragged last row tile included."""
+    ragged last row tile included.  (tests/test_gemm_split3_cpu.py::test_relation_192_row_tiles: the K = 4096 and K = 512 cases reach
+    the 192-row kernel; at K = 256 and 128 the model picks 256 x 128 tiles under both settings.)"""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(11)
     rn = lambda *sh, scale=1.0: torch.randn(*sh, device=dev, generator=g) * scale
