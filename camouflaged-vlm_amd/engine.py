@@ -34,6 +34,7 @@ from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIE
                        THIN_MAX_ITER, THIN_MAX_STEPS, ClDiceTotals, MaskThin, thin_request,
                        REGIONS_MAXM, MaskRegions, RegionClasses, instances_to_coco, regions_request,
                        NMS_MAX_PAIRS, MaskNms, NmsRequest, nms_request,
+                       RENDER_MAX_ROWS, Rendered, RenderLayer, RenderRequest, SizedImages, image_tables, render_request, sized_images,
                        PQ_MAX_CELLS, PanopticGroundTruth, PanopticTotals, pq_request, pq_segments_request,
                        label_tables, labels_request, morph_request, pairs_request, polygons_request, rle_decode_request, rle_request, sized_request, sized_tables)
 from .spec import ClipGeometry, SamGeometry

@@ -116,6 +116,8 @@ _SIGNATURES = {
     "cvlm_debug_mask_nms_inter_host": "i:plppppipppilpp",
     "cvlm_mask_nms": "i:pppiplpppiiippppppps",
     "cvlm_debug_mask_nms_host": "i:pppiplpppiiippppppp",
+    "cvlm_render": "i:plppilppiplplplppipps",
+    "cvlm_debug_render_host": "i:plppilppiplplplppipp",
     "cvlm_label_init": "i:ppplppiipps",
     "cvlm_label_accumulate": "i:piiiiiipppipppllpps",
     "cvlm_label_finish": "i:iipppppllpppps",
@@ -1723,6 +1725,37 @@ def mask_nms(group_offsets: torch.Tensor, member: torch.Tensor, pair_offsets: to
     _call("cvlm_debug_mask_nms_host" if host else "cvlm_mask_nms", group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G,
           inter.data_ptr() if N else None, N, area.data_ptr(), score.data_ptr(), _p(category), Q, int(measure), int(method),
           C.addressof(params), order.data_ptr(), keep.data_ptr(), by.data_ptr(), decay.data_ptr(), n_keep.data_ptr(), status.data_ptr())
+
+
+RENDER_KINDS = {"bits": 0, "levels": 1, "labels": 2}      # csrc/render_logic.h: RD_BITS, RD_LEVELS, RD_LABELS
+RENDER_EDGES, RENDER_INVERT = 1, 2                        # flags: RD_EDGES (labels), RD_INVERT (bits)
+
+
+def render(img: torch.Tensor, img_offsets: torch.Tensor, dims: torch.Tensor, max_pixels: int, layer_offsets: torch.Tensor,
+           layers: Optional[torch.Tensor], bits: Optional[torch.Tensor], levels: Optional[torch.Tensor], labels: Optional[torch.Tensor],
+           rgb: torch.Tensor, alpha: torch.Tensor, out: torch.Tensor, status: torch.Tensor, host: bool = False) -> None:
+    """Layers painted over B interleaved 3-channel uint8 images of their own sizes (include/cvlm.h: cvlm_render): img and
+    out flat uint8 of equal length (out may BE img: in place), img_offsets int64 [B + 1] in bytes, dims int32 [B][2], layer_offsets int32
+    [B + 1] into layers int64 [L][4] = (kind | flags << 8, src, first, rows) (None: L = 0); the sources bits uint8, levels uint8 and
+    labels int32, each flat or None; the table rgb uint8 [T][3] and alpha f32 [T]; status int32 [1]: bit 0 an image was refused, bit 1
+    a layer skipped, bit 2 a table row with an alpha that paints nothing was selected.  host=True: the same on HOST tensors without a
+    device (cvlm_debug_render_host)."""
+    B, T = int(dims.shape[0]), int(alpha.numel())
+    L = 0 if layers is None else int(layers.shape[0])
+    u8, i32, i64 = torch.uint8, torch.int32, torch.int64
+    for t, dtype, shape in ((img, u8, (img.numel(),)), (out, u8, (img.numel(),)), (img_offsets, i64, (B + 1,)), (dims, i32, (B, 2)),
+                            (layer_offsets, i32, (B + 1,)), (rgb, u8, (T, 3)), (alpha, torch.float32, (T,)), (status, i32, (1,))) + \
+            (() if layers is None else ((layers, i64, (L, 4)),)) + (() if bits is None else ((bits, u8, (bits.numel(),)),)) + \
+            (() if levels is None else ((levels, u8, (levels.numel(),)),)) + (() if labels is None else ((labels, i32, (labels.numel(),)),)):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == img.device, (t.dtype, tuple(t.shape), shape)
+    if host:
+        assert not img.is_cuda
+    else:
+        _on_current_device(img)
+    n = lambda t: 0 if t is None else int(t.numel())
+    _call("cvlm_debug_render_host" if host else "cvlm_render", img.data_ptr(), img.numel(), img_offsets.data_ptr(), dims.data_ptr(), B,
+          int(max_pixels), layer_offsets.data_ptr(), _p(layers) if L else None, L, _p(bits), n(bits), _p(levels), n(levels), _p(labels),
+          n(labels), rgb.data_ptr(), alpha.data_ptr(), T, out.data_ptr(), status.data_ptr())
 
 
 def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,

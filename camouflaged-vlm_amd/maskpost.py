@@ -1526,6 +1526,254 @@ class MaskNms:
         return out, idx
 
 
+RENDER_MAX_IMAGES = 65535         # images of one render: the size lists of this module hold 65535 (the entry takes 2^16)
+RENDER_MAX_LAYERS = 1 << 20       # layers of one render (RD_MAX_L)
+RENDER_MAX_ROWS = 1 << 24         # rows of its colour table (RD_MAX_T)
+
+
+def image_tables(sizes):
+    """Host tables of interleaved 3-channel uint8 images for a list of per-image (h, w): dims int32 (B, 2), byte offsets
+    int64 (B + 1) -- image b is its 3 h w bytes, row pitch 3 w, followed by the 0 .. 3 pad bytes that bring the next image to a multiple
+    of 4 -- and the largest image's pixel count."""
+    dims = np.asarray(sizes, dtype=np.int32).reshape(-1, 2)
+    pixels = dims[:, 0].astype(np.int64) * dims[:, 1].astype(np.int64)
+    offsets = np.zeros(dims.shape[0] + 1, dtype=np.int64)
+    np.cumsum((3 * pixels + 3) // 4 * 4, out=offsets[1:])
+    return dims, offsets, int(pixels.max()) if len(pixels) else 0
+
+
+@dataclass
+class SizedImages:
+    """Interleaved 3-channel uint8 images, each at its own size, in one flat buffer (`sized_images`): what
+    Cascade.render paints on.  Image b is its 3 h w bytes from byte offsets[b] of `data` on; the channel order is the caller's."""
+    data: torch.Tensor              # (total bytes,) uint8
+    offsets: torch.Tensor           # (B + 1,) int64 in bytes, multiples of 4, on the device of data
+    dims: torch.Tensor              # (B, 2) int32 (h, w), on the device of data
+    sizes: list                     # B (h, w) pairs, on the host
+
+    def byte_range(self, b: int) -> Tuple[int, int]:
+        """Where image b's 3 h w bytes lie in `data`, from the sizes alone: no read of the device."""
+        _, offsets, _ = image_tables(self.sizes)
+        h, w = self.sizes[b]
+        return int(offsets[b]), int(offsets[b]) + 3 * h * w
+
+    def image(self, b: int) -> torch.Tensor:
+        """Image b as a uint8 view (h, w, 3) of `data`."""
+        lo, hi = self.byte_range(b)
+        return self.data[lo:hi].view(*self.sizes[b], 3)
+
+    def to_numpy(self, b: int) -> np.ndarray:
+        """Image b as a uint8 array (h, w, 3) on the host (synchronises)."""
+        return self.image(b).cpu().numpy()
+
+
+def sized_images(images, device) -> SizedImages:
+    """A list of (h, w, 3) uint8 numpy arrays or tensors -> SizedImages on `device`: the host images go up in one copy of the flat buffer,
+    images that are tensors on a device are copied into their slices.  ValueError for anything else; the pad bytes are 0."""
+    if isinstance(images, (np.ndarray, torch.Tensor)) or not hasattr(images, "__len__") or not 1 <= len(images) <= RENDER_MAX_IMAGES:
+        raise ValueError(f"sized_images: a list of 1 .. {RENDER_MAX_IMAGES} (h, w, 3) uint8 images")
+    sizes = []
+    for b, im in enumerate(images):
+        ok = isinstance(im, (np.ndarray, torch.Tensor)) and im.ndim == 3 and int(im.shape[2]) == 3 and \
+            im.dtype in (np.uint8, torch.uint8) and 1 <= int(im.shape[0]) <= SIZED_MAX_SIDE and 1 <= int(im.shape[1]) <= SIZED_MAX_SIDE
+        if not ok:
+            raise ValueError(f"sized_images: image {b} must be a uint8 array or tensor (h, w, 3) with 1 <= h, w <= {SIZED_MAX_SIDE}")
+        sizes.append((int(im.shape[0]), int(im.shape[1])))
+    dims, offsets, _ = image_tables(sizes)
+    flat = np.zeros(int(offsets[-1]), dtype=np.uint8)
+    for b, im in enumerate(images):
+        if not (isinstance(im, torch.Tensor) and im.is_cuda):
+            host = im.detach().numpy() if isinstance(im, torch.Tensor) else im
+            flat[int(offsets[b]):int(offsets[b]) + host.size] = np.ascontiguousarray(host).reshape(-1)
+    dev = torch.device(device)
+    data = torch.from_numpy(flat).to(dev)
+    for b, im in enumerate(images):
+        if isinstance(im, torch.Tensor) and im.is_cuda:
+            data[int(offsets[b]):int(offsets[b]) + im.numel()] = im.detach().to(dev).reshape(-1)
+    return SizedImages(data=data, offsets=torch.from_numpy(offsets).to(dev), dims=torch.from_numpy(dims).to(dev), sizes=sizes)
+
+
+def palette(n: int) -> np.ndarray:
+    """A deterministic colour table, uint8 (n, 3), by the well-known bit-interleave rule: bits 0, 1 and 2 of the id feed r, g and b from
+    the top bit down, three bits of the id per round -- 0 black, 1 (128, 0, 0), 2 (0, 128, 0), 3 (128, 128, 0), 4 (0, 0, 128), ..., 15
+    (192, 128, 128), ..., 255 (224, 224, 192); ids from 256 on repeat the table."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= RENDER_MAX_ROWS:
+        raise ValueError(f"palette: n must be an int in [1, {RENDER_MAX_ROWS}], got {n!r}")
+    ids = np.arange(int(n), dtype=np.int64) & 255
+    out = np.zeros((int(n), 3), dtype=np.uint8)
+    for j in range(8):
+        for ch in range(3):
+            out[:, ch] |= (((ids >> (3 * j + ch)) & 1) << (7 - j)).astype(np.uint8)
+    return out
+
+
+@dataclass
+class RenderLayer:
+    """One layer of a render, on the host but for its source: what `fill`, `heat` and `classes` build."""
+    kind: int                       # hip.RENDER_KINDS
+    flags: int                      # hip.RENDER_EDGES (labels), hip.RENDER_INVERT (bits)
+    source: torch.Tensor            # the flat buffer the layer reads: packed bits uint8, levels uint8 or labels int32
+    src: int                        # where its plane or map starts: bytes (bits, levels) or elements (labels)
+    size: Tuple[int, int]           # the (h, w) of that plane or map: the size of the image it may be painted on
+    rgb: np.ndarray                 # (rows, 3) the colour of each table row
+    alpha: np.ndarray               # (rows,) the opacity of each table row
+
+
+def _render_colors(who: str, name: str, v, n: Optional[int]) -> np.ndarray:
+    """Colours checked -> uint8 (n, 3): ints in 0 .. 255, no bools, no floats; n None: any number of rows >= 1."""
+    try:
+        arr = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+    except Exception:
+        arr = np.asarray(None)
+    if arr.dtype.kind not in "iu" or arr.ndim != 2 or arr.shape[1] != 3 or arr.shape[0] < 1 or (n is not None and arr.shape[0] != n):
+        raise ValueError(f"{who}: {name} must hold {'rows' if n is None else n} x 3 ints in 0 .. 255")
+    if int(arr.min()) < 0 or int(arr.max()) > 255:
+        raise ValueError(f"{who}: {name} must hold ints in 0 .. 255")
+    return np.ascontiguousarray(arr.astype(np.uint8))
+
+
+def _render_alphas(who: str, v, n: int) -> np.ndarray:
+    """Opacities checked -> f32 (n,): one finite real in [0, 1] for all rows or one per row; no bools."""
+    try:
+        arr = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+    except Exception:
+        arr = np.asarray(None)
+    if arr.dtype.kind not in "iuf" or arr.shape not in ((), (n,)):
+        raise ValueError(f"{who}: alpha must be a real in [0, 1] or hold one per row, {n} of them")
+    arr = np.broadcast_to(arr.astype(np.float32), (n,))
+    if not bool(np.all(np.isfinite(arr))) or float(arr.min()) < 0.0 or float(arr.max()) > 1.0:
+        raise ValueError(f"{who}: an alpha must be finite and in [0, 1]")
+    return np.ascontiguousarray(arr)
+
+
+def _render_index(who: str, name: str, v, n: int) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < n:
+        raise ValueError(f"{who}: {name} must be an int in [0, {n}), got {v!r}")
+    return int(v)
+
+
+def fill(sized: "SizedMasks", p: int, *, color, alpha=0.5, invert: bool = False) -> RenderLayer:
+    """A BITS layer: plane p of a SizedMasks painted in one colour at one opacity where its bit is set -- invert=True: where it is
+    clear.  Only host rows are built; the plane stays where it is."""
+    if not isinstance(sized, SizedMasks) or not isinstance(invert, (bool, np.bool_)):
+        raise ValueError("fill: sized must be a SizedMasks and invert a bool")
+    p = _render_index("fill", "p", p, len(sized.sizes))
+    return RenderLayer(kind=hip.RENDER_KINDS["bits"], flags=hip.RENDER_INVERT if invert else 0, source=sized.bits, src=sized.byte_range(p)[0],
+                       size=tuple(int(v) for v in sized.sizes[p]), rgb=_render_colors("fill", "color", [color] if np.ndim(color) == 1 else color, 1),
+                       alpha=_render_alphas("fill", alpha, 1))
+
+
+def heat(levels_u8: torch.Tensor, b: int, *, lut, alpha) -> RenderLayer:
+    """A LEVELS layer: map b of a uint8 tensor (N, h, w) or (N, 1, h, w) -- e.g. `mask_to_u8`'s soft masks -- painted through a 256-row
+    look-up table of colours at one opacity or one per level (an alpha-0 level leaves its pixels alone)."""
+    if not isinstance(levels_u8, torch.Tensor) or levels_u8.dtype != torch.uint8 or levels_u8.dim() not in (3, 4) or \
+            (levels_u8.dim() == 4 and levels_u8.shape[1] != 1) or not levels_u8.is_contiguous():
+        raise ValueError("heat: levels must be a contiguous uint8 tensor (N, h, w) or (N, 1, h, w)")
+    h, w = int(levels_u8.shape[-2]), int(levels_u8.shape[-1])
+    b = _render_index("heat", "b", b, int(levels_u8.shape[0]))
+    return RenderLayer(kind=hip.RENDER_KINDS["levels"], flags=0, source=levels_u8.detach().view(-1), src=b * h * w, size=(h, w),
+                       rgb=_render_colors("heat", "lut", lut, 256), alpha=_render_alphas("heat", alpha, 256))
+
+
+def classes(label_map: torch.Tensor, label_maps, b: int, *, palette, alpha=0.7, edges: bool = False) -> RenderLayer:
+    """A LABELS layer: image b of a flat int32 map of `label_maps` (a LabelMaps: what its `categories()` and `panoptic()` return)
+    painted with palette[id] for ids in [0, len(palette)), every other id void; edges=True: only the pixels with a 4-neighbour of
+    another id -- the segment outlines."""
+    sizes = getattr(label_maps, "sizes", None)
+    if not isinstance(sizes, (list, tuple)) or not isinstance(edges, (bool, np.bool_)):
+        raise ValueError("classes: label_maps must be the LabelMaps of the map and edges a bool")
+    _, offsets, _ = label_tables(sizes)
+    if not isinstance(label_map, torch.Tensor) or label_map.dtype != torch.int32 or not label_map.is_contiguous() or \
+            label_map.numel() != int(offsets[-1]):
+        raise ValueError(f"classes: the map must be a contiguous int32 tensor of the label maps' {int(offsets[-1])} pixels")
+    b = _render_index("classes", "b", b, len(sizes))
+    rgb = _render_colors("classes", "palette", palette, None)
+    return RenderLayer(kind=hip.RENDER_KINDS["labels"], flags=hip.RENDER_EDGES if edges else 0, source=label_map.detach().view(-1),
+                       src=int(offsets[b]), size=tuple(int(v) for v in sizes[b]), rgb=rgb, alpha=_render_alphas("classes", alpha, rgb.shape[0]))
+
+
+@dataclass
+class RenderRequest:
+    """What `render_request` returns: the tables cvlm_render takes, on the host, and the source buffers the layers name."""
+    layer_offsets: np.ndarray       # (B + 1,) int32 rows of layers
+    layers: np.ndarray              # (L, 4) int64: kind | flags << 8, src (shifted to its place among the sources of its kind), first, rows
+    rgb: np.ndarray                 # (T, 3) uint8
+    alpha: np.ndarray               # (T,) f32
+    sources: dict                   # kind -> the distinct flat tensors of that kind in the order of their first use: cat gives the buffer
+
+    @property
+    def L(self) -> int:
+        return int(self.layers.shape[0])
+
+
+def render_request(sizes, layers, *, device=None, who: str = "render") -> RenderRequest:
+    """Every check of Cascade.render that the host can make, before anything is launched (ValueError) -> RenderRequest.
+    sizes: the (h, w) of each image; layers: one sequence of RenderLayers per image, in painter's order (an empty one: the image is
+    copied).  A layer's plane or map has the size of the image it is painted on and lies inside its source; colours are ints in 0 ..
+    255; alphas are finite and in [0, 1]; a LUT has 256 rows; sources live on `device`; at most 2^20 layers and 2^24 table rows."""
+    sizes = _plane_sizes(sizes, who)
+    B = len(sizes)
+    if B > RENDER_MAX_IMAGES:
+        raise ValueError(f"{who}: at most {RENDER_MAX_IMAGES} images are taken, got {B}")
+    if isinstance(layers, (str, bytes, RenderLayer)) or not hasattr(layers, "__len__") or len(layers) != B or \
+            any(isinstance(ls, (str, bytes, RenderLayer)) or not hasattr(ls, "__iter__") for ls in layers):
+        raise ValueError(f"{who}: layers must hold one sequence of layers per image, {B} of them")
+    rows, rgb, alpha, counts = [], [], [], []
+    sources = {k: [] for k in hip.RENDER_KINDS.values()}
+    bases = {k: {} for k in hip.RENDER_KINDS.values()}
+    ends = {k: 0 for k in hip.RENDER_KINDS.values()}
+    T = 0
+    for b, ls in enumerate(layers):
+        ls = list(ls)
+        counts.append(len(ls))
+        for q in ls:
+            if not isinstance(q, RenderLayer) or q.kind not in sources or not isinstance(q.source, torch.Tensor) or q.source.dim() != 1:
+                raise ValueError(f"{who}: image {b}: a layer must be what fill, heat or classes built")
+            if tuple(q.size) != sizes[b]:
+                raise ValueError(f"{who}: image {b} is {sizes[b]}, a layer's plane is {tuple(q.size)}")
+            h, w = sizes[b]
+            kind = q.kind
+            names = {v: k for k, v in hip.RENDER_KINDS.items()}
+            n_rows = {0: 1, 1: 256}.get(kind)
+            q_rgb = _render_colors(who, "a layer's colours", q.rgb, n_rows)
+            q_alpha = _render_alphas(who, q.alpha, q_rgb.shape[0])
+            allowed = {0: hip.RENDER_INVERT, 1: 0, 2: hip.RENDER_EDGES}[kind]
+            need = {0: 4 * h * ((w + 31) // 32), 1: h * w, 2: h * w}[kind]
+            dtype = torch.int32 if kind == 2 else torch.uint8
+            if q.flags & ~allowed or q.source.dtype != dtype or not isinstance(q.src, (int, np.integer)) or q.src < 0 or \
+                    int(q.src) + need > q.source.numel() or (kind == 0 and (q.src % 4 or q.source.numel() % 4)):
+                raise ValueError(f"{who}: image {b}: a {names[kind]} layer's flags, source or slice do not fit")
+            if device is not None and q.source.device != torch.device(device):
+                raise ValueError(f"{who}: image {b}: a layer's source lives on {q.source.device}, the images on {device}")
+            key = (q.source.data_ptr(), q.source.numel())
+            if key not in bases[kind]:
+                bases[kind][key] = ends[kind]
+                ends[kind] += q.source.numel()
+                sources[kind].append(q.source)
+            rows.append((kind | q.flags << 8, bases[kind][key] + int(q.src), T, q_rgb.shape[0]))
+            rgb.append(q_rgb)
+            alpha.append(q_alpha)
+            T += q_rgb.shape[0]
+    if len(rows) > RENDER_MAX_LAYERS or T > RENDER_MAX_ROWS:
+        raise ValueError(f"{who}: {len(rows)} layers with {T} table rows: at most 2^20 layers and 2^24 rows are taken")
+    return RenderRequest(layer_offsets=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
+                         layers=np.asarray(rows, dtype=np.int64).reshape(-1, 4),
+                         rgb=np.concatenate(rgb) if rgb else np.zeros((1, 3), np.uint8),
+                         alpha=np.concatenate(alpha) if alpha else np.zeros(1, np.float32), sources=sources)
+
+
+@dataclass
+class Rendered(SizedImages):
+    """The images of Cascade.render with their layers painted: a SizedImages plus the kernel's status."""
+    status: Optional[torch.Tensor] = None     # (1,) int32: bit 0 an image was refused, bit 1 a layer skipped, bit 2 a refused table row
+
+    def check(self) -> None:
+        """RuntimeError if the kernel refused an image, a layer or a table row (synchronises).  `render_request` has checked everything
+        on the host, so this says that a source's bytes do not belong to its sizes, or that the library is broken."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError(f"render: cvlm_render refused an image (1), a layer (2) or a table row (4): status {int(self.status.item())}")
+
+
 @dataclass
 class CocoMatches:
     """The COCO matching of detections and annotations (Cascade.coco_match; cvlm_coco_match), on the device.  Rows are
@@ -2493,6 +2741,78 @@ class MaskUtilities:
         hip.mask_nms(group_offsets, member, pair_offsets, out.inter, instances.area.contiguous(), score, cat, req.measure, req.method,
                      req.thr, req.sigma, out.order, out.keep, out.by, out.decay, out.n_keep, status[1:2])
         return out
+
+    # ---- Rendering: overlays, outlines and label colour maps ------------------------------------------------------------------
+    def render(self, images: "SizedImages", layers, *, host: bool = False) -> "Rendered":
+        """The layers painted over the images -> Rendered, a new SizedImages with the kernel's status (cvlm_render).
+        images: a SizedImages on the device (`sized_images`); layers: one sequence per image of what `fill`, `heat` and `classes` built,
+        applied in order.  `render_request` checks everything on the host before anything is launched (ValueError).  One upload of the
+        tables, one entry call on the caller's stream, no workspace, no synchronisation; layers whose sources are different tensors
+        cost one torch.cat of those per kind.  No layer for any image: nothing is launched and the result is a clone.  The pad bytes
+        behind an image of the result are not written.  host=True: images and sources on the HOST, through the sequential host entry
+        (cvlm_debug_render_host) -- for tests and for looking at a result where there is no device, never taken silently."""
+        if not isinstance(images, SizedImages) or not isinstance(images.data, torch.Tensor) or images.data.is_cuda == bool(host):
+            raise ValueError("render: images must be a SizedImages on the device (host=True: on the host)")
+        dev = images.data.device
+        req = render_request(images.sizes, layers, device=dev)
+        sizes = [tuple(z) for z in images.sizes]
+        if req.L == 0:
+            return Rendered(data=images.data.clone(), offsets=images.offsets, dims=images.dims, sizes=sizes,
+                            status=torch.zeros(1, dtype=torch.int32, device=dev))
+        B, L, T = len(sizes), req.L, int(req.alpha.shape[0])
+        tables = np.concatenate([req.layers.reshape(-1).view(np.uint8), req.layer_offsets.view(np.uint8), req.alpha.view(np.uint8),
+                                 req.rgb.reshape(-1)])
+        tables = torch.from_numpy(tables).to(dev)                     # the one upload: the int64 table first, so every view is aligned
+        at = np.cumsum([0, 32 * L, 4 * (B + 1), 4 * T, 3 * T])
+        rows = tables[at[0]:at[1]].view(torch.int64).view(L, 4)
+        layer_offsets = tables[at[1]:at[2]].view(torch.int32)
+        alpha = tables[at[2]:at[3]].view(torch.float32)
+        rgb = tables[at[3]:at[4]].view(T, 3)
+
+        def buffer(kind):
+            parts = req.sources[kind]
+            if not parts:
+                return None
+            t = parts[0] if len(parts) == 1 else torch.cat(parts)
+            return t.clone() if t.data_ptr() % 4 else t               # the kernel reads bits and labels as 32-bit words
+
+        out = Rendered(data=torch.empty_like(images.data), offsets=images.offsets, dims=images.dims, sizes=sizes,
+                       status=torch.empty(1, dtype=torch.int32, device=dev))
+        _, _, max_pixels = image_tables(sizes)
+        hip.render(images.data, images.offsets, images.dims, max_pixels, layer_offsets, rows, buffer(0), buffer(1), buffer(2), rgb, alpha,
+                   out.data, out.status, host=bool(host))
+        return out
+
+    def render_overlay(self, images: "SizedImages", sized: "SizedMasks", *, image_of, colors=(0, 255, 0), alpha=0.5, outline=None,
+                       outline_color=(255, 255, 255), host: bool = False) -> "Rendered":
+        """demo.py's picture without its text (save_array_as_image, lines 51-56): every plane of `sized` painted over image image_of[p]
+        in its colour at `alpha` -- colors: one colour for all planes or one per plane, in the images' channel order --, the planes of
+        an image in their order.  outline=r: the boundary of radius r of every plane (`mask_boundary_sized`) painted afterwards in
+        outline_color at alpha 1.  `render_overlay(images, pack_masks_sized(logits, sizes, level=1), image_of=range(B))` is the demo's
+        `overlay[data_array > 0] = (0, 255, 0)` blended half and half.  host=True: `render`'s, without outline=."""
+        if not isinstance(images, SizedImages) or not isinstance(sized, SizedMasks):
+            raise ValueError("render_overlay: images must be a SizedImages and sized a SizedMasks")
+        B, P = len(images.sizes), len(sized.sizes)
+        if isinstance(image_of, (str, bytes)) or not hasattr(image_of, "__len__") or len(image_of) != P:
+            raise ValueError(f"render_overlay: image_of must hold one image index per plane, {P} of them")
+        image_of = [_render_index("render_overlay", "an image index", b, B) for b in image_of]
+        cols = np.asarray(colors)
+        if cols.ndim == 1:
+            cols = np.broadcast_to(cols, (P,) + cols.shape)
+        if cols.shape != (P, 3):
+            raise ValueError(f"render_overlay: colors must be one colour or hold one per plane, {P} of them")
+        layers = [[] for _ in range(B)]
+        for p, b in enumerate(image_of):
+            layers[b].append(fill(sized, p, color=cols[p], alpha=alpha))
+        if outline is not None:
+            if host or not images.data.is_cuda:
+                raise ValueError("render_overlay: outline= needs images and planes on the device")
+            render_request(images.sizes, layers, device=images.data.device, who="render_overlay")    # everything, before the first launch
+            _render_colors("render_overlay", "outline_color", [outline_color] if np.ndim(outline_color) == 1 else outline_color, 1)
+            edges = self.mask_boundary_sized(sized, radius=outline)
+            for p, b in enumerate(image_of):
+                layers[b].append(fill(edges, p, color=outline_color, alpha=1.0))
+        return self.render(images, layers, host=host)
 
     # ---- COCO matching on the device (DESIGN.md §22) ---------------------------------------------------------------------------------------
     def coco_match(self, dets: Optional["SizedMasks"], gts: Optional["SizedMasks"], *, scores, det_image, gt_image, det_category=None,

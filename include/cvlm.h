@@ -1346,6 +1346,51 @@ int cvlm_debug_mask_nms_host(const int32_t* group_offsets, const int32_t* member
                              int32_t method, const double* params, int32_t* order, uint8_t* keep, int32_t* by, float* decay, int32_t* n_keep,
                              int32_t* status);
 
+/* Rendering: overlays, outlines and label colour maps painted over the images on the device -- demo.py:51-56
+ * (save_array_as_image) without its text, the visualizer's draw_binary_mask / draw_soft_mask / draw_sem_seg / draw_panoptic_seg without
+ * matplotlib's anti-aliasing.
+ * Images: B interleaved 3-channel uint8 images, each at its own size dims int32 [B][2] = (h, w): image b is its 3 h w bytes, row pitch
+ * 3 w, from byte img_offsets[b] of img on; img_offsets int64 [B + 1], multiples of 4 and non-decreasing, img_offsets[b + 1] -
+ * img_offsets[b] = 3 h w rounded up to a multiple of 4: the 0 .. 3 bytes behind an image's 3 h w are pad and are never written (the
+ * caller's table is non-decreasing as a whole: images that pass on their own and still share bytes are painted in no defined order).
+ * out has the same layout; out == img (in place) is allowed.  The channel order is the caller's: colours are given in it.  max_pixels: the largest h w of the call (it
+ * sizes the grid and nothing else).
+ * Layers: image b owns rows layer_offsets[b] .. layer_offsets[b + 1] - 1 (int32 [B + 1]) of layers int64 [L][4] = (kind | flags << 8,
+ * src, first, rows), applied in that order, each over the result of the one before.  Colours and opacities come from one table: rgb
+ * uint8 [T][3], alpha f32 [T].  A selected pixel's channels become blend(c, col, a) with the row's (col, a):
+ *   b = 1.0f - a;  v = (float)c * b + (float)col * a -- two f32 products and one f32 sum, each rounded on its own, never an fma --;
+ *   (uint8) clamp(rintf(v), 0, 255), round half to even.  At a = 0.5 both products are exact and this is cv2.addWeighted's documented
+ *   saturate(round((c + col) / 2)).  A pixel that a layer does not select is left as it is.
+ *   kind 0, BITS: src = the byte offset in bits of a sized plane (cvlm_mask_pack_sized's layout) of the image's own (h, w), a multiple
+ *     of 4; selected where the bit is 1 -- with flag 2 (INVERT) where it is 0; pad bits are never read as pixels; rows == 1, row first.
+ *   kind 1, LEVELS: src = the byte offset in levels of a uint8 (h, w) map, pitch w; every pixel selected; rows == 256, row first + v.
+ *   kind 2, LABELS: src = the element offset in labels of an int32 (h, w) map, pitch w; selected where id is in [0, rows) -- with flag 1
+ *     (EDGES) only where a 4-neighbour inside the image holds another raw id; row first + id.  Other ids are void.
+ * status int32 [1], zeroed by the call, then ORed on the device -- nothing here faults:
+ *   1: an image was refused whole and none of its bytes written: h or w outside [1, 16384]; an offset of its slice off a multiple of
+ *      4, running backwards, leaving img_bytes or not its 3 h w bytes and their pad; a layer range running backwards or leaving [0, L];
+ *   2: a layer was skipped as if absent: an unknown kind or flag, a flag on the wrong kind, a NULL source buffer, src negative, off a
+ *      multiple of 4 (BITS) or with a slice that does not fit its buffer, first or rows leaving [0, T], rows != 1 (BITS) / 256 (LEVELS);
+ *   4: a pixel selected a table row whose alpha is NaN or outside [0, 1]: the row paints nothing.
+ * An init launch plus one launch (one more per 65535 images): each lane owns 16 consecutive pixels of the flat image -- 48 bytes --,
+ * loads them once, keeps them in registers across the image's layers and stores them once.  L == 0 is a copy.  No workspace, no
+ * allocation, no synchronisation, 64-bit offsets, the same bytes whatever the schedule.
+ * CVLM_E_BADARG, before anything touches the device: a NULL img, img_offsets, dims, layer_offsets, rgb, alpha, out or status, or a NULL
+ * layers with L > 0 (bits, levels and labels may be NULL); img, out, dims, layer_offsets, bits, labels, alpha or status not 4-byte,
+ * img_offsets or layers not 8-byte aligned; B outside [1, 2^16], L outside [0, 2^20], T outside [1, 2^24]; img_bytes < 4, a negative
+ * bits_bytes, levels_bytes or labels_n; max_pixels outside [1, 2^28]; out[0, img_bytes) sharing a byte with an input other than exactly
+ * img, or status with anything. */
+int cvlm_render(const uint8_t* img, int64_t img_bytes, const int64_t* img_offsets, const int32_t* dims, int32_t B, int64_t max_pixels,
+                const int32_t* layer_offsets, const int64_t* layers, int32_t L, const uint8_t* bits, int64_t bits_bytes,
+                const uint8_t* levels, int64_t levels_bytes, const int32_t* labels, int64_t labels_n, const uint8_t* rgb, const float* alpha,
+                int32_t T, uint8_t* out, int32_t* status, void* stream);
+/* Outside the ABI contract: the entry on HOST memory, no stream -- the same per-pixel functions (csrc/render_logic.h) run sequentially
+ * on the CPU.  Same bytes, same refusals. */
+int cvlm_debug_render_host(const uint8_t* img, int64_t img_bytes, const int64_t* img_offsets, const int32_t* dims, int32_t B,
+                           int64_t max_pixels, const int32_t* layer_offsets, const int64_t* layers, int32_t L, const uint8_t* bits,
+                           int64_t bits_bytes, const uint8_t* levels, int64_t levels_bytes, const int32_t* labels, int64_t labels_n,
+                           const uint8_t* rgb, const float* alpha, int32_t T, uint8_t* out, int32_t* status);
+
 /* Weighted F-measure ingredients (pysodmetrics 1.4.2 WeightedFmeasure.cal_wfm behind recorder/ovcos_metricer.py:49-66):
  * exact Euclidean distance transform with nearest-foreground index (scipy's tie order), E carried over from the nearest
  * foreground pixel, 7x7 Gaussian (gauss49: the 49 f64 weights, device memory), pixel importance, all in f64.
