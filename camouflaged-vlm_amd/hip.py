@@ -233,6 +233,19 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _pn(t: Optional[torch.Tensor]) -> Optional[int]:
+    """`_p`, and NULL for an empty tensor too: the entries refuse a pointer that comes with a count of 0."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _workspace_bytes(symbol: str, *sizes) -> int:
+    """The bytes of workspace the host arithmetic `symbol` of an entry gives for these sizes."""
+    n = int(getattr(load(), symbol)(*(int(v) for v in sizes)))
+    if n < 0:
+        raise RuntimeError(f"{symbol}{tuple(int(v) for v in sizes)}: sizes outside the entry's bounds (code {n})")
+    return n
+
+
 def _planes(x: Optional["H2"]) -> Tuple[Optional[int], Optional[int]]:
     return (None, None) if x is None else (x.hi.data_ptr(), x.lo.data_ptr())
 
@@ -728,10 +741,7 @@ def clip_head(img, txt, logit_scale_exp: float, B: int, Cc: int, D: int, img_n, 
 
 
 def clip_head_wide_workspace_bytes(P: int, Cc: int) -> int:
-    n = load().cvlm_clip_head_wide_workspace_bytes(P, Cc)
-    if n < 0:
-        raise RuntimeError(f"cvlm_clip_head_wide_workspace_bytes: P = {P}, C = {Cc} outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_clip_head_wide_workspace_bytes", P, Cc)
 
 
 def clip_head_wide(img, txt, logit_scale_exp: float, P: int, Cc: int, D: int, img_n, logits, pred, txt_sel, workspace: torch.Tensor) -> None:
@@ -788,16 +798,56 @@ def mask_joint_hist(pre: torch.Tensor, gt: torch.Tensor, stats: torch.Tensor, hi
     _call("cvlm_mask_joint_hist", pre.data_ptr(), gt.data_ptr(), N, h, w, stats.data_ptr(), hist.data_ptr())
 
 
+# ---- packed masks and what is computed from them: every launcher below checks its tensors through `_check_tensors` and names its entry
+# ---- through `_entry`; a device entry and its sequential host twin (include/cvlm.h: cvlm_debug_*_host) share one body `_x(host, ...)` under the two
+# ---- public names, or one function with `host: bool` ----------------------------------------------------------------------------------------------------
+_U8, _I16, _I32, _I64, _F32, _F64 = torch.uint8, torch.int16, torch.int32, torch.int64, torch.float32, torch.float64
+
+
+def _check_tensors(like: torch.Tensor, *rows, optional=(), together=()) -> None:
+    """The one argument check of the packed-mask launchers.  rows: (argument name, tensor, dtype, shape); every tensor must have that
+    dtype and exactly that shape (a None element: any length; shape None: the caller checks it), be contiguous and live on `like`'s
+    device.  None is allowed for the names in `optional` and for the members of the groups in `together`, each of which is given whole
+    or not at all.  Raises AssertionError naming the argument, what was required and what came."""
+    device, missing = like.device, []
+    for name, t, dtype, shape in rows:
+        if t is None:
+            missing.append(name)
+            continue
+        got = t.shape
+        assert (t.dtype == dtype and t.is_contiguous() and t.device == device and
+                (got == shape or shape is None or (len(got) == len(shape) and all(w is None or w == g for w, g in zip(shape, got))))), \
+            f"{name}: {dtype} {shape} contiguous on {device} required, got {t.dtype} {tuple(got)} strides {t.stride()} on {t.device}"
+    for group in together:
+        assert sum(name in missing for name in group) in (0, len(group)), f"{', '.join(group)}: given together or not at all"
+    for name in missing:
+        assert name in optional or any(name in group for group in together), f"{name}: required, got None"
+
+
+def _entry(symbol: str, host: bool, like: torch.Tensor) -> str:
+    """The entry a launcher calls, after the check of where its tensors live: the device entry `symbol` on the current device, or with
+    host=True its twin cvlm_debug_<...>_host, which runs the kernels' per-thread functions sequentially on HOST tensors without a device."""
+    if host:
+        assert not like.is_cuda, f"{symbol}: the host form runs on host tensors, got one on {like.device}"
+        return "cvlm_debug_" + symbol[5:] + "_host"
+    _on_current_device(like)
+    return symbol
+
+
+def _sized_planes(bits, offsets, dims, prefix: str = "") -> int:
+    """The check of a set of sized planes -- flat uint8 bits, byte offsets int64 [P + 1], dims int32 [P][2] = (h, w) -> P."""
+    P = int(dims.shape[0])
+    _check_tensors(bits, (prefix + "bits", bits, _U8, (None,)), (prefix + "offsets", offsets, _I64, (P + 1,)), (prefix + "dims", dims, _I32, (P, 2)))
+    return P
+
+
 def mask_pack(logits: torch.Tensor, bits: torch.Tensor, area: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None) -> None:
     """logits f32 [P][H][W] -> bits uint8 [P][H * W / 8] in numpy.packbits' order (bit set iff logit > 0), area int32 [P], box int32
     [P][4] = inclusive (x0, y0, x1, y1), -1 for an empty plane; area and box together or not at all (include/cvlm.h)."""
     P, H, W = logits.shape
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and (H * W) % 32 == 0
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous()
-    assert (area is None) == (box is None)
-    if area is not None:
-        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
+    assert (H * W) % 32 == 0
+    _check_tensors(logits, ("logits", logits, _F32, (P, H, W)), ("bits", bits, _U8, (P, H * W // 8)), ("area", area, _I32, (P,)),
+                   ("box", box, _I32, (P, 4)), together=(("area", "box"),))
     _on_current_device(logits)
     _call("cvlm_mask_pack", logits.data_ptr(), P, H * W, W, bits.data_ptr(), _p(area), _p(box))
 
@@ -806,36 +856,29 @@ def mask_overlap(bits: torch.Tensor, inter: torch.Tensor) -> None:
     """bits uint8 [n][K][bytes] (mask_pack's planes, bytes % 4 == 0) -> inter int32 [n][K][K] = popcount(plane a AND plane b) per
     image, the full symmetric matrix (overwritten; include/cvlm.h)."""
     n, K, nbytes = bits.shape
-    assert bits.dtype == torch.uint8 and bits.is_contiguous() and nbytes % 4 == 0 and bits.data_ptr() % 4 == 0
-    assert inter.dtype == torch.int32 and tuple(inter.shape) == (n, K, K) and inter.is_contiguous()
+    assert nbytes % 4 == 0 and bits.data_ptr() % 4 == 0
+    _check_tensors(bits, ("bits", bits, _U8, (n, K, nbytes)), ("inter", inter, _I32, (n, K, K)))
     _on_current_device(bits)
     _call("cvlm_mask_overlap", bits.data_ptr(), n, K, nbytes // 4, inter.data_ptr())
 
 
 def mask_components_workspace_bytes(P: int, H: int, W: int) -> int:
     """Bytes cvlm_mask_components wants to keep all P planes of H x W in flight (14 per pixel and plane); P = 1: the minimum it takes."""
-    n = load().cvlm_mask_components_workspace_bytes(P, H, W)
-    if n < 0:
-        raise RuntimeError(f"cvlm_mask_components_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_mask_components_workspace_bytes", P, H, W)
 
 
-def _components_args(bits: torch.Tensor, H: int, W: int, n_comp, comps, n_kept, kept_bits, kept_area, kept_box):
-    """Shape and dtype checks shared by `mask_components` and `mask_components_host` -> (P, M)."""
-    P = int(bits.shape[0])
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
-    assert n_comp.dtype == torch.int32 and tuple(n_comp.shape) == (P,) and n_comp.is_contiguous()
-    M = 0
-    if comps is not None:
-        M = int(comps.shape[1])
-        assert comps.dtype == torch.int32 and tuple(comps.shape) == (P, M, 6) and comps.is_contiguous()
-    assert len({t is None for t in (n_kept, kept_bits, kept_area, kept_box)}) == 1
-    if n_kept is not None:
-        assert n_kept.dtype == torch.int32 and tuple(n_kept.shape) == (P,) and n_kept.is_contiguous()
-        assert kept_bits.dtype == torch.uint8 and tuple(kept_bits.shape) == (P, H * W // 8) and kept_bits.is_contiguous()
-        assert kept_area.dtype == torch.int32 and tuple(kept_area.shape) == (P,) and kept_area.is_contiguous()
-        assert kept_box.dtype == torch.int32 and tuple(kept_box.shape) == (P, 4) and kept_box.is_contiguous()
-    return P, M
+def _mask_components(host: bool, bits, H, W, connectivity, min_area, workspace, n_comp, comps=None, n_kept=None, kept_bits=None,
+                     kept_area=None, kept_box=None) -> None:
+    """The body of `mask_components` and of its host twin."""
+    P, M = int(bits.shape[0]), 0 if comps is None else int(comps.shape[1])
+    assert W % 32 == 0
+    _check_tensors(bits, ("bits", bits, _U8, (P, H * W // 8)), ("workspace", workspace, _U8, (None,)), ("n_comp", n_comp, _I32, (P,)),
+                   ("comps", comps, _I32, (P, M, 6)), ("n_kept", n_kept, _I32, (P,)), ("kept_bits", kept_bits, _U8, (P, H * W // 8)),
+                   ("kept_area", kept_area, _I32, (P,)), ("kept_box", kept_box, _I32, (P, 4)),
+                   optional=("comps", "workspace") if host else ("comps",), together=(("n_kept", "kept_bits", "kept_area", "kept_box"),))
+    _call(_entry("cvlm_mask_components", host, bits), bits.data_ptr(), P, H, W, connectivity, M, min_area,
+          *(() if host else (workspace.data_ptr(), workspace.numel())), n_comp.data_ptr(), _p(comps), _p(n_kept), _p(kept_bits), _p(kept_area),
+          _p(kept_box))
 
 
 def mask_components(bits: torch.Tensor, H: int, W: int, connectivity: int, min_area: int, workspace: torch.Tensor, n_comp: torch.Tensor,
@@ -845,11 +888,7 @@ def mask_components(bits: torch.Tensor, H: int, W: int, connectivity: int, min_a
     largest regions (M = comps.shape[1]; None: no table) and, with min_area >= 1, n_kept [P], kept_bits like bits, kept_area [P],
     kept_box [P][4] (all four or none).  workspace: uint8, at least mask_components_workspace_bytes(1, H, W) bytes; fewer than P planes'
     worth makes the entry walk the planes in rounds (include/cvlm.h)."""
-    P, M = _components_args(bits, H, W, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
-    _on_current_device(bits)
-    _call("cvlm_mask_components", bits.data_ptr(), P, H, W, connectivity, M, min_area, workspace.data_ptr(), workspace.numel(),
-          n_comp.data_ptr(), _p(comps), _p(n_kept), _p(kept_bits), _p(kept_area), _p(kept_box))
+    _mask_components(False, bits, H, W, connectivity, min_area, workspace, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
 
 
 def mask_components_host(bits: torch.Tensor, H: int, W: int, connectivity: int, min_area: int, n_comp: torch.Tensor,
@@ -857,35 +896,26 @@ def mask_components_host(bits: torch.Tensor, H: int, W: int, connectivity: int, 
                          kept_area: Optional[torch.Tensor] = None, kept_box: Optional[torch.Tensor] = None) -> None:
     """`mask_components` on HOST tensors without a device (cvlm_debug_mask_components_host: the kernels' per-thread functions run
     sequentially on the CPU)."""
-    P, M = _components_args(bits, H, W, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_components_host", bits.data_ptr(), P, H, W, connectivity, M, min_area, n_comp.data_ptr(), _p(comps), _p(n_kept),
-          _p(kept_bits), _p(kept_area), _p(kept_box))
+    _mask_components(True, bits, H, W, connectivity, min_area, None, n_comp, comps, n_kept, kept_bits, kept_area, kept_box)
 
 
 def mask_holes_workspace_bytes(P: int, H: int, W: int) -> int:
     """Bytes cvlm_mask_holes wants to keep all P planes of H x W in flight (14 per pixel and plane); P = 1: the minimum it takes."""
-    n = load().cvlm_mask_holes_workspace_bytes(P, H, W)
-    if n < 0:
-        raise RuntimeError(f"cvlm_mask_holes_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_mask_holes_workspace_bytes", P, H, W)
 
 
-def _holes_args(bits: torch.Tensor, H: int, W: int, n_holes, holes, n_filled, filled_bits, filled_area):
-    """Shape and dtype checks shared by `mask_holes` and `mask_holes_host` -> (P, M)."""
-    P = int(bits.shape[0])
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
-    assert n_holes.dtype == torch.int32 and tuple(n_holes.shape) == (P,) and n_holes.is_contiguous()
-    M = 0
-    if holes is not None:
-        M = int(holes.shape[1])
-        assert holes.dtype == torch.int32 and tuple(holes.shape) == (P, M, 6) and holes.is_contiguous()
-    assert len({t is None for t in (n_filled, filled_bits, filled_area)}) == 1
-    if n_filled is not None:
-        assert n_filled.dtype == torch.int32 and tuple(n_filled.shape) == (P,) and n_filled.is_contiguous()
-        assert filled_bits.dtype == torch.uint8 and tuple(filled_bits.shape) == (P, H * W // 8) and filled_bits.is_contiguous()
-        assert filled_area.dtype == torch.int32 and tuple(filled_area.shape) == (P,) and filled_area.is_contiguous()
-    return P, M
+def _mask_holes(host: bool, bits, H, W, connectivity, fill_below, workspace, n_holes, holes=None, n_filled=None, filled_bits=None,
+                filled_area=None) -> None:
+    """The body of `mask_holes` and of its host twin."""
+    P, M = int(bits.shape[0]), 0 if holes is None else int(holes.shape[1])
+    assert W % 32 == 0
+    _check_tensors(bits, ("bits", bits, _U8, (P, H * W // 8)), ("workspace", workspace, _U8, (None,)), ("n_holes", n_holes, _I32, (P,)),
+                   ("holes", holes, _I32, (P, M, 6)), ("n_filled", n_filled, _I32, (P,)), ("filled_bits", filled_bits, _U8, (P, H * W // 8)),
+                   ("filled_area", filled_area, _I32, (P,)),
+                   optional=("holes", "workspace") if host else ("holes",), together=(("n_filled", "filled_bits", "filled_area"),))
+    _call(_entry("cvlm_mask_holes", host, bits), bits.data_ptr(), P, H, W, connectivity, M, fill_below,
+          *(() if host else (workspace.data_ptr(), workspace.numel())), n_holes.data_ptr(), _p(holes), _p(n_filled), _p(filled_bits),
+          _p(filled_area))
 
 
 def mask_holes(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below: int, workspace: torch.Tensor, n_holes: torch.Tensor,
@@ -895,11 +925,7 @@ def mask_holes(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below
     largest holes (M = holes.shape[1]; None: no table) and, with fill_below >= 1, n_filled [P], filled_bits like bits, filled_area [P]
     (all three or none).  connectivity is the FOREGROUND's; the clear pixels connect at its dual.  workspace: uint8, at least
     mask_holes_workspace_bytes(1, H, W) bytes; fewer than P planes' worth makes the entry walk the planes in rounds (include/cvlm.h)."""
-    P, M = _holes_args(bits, H, W, n_holes, holes, n_filled, filled_bits, filled_area)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
-    _on_current_device(bits)
-    _call("cvlm_mask_holes", bits.data_ptr(), P, H, W, connectivity, M, fill_below, workspace.data_ptr(), workspace.numel(),
-          n_holes.data_ptr(), _p(holes), _p(n_filled), _p(filled_bits), _p(filled_area))
+    _mask_holes(False, bits, H, W, connectivity, fill_below, workspace, n_holes, holes, n_filled, filled_bits, filled_area)
 
 
 def mask_holes_host(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below: int, n_holes: torch.Tensor,
@@ -907,23 +933,18 @@ def mask_holes_host(bits: torch.Tensor, H: int, W: int, connectivity: int, fill_
                     filled_area: Optional[torch.Tensor] = None) -> None:
     """`mask_holes` on HOST tensors without a device (cvlm_debug_mask_holes_host: the kernels' per-thread functions run sequentially on
     the CPU)."""
-    P, M = _holes_args(bits, H, W, n_holes, holes, n_filled, filled_bits, filled_area)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_holes_host", bits.data_ptr(), P, H, W, connectivity, M, fill_below, n_holes.data_ptr(), _p(holes), _p(n_filled),
-          _p(filled_bits), _p(filled_area))
+    _mask_holes(True, bits, H, W, connectivity, fill_below, None, n_holes, holes, n_filled, filled_bits, filled_area)
 
 
-def _morph_args(bits: torch.Tensor, H: int, W: int, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area) -> int:
-    """Shape and dtype checks shared by `mask_morph` and `mask_morph_host` -> P."""
-    P = int(bits.shape[0])
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
-    for plane, area in ((dil_bits, dil_area), (ero_bits, ero_area), (band_bits, band_area)):
-        assert (plane is None) == (area is None)
-        if plane is not None:
-            assert plane.dtype == torch.uint8 and tuple(plane.shape) == (P, H * W // 8) and plane.is_contiguous()
-            assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-            assert plane.device == bits.device and area.device == bits.device
-    return P
+def _mask_morph(host: bool, bits, H, W, radius, dil_bits=None, dil_area=None, ero_bits=None, ero_area=None, band_bits=None, band_area=None) -> None:
+    """The body of `mask_morph` and of its host twin."""
+    P, plane = int(bits.shape[0]), (int(bits.shape[0]), H * W // 8)
+    assert W % 32 == 0
+    _check_tensors(bits, ("bits", bits, _U8, plane), ("dil_bits", dil_bits, _U8, plane), ("dil_area", dil_area, _I32, (P,)),
+                   ("ero_bits", ero_bits, _U8, plane), ("ero_area", ero_area, _I32, (P,)), ("band_bits", band_bits, _U8, plane),
+                   ("band_area", band_area, _I32, (P,)), together=(("dil_bits", "dil_area"), ("ero_bits", "ero_area"), ("band_bits", "band_area")))
+    _call(_entry("cvlm_mask_morph", host, bits), bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area),
+          _p(band_bits), _p(band_area))
 
 
 def mask_morph(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: Optional[torch.Tensor] = None,
@@ -932,36 +953,25 @@ def mask_morph(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: Option
     """bits uint8 [P][H * W / 8] (mask_pack's planes) -> dilation, erosion and band = dil & ~ero by the (2 * radius + 1)^2 square, each
     a pair (planes like bits, popcount int32 [P]); a pair is given whole or not at all, at least one is asked for, and no output may
     overlap the input or another output.  Pixels outside the plane are clear to dilation and set to erosion (include/cvlm.h)."""
-    P = _morph_args(bits, H, W, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area)
-    _on_current_device(bits)
-    _call("cvlm_mask_morph", bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area), _p(band_bits),
-          _p(band_area))
+    _mask_morph(False, bits, H, W, radius, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area)
 
 
-def mask_morph_host(bits: torch.Tensor, H: int, W: int, radius: int, dil_bits: Optional[torch.Tensor] = None,
-                    dil_area: Optional[torch.Tensor] = None, ero_bits: Optional[torch.Tensor] = None, ero_area: Optional[torch.Tensor] = None,
-                    band_bits: Optional[torch.Tensor] = None, band_area: Optional[torch.Tensor] = None) -> None:
+@functools.wraps(mask_morph, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_morph_host(*args, **kw) -> None:
     """`mask_morph` on HOST tensors without a device (cvlm_debug_mask_morph_host: the kernel's per-thread functions run sequentially on
     the CPU)."""
-    P = _morph_args(bits, H, W, dil_bits, dil_area, ero_bits, ero_area, band_bits, band_area)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_morph_host", bits.data_ptr(), P, H, W, radius, _p(dil_bits), _p(dil_area), _p(ero_bits), _p(ero_area),
-          _p(band_bits), _p(band_area))
+    _mask_morph(True, *args, **kw)
 
 
-def _edge_args(prob: torch.Tensor, hout: int, wout: int, bits, area, with_bits, with_inter) -> Tuple[int, int, int]:
-    """Shape and dtype checks shared by `edge_pack` and `edge_pack_host` -> (P, hin, win)."""
+def _edge_pack(host: bool, prob, hout, wout, threshold, bits, area, with_bits=None, with_inter=None) -> None:
+    """The body of `edge_pack` and of its host twin."""
     P, hin, win = (int(v) for v in prob.shape)
-    nbytes = hout * wout // 8
-    assert prob.dtype == torch.float32 and prob.is_contiguous() and wout % 32 == 0
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, nbytes) and bits.is_contiguous()
-    assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-    assert (with_bits is None) == (with_inter is None)
-    if with_bits is not None:
-        assert with_bits.dtype == torch.uint8 and tuple(with_bits.shape) == (P, nbytes) and with_bits.is_contiguous()
-        assert with_inter.dtype == torch.int32 and tuple(with_inter.shape) == (P,) and with_inter.is_contiguous()
-    assert all(t is None or t.device == prob.device for t in (bits, area, with_bits, with_inter))
-    return P, hin, win
+    assert wout % 32 == 0
+    _check_tensors(prob, ("prob", prob, _F32, (P, hin, win)), ("bits", bits, _U8, (P, hout * wout // 8)), ("area", area, _I32, (P,)),
+                   ("with_bits", with_bits, _U8, (P, hout * wout // 8)), ("with_inter", with_inter, _I32, (P,)),
+                   together=(("with_bits", "with_inter"),))
+    _call(_entry("cvlm_edge_pack", host, prob), prob.data_ptr(), P, hin, win, hout, wout, threshold, bits.data_ptr(), area.data_ptr(),
+          _p(with_bits), _p(with_inter))
 
 
 def edge_pack(prob: torch.Tensor, hout: int, wout: int, threshold: float, bits: torch.Tensor, area: torch.Tensor,
@@ -970,20 +980,14 @@ def edge_pack(prob: torch.Tensor, hout: int, wout: int, threshold: float, bits: 
     value at that output pixel -- float32, one rounding per operation -- is > threshold (0 < threshold < 1; NaN clear, +inf set), area
     int32 [P] = set bits; with_bits (planes like bits) and with_inter int32 [P] = popcount(bits & with_bits) together or not at all.
     No output may overlap an input or another output (include/cvlm.h)."""
-    P, hin, win = _edge_args(prob, hout, wout, bits, area, with_bits, with_inter)
-    _on_current_device(prob)
-    _call("cvlm_edge_pack", prob.data_ptr(), P, hin, win, hout, wout, threshold, bits.data_ptr(), area.data_ptr(), _p(with_bits),
-          _p(with_inter))
+    _edge_pack(False, prob, hout, wout, threshold, bits, area, with_bits, with_inter)
 
 
-def edge_pack_host(prob: torch.Tensor, hout: int, wout: int, threshold: float, bits: torch.Tensor, area: torch.Tensor,
-                   with_bits: Optional[torch.Tensor] = None, with_inter: Optional[torch.Tensor] = None) -> None:
+@functools.wraps(edge_pack, assigned=())        # help() and inspect.signature show the parameter list above
+def edge_pack_host(*args, **kw) -> None:
     """`edge_pack` on HOST tensors without a device (cvlm_debug_edge_pack_host: the kernel's per-pixel functions run sequentially on
     the CPU)."""
-    P, hin, win = _edge_args(prob, hout, wout, bits, area, with_bits, with_inter)
-    assert not prob.is_cuda
-    _call("cvlm_debug_edge_pack_host", prob.data_ptr(), P, hin, win, hout, wout, threshold, bits.data_ptr(), area.data_ptr(), _p(with_bits),
-          _p(with_inter))
+    _edge_pack(True, *args, **kw)
 
 
 def edge_pack_staged(hin: int, win: int, hout: int, wout: int) -> bool:
@@ -997,32 +1001,38 @@ def edge_pack_staged(hin: int, win: int, hout: int, wout: int) -> bool:
 
 def mask_rle_workspace_bytes(P: int, H: int, W: int) -> int:
     """Bytes cvlm_mask_rle_emit wants to keep all P planes of H x W in flight (12 per 32 pixels and plane); P = 1: the minimum it takes."""
-    n = load().cvlm_mask_rle_workspace_bytes(P, H, W)
-    if n < 0:
-        raise RuntimeError(f"cvlm_mask_rle_workspace_bytes({P}, {H}, {W}): sizes outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_mask_rle_workspace_bytes", P, H, W)
 
 
-def _rle_args(bits: torch.Tensor, H: int, W: int, n_runs, offsets, counts, status) -> int:
-    """Shape and dtype checks shared by `mask_rle_count`, `mask_rle_emit` and `mask_rle_host` -> P."""
+def _rle(kind: str, bits, H: int, W: int, Wt: Optional[int], n_runs, offsets, counts, status, workspace) -> None:
+    """The body of the run-length launchers: `kind` "count" (n_runs), "emit" (offsets, counts, status, workspace) or "host" (the merged
+    host entry: n_runs and, all three or none, offsets, counts, status); Wt None: the planes' rows are full, otherwise the `_w` entry."""
     P = int(bits.shape[0])
-    assert bits.dtype == torch.uint8 and tuple(bits.shape) == (P, H * W // 8) and bits.is_contiguous() and W % 32 == 0
-    if n_runs is not None:
-        assert n_runs.dtype == torch.int32 and tuple(n_runs.shape) == (P,) and n_runs.is_contiguous() and n_runs.device == bits.device
-    if counts is not None:
-        assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
-        assert counts.dtype == torch.int32 and counts.dim() == 1 and counts.is_contiguous() and counts.numel() >= 1
-        assert status.dtype == torch.int32 and status.numel() == 1
-        assert all(t.device == bits.device for t in (offsets, counts, status))
-    return P
+    assert W % 32 == 0
+    assert Wt is None or W - 32 < Wt <= W, "the true width ends inside the last word of the row pitch"
+    _check_tensors(bits, ("bits", bits, _U8, (P, H * W // 8)), ("n_runs", n_runs, _I32, (P,)), ("offsets", offsets, _I64, (P + 1,)),
+                   ("counts", counts, _I32, (None,)), ("status", status, _I32, (1,)), ("workspace", workspace, _U8, (None,)),
+                   optional={"count": ("offsets", "counts", "status", "workspace"), "emit": ("n_runs",), "host": ("workspace",)}[kind],
+                   together=(("offsets", "counts", "status"),) if kind == "host" else ())
+    assert counts is None or counts.numel() >= 1
+    w, wt = ("", ()) if Wt is None else ("_w", (Wt,))
+    if kind == "host":
+        assert not bits.is_cuda
+        _call("cvlm_debug_mask_rle_host" + w, bits.data_ptr(), P, H, W, *wt, n_runs.data_ptr(), _p(offsets), _p(counts),
+              0 if counts is None else counts.numel(), _p(status))
+        return
+    _on_current_device(bits)
+    if kind == "count":
+        _call("cvlm_mask_rle_count" + w, bits.data_ptr(), P, H, W, *wt, n_runs.data_ptr())
+    else:
+        _call("cvlm_mask_rle_emit" + w, bits.data_ptr(), P, H, W, *wt, offsets.data_ptr(), counts.data_ptr(), counts.numel(), status.data_ptr(),
+              workspace.data_ptr(), workspace.numel())
 
 
 def mask_rle_count(bits: torch.Tensor, H: int, W: int, n_runs: torch.Tensor) -> None:
     """bits uint8 [P][H * W / 8] (mask_pack's planes) -> n_runs int32 [P]: the counts of each plane's COCO run-length encoding
     (column-major, starting with the run of 0s; include/cvlm.h).  Two launches, no workspace."""
-    P = _rle_args(bits, H, W, n_runs, None, None, None)
-    _on_current_device(bits)
-    _call("cvlm_mask_rle_count", bits.data_ptr(), P, H, W, n_runs.data_ptr())
+    _rle("count", bits, H, W, None, n_runs, None, None, None, None)
 
 
 def mask_rle_emit(bits: torch.Tensor, H: int, W: int, offsets: torch.Tensor, counts: torch.Tensor, status: torch.Tensor,
@@ -1031,72 +1041,44 @@ def mask_rle_emit(bits: torch.Tensor, H: int, W: int, offsets: torch.Tensor, cou
     [offsets[p], offsets[p + 1]) (offsets int64 [P + 1], on the device); a count that would leave its slice or counts is dropped and
     status int32 [1] becomes 1, otherwise 0.  workspace: uint8, at least mask_rle_workspace_bytes(1, H, W) bytes; fewer than P planes'
     worth makes the entry walk the planes in rounds (include/cvlm.h)."""
-    P = _rle_args(bits, H, W, None, offsets, counts, status)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
-    _on_current_device(bits)
-    _call("cvlm_mask_rle_emit", bits.data_ptr(), P, H, W, offsets.data_ptr(), counts.data_ptr(), counts.numel(), status.data_ptr(),
-          workspace.data_ptr(), workspace.numel())
+    _rle("emit", bits, H, W, None, None, offsets, counts, status, workspace)
 
 
 def mask_rle_host(bits: torch.Tensor, H: int, W: int, n_runs: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                   counts: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
     """`mask_rle_count` and, with counts, `mask_rle_emit` on HOST tensors without a device (cvlm_debug_mask_rle_host: the kernels'
     per-thread functions run sequentially on the CPU)."""
-    P = _rle_args(bits, H, W, n_runs, offsets, counts, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_rle_host", bits.data_ptr(), P, H, W, n_runs.data_ptr(), _p(offsets), _p(counts),
-          0 if counts is None else counts.numel(), _p(status))
-
-
-def _rle_w_args(bits: torch.Tensor, H: int, W: int, Wt: int) -> None:
-    assert W % 32 == 0 and W - 32 < Wt <= W, "the true width ends inside the last word of the row pitch"
+    _rle("host", bits, H, W, None, n_runs, offsets, counts, status, None)
 
 
 def mask_rle_count_w(bits: torch.Tensor, H: int, W: int, Wt: int, n_runs: torch.Tensor) -> None:
     """`mask_rle_count` of planes uint8 [P][H * W / 8] whose rows hold Wt <= W pixels, W - 32 < Wt (cvlm_mask_pack_sized's planes): the
     counts of the encoding of the H x Wt image (include/cvlm.h: cvlm_mask_rle_count_w)."""
-    _rle_w_args(bits, H, W, Wt)
-    P = _rle_args(bits, H, W, n_runs, None, None, None)
-    _on_current_device(bits)
-    _call("cvlm_mask_rle_count_w", bits.data_ptr(), P, H, W, Wt, n_runs.data_ptr())
+    _rle("count", bits, H, W, Wt, n_runs, None, None, None, None)
 
 
 def mask_rle_emit_w(bits: torch.Tensor, H: int, W: int, Wt: int, offsets: torch.Tensor, counts: torch.Tensor, status: torch.Tensor,
                     workspace: torch.Tensor) -> None:
     """`mask_rle_emit` of planes uint8 [P][H * W / 8] whose rows hold Wt <= W pixels (cvlm_mask_rle_emit_w); the workspace is
     mask_rle_workspace_bytes of the pitch W."""
-    _rle_w_args(bits, H, W, Wt)
-    P = _rle_args(bits, H, W, None, offsets, counts, status)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
-    _on_current_device(bits)
-    _call("cvlm_mask_rle_emit_w", bits.data_ptr(), P, H, W, Wt, offsets.data_ptr(), counts.data_ptr(), counts.numel(), status.data_ptr(),
-          workspace.data_ptr(), workspace.numel())
+    _rle("emit", bits, H, W, Wt, None, offsets, counts, status, workspace)
 
 
 def mask_rle_host_w(bits: torch.Tensor, H: int, W: int, Wt: int, n_runs: torch.Tensor, offsets: Optional[torch.Tensor] = None,
                     counts: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
     """`mask_rle_count_w` and, with counts, `mask_rle_emit_w` on HOST tensors without a device (cvlm_debug_mask_rle_host_w)."""
-    _rle_w_args(bits, H, W, Wt)
-    P = _rle_args(bits, H, W, n_runs, offsets, counts, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_rle_host_w", bits.data_ptr(), P, H, W, Wt, n_runs.data_ptr(), _p(offsets), _p(counts),
-          0 if counts is None else counts.numel(), _p(status))
+    _rle("host", bits, H, W, Wt, n_runs, offsets, counts, status, None)
 
 
-def _sized_args(logits, dims, offsets, level, bits, area, box, status) -> Tuple[int, int, int]:
-    """Shape and dtype checks shared by `mask_pack_sized` and `mask_pack_sized_host` -> (P, Hs, Ws)."""
+def _mask_pack_sized(host: bool, logits, dims, offsets, level, bits, max_words, area, box, status) -> None:
+    """The body of `mask_pack_sized` and of its host twin."""
     P, Hs, Ws = logits.shape
-    assert logits.dtype == torch.float32 and logits.is_contiguous()
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
-    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
-    assert isinstance(level, int) and (area is None) == (box is None)
-    if area is not None:
-        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == logits.device for t in (dims, offsets, bits, area, box, status))
-    return P, Hs, Ws
+    assert isinstance(level, int)
+    _check_tensors(logits, ("logits", logits, _F32, (P, Hs, Ws)), ("dims", dims, _I32, (P, 2)), ("offsets", offsets, _I64, (P + 1,)),
+                   ("bits", bits, _U8, (None,)), ("area", area, _I32, (P,)), ("box", box, _I32, (P, 4)), ("status", status, _I32, (1,)),
+                   together=(("area", "box"),))
+    _call(_entry("cvlm_mask_pack_sized", host, logits), logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level,
+          bits.data_ptr(), bits.numel(), int(max_words), _p(area), _p(box), status.data_ptr())
 
 
 def mask_pack_sized(logits: torch.Tensor, dims: torch.Tensor, offsets: torch.Tensor, level: int, bits: torch.Tensor, max_words: int,
@@ -1105,45 +1087,33 @@ def mask_pack_sized(logits: torch.Tensor, dims: torch.Tensor, offsets: torch.Ten
     ceil(w / 32) words in numpy.packbits' order from byte offsets[p] of the flat uint8 tensor `bits` on (offsets int64 [P + 1]); area
     int32 [P] and box int32 [P][4] together or not at all; status int32 [1] becomes 1 if a plane's slice did not fit its size or left
     `bits` -- that plane is skipped --, otherwise 0.  max_words: the largest h * ceil(w / 32) of the call (include/cvlm.h)."""
-    P, Hs, Ws = _sized_args(logits, dims, offsets, level, bits, area, box, status)
-    _on_current_device(logits)
-    _call("cvlm_mask_pack_sized", logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level, bits.data_ptr(), bits.numel(),
-          int(max_words), _p(area), _p(box), status.data_ptr())
+    _mask_pack_sized(False, logits, dims, offsets, level, bits, max_words, area, box, status)
 
 
-def mask_pack_sized_host(logits: torch.Tensor, dims: torch.Tensor, offsets: torch.Tensor, level: int, bits: torch.Tensor, max_words: int,
-                         area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor) -> None:
+@functools.wraps(mask_pack_sized, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_pack_sized_host(*args, **kw) -> None:
     """`mask_pack_sized` on HOST tensors without a device (cvlm_debug_mask_pack_sized_host: the kernel's per-pixel functions run
     sequentially on the CPU)."""
-    P, Hs, Ws = _sized_args(logits, dims, offsets, level, bits, area, box, status)
-    assert not logits.is_cuda
-    _call("cvlm_debug_mask_pack_sized_host", logits.data_ptr(), P, Hs, Ws, dims.data_ptr(), offsets.data_ptr(), level, bits.data_ptr(),
-          bits.numel(), int(max_words), _p(area), _p(box), status.data_ptr())
+    _mask_pack_sized(True, *args, **kw)
 
 
 def mask_rle_decode_workspace_bytes(P: int, max_pixels: int) -> int:
     """Bytes cvlm_mask_rle_decode wants to keep all P planes of at most max_pixels pixels in flight (16 + one bit per pixel and plane);
     P = 1: the minimum it takes."""
-    n = load().cvlm_mask_rle_decode_workspace_bytes(P, max_pixels)
-    if n < 0:
-        raise RuntimeError(f"cvlm_mask_rle_decode_workspace_bytes({P}, {max_pixels}): sizes outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_mask_rle_decode_workspace_bytes", P, max_pixels)
 
 
-def _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status) -> int:
-    """Shape and dtype checks shared by `mask_rle_decode` and `mask_rle_decode_host` -> P."""
+def _mask_rle_decode(host: bool, counts, run_offsets, dims, bit_offsets, max_pixels, bits, area, box, status, workspace=None) -> None:
+    """The body of `mask_rle_decode` and of its host twin."""
     P = int(dims.shape[0])
-    assert counts.dtype == torch.int32 and counts.dim() == 1 and counts.is_contiguous() and counts.numel() >= 1
-    assert run_offsets.dtype == torch.int64 and tuple(run_offsets.shape) == (P + 1,) and run_offsets.is_contiguous()
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (P + 1,) and bit_offsets.is_contiguous()
-    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous() and (area is None) == (box is None)
-    if area is not None:
-        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == counts.device for t in (run_offsets, dims, bit_offsets, bits, area, box, status))
-    return P
+    _check_tensors(counts, ("counts", counts, _I32, (None,)), ("run_offsets", run_offsets, _I64, (P + 1,)), ("dims", dims, _I32, (P, 2)),
+                   ("bit_offsets", bit_offsets, _I64, (P + 1,)), ("bits", bits, _U8, (None,)), ("area", area, _I32, (P,)),
+                   ("box", box, _I32, (P, 4)), ("status", status, _I32, (1,)), ("workspace", workspace, _U8, (None,)),
+                   optional=("workspace",) if host else (), together=(("area", "box"),))
+    assert counts.numel() >= 1
+    _call(_entry("cvlm_mask_rle_decode", host, counts), counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(),
+          bit_offsets.data_ptr(), P, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(),
+          *(() if host else (workspace.data_ptr(), workspace.numel())))
 
 
 def mask_rle_decode(counts: torch.Tensor, run_offsets: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor, max_pixels: int,
@@ -1156,47 +1126,33 @@ def mask_rle_decode(counts: torch.Tensor, run_offsets: torch.Tensor, dims: torch
     does not fit; such a plane is zero where its table holds and untouched where it does not --, otherwise 0.  max_pixels: the largest
     h * w of the call.  workspace: uint8, at least mask_rle_decode_workspace_bytes(1, max_pixels) bytes; fewer than P planes' worth makes
     the entry walk the planes in rounds."""
-    P = _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == counts.device
-    _on_current_device(counts)
-    _call("cvlm_mask_rle_decode", counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(), bit_offsets.data_ptr(), P,
-          int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(), workspace.data_ptr(), workspace.numel())
+    _mask_rle_decode(False, counts, run_offsets, dims, bit_offsets, max_pixels, bits, area, box, status, workspace)
 
 
 def mask_rle_decode_host(counts: torch.Tensor, run_offsets: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor, max_pixels: int,
                          bits: torch.Tensor, area: Optional[torch.Tensor], box: Optional[torch.Tensor], status: torch.Tensor) -> None:
     """`mask_rle_decode` on HOST tensors without a device (cvlm_debug_mask_rle_decode_host: the kernels' per-thread functions run
     sequentially on the CPU)."""
-    P = _rle_decode_args(counts, run_offsets, dims, bit_offsets, bits, area, box, status)
-    assert not counts.is_cuda
-    _call("cvlm_debug_mask_rle_decode_host", counts.data_ptr(), counts.numel(), run_offsets.data_ptr(), dims.data_ptr(),
-          bit_offsets.data_ptr(), P, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr())
+    _mask_rle_decode(True, counts, run_offsets, dims, bit_offsets, max_pixels, bits, area, box, status)
 
 
 def mask_poly_decode_workspace_bytes(P: int, max_pixels: int) -> int:
     """Bytes cvlm_mask_poly_decode wants to keep all P planes of at most max_pixels pixels in flight (two streams of 16 bytes + one bit
     per pixel per plane); P = 1: the minimum it takes."""
-    n = load().cvlm_mask_poly_decode_workspace_bytes(P, max_pixels)
-    if n < 0:
-        raise RuntimeError(f"cvlm_mask_poly_decode_workspace_bytes({P}, {max_pixels}): sizes outside the entry's bounds")
-    return n
+    return _workspace_bytes("cvlm_mask_poly_decode_workspace_bytes", P, max_pixels)
 
 
-def _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status) -> Tuple[int, int]:
-    """Shape and dtype checks shared by `mask_poly_decode` and `mask_poly_decode_host` -> (P, Q)."""
+def _mask_poly_decode(host: bool, xy, poly_offsets, plane_polys, dims, bit_offsets, max_pixels, bits, area, box, status, workspace=None) -> None:
+    """The body of `mask_poly_decode` and of its host twin."""
     P, Q = int(dims.shape[0]), int(poly_offsets.shape[0]) - 1
-    assert xy.dtype == torch.float64 and xy.dim() == 1 and xy.is_contiguous() and xy.numel() >= 1
-    assert poly_offsets.dtype == torch.int64 and poly_offsets.dim() == 1 and Q >= 1 and poly_offsets.is_contiguous()
-    assert plane_polys.dtype == torch.int32 and tuple(plane_polys.shape) == (P + 1,) and plane_polys.is_contiguous()
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (P + 1,) and bit_offsets.is_contiguous()
-    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous() and (area is None) == (box is None)
-    if area is not None:
-        assert area.dtype == torch.int32 and tuple(area.shape) == (P,) and area.is_contiguous()
-        assert box.dtype == torch.int32 and tuple(box.shape) == (P, 4) and box.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == xy.device for t in (poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status))
-    return P, Q
+    _check_tensors(xy, ("xy", xy, _F64, (None,)), ("poly_offsets", poly_offsets, _I64, (Q + 1,)), ("plane_polys", plane_polys, _I32, (P + 1,)),
+                   ("dims", dims, _I32, (P, 2)), ("bit_offsets", bit_offsets, _I64, (P + 1,)), ("bits", bits, _U8, (None,)),
+                   ("area", area, _I32, (P,)), ("box", box, _I32, (P, 4)), ("status", status, _I32, (1,)), ("workspace", workspace, _U8, (None,)),
+                   optional=("workspace",) if host else (), together=(("area", "box"),))
+    assert xy.numel() >= 1 and Q >= 1
+    _call(_entry("cvlm_mask_poly_decode", host, xy), xy.data_ptr(), xy.numel(), poly_offsets.data_ptr(), plane_polys.data_ptr(), dims.data_ptr(),
+          bit_offsets.data_ptr(), P, Q, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(),
+          *(() if host else (workspace.data_ptr(), workspace.numel())))
 
 
 def mask_poly_decode(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_polys: torch.Tensor, dims: torch.Tensor, bit_offsets: torch.Tensor,
@@ -1210,12 +1166,7 @@ def mask_poly_decode(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_polys: 
     plane is zero where its table holds and untouched where it does not --, otherwise 0.  max_pixels: the largest h * w of the call.
     workspace: uint8, at least mask_poly_decode_workspace_bytes(1, max_pixels) bytes; fewer than P planes' worth makes the entry walk
     the planes in rounds."""
-    P, Q = _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == xy.device
-    _on_current_device(xy)
-    _call("cvlm_mask_poly_decode", xy.data_ptr(), xy.numel(), poly_offsets.data_ptr(), plane_polys.data_ptr(), dims.data_ptr(),
-          bit_offsets.data_ptr(), P, Q, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr(),
-          workspace.data_ptr(), workspace.numel())
+    _mask_poly_decode(False, xy, poly_offsets, plane_polys, dims, bit_offsets, max_pixels, bits, area, box, status, workspace)
 
 
 def mask_poly_decode_host(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_polys: torch.Tensor, dims: torch.Tensor,
@@ -1223,24 +1174,17 @@ def mask_poly_decode_host(xy: torch.Tensor, poly_offsets: torch.Tensor, plane_po
                           box: Optional[torch.Tensor], status: torch.Tensor) -> None:
     """`mask_poly_decode` on HOST tensors without a device (cvlm_debug_mask_poly_decode_host: the kernels' per-thread functions run
     sequentially on the CPU)."""
-    P, Q = _poly_decode_args(xy, poly_offsets, plane_polys, dims, bit_offsets, bits, area, box, status)
-    assert not xy.is_cuda
-    _call("cvlm_debug_mask_poly_decode_host", xy.data_ptr(), xy.numel(), poly_offsets.data_ptr(), plane_polys.data_ptr(), dims.data_ptr(),
-          bit_offsets.data_ptr(), P, Q, int(max_pixels), bits.data_ptr(), bits.numel(), _p(area), _p(box), status.data_ptr())
+    _mask_poly_decode(True, xy, poly_offsets, plane_polys, dims, bit_offsets, max_pixels, bits, area, box, status)
 
 
-def _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status) -> Tuple[int, int, int]:
-    """Shape and dtype checks shared by `mask_inter_sized` and `mask_inter_sized_host` -> (Pa, Pb, N)."""
-    Pa, Pb, N = int(a_dims.shape[0]), int(b_dims.shape[0]), int(pairs.shape[0])
-    for bits, offsets, dims, P in ((a_bits, a_offsets, a_dims, Pa), (b_bits, b_offsets, b_dims, Pb)):
-        assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
-        assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
-        assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert pairs.dtype == torch.int32 and tuple(pairs.shape) == (N, 2) and pairs.is_contiguous()
-    assert inter.dtype == torch.int32 and tuple(inter.shape) == (N,) and inter.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == a_bits.device for t in (a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status))
-    return Pa, Pb, N
+def _mask_inter_sized(host: bool, a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, max_words, inter, status) -> None:
+    """The body of `mask_inter_sized` and of its host twin."""
+    Pa, Pb, N = _sized_planes(a_bits, a_offsets, a_dims, "a_"), _sized_planes(b_bits, b_offsets, b_dims, "b_"), int(pairs.shape[0])
+    _check_tensors(a_bits, ("b_bits", b_bits, _U8, (None,)), ("pairs", pairs, _I32, (N, 2)), ("inter", inter, _I32, (N,)),
+                   ("status", status, _I32, (1,)))
+    _call(_entry("cvlm_mask_inter_sized", host, a_bits), a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa,
+          b_bits.data_ptr(), b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words),
+          inter.data_ptr(), status.data_ptr())
 
 
 def mask_inter_sized(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_bits: torch.Tensor, b_offsets: torch.Tensor,
@@ -1249,37 +1193,33 @@ def mask_inter_sized(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torc
     int32 [N][2] = (plane of A, plane of B) -> inter int32 [N] = |A[a] AND B[b]| over the columns below w (include/cvlm.h:
     cvlm_mask_inter_sized); a pair with an index out of range, a table that does not fit or two different sizes gives -1 and status
     int32 [1] = 1, otherwise 0.  max_words: the largest h * ceil(w / 32) of the call."""
-    Pa, Pb, N = _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status)
-    _on_current_device(a_bits)
-    _call("cvlm_mask_inter_sized", a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa, b_bits.data_ptr(),
-          b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words), inter.data_ptr(),
-          status.data_ptr())
+    _mask_inter_sized(False, a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, max_words, inter, status)
 
 
-def mask_inter_sized_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_bits: torch.Tensor,
-                          b_offsets: torch.Tensor, b_dims: torch.Tensor, pairs: torch.Tensor, max_words: int, inter: torch.Tensor,
-                          status: torch.Tensor) -> None:
+@functools.wraps(mask_inter_sized, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_inter_sized_host(*args, **kw) -> None:
     """`mask_inter_sized` on HOST tensors without a device (cvlm_debug_mask_inter_sized_host)."""
-    Pa, Pb, N = _inter_sized_args(a_bits, a_offsets, a_dims, b_bits, b_offsets, b_dims, pairs, inter, status)
-    assert not a_bits.is_cuda
-    _call("cvlm_debug_mask_inter_sized_host", a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa,
-          b_bits.data_ptr(), b_bits.numel(), b_offsets.data_ptr(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, int(max_words),
-          inter.data_ptr(), status.data_ptr())
+    _mask_inter_sized(True, *args, **kw)
 
 
-def _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd, iou_thrs, area_rngs,
-                     dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status) -> Tuple[int, int, int, int, int, int]:
-    """Shape and dtype checks shared by `coco_match` and `coco_match_host` -> (E, N, ND, NG, T, A)."""
+def _coco_match(host: bool, boundary, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
+                iou_thrs, area_rngs, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status) -> None:
+    """The body of `coco_match` (boundary None), of `coco_match_boundary` (boundary = (inter_b, det_area_b, gt_area_b)) and of their host twins."""
     E, N, ND, NG = int(det_offsets.numel()) - 1, int(inter.numel()), int(det_area.numel()), int(gt_area.numel())
     T, A = int(iou_thrs.numel()), int(area_rngs.shape[0])
-    i32, u8, f64 = torch.int32, torch.uint8, torch.float64
-    for t, dtype, shape in ((det_offsets, i32, (E + 1,)), (gt_offsets, i32, (E + 1,)), (pair_offsets, torch.int64, (E + 1,)), (inter, i32, (N,)),
-                            (det_area, i32, (ND,)), (score, torch.float32, (ND,)), (gt_area, i32, (NG,)), (gt_range_area, f64, (NG,)),
-                            (gt_crowd, u8, (NG,)), (iou_thrs, f64, (T,)), (area_rngs, f64, (A, 2)), (dt_order, i32, (ND,)),
-                            (dt_match, i32, (A, T, ND)), (dt_ignore, u8, (A, T, ND)), (gt_match, i32, (A, T, NG)), (gt_ignore, u8, (A, NG)),
-                            (status, i32, (1,))):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == det_offsets.device, (t.dtype, tuple(t.shape), shape)
-    return E, N, ND, NG, T, A
+    inter_b, det_area_b, gt_area_b = boundary or (None, None, None)
+    _check_tensors(det_offsets, ("det_offsets", det_offsets, _I32, (E + 1,)), ("gt_offsets", gt_offsets, _I32, (E + 1,)),
+                   ("pair_offsets", pair_offsets, _I64, (E + 1,)), ("inter", inter, _I32, (N,)), ("det_area", det_area, _I32, (ND,)),
+                   ("score", score, _F32, (ND,)), ("gt_area", gt_area, _I32, (NG,)), ("gt_range_area", gt_range_area, _F64, (NG,)),
+                   ("gt_crowd", gt_crowd, _U8, (NG,)), ("iou_thrs", iou_thrs, _F64, (T,)), ("area_rngs", area_rngs, _F64, (A, 2)),
+                   ("inter_b", inter_b, _I32, (N,)), ("det_area_b", det_area_b, _I32, (ND,)), ("gt_area_b", gt_area_b, _I32, (NG,)),
+                   ("dt_order", dt_order, _I32, (ND,)), ("dt_match", dt_match, _I32, (A, T, ND)), ("dt_ignore", dt_ignore, _U8, (A, T, ND)),
+                   ("gt_match", gt_match, _I32, (A, T, NG)), ("gt_ignore", gt_ignore, _U8, (A, NG)), ("status", status, _I32, (1,)),
+                   optional=() if boundary else ("inter_b", "det_area_b", "gt_area_b"))
+    _call(_entry("cvlm_coco_match_boundary" if boundary else "cvlm_coco_match", host, det_offsets), det_offsets.data_ptr(), gt_offsets.data_ptr(),
+          pair_offsets.data_ptr(), E, _pn(inter), N, _pn(det_area), _pn(score), ND, _pn(gt_area), _pn(gt_range_area), _pn(gt_crowd), NG,
+          iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det), *(_pn(t) for t in boundary or ()), _pn(dt_order), _pn(dt_match),
+          _pn(dt_ignore), _pn(gt_match), _pn(gt_ignore), status.data_ptr())
 
 
 def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor, det_area: torch.Tensor,
@@ -1290,42 +1230,50 @@ def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets
     int32 / int64 [E + 1], inter int32 [N] in D_e x G_e blocks, det_area int32 and score f32 [sum D], gt_area int32, gt_range_area f64 and
     gt_crowd uint8 [sum G], iou_thrs f64 [T], area_rngs f64 [A][2] -> dt_order int32 [sum D], dt_match int32 and dt_ignore uint8 [A][T][sum D]
     in rank order, gt_match int32 [A][T][sum G], gt_ignore uint8 [A][sum G], status int32 [1] = 1 if a group was refused."""
-    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
-                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
-    _on_current_device(det_offsets)
-    p = lambda t: t.data_ptr() if t.numel() else None
-    _call("cvlm_coco_match", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area), p(score), ND,
-          p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det), p(dt_order),
-          p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+    _coco_match(False, None, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd, iou_thrs,
+                area_rngs, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
 
 
-def coco_match_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
-                    det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor,
-                    iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, dt_order: torch.Tensor, dt_match: torch.Tensor,
-                    dt_ignore: torch.Tensor, gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+@functools.wraps(coco_match, assigned=())        # help() and inspect.signature show the parameter list above
+def coco_match_host(*args, **kw) -> None:
     """`coco_match` on HOST tensors without a device (cvlm_debug_coco_match_host: the same per-thread functions, run sequentially)."""
-    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
-                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
-    assert not det_offsets.is_cuda
-    p = lambda t: t.data_ptr() if t.numel() else None
-    _call("cvlm_debug_coco_match_host", det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area),
-          p(score), ND, p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det),
-          p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
+    _coco_match(True, None, *args, **kw)
+
+
+def _coco_match_boundary(host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
+                         iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore, gt_match, gt_ignore,
+                         status) -> None:
+    """The body of `coco_match_boundary` and of its host twin."""
+    _coco_match(host, (inter_b, det_area_b, gt_area_b), det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,
+                gt_crowd, iou_thrs, area_rngs, max_det, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
+
+
+def coco_match_boundary(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
+                        det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor,
+                        iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, inter_b: torch.Tensor, det_area_b: torch.Tensor,
+                        gt_area_b: torch.Tensor, dt_order: torch.Tensor, dt_match: torch.Tensor, dt_ignore: torch.Tensor,
+                        gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
+    """`coco_match` with the IoU of a pair replaced by min(mask IoU, boundary IoU) (include/cvlm.h: cvlm_coco_match_boundary; DESIGN.md
+    §25): inter_b int32 [N], det_area_b int32 [sum D] and gt_area_b int32 [sum G] are the boundaries' intersections and areas, in the
+    order of inter, det_area and gt_area."""
+    _coco_match_boundary(False, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd, iou_thrs,
+                         area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
+
+
+@functools.wraps(coco_match_boundary, assigned=())        # help() and inspect.signature show the parameter list above
+def coco_match_boundary_host(*args, **kw) -> None:
+    """`coco_match_boundary` on HOST tensors without a device (cvlm_debug_coco_match_boundary_host)."""
+    _coco_match_boundary(True, *args, **kw)
 
 
 # ---- Boundary IoU (DESIGN.md §25) ---------------------------------------------------------------------------------------------------------
-def _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status) -> int:
-    """Shape and dtype checks shared by `mask_boundary_sized` and `mask_boundary_sized_host` -> P."""
-    P = int(dims.shape[0])
-    for t in (bits, out_bits, workspace):
-        assert t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous() and t.numel() == bits.numel()
-    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert radius.dtype == torch.int32 and tuple(radius.shape) == (P,) and radius.is_contiguous()
-    assert out_area is None or (out_area.dtype == torch.int32 and tuple(out_area.shape) == (P,) and out_area.is_contiguous())
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == bits.device for t in (offsets, dims, radius, workspace, out_bits, out_area, status))
-    return P
+def _mask_boundary_sized(host: bool, bits, offsets, dims, radius, max_words, workspace, out_bits, out_area, status) -> None:
+    """The body of `mask_boundary_sized` and of its host twin."""
+    P, n = _sized_planes(bits, offsets, dims), bits.numel()
+    _check_tensors(bits, ("radius", radius, _I32, (P,)), ("workspace", workspace, _U8, (n,)), ("out_bits", out_bits, _U8, (n,)),
+                   ("out_area", out_area, _I32, (P,)), ("status", status, _I32, (1,)), optional=("out_area",))
+    _call(_entry("cvlm_mask_boundary_sized", host, bits), bits.data_ptr(), n, offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
+          int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
 
 
 def mask_boundary_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, radius: torch.Tensor, max_words: int,
@@ -1334,60 +1282,36 @@ def mask_boundary_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.T
     byte offsets int64 [P + 1], dims int32 [P][2], radius int32 [P] in 1 .. 16384 -> out_bits (the same layout, X & ~erode(X, radius) with
     the outside of the plane clear), out_area int32 [P] or None, status int32 [1] = 1 if a plane was refused.  workspace: uint8, as
     many bytes as bits.  max_words: the largest h * ceil(w / 32) of the call."""
-    P = _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status)
-    _on_current_device(bits)
-    _call("cvlm_mask_boundary_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
-          int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
+    _mask_boundary_sized(False, bits, offsets, dims, radius, max_words, workspace, out_bits, out_area, status)
 
 
-def mask_boundary_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, radius: torch.Tensor, max_words: int,
-                             workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor], status: torch.Tensor) -> None:
+@functools.wraps(mask_boundary_sized, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_boundary_sized_host(*args, **kw) -> None:
     """`mask_boundary_sized` on HOST tensors without a device (cvlm_debug_mask_boundary_sized_host: the kernels' per-thread functions
     run sequentially)."""
-    P = _boundary_sized_args(bits, offsets, dims, radius, workspace, out_bits, out_area, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_boundary_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), radius.data_ptr(), P,
-          int(max_words), workspace.data_ptr(), out_bits.data_ptr(), _p(out_area), status.data_ptr())
+    _mask_boundary_sized(True, *args, **kw)
 
 
 # ---- Contours: COCO polygons out (DESIGN.md §26) ------------------------------------------------------------------------------------------
-def _contour_planes(bits, offsets, dims) -> int:
-    """Shape and dtype checks of the planes of the contour entries -> P."""
-    P = int(dims.shape[0])
-    assert bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous()
-    assert offsets.dtype == torch.int64 and tuple(offsets.shape) == (P + 1,) and offsets.is_contiguous()
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (P, 2) and dims.is_contiguous()
-    assert offsets.device == bits.device and dims.device == bits.device
-    return P
-
-
-def _contour_outputs(P, dev, vertex_offsets, xy, ring_start, n_rings, status) -> int:
-    """Shape and dtype checks of the outputs of the contour emit -> total."""
-    total = int(xy.shape[0])
-    assert vertex_offsets.dtype == torch.int64 and tuple(vertex_offsets.shape) == (P + 1,) and vertex_offsets.is_contiguous()
-    assert xy.dtype == torch.int16 and tuple(xy.shape) == (total, 2) and xy.is_contiguous()
-    assert ring_start.dtype == torch.uint8 and tuple(ring_start.shape) == (total,) and ring_start.is_contiguous()
-    assert n_rings.dtype == torch.int32 and tuple(n_rings.shape) == (P, 2) and n_rings.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == dev for t in (vertex_offsets, xy, ring_start, n_rings, status))
+def _contour_outputs(P: int, like, vertex_offsets, xy, ring_start, n_rings, all_or_none: bool = False) -> int:
+    """The check of the outputs of the contour emit (all_or_none: the host entry, which only counts without them) -> total."""
+    total = 0 if xy is None else int(xy.shape[0])
+    _check_tensors(like, ("vertex_offsets", vertex_offsets, _I64, (P + 1,)), ("xy", xy, _I16, (total, 2)), ("ring_start", ring_start, _U8, (total,)),
+                   ("n_rings", n_rings, _I32, (P, 2)), together=(("vertex_offsets", "xy", "ring_start", "n_rings"),) if all_or_none else ())
     return total
 
 
 def mask_contour_workspace_bytes(P: int, round_vertices: int, max_words: int) -> int:
     """Bytes of workspace of one `mask_contour_emit` call on P planes that hold round_vertices vertices together (host arithmetic)."""
-    need = int(load().cvlm_mask_contour_workspace_bytes(int(P), int(round_vertices), int(max_words)))
-    if need < 0:
-        raise RuntimeError(f"cvlm_mask_contour_workspace_bytes failed with code {need}")
-    return need
+    return _workspace_bytes("cvlm_mask_contour_workspace_bytes", P, round_vertices, max_words)
 
 
 def mask_contour_count(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, connectivity: int, max_words: int,
                        n_vertices: torch.Tensor, status: torch.Tensor) -> None:
     """Vertices of the crack contour of each sized plane (include/cvlm.h: cvlm_mask_contour_count): bits flat uint8, byte
     offsets int64 [P + 1], dims int32 [P][2] -> n_vertices int32 [P], status int32 [1] = 1 if a plane was refused."""
-    P = _contour_planes(bits, offsets, dims)
-    assert n_vertices.dtype == torch.int32 and tuple(n_vertices.shape) == (P,) and n_vertices.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1 and n_vertices.device == bits.device and status.device == bits.device
+    P = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("n_vertices", n_vertices, _I32, (P,)), ("status", status, _I32, (1,)))
     _on_current_device(bits)
     _call("cvlm_mask_contour_count", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity), int(max_words),
           n_vertices.data_ptr(), status.data_ptr())
@@ -1399,33 +1323,26 @@ def mask_contour_emit(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Ten
     """The rings of each sized plane (include/cvlm.h: cvlm_mask_contour_emit).  offsets / dims / vertex_offsets / n_rings
     may be views of longer tables -- one round of planes of a larger call --; xy int16 [total][2] and ring_start uint8 [total] are whole
     and vertex_offsets absolute.  round_vertices: at least the vertices of these planes."""
-    P = _contour_planes(bits, offsets, dims)
-    total = _contour_outputs(P, bits.device, vertex_offsets, xy, ring_start, n_rings, status)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == bits.device
+    P = _sized_planes(bits, offsets, dims)
+    total = _contour_outputs(P, bits, vertex_offsets, xy, ring_start, n_rings)
+    _check_tensors(bits, ("status", status, _I32, (1,)), ("workspace", workspace, _U8, (None,)))
     _on_current_device(bits)
-    p = lambda t: t.data_ptr() if t.numel() else None
     _call("cvlm_mask_contour_emit", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity), int(max_words),
-          vertex_offsets.data_ptr(), int(round_vertices), p(xy), p(ring_start), n_rings.data_ptr(), total, status.data_ptr(),
+          vertex_offsets.data_ptr(), int(round_vertices), _pn(xy), _pn(ring_start), n_rings.data_ptr(), total, status.data_ptr(),
           workspace.data_ptr(), workspace.numel())
 
 
 def mask_contour_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, connectivity: int, n_vertices: torch.Tensor,
                       status: torch.Tensor, vertex_offsets: Optional[torch.Tensor] = None, xy: Optional[torch.Tensor] = None,
                       ring_start: Optional[torch.Tensor] = None, n_rings: Optional[torch.Tensor] = None) -> None:
-    """`mask_contour_count` (vertex_offsets None) or count and emit on HOST tensors without a device (cvlm_debug_mask_contour_host: the
-    kernels' maps and successors, the rings followed sequentially)."""
-    P = _contour_planes(bits, offsets, dims)
+    """`mask_contour_count` (vertex_offsets, xy, ring_start and n_rings None) or count and emit (all four) on HOST tensors without a device
+    (cvlm_debug_mask_contour_host: the kernels' maps and successors, the rings followed sequentially)."""
+    P = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("n_vertices", n_vertices, _I32, (P,)), ("status", status, _I32, (1,)))
+    total = _contour_outputs(P, bits, vertex_offsets, xy, ring_start, n_rings, all_or_none=True)
     assert not bits.is_cuda
-    assert n_vertices.dtype == torch.int32 and tuple(n_vertices.shape) == (P,) and n_vertices.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    if vertex_offsets is None:
-        _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
-              n_vertices.data_ptr(), None, None, None, None, 0, status.data_ptr())
-        return
-    total = _contour_outputs(P, bits.device, vertex_offsets, xy, ring_start, n_rings, status)
-    p = lambda t: t.data_ptr() if t.numel() else None
     _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
-          n_vertices.data_ptr(), vertex_offsets.data_ptr(), p(xy), p(ring_start), n_rings.data_ptr(), total, status.data_ptr())
+          n_vertices.data_ptr(), _p(vertex_offsets), _pn(xy), _pn(ring_start), _p(n_rings), total, status.data_ptr())
 
 
 # ---- Distance maps and surface totals (DESIGN.md §27) --------------------------------------------------------------------------------------
@@ -1434,30 +1351,22 @@ DT_FAR = 0x7fffffff               # D2 of a pixel with no set pixel within reach
 
 def mask_distance_workspace_bytes(P: int, max_pixels: int) -> int:
     """Bytes of workspace that hold `mask_distance_sized` on P planes of at most max_pixels pixels lying back to back (host arithmetic)."""
-    need = int(load().cvlm_mask_distance_workspace_bytes(int(P), int(max_pixels)))
-    if need < 0:
-        raise RuntimeError(f"cvlm_mask_distance_workspace_bytes failed with code {need}")
-    return need
+    return _workspace_bytes("cvlm_mask_distance_workspace_bytes", P, max_pixels)
 
 
 def mask_surface_workspace_bytes(N: int) -> int:
     """Bytes of workspace of one `mask_surface_totals` call on N pairs (host arithmetic)."""
-    need = int(load().cvlm_mask_surface_workspace_bytes(int(N)))
-    if need < 0:
-        raise RuntimeError(f"cvlm_mask_surface_workspace_bytes failed with code {need}")
-    return need
+    return _workspace_bytes("cvlm_mask_surface_workspace_bytes", N)
 
 
-def _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status) -> int:
-    """Shape and dtype checks shared by `mask_distance_sized` and `mask_distance_sized_host` -> P."""
-    P = _contour_planes(bits, offsets, dims)
-    assert reach.dtype == torch.int32 and tuple(reach.shape) == (P,) and reach.is_contiguous()
-    assert pix_offsets.dtype == torch.int64 and tuple(pix_offsets.shape) == (P + 1,) and pix_offsets.is_contiguous()
-    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
-    assert out_d2.dtype == torch.int32 and out_d2.dim() == 1 and out_d2.is_contiguous() and out_d2.numel() >= 1
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == bits.device for t in (reach, pix_offsets, workspace, out_d2, status))
-    return P
+def _mask_distance_sized(host: bool, bits, offsets, dims, reach, max_words, pix_offsets, workspace, out_d2, status) -> None:
+    """The body of `mask_distance_sized` and of its host twin."""
+    P = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("reach", reach, _I32, (P,)), ("pix_offsets", pix_offsets, _I64, (P + 1,)), ("workspace", workspace, _U8, (None,)),
+                   ("out_d2", out_d2, _I32, (None,)), ("status", status, _I32, (1,)))
+    assert out_d2.numel() >= 1
+    _call(_entry("cvlm_mask_distance_sized", host, bits), bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), reach.data_ptr(), P,
+          int(max_words), pix_offsets.data_ptr(), out_d2.numel(), workspace.data_ptr(), workspace.numel(), out_d2.data_ptr(), status.data_ptr())
 
 
 def mask_distance_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, reach: torch.Tensor, max_words: int,
@@ -1466,45 +1375,29 @@ def mask_distance_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.T
     offsets int64 [P + 1], dims int32 [P][2], reach int32 [P] in 0 .. 23170 (0: unlimited) -> out_d2 int32 [n_pix], plane p's h * w
     values at pix_offsets[p] (int64 [P + 1], in pixels), DT_FAR where no set pixel is within reach; status int32 [1] = 1 if a plane was
     refused.  workspace: uint8, 2 bytes per entry of out_d2 rounded up to 16.  max_words: the largest h * ceil(w / 32) of the call."""
-    P = _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status)
-    _on_current_device(bits)
-    _call("cvlm_mask_distance_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), reach.data_ptr(), P, int(max_words),
-          pix_offsets.data_ptr(), out_d2.numel(), workspace.data_ptr(), workspace.numel(), out_d2.data_ptr(), status.data_ptr())
+    _mask_distance_sized(False, bits, offsets, dims, reach, max_words, pix_offsets, workspace, out_d2, status)
 
 
-def mask_distance_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, reach: torch.Tensor, max_words: int,
-                             pix_offsets: torch.Tensor, workspace: torch.Tensor, out_d2: torch.Tensor, status: torch.Tensor) -> None:
+@functools.wraps(mask_distance_sized, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_distance_sized_host(*args, **kw) -> None:
     """`mask_distance_sized` on HOST tensors without a device (cvlm_debug_mask_distance_sized_host: the kernels' per-thread functions
     run sequentially)."""
-    P = _distance_args(bits, offsets, dims, reach, pix_offsets, workspace, out_d2, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_distance_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), reach.data_ptr(), P,
-          int(max_words), pix_offsets.data_ptr(), out_d2.numel(), workspace.data_ptr(), workspace.numel(), out_d2.data_ptr(), status.data_ptr())
+    _mask_distance_sized(True, *args, **kw)
 
 
-def _surface_totals(name: str, a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n, far, within,
-                    max_d2, sum_d2, sum_d, status) -> None:
-    Pa = _contour_planes(a_bits, a_offsets, a_dims)
-    Pb = int(b_dims.shape[0])
+def _mask_surface_totals(host: bool, a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n, far,
+                         within, max_d2, sum_d2, sum_d, status) -> None:
+    """The body of `mask_surface_totals` and of its host twin."""
+    Pa, Pb = _sized_planes(a_bits, a_offsets, a_dims, "a_"), int(b_dims.shape[0])
     N, T = int(pairs.shape[0]), int(radii.shape[-1])
-    dev = a_bits.device
-    assert b_d2.dtype == torch.int32 and b_d2.dim() == 1 and b_d2.is_contiguous()
-    assert b_pix_offsets.dtype == torch.int64 and tuple(b_pix_offsets.shape) == (Pb + 1,) and b_pix_offsets.is_contiguous()
-    assert b_dims.dtype == torch.int32 and tuple(b_dims.shape) == (Pb, 2) and b_dims.is_contiguous()
-    assert pairs.dtype == torch.int32 and tuple(pairs.shape) == (N, 2) and pairs.is_contiguous()
-    assert radii.dtype == torch.int32 and tuple(radii.shape) == (N, T) and radii.is_contiguous()
-    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
-    for t in (n, far, max_d2):
-        assert t.dtype == torch.int32 and tuple(t.shape) == (N,) and t.is_contiguous()
-    assert within.dtype == torch.int32 and tuple(within.shape) == (N, T) and within.is_contiguous()
-    assert sum_d2.dtype == torch.int64 and tuple(sum_d2.shape) == (N,) and sum_d2.is_contiguous()
-    assert sum_d.dtype == torch.float64 and tuple(sum_d.shape) == (N,) and sum_d.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == dev for t in (b_d2, b_pix_offsets, b_dims, pairs, radii, workspace, n, far, within, max_d2, sum_d2, sum_d, status))
-    _call(name, a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa, b_d2.data_ptr(), b_pix_offsets.data_ptr(),
-          b_d2.numel(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, radii.data_ptr(), T, int(max_words), workspace.data_ptr(),
-          workspace.numel(), n.data_ptr(), far.data_ptr(), within.data_ptr(), max_d2.data_ptr(), sum_d2.data_ptr(), sum_d.data_ptr(),
-          status.data_ptr())
+    _check_tensors(a_bits, ("b_d2", b_d2, _I32, (None,)), ("b_pix_offsets", b_pix_offsets, _I64, (Pb + 1,)), ("b_dims", b_dims, _I32, (Pb, 2)),
+                   ("pairs", pairs, _I32, (N, 2)), ("radii", radii, _I32, (N, T)), ("workspace", workspace, _U8, (None,)), ("n", n, _I32, (N,)),
+                   ("far", far, _I32, (N,)), ("within", within, _I32, (N, T)), ("max_d2", max_d2, _I32, (N,)), ("sum_d2", sum_d2, _I64, (N,)),
+                   ("sum_d", sum_d, _F64, (N,)), ("status", status, _I32, (1,)))
+    _call(_entry("cvlm_mask_surface_totals", host, a_bits), a_bits.data_ptr(), a_bits.numel(), a_offsets.data_ptr(), a_dims.data_ptr(), Pa,
+          b_d2.data_ptr(), b_pix_offsets.data_ptr(), b_d2.numel(), b_dims.data_ptr(), Pb, pairs.data_ptr(), N, radii.data_ptr(), T,
+          int(max_words), workspace.data_ptr(), workspace.numel(), n.data_ptr(), far.data_ptr(), within.data_ptr(), max_d2.data_ptr(),
+          sum_d2.data_ptr(), sum_d.data_ptr(), status.data_ptr())
 
 
 def mask_surface_totals(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_d2: torch.Tensor, b_pix_offsets: torch.Tensor,
@@ -1515,19 +1408,14 @@ def mask_surface_totals(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: t
     pairs[i, 0] of A (sized planes) against map pairs[i, 1] of B (`mask_distance_sized`'s out_d2, pix_offsets and dims) -> n, far, max_d2
     int32 [N], within int32 [N][T] at radii int32 [N][T], sum_d2 int64 [N], sum_d float64 [N]; status int32 [1] = 1 if a pair was refused
     (-1 in its integers).  workspace: uint8, `mask_surface_workspace_bytes(N)`."""
-    _on_current_device(a_bits)
-    _surface_totals("cvlm_mask_surface_totals", a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n,
-                    far, within, max_d2, sum_d2, sum_d, status)
+    _mask_surface_totals(False, a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words, workspace, n, far, within,
+                         max_d2, sum_d2, sum_d, status)
 
 
-def mask_surface_totals_host(a_bits: torch.Tensor, a_offsets: torch.Tensor, a_dims: torch.Tensor, b_d2: torch.Tensor,
-                             b_pix_offsets: torch.Tensor, b_dims: torch.Tensor, pairs: torch.Tensor, radii: torch.Tensor, max_words: int,
-                             workspace: torch.Tensor, n: torch.Tensor, far: torch.Tensor, within: torch.Tensor, max_d2: torch.Tensor,
-                             sum_d2: torch.Tensor, sum_d: torch.Tensor, status: torch.Tensor) -> None:
+@functools.wraps(mask_surface_totals, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_surface_totals_host(*args, **kw) -> None:
     """`mask_surface_totals` on HOST tensors without a device (cvlm_debug_mask_surface_totals_host)."""
-    assert not a_bits.is_cuda
-    _surface_totals("cvlm_debug_mask_surface_totals_host", a_bits, a_offsets, a_dims, b_d2, b_pix_offsets, b_dims, pairs, radii, max_words,
-                    workspace, n, far, within, max_d2, sum_d2, sum_d, status)
+    _mask_surface_totals(True, *args, **kw)
 
 
 # ---- Thinning: skeletons, thin edges, clDice (DESIGN.md §28) ----------------------------------------------------------------------------------
@@ -1538,10 +1426,7 @@ THIN_MAX_STEPS = 1024             # iterations the stepping path launches in one
 def mask_thin_workspace_bytes(n_bytes: int, P: int, steps: int) -> int:
     """Bytes of workspace of one `mask_thin_sized` call on P planes of n_bytes bytes in all with `steps` stepped iterations (host
     arithmetic): the stepped state plus the flags."""
-    need = int(load().cvlm_mask_thin_workspace_bytes(int(n_bytes), int(P), int(steps)))
-    if need < 0:
-        raise RuntimeError(f"cvlm_mask_thin_workspace_bytes failed with code {need}")
-    return need
+    return _workspace_bytes("cvlm_mask_thin_workspace_bytes", n_bytes, P, steps)
 
 
 def mask_thin_resident(h: int, w: int) -> bool:
@@ -1549,19 +1434,16 @@ def mask_thin_resident(h: int, w: int) -> bool:
     return bool(load().cvlm_mask_thin_resident(int(h), int(w)))
 
 
-def _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status) -> int:
-    """Shape and dtype checks shared by `mask_thin_sized` and `mask_thin_sized_host` -> P."""
-    P = _contour_planes(bits, offsets, dims)
-    assert out_bits.dtype == torch.uint8 and out_bits.dim() == 1 and out_bits.is_contiguous() and out_bits.numel() == bits.numel()
-    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
-    for t in (max_iter, out_iters, out_done):
-        assert t.dtype == torch.int32 and tuple(t.shape) == (P,) and t.is_contiguous()
-    assert (out_area is None) == (out_box is None)
-    assert out_area is None or (out_area.dtype == torch.int32 and tuple(out_area.shape) == (P,) and out_area.is_contiguous())
-    assert out_box is None or (out_box.dtype == torch.int32 and tuple(out_box.shape) == (P, 4) and out_box.is_contiguous())
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == bits.device for t in (max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status))
-    return P
+def _mask_thin_sized(host: bool, bits, offsets, dims, max_iter, max_words, mode, steps, workspace, out_bits, out_area, out_box, out_iters,
+                     out_done, status) -> None:
+    """The body of `mask_thin_sized` and of its host twin."""
+    P = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("max_iter", max_iter, _I32, (P,)), ("workspace", workspace, _U8, (None,)), ("out_bits", out_bits, _U8, (bits.numel(),)),
+                   ("out_area", out_area, _I32, (P,)), ("out_box", out_box, _I32, (P, 4)), ("out_iters", out_iters, _I32, (P,)),
+                   ("out_done", out_done, _I32, (P,)), ("status", status, _I32, (1,)), together=(("out_area", "out_box"),))
+    _call(_entry("cvlm_mask_thin_sized", host, bits), bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P,
+          int(max_words), int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box),
+          out_iters.data_ptr(), out_done.data_ptr(), status.data_ptr())
 
 
 def mask_thin_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_iter: torch.Tensor, max_words: int, mode: int,
@@ -1573,23 +1455,15 @@ def mask_thin_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tenso
     `steps` ran out), status int32 [1] = 1 if a plane was refused.  mode 0: planes that fit the resident kernel's LDS are thinned there,
     the others in `steps` stepped iterations; mode 1: every plane is stepped.  workspace: uint8, `mask_thin_workspace_bytes`.
     max_words: the largest h * ceil(w / 32) of the call."""
-    P = _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status)
-    _on_current_device(bits)
-    _call("cvlm_mask_thin_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P, int(max_words),
-          int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box), out_iters.data_ptr(),
-          out_done.data_ptr(), status.data_ptr())
+    _mask_thin_sized(False, bits, offsets, dims, max_iter, max_words, mode, steps, workspace, out_bits, out_area, out_box, out_iters,
+                     out_done, status)
 
 
-def mask_thin_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_iter: torch.Tensor, max_words: int, mode: int,
-                         steps: int, workspace: torch.Tensor, out_bits: torch.Tensor, out_area: Optional[torch.Tensor],
-                         out_box: Optional[torch.Tensor], out_iters: torch.Tensor, out_done: torch.Tensor, status: torch.Tensor) -> None:
+@functools.wraps(mask_thin_sized, assigned=())        # help() and inspect.signature show the parameter list above
+def mask_thin_sized_host(*args, **kw) -> None:
     """`mask_thin_sized` on HOST tensors without a device (cvlm_debug_mask_thin_sized_host: the same word function run sequentially,
     every plane to its fixed point or its max_iter)."""
-    P = _thin_args(bits, offsets, dims, max_iter, workspace, out_bits, out_area, out_box, out_iters, out_done, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_thin_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), max_iter.data_ptr(), P,
-          int(max_words), int(mode), int(steps), workspace.data_ptr(), workspace.numel(), out_bits.data_ptr(), _p(out_area), _p(out_box),
-          out_iters.data_ptr(), out_done.data_ptr(), status.data_ptr())
+    _mask_thin_sized(True, *args, **kw)
 
 
 # ---- Instances: regions of sized planes, the alpha of a region (DESIGN.md §29) -----------------------------------------------------------------
@@ -1599,23 +1473,19 @@ REGIONS_MAXM = 64                 # rows of the table, and planes a plane is spl
 def mask_regions_workspace_bytes(n_bytes: int, P: int, max_words: int) -> int:
     """Bytes of workspace that keep all P planes of one `mask_regions_sized` call in flight (112 per byte of bits, host arithmetic);
     `mask_regions_workspace_bytes(4 * max_words, 1, max_words)`, the largest plane's alone, is the least the entry takes."""
-    need = int(load().cvlm_mask_regions_workspace_bytes(int(n_bytes), int(P), int(max_words)))
-    if need < 0:
-        raise RuntimeError(f"cvlm_mask_regions_workspace_bytes failed with code {need}")
-    return need
+    return _workspace_bytes("cvlm_mask_regions_workspace_bytes", n_bytes, P, max_words)
 
 
-def _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status) -> Tuple[int, int]:
-    """Shape and dtype checks shared by `mask_regions_sized` and `mask_regions_sized_host` -> (P, M)."""
-    P = _contour_planes(bits, offsets, dims)
-    assert regions.dtype == torch.int32 and regions.dim() == 3 and regions.is_contiguous()
+def _mask_regions_sized(host: bool, bits, offsets, dims, max_words, connectivity, min_area, workspace, n_regions, regions, out_bits, status) -> None:
+    """The body of `mask_regions_sized` and of its host twin."""
+    P = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("regions", regions, _I32, (P, None, 6)), ("workspace", workspace, _U8, (None,)), ("n_regions", n_regions, _I32, (P,)),
+                   ("out_bits", out_bits, _U8, (None,)), ("status", status, _I32, (1,)), optional=("workspace",) if host else ())
     M = int(regions.shape[1])
-    assert tuple(regions.shape) == (P, M, 6)
-    assert n_regions.dtype == torch.int32 and tuple(n_regions.shape) == (P,) and n_regions.is_contiguous()
-    assert out_bits.dtype == torch.uint8 and out_bits.dim() == 1 and out_bits.is_contiguous() and out_bits.numel() == M * bits.numel()
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == bits.device for t in (n_regions, regions, out_bits, status))
-    return P, M
+    assert out_bits.numel() == M * bits.numel()
+    _call(_entry("cvlm_mask_regions_sized", host, bits), bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(max_words),
+          int(connectivity), M, int(min_area), *(() if host else (workspace.data_ptr(), workspace.numel())), n_regions.data_ptr(),
+          regions.data_ptr(), out_bits.data_ptr(), status.data_ptr())
 
 
 def mask_regions_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_words: int, connectivity: int, min_area: int,
@@ -1626,35 +1496,24 @@ def mask_regions_sized(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Te
     [P][M][6] = (area, x0, y0, x1, y1, seed) of the M largest, out_bits uint8 [M * bits.numel()]: plane (p, m) at byte M * offsets[p] +
     m * (offsets[p + 1] - offsets[p]); status int32 [1] = 1 if a plane was refused.  workspace: uint8, at least the largest plane's
     `mask_regions_workspace_bytes`; less than all planes' makes the entry walk them in rounds.  max_words: the largest h * ceil(w / 32)."""
-    P, _ = _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status)
-    assert workspace.dtype == torch.uint8 and workspace.dim() == 1 and workspace.is_contiguous()
-    _on_current_device(bits)
-    _call("cvlm_mask_regions_sized", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(max_words), int(connectivity),
-          int(regions.shape[1]), int(min_area), workspace.data_ptr(), workspace.numel(), n_regions.data_ptr(), regions.data_ptr(),
-          out_bits.data_ptr(), status.data_ptr())
+    _mask_regions_sized(False, bits, offsets, dims, max_words, connectivity, min_area, workspace, n_regions, regions, out_bits, status)
 
 
 def mask_regions_sized_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, max_words: int, connectivity: int, min_area: int,
                             n_regions: torch.Tensor, regions: torch.Tensor, out_bits: torch.Tensor, status: torch.Tensor) -> None:
     """`mask_regions_sized` on HOST tensors without a device or a workspace (cvlm_debug_mask_regions_sized_host)."""
-    P, _ = _regions_args(bits, offsets, dims, n_regions, regions, out_bits, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_mask_regions_sized_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(max_words),
-          int(connectivity), int(regions.shape[1]), int(min_area), n_regions.data_ptr(), regions.data_ptr(), out_bits.data_ptr(),
-          status.data_ptr())
+    _mask_regions_sized(True, bits, offsets, dims, max_words, connectivity, min_area, None, n_regions, regions, out_bits, status)
 
 
-def _region_alpha_args(bits, offsets, dims, alpha, src, out, status) -> Tuple[int, int, int]:
-    """Shape and dtype checks shared by `region_alpha` and `region_alpha_host` -> (Q, N, R)."""
-    Q = _contour_planes(bits, offsets, dims)
-    assert alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.dim() in (3, 4) and alpha.shape[-1] == alpha.shape[-2]
+def _region_alpha(host: bool, bits, offsets, dims, alpha, src, out, status) -> None:
+    """The body of `region_alpha` and of its host twin."""
+    Q = _sized_planes(bits, offsets, dims)
+    _check_tensors(bits, ("alpha", alpha, _F32, None), ("src", src, _I32, (Q,)), ("out", out, _F32, None), ("status", status, _I32, (1,)))
+    assert alpha.dim() in (3, 4) and alpha.shape[-1] == alpha.shape[-2]
     N, R = int(alpha.shape[0]), int(alpha.shape[-1])
-    assert alpha.numel() == N * R * R
-    assert src.dtype == torch.int32 and tuple(src.shape) == (Q,) and src.is_contiguous()
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == Q * R * R
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t.device == bits.device for t in (alpha, src, out, status))
-    return Q, N, R
+    assert alpha.numel() == N * R * R and out.numel() == Q * R * R
+    _call(_entry("cvlm_region_alpha", host, bits), bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R,
+          src.data_ptr(), out.data_ptr(), status.data_ptr())
 
 
 def region_alpha(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, alpha: torch.Tensor, src: torch.Tensor, out: torch.Tensor,
@@ -1662,19 +1521,13 @@ def region_alpha(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, 
     """The stage-2 alpha of Q regions (include/cvlm.h: cvlm_region_alpha): out[q] = alpha[src[q]] * the bits of sized plane
     q resized to R x R by `bilinear`'s arithmetic.  alpha f32 [N][R][R] or [N][1][R][R], src int32 [Q] in [0, N), out f32 of Q * R * R
     values; status int32 [1] = 1 if a plane or a src was refused (its out is 0)."""
-    Q, N, R = _region_alpha_args(bits, offsets, dims, alpha, src, out, status)
-    _on_current_device(bits)
-    _call("cvlm_region_alpha", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R, src.data_ptr(),
-          out.data_ptr(), status.data_ptr())
+    _region_alpha(False, bits, offsets, dims, alpha, src, out, status)
 
 
-def region_alpha_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor, alpha: torch.Tensor, src: torch.Tensor, out: torch.Tensor,
-                      status: torch.Tensor) -> None:
+@functools.wraps(region_alpha, assigned=())        # help() and inspect.signature show the parameter list above
+def region_alpha_host(*args, **kw) -> None:
     """`region_alpha` on HOST tensors without a device (cvlm_debug_region_alpha_host)."""
-    Q, N, R = _region_alpha_args(bits, offsets, dims, alpha, src, out, status)
-    assert not bits.is_cuda
-    _call("cvlm_debug_region_alpha_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), Q, alpha.data_ptr(), N, R,
-          src.data_ptr(), out.data_ptr(), status.data_ptr())
+    _region_alpha(True, *args, **kw)
 
 
 NMS_MEASURES = {"iou": 0, "min": 1}               # csrc/nms_logic.h: NM_IOU, NM_MIN
@@ -1688,19 +1541,13 @@ def mask_nms_inter(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Tensor
     §30): the sized table of Q planes with area int32 [Q] and box int32 [Q][4], group_offsets int32 [G + 1] into member int32 [Q],
     pair_offsets int64 [G + 1] -> inter int32 [N], group g's triangle at pair_offsets[g], -1 for a refused pair; status int32 [1]: bit 0
     a pair, bit 1 a group was refused.  host=True: the same on HOST tensors without a device (cvlm_debug_mask_nms_inter_host)."""
-    Q = _contour_planes(bits, offsets, dims)
+    Q = _sized_planes(bits, offsets, dims)
     G, N = int(group_offsets.numel()) - 1, int(inter.numel())
-    i32 = torch.int32
-    for t, dtype, shape in ((area, i32, (Q,)), (box, i32, (Q, 4)), (group_offsets, i32, (G + 1,)), (member, i32, (Q,)),
-                            (pair_offsets, torch.int64, (G + 1,)), (inter, i32, (N,)), (status, i32, (1,))):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == bits.device, (t.dtype, tuple(t.shape), shape)
-    if host:
-        assert not bits.is_cuda
-    else:
-        _on_current_device(bits)
-    _call("cvlm_debug_mask_nms_inter_host" if host else "cvlm_mask_nms_inter", bits.data_ptr(), bits.numel(), offsets.data_ptr(),
-          dims.data_ptr(), area.data_ptr(), box.data_ptr(), Q, group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G, N,
-          inter.data_ptr() if N else None, status.data_ptr())
+    _check_tensors(bits, ("area", area, _I32, (Q,)), ("box", box, _I32, (Q, 4)), ("group_offsets", group_offsets, _I32, (G + 1,)),
+                   ("member", member, _I32, (Q,)), ("pair_offsets", pair_offsets, _I64, (G + 1,)), ("inter", inter, _I32, (N,)),
+                   ("status", status, _I32, (1,)))
+    _call(_entry("cvlm_mask_nms_inter", host, bits), bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), area.data_ptr(),
+          box.data_ptr(), Q, group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G, N, _pn(inter), status.data_ptr())
 
 
 def mask_nms(group_offsets: torch.Tensor, member: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor, area: torch.Tensor,
@@ -1711,20 +1558,14 @@ def mask_nms(group_offsets: torch.Tensor, member: torch.Tensor, pair_offsets: to
     int32 and decay f32 [Q], n_keep int32 [G], status int32 [1]: bit 1 a group was refused.  host=True: the same on HOST tensors without
     a device (cvlm_debug_mask_nms_host)."""
     G, N, Q = int(group_offsets.numel()) - 1, int(inter.numel()), int(area.numel())
-    i32 = torch.int32
-    for t, dtype, shape in ((group_offsets, i32, (G + 1,)), (member, i32, (Q,)), (pair_offsets, torch.int64, (G + 1,)), (inter, i32, (N,)),
-                            (area, i32, (Q,)), (score, torch.float32, (Q,)), (order, i32, (Q,)), (keep, torch.uint8, (Q,)), (by, i32, (Q,)),
-                            (decay, torch.float32, (Q,)), (n_keep, i32, (G,)), (status, i32, (1,))) + \
-            (() if category is None else ((category, i32, (Q,)),)):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == area.device, (t.dtype, tuple(t.shape), shape)
-    if host:
-        assert not area.is_cuda
-    else:
-        _on_current_device(area)
+    _check_tensors(area, ("group_offsets", group_offsets, _I32, (G + 1,)), ("member", member, _I32, (Q,)), ("pair_offsets", pair_offsets, _I64, (G + 1,)),
+                   ("inter", inter, _I32, (N,)), ("area", area, _I32, (Q,)), ("score", score, _F32, (Q,)), ("category", category, _I32, (Q,)),
+                   ("order", order, _I32, (Q,)), ("keep", keep, _U8, (Q,)), ("by", by, _I32, (Q,)), ("decay", decay, _F32, (Q,)),
+                   ("n_keep", n_keep, _I32, (G,)), ("status", status, _I32, (1,)), optional=("category",))
     params = (C.c_double * 2)(float(thr), float(sigma))               # host memory: the entry reads it before it returns
-    _call("cvlm_debug_mask_nms_host" if host else "cvlm_mask_nms", group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G,
-          inter.data_ptr() if N else None, N, area.data_ptr(), score.data_ptr(), _p(category), Q, int(measure), int(method),
-          C.addressof(params), order.data_ptr(), keep.data_ptr(), by.data_ptr(), decay.data_ptr(), n_keep.data_ptr(), status.data_ptr())
+    _call(_entry("cvlm_mask_nms", host, area), group_offsets.data_ptr(), member.data_ptr(), pair_offsets.data_ptr(), G, _pn(inter), N,
+          area.data_ptr(), score.data_ptr(), _p(category), Q, int(measure), int(method), C.addressof(params), order.data_ptr(), keep.data_ptr(),
+          by.data_ptr(), decay.data_ptr(), n_keep.data_ptr(), status.data_ptr())
 
 
 RENDER_KINDS = {"bits": 0, "levels": 1, "labels": 2}      # csrc/render_logic.h: RD_BITS, RD_LEVELS, RD_LABELS
@@ -1742,97 +1583,35 @@ def render(img: torch.Tensor, img_offsets: torch.Tensor, dims: torch.Tensor, max
     device (cvlm_debug_render_host)."""
     B, T = int(dims.shape[0]), int(alpha.numel())
     L = 0 if layers is None else int(layers.shape[0])
-    u8, i32, i64 = torch.uint8, torch.int32, torch.int64
-    for t, dtype, shape in ((img, u8, (img.numel(),)), (out, u8, (img.numel(),)), (img_offsets, i64, (B + 1,)), (dims, i32, (B, 2)),
-                            (layer_offsets, i32, (B + 1,)), (rgb, u8, (T, 3)), (alpha, torch.float32, (T,)), (status, i32, (1,))) + \
-            (() if layers is None else ((layers, i64, (L, 4)),)) + (() if bits is None else ((bits, u8, (bits.numel(),)),)) + \
-            (() if levels is None else ((levels, u8, (levels.numel(),)),)) + (() if labels is None else ((labels, i32, (labels.numel(),)),)):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == img.device, (t.dtype, tuple(t.shape), shape)
-    if host:
-        assert not img.is_cuda
-    else:
-        _on_current_device(img)
+    _check_tensors(img, ("img", img, _U8, (None,)), ("out", out, _U8, (img.numel(),)), ("img_offsets", img_offsets, _I64, (B + 1,)),
+                   ("dims", dims, _I32, (B, 2)), ("layer_offsets", layer_offsets, _I32, (B + 1,)), ("rgb", rgb, _U8, (T, 3)), ("alpha", alpha, _F32, (T,)),
+                   ("status", status, _I32, (1,)), ("layers", layers, _I64, (L, 4)), ("bits", bits, _U8, (None,)), ("levels", levels, _U8, (None,)),
+                   ("labels", labels, _I32, (None,)), optional=("layers", "bits", "levels", "labels"))
     n = lambda t: 0 if t is None else int(t.numel())
-    _call("cvlm_debug_render_host" if host else "cvlm_render", img.data_ptr(), img.numel(), img_offsets.data_ptr(), dims.data_ptr(), B,
-          int(max_pixels), layer_offsets.data_ptr(), _p(layers) if L else None, L, _p(bits), n(bits), _p(levels), n(levels), _p(labels),
-          n(labels), rgb.data_ptr(), alpha.data_ptr(), T, out.data_ptr(), status.data_ptr())
-
-
-def _coco_match_boundary(name: str, host: bool, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area,
-                         gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore, gt_match,
-                         gt_ignore, status) -> None:
-    E, N, ND, NG, T, A = _coco_match_args(det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area, gt_range_area, gt_crowd,
-                                          iou_thrs, area_rngs, dt_order, dt_match, dt_ignore, gt_match, gt_ignore, status)
-    for t, n in ((inter_b, N), (det_area_b, ND), (gt_area_b, NG)):
-        assert t.dtype == torch.int32 and tuple(t.shape) == (n,) and t.is_contiguous() and t.device == det_offsets.device
-    if host:
-        assert not det_offsets.is_cuda
-    else:
-        _on_current_device(det_offsets)
-    p = lambda t: t.data_ptr() if t.numel() else None
-    _call(name, det_offsets.data_ptr(), gt_offsets.data_ptr(), pair_offsets.data_ptr(), E, p(inter), N, p(det_area), p(score), ND,
-          p(gt_area), p(gt_range_area), p(gt_crowd), NG, iou_thrs.data_ptr(), T, area_rngs.data_ptr(), A, int(max_det), p(inter_b),
-          p(det_area_b), p(gt_area_b), p(dt_order), p(dt_match), p(dt_ignore), p(gt_match), p(gt_ignore), status.data_ptr())
-
-
-def coco_match_boundary(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
-                        det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor, gt_crowd: torch.Tensor,
-                        iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, inter_b: torch.Tensor, det_area_b: torch.Tensor,
-                        gt_area_b: torch.Tensor, dt_order: torch.Tensor, dt_match: torch.Tensor, dt_ignore: torch.Tensor,
-                        gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
-    """`coco_match` with the IoU of a pair replaced by min(mask IoU, boundary IoU) (include/cvlm.h: cvlm_coco_match_boundary; DESIGN.md
-    §25): inter_b int32 [N], det_area_b int32 [sum D] and gt_area_b int32 [sum G] are the boundaries' intersections and areas, in the
-    order of inter, det_area and gt_area."""
-    _coco_match_boundary("cvlm_coco_match_boundary", False, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area,
-                         gt_range_area, gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore,
-                         gt_match, gt_ignore, status)
-
-
-def coco_match_boundary_host(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, pair_offsets: torch.Tensor, inter: torch.Tensor,
-                             det_area: torch.Tensor, score: torch.Tensor, gt_area: torch.Tensor, gt_range_area: torch.Tensor,
-                             gt_crowd: torch.Tensor, iou_thrs: torch.Tensor, area_rngs: torch.Tensor, max_det: int, inter_b: torch.Tensor,
-                             det_area_b: torch.Tensor, gt_area_b: torch.Tensor, dt_order: torch.Tensor, dt_match: torch.Tensor,
-                             dt_ignore: torch.Tensor, gt_match: torch.Tensor, gt_ignore: torch.Tensor, status: torch.Tensor) -> None:
-    """`coco_match_boundary` on HOST tensors without a device (cvlm_debug_coco_match_boundary_host)."""
-    _coco_match_boundary("cvlm_debug_coco_match_boundary_host", True, det_offsets, gt_offsets, pair_offsets, inter, det_area, score, gt_area,
-                         gt_range_area, gt_crowd, iou_thrs, area_rngs, max_det, inter_b, det_area_b, gt_area_b, dt_order, dt_match, dt_ignore,
-                         gt_match, gt_ignore, status)
+    _call(_entry("cvlm_render", host, img), img.data_ptr(), img.numel(), img_offsets.data_ptr(), dims.data_ptr(), B, int(max_pixels),
+          layer_offsets.data_ptr(), _p(layers) if L else None, L, _p(bits), n(bits), _p(levels), n(levels), _p(labels), n(labels), rgb.data_ptr(),
+          alpha.data_ptr(), T, out.data_ptr(), status.data_ptr())
 
 
 # ---- label maps (DESIGN.md §23): the tensors below live on the device for the cvlm_label_* entries and on the host for `host=True` ----
-def _label_state(score, winner, segment, areas, segment_id, n_segments, status, B: int, K: int) -> int:
-    """Shape and dtype checks of the state and outputs of the label entries (score None: an entry that does not take it) -> n_pix."""
+def _label_state(score, winner, segment, areas, segment_id, n_segments, status, B: int, K: int, without=()) -> int:
+    """The check of the state and outputs of the label entries (`without`: what an entry does not take) -> n_pix."""
     n_pix = winner.numel()
-    assert score is None or (score.dtype == torch.float32 and tuple(score.shape) == (n_pix,) and score.is_contiguous())
-    for t in (winner, segment):
-        assert t.dtype == torch.int16 and tuple(t.shape) == (n_pix,) and t.is_contiguous()
-    assert areas.dtype == torch.int32 and tuple(areas.shape) == (3, B * K) and areas.is_contiguous()
-    assert segment_id is None or (segment_id.dtype == torch.int32 and tuple(segment_id.shape) == (B * K,) and segment_id.is_contiguous())
-    assert n_segments is None or (n_segments.dtype == torch.int32 and tuple(n_segments.shape) == (B,) and n_segments.is_contiguous())
-    assert status.dtype == torch.int32 and status.numel() == 1
-    assert all(t is None or t.device == winner.device for t in (score, segment, areas, segment_id, n_segments, status))
+    _check_tensors(winner, ("score", score, _F32, (n_pix,)), ("winner", winner, _I16, (n_pix,)), ("segment", segment, _I16, (n_pix,)),
+                   ("areas", areas, _I32, (3, B * K)), ("segment_id", segment_id, _I32, (B * K,)), ("n_segments", n_segments, _I32, (B,)),
+                   ("status", status, _I32, (1,)), optional=without)
     return n_pix
 
 
 def _label_tables(dims, pix_offsets, B: int, like: torch.Tensor) -> None:
-    assert dims.dtype == torch.int32 and tuple(dims.shape) == (B, 2) and dims.is_contiguous() and dims.device == like.device
-    assert pix_offsets.dtype == torch.int64 and tuple(pix_offsets.shape) == (B + 1,) and pix_offsets.is_contiguous()
-    assert pix_offsets.device == like.device
-
-
-def _label_entry(name: str, host: bool, t: torch.Tensor) -> str:
-    assert t.is_cuda != host, "host=True runs on host tensors, the device entry on device tensors"
-    if host:
-        return "cvlm_debug_" + name[5:] + "_host"
-    _on_current_device(t)
-    return name
+    _check_tensors(like, ("dims", dims, _I32, (B, 2)), ("pix_offsets", pix_offsets, _I64, (B + 1,)))
 
 
 def label_init(score, winner, segment, areas, segment_id, n_segments, status, B: int, K: int, host: bool = False) -> None:
     """The fill of a label-map state (include/cvlm.h: cvlm_label_init): score f32 [n_pix] = 0, winner / segment int16 [n_pix] = -1,
     areas int32 [3][B * K] = segment_id int32 [B * K] = n_segments int32 [B] = 0, status int32 [1] = 0."""
     n_pix = _label_state(score, winner, segment, areas, segment_id, n_segments, status, B, K)
-    _call(_label_entry("cvlm_label_init", host, score), score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, areas.data_ptr(),
+    _call(_entry("cvlm_label_init", host, score), score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, areas.data_ptr(),
           segment_id.data_ptr(), B, K, n_segments.data_ptr(), status.data_ptr())
 
 
@@ -1841,25 +1620,24 @@ def label_accumulate(planes: torch.Tensor, p0: int, B: int, K: int, dims, pix_of
     """planes f32 [n][Hs][Ws] = the planes p0 .. p0 + n - 1 of B * K, offered in increasing k to the pixels of their images
     (cvlm_label_accumulate): dims int32 [B][2], pix_offsets int64 [B + 1] in pixels, weights f32 [B * K] or None."""
     n, Hs, Ws = planes.shape
-    assert planes.dtype == torch.float32 and planes.is_contiguous() and isinstance(level, int)
-    n_pix = _label_state(score, winner, segment, areas, None, None, status, B, K)
+    assert isinstance(level, int)
+    n_pix = _label_state(score, winner, segment, areas, None, None, status, B, K, without=("segment_id", "n_segments"))
     _label_tables(dims, pix_offsets, B, score)
-    assert weights is None or (weights.dtype == torch.float32 and weights.numel() == B * K and weights.is_contiguous()
-                               and weights.device == score.device)
-    assert planes.device == score.device
-    _call(_label_entry("cvlm_label_accumulate", host, score), planes.data_ptr(), p0, p0 + n, Hs, Ws, B, K, dims.data_ptr(),
-          pix_offsets.data_ptr(), _p(weights), level, score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, int(max_pixels),
-          areas.data_ptr(), status.data_ptr())
+    _check_tensors(score, ("planes", planes, _F32, (n, Hs, Ws)), ("weights", weights, _F32, None), optional=("weights",))
+    assert weights is None or weights.numel() == B * K
+    _call(_entry("cvlm_label_accumulate", host, score), planes.data_ptr(), p0, p0 + n, Hs, Ws, B, K, dims.data_ptr(), pix_offsets.data_ptr(),
+          _p(weights), level, score.data_ptr(), winner.data_ptr(), segment.data_ptr(), n_pix, int(max_pixels), areas.data_ptr(),
+          status.data_ptr())
 
 
 def label_finish(B: int, K: int, dims, pix_offsets, overlap_threshold: float, winner, segment, max_pixels: int, areas, segment_id,
                  n_segments, status, host: bool = False) -> None:
     """won_area, kept_area, kept / segment_id / n_segments and the final `segment` map from the state (cvlm_label_finish); the
     threshold is handed over as one host double."""
-    n_pix = _label_state(None, winner, segment, areas, segment_id, n_segments, status, B, K)
+    n_pix = _label_state(None, winner, segment, areas, segment_id, n_segments, status, B, K, without=("score",))
     _label_tables(dims, pix_offsets, B, winner)
     thr = C.c_double(overlap_threshold)
-    _call(_label_entry("cvlm_label_finish", host, winner), B, K, dims.data_ptr(), pix_offsets.data_ptr(), C.addressof(thr), winner.data_ptr(),
+    _call(_entry("cvlm_label_finish", host, winner), B, K, dims.data_ptr(), pix_offsets.data_ptr(), C.addressof(thr), winner.data_ptr(),
           segment.data_ptr(), n_pix, int(max_pixels), areas.data_ptr(), segment_id.data_ptr(), n_segments.data_ptr(), status.data_ptr())
 
 
@@ -1867,26 +1645,22 @@ def label_lookup(map_: torch.Tensor, B: int, K: int, dims, pix_offsets, max_pixe
                  status: torch.Tensor, host: bool = False) -> None:
     """out int32 [n_pix] = map < 0 ? void : table[b * K + map] for the pixels of every image (cvlm_label_lookup)."""
     n_pix = map_.numel()
-    assert map_.dtype == torch.int16 and map_.dim() == 1 and map_.is_contiguous()
-    assert table.dtype == torch.int32 and table.numel() == B * K and table.is_contiguous()
-    assert out.dtype == torch.int32 and tuple(out.shape) == (n_pix,) and out.is_contiguous()
-    assert status.dtype == torch.int32 and status.numel() == 1
+    _check_tensors(map_, ("map_", map_, _I16, (n_pix,)), ("table", table, _I32, None), ("out", out, _I32, (n_pix,)), ("status", status, _I32, (1,)))
+    assert table.numel() == B * K
     _label_tables(dims, pix_offsets, B, map_)
-    assert table.device == map_.device and out.device == map_.device and status.device == map_.device
-    _call(_label_entry("cvlm_label_lookup", host, map_), map_.data_ptr(), B, K, dims.data_ptr(), pix_offsets.data_ptr(), n_pix,
-          int(max_pixels), table.data_ptr(), int(void), out.data_ptr(), status.data_ptr())
+    _call(_entry("cvlm_label_lookup", host, map_), map_.data_ptr(), B, K, dims.data_ptr(), pix_offsets.data_ptr(), n_pix, int(max_pixels),
+          table.data_ptr(), int(void), out.data_ptr(), status.data_ptr())
 
 
 def label_iou_hist(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, ignore_index: int, reduce_zero_label: bool, zero_first: bool,
                    totals: torch.Tensor, host: bool = False) -> None:
     """totals int64 [3][C] += (area_intersect, area_pred_label, area_label) of pred int32 [n] against gt int32 or uint8 [n]
     (cvlm_label_iou_hist: mmseg's intersect_and_union)."""
-    assert pred.dtype == torch.int32 and pred.dim() == 1 and pred.is_contiguous()
-    assert gt.dtype in (torch.int32, torch.uint8) and tuple(gt.shape) == tuple(pred.shape) and gt.is_contiguous()
-    assert totals.dtype == torch.int64 and tuple(totals.shape) == (3, num_classes) and totals.is_contiguous()
-    assert gt.device == pred.device and totals.device == pred.device
-    _call(_label_entry("cvlm_label_iou_hist", host, pred), pred.data_ptr(), gt.data_ptr(), int(gt.dtype == torch.uint8), pred.numel(),
-          num_classes, int(ignore_index), int(bool(reduce_zero_label)), int(bool(zero_first)), totals.data_ptr())
+    gt_u8 = gt.dtype == _U8
+    _check_tensors(pred, ("pred", pred, _I32, (None,)), ("gt", gt, _U8 if gt_u8 else _I32, tuple(pred.shape)),
+                   ("totals", totals, _I64, (3, num_classes)))
+    _call(_entry("cvlm_label_iou_hist", host, pred), pred.data_ptr(), gt.data_ptr(), int(gt_u8), pred.numel(), num_classes, int(ignore_index),
+          int(bool(reduce_zero_label)), int(bool(zero_first)), totals.data_ptr())
 
 
 # ---- panoptic quality (DESIGN.md §24): device tensors for the cvlm_pan_* entries, host tensors for `host=True` ------------------------------
@@ -1895,52 +1669,42 @@ def pan_lds_cells() -> int:
     return int(load().cvlm_debug_pan_lds_cells())
 
 
-def _pan_tensor(t: torch.Tensor, shape, like: torch.Tensor, dtype=torch.int32) -> None:
-    assert t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == like.device
-
-
 def pan_remap(raw: torch.Tensor, B: int, dims, pix_offsets, max_pixels: int, keys, vals, table_offsets, out, unknown, status,
               host: bool = False) -> None:
     """out int32 [n_pix] = the dense index of each pixel's raw id -- raw uint8 [n_pix][3] (rgb2id) or int32 [n_pix] -- looked up in image
     b's slice table_offsets[b] .. table_offsets[b + 1] of keys (ascending) / vals; unknown int32 [B] = the pixels whose non-zero id the
     table does not hold (cvlm_pan_remap)."""
-    rgb = raw.dtype == torch.uint8
-    n_pix = out.numel()
-    assert raw.is_contiguous() and (tuple(raw.shape) == (n_pix, 3) if rgb else (raw.dtype == torch.int32 and tuple(raw.shape) == (n_pix,)))
+    rgb = raw.dtype == _U8
+    n_pix, n_keys = out.numel(), keys.numel()
+    _check_tensors(raw, ("raw", raw, _U8 if rgb else _I32, (n_pix, 3) if rgb else (n_pix,)), ("keys", keys, _I32, (n_keys,)),
+                   ("vals", vals, _I32, (n_keys,)), ("table_offsets", table_offsets, _I64, (B + 1,)), ("out", out, _I32, (n_pix,)),
+                   ("unknown", unknown, _I32, (B,)), ("status", status, _I32, (1,)))
     _label_tables(dims, pix_offsets, B, raw)
-    n_keys = keys.numel()
-    _pan_tensor(keys, (n_keys,), raw), _pan_tensor(vals, (n_keys,), raw), _pan_tensor(table_offsets, (B + 1,), raw, torch.int64)
-    _pan_tensor(out, (n_pix,), raw), _pan_tensor(unknown, (B,), raw)
-    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == raw.device
-    _call(_label_entry("cvlm_pan_remap", host, raw), raw.data_ptr(), int(rgb), B, dims.data_ptr(), pix_offsets.data_ptr(), n_pix,
-          int(max_pixels), keys.data_ptr(), vals.data_ptr(), table_offsets.data_ptr(), n_keys, out.data_ptr(), unknown.data_ptr(),
-          status.data_ptr())
+    _call(_entry("cvlm_pan_remap", host, raw), raw.data_ptr(), int(rgb), B, dims.data_ptr(), pix_offsets.data_ptr(), n_pix, int(max_pixels),
+          keys.data_ptr(), vals.data_ptr(), table_offsets.data_ptr(), n_keys, out.data_ptr(), unknown.data_ptr(), status.data_ptr())
 
 
 def pan_pair_hist(pred, gt, B: int, G: int, S: int, dims, pix_offsets, max_pixels: int, zero_first: bool, inter, status,
                   host: bool = False) -> None:
     """inter int32 [B][G][S] += the pixels of image b with gt = g and pred = s, both int32 [n_pix] (cvlm_pan_pair_hist)."""
     n_pix = pred.numel()
-    assert pred.dtype == torch.int32 and pred.dim() == 1 and pred.is_contiguous()
-    _pan_tensor(gt, (n_pix,), pred), _pan_tensor(inter, (B, G, S), pred)
+    _check_tensors(pred, ("pred", pred, _I32, (n_pix,)), ("gt", gt, _I32, (n_pix,)), ("inter", inter, _I32, (B, G, S)), ("status", status, _I32, (1,)))
     _label_tables(dims, pix_offsets, B, pred)
-    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == pred.device
-    _call(_label_entry("cvlm_pan_pair_hist", host, pred), pred.data_ptr(), gt.data_ptr(), B, G, S, dims.data_ptr(), pix_offsets.data_ptr(),
-          n_pix, int(max_pixels), int(bool(zero_first)), inter.data_ptr(), status.data_ptr())
+    _call(_entry("cvlm_pan_pair_hist", host, pred), pred.data_ptr(), gt.data_ptr(), B, G, S, dims.data_ptr(), pix_offsets.data_ptr(), n_pix,
+          int(max_pixels), int(bool(zero_first)), inter.data_ptr(), status.data_ptr())
 
 
 def pan_match(inter, pred_cat, gt_cat, gt_crowd, num_classes: int, pred_match, pred_iou, gt_match, pred_area, gt_area,
               host: bool = False) -> None:
     """Steps 2 to 4 of DESIGN.md §24 per image from inter int32 [B][G][S], pred_cat int32 [B][S], gt_cat int32 [B][G] and gt_crowd uint8
     [B][G] -> pred_match / pred_area int32 [B][S], pred_iou f64 [B][S], gt_match / gt_area int32 [B][G] (cvlm_pan_match)."""
-    assert inter.dtype == torch.int32 and inter.dim() == 3 and inter.is_contiguous()
+    assert inter.dim() == 3
     B, G, S = inter.shape
-    _pan_tensor(pred_cat, (B, S), inter), _pan_tensor(gt_cat, (B, G), inter), _pan_tensor(gt_crowd, (B, G), inter, torch.uint8)
-    _pan_tensor(pred_match, (B, S), inter), _pan_tensor(pred_area, (B, S), inter), _pan_tensor(pred_iou, (B, S), inter, torch.float64)
-    _pan_tensor(gt_match, (B, G), inter), _pan_tensor(gt_area, (B, G), inter)
-    _call(_label_entry("cvlm_pan_match", host, inter), inter.data_ptr(), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(),
-          gt_crowd.data_ptr(), int(num_classes), pred_match.data_ptr(), pred_iou.data_ptr(), gt_match.data_ptr(), pred_area.data_ptr(),
-          gt_area.data_ptr())
+    _check_tensors(inter, ("inter", inter, _I32, (B, G, S)), ("pred_cat", pred_cat, _I32, (B, S)), ("gt_cat", gt_cat, _I32, (B, G)),
+                   ("gt_crowd", gt_crowd, _U8, (B, G)), ("pred_match", pred_match, _I32, (B, S)), ("pred_iou", pred_iou, _F64, (B, S)),
+                   ("gt_match", gt_match, _I32, (B, G)), ("pred_area", pred_area, _I32, (B, S)), ("gt_area", gt_area, _I32, (B, G)))
+    _call(_entry("cvlm_pan_match", host, inter), inter.data_ptr(), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(), gt_crowd.data_ptr(),
+          int(num_classes), pred_match.data_ptr(), pred_iou.data_ptr(), gt_match.data_ptr(), pred_area.data_ptr(), gt_area.data_ptr())
 
 
 def pan_accumulate(pred_cat, gt_cat, pred_match, pred_iou, gt_match, num_classes: int, zero_first: bool, counts, iou_sum,
@@ -1948,18 +1712,18 @@ def pan_accumulate(pred_cat, gt_cat, pred_match, pred_iou, gt_match, num_classes
     """counts int64 [3][C] (tp, fp, fn) and iou_sum f64 [C] += what cvlm_pan_match stored for a batch (cvlm_pan_accumulate)."""
     B, S = pred_cat.shape
     G = gt_cat.shape[1]
-    _pan_tensor(pred_cat, (B, S), pred_cat), _pan_tensor(gt_cat, (B, G), pred_cat), _pan_tensor(pred_match, (B, S), pred_cat)
-    _pan_tensor(pred_iou, (B, S), pred_cat, torch.float64), _pan_tensor(gt_match, (B, G), pred_cat)
-    _pan_tensor(counts, (3, num_classes), pred_cat, torch.int64), _pan_tensor(iou_sum, (num_classes,), pred_cat, torch.float64)
-    _call(_label_entry("cvlm_pan_accumulate", host, pred_cat), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(), pred_match.data_ptr(),
+    _check_tensors(pred_cat, ("pred_cat", pred_cat, _I32, (B, S)), ("gt_cat", gt_cat, _I32, (B, G)), ("pred_match", pred_match, _I32, (B, S)),
+                   ("pred_iou", pred_iou, _F64, (B, S)), ("gt_match", gt_match, _I32, (B, G)), ("counts", counts, _I64, (3, num_classes)),
+                   ("iou_sum", iou_sum, _F64, (num_classes,)))
+    _call(_entry("cvlm_pan_accumulate", host, pred_cat), B, G, S, pred_cat.data_ptr(), gt_cat.data_ptr(), pred_match.data_ptr(),
           pred_iou.data_ptr(), gt_match.data_ptr(), int(num_classes), int(bool(zero_first)), counts.data_ptr(), iou_sum.data_ptr())
 
 
 def topk_accumulate(scores: torch.Tensor, labels: torch.Tensor, pred: Optional[torch.Tensor], counters: torch.Tensor) -> None:
     """scores f32 [B][C], labels int32 [B] -> pred int32 [B]; counters int32 [3] += (top-1, top-5, rows)."""
     B, Cc = scores.shape
-    assert scores.dtype == torch.float32 and labels.dtype == torch.int32 and counters.dtype == torch.int32
-    assert scores.is_contiguous() and labels.numel() == B and counters.numel() == 3
+    _check_tensors(scores, ("scores", scores, _F32, (B, Cc)), ("labels", labels, _I32, None), ("counters", counters, _I32, None))
+    assert labels.numel() == B and counters.numel() == 3
     _call("cvlm_topk_accumulate", scores.data_ptr(), labels.data_ptr(), B, Cc, _p(pred), counters.data_ptr())
 
 

@@ -938,7 +938,7 @@ class MaskContours:
         return [np.asarray([area(r) for r in rings], dtype=np.float64) for rings in self._host_rings()]
 
 
-DISTANCE_FAR = 0x7fffffff        # D2 of a pixel with no set pixel within reach (csrc/distance_logic.h: DT_FAR)
+DISTANCE_FAR = hip.DT_FAR        # D2 of a pixel with no set pixel within reach
 DISTANCE_MAX_REACH = 23170        # a reach and a tolerance radius: 0 .. 23170, 23170^2 < 2^31 (DT_MAX_REACH)
 SURFACE_MAX_T = 8                 # tolerances of one Cascade.mask_surface_distances call (DT_MAX_T)
 SURFACE_RATIO = 0.008             # the tolerance of the published boundary F-measure: this share of the image's diagonal
@@ -1136,8 +1136,8 @@ class SurfaceTotals:
                     status=int(self.status.item()))
 
 
-THIN_MAX_ITER = 1 << 30           # max_iter of a thinning: 1 .. 2^30, None for none (csrc/thin_logic.h: TH_MAX_ITER)
-THIN_MAX_STEPS = 1024             # iterations of one round of the stepping path (TH_MAX_STEPS)
+THIN_MAX_ITER = hip.THIN_MAX_ITER     # max_iter of a thinning: 1 .. 2^30, None for none
+THIN_MAX_STEPS = hip.THIN_MAX_STEPS   # iterations of one round of the stepping path
 THIN_PATHS = ("auto", "steps")
 
 
@@ -1207,7 +1207,7 @@ class ClDiceTotals:
         return dict(out, pairs=self.pairs.cpu().numpy(), status=int(self.status.item()))
 
 
-REGIONS_MAXM = 64                 # regions a plane is split into at most (csrc/regions_logic.h: RG_MAXM)
+REGIONS_MAXM = hip.REGIONS_MAXM   # regions a plane is split into at most
 
 
 def regions_request(sizes, *, regions=8, min_area=0, connectivity=8, who: str = "mask_regions_sized"):
