@@ -1,18 +1,148 @@
-"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §22): packed masks with areas, boxes and overlaps, connected
+"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §31): packed masks with areas, boxes and overlaps, connected
 components, holes, the edge band, packed edge maps, COCO run-length encoding, masks at each image's own size, their intersections
-with ground truth and COCO's matching of detections to annotations.  Three layers: the pure host checks of every argument
-(`*_request`) with the result types; `MaskUtilities`, the stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan of
-these outputs for one Cascade.infer_classes / decode call. `engine` imports every public name back: callers keep importing them from
-there.  Kernels are called as `hip.<name>(...)`, looked up at call time, so that a test can stand in for a launch."""
+with ground truth and COCO's matching of detections to annotations, label maps, panoptic quality, boundaries, contours, distance
+maps, thinning, regions, mask NMS and rendering.  Three layers: the pure host checks of every argument (`*_request`) with the result
+types; `MaskUtilities`, the stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan of these outputs for one
+Cascade.infer_classes / decode call.  All three are written in the few private helpers at the top of the file: what an
+int, a real and a sequence are, the one check of an (h, w) list, of "one int or one per plane", of the connectivity and of a
+SizedMasks argument, the one upload, allocator and workspace rule.  `engine` imports every public name back: callers keep importing
+them from there.  Kernels are called as `hip.<name>(...)`, looked up at call time, so that a test can stand in for a launch."""
 from __future__ import annotations
 
 from dataclasses import InitVar, dataclass
+from functools import partial
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import hip
+
+
+# ---- what every check, table and allocation below is made of ---------------------------------------------------------
+def _is_int(v) -> bool:
+    """An int, Python's or numpy's; a bool is none."""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_real(v) -> bool:
+    """An int or a float, Python's or numpy's; a bool is none."""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_seq(v) -> bool:
+    """Something with a length that is no string."""
+    return not isinstance(v, (str, bytes)) and hasattr(v, "__len__")
+
+
+def _int_in(who: str, name: str, v, lo: int, hi: Optional[int] = None, none: bool = False) -> int:
+    """v as an int in [lo, hi] (hi None: at least lo), no bool (ValueError otherwise); none=True only words the message for a caller
+    that has taken None out before."""
+    if not _is_int(v) or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError(f"{who}: {name} must be {'None or ' if none else ''}an int {f'>= {lo}' if hi is None else f'in [{lo}, {hi}]'}, got {v!r}")
+    return int(v)
+
+
+def _connectivity(who: str, v) -> int:
+    if not _is_int(v) or int(v) not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be the int 4 or 8, got {v!r}")
+    return int(v)
+
+
+def _int_list(who: str, name: str, seq, n: int, per: str = "plane") -> list:
+    """n ints, no bools -> the list as ints (ValueError otherwise)."""
+    if not _is_seq(seq) or len(seq) != n or not all(_is_int(v) for v in seq):
+        raise ValueError(f"{who}: {name} must hold one int per {per}, {n} of them")
+    return [int(v) for v in seq]
+
+
+def _size_pair(who: str, what: str, pair) -> Tuple[int, int]:
+    """One (h, w): two ints in [1, SIZED_MAX_SIDE], no bools -> the pair as ints (ValueError otherwise, naming it `what`)."""
+    if not _is_seq(pair) or len(pair) != 2:
+        raise ValueError(f"{who}: {what} must be an (h, w) pair, got {pair!r}")
+    h, w = pair
+    if not _is_int(h) or not _is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
+        raise ValueError(f"{who}: {what} must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
+    return int(h), int(w)
+
+
+def _plane_sizes(sizes, who: str, name: str = "sizes", n: Optional[int] = None, of: str = "planes") -> list:
+    """(h, w) pairs of ints in [1, 16384], no bools -- 1 .. 65535 of them (`of` says of what), or with n= exactly n -> the pairs as ints
+    (ValueError otherwise)."""
+    if not _is_seq(sizes) or not hasattr(sizes, "__iter__"):
+        raise ValueError(f"{who}: {name} must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
+    if n is not None and len(sizes) != n:
+        raise ValueError(f"{who}: {name} holds {len(sizes)} pairs for {n} images")
+    if n is None and not 1 <= len(sizes) <= 65535:
+        raise ValueError(f"{who}: 1 .. 65535 {of}, got {len(sizes)}")
+    return [_size_pair(who, f"a size of {name}", pair) for pair in sizes]
+
+
+def _sized_arg(who: str, name: str, s, *, areas: bool = False, boxes: bool = False, optional: bool = False, empty: bool = False):
+    """A SizedMasks argument of a utility: 1 .. 65535 planes on the device, with areas / boxes where the utility reads them; optional:
+    None passes; empty: so does one without a plane, wherever it lives (ValueError otherwise) -> s."""
+    if s is None and optional:
+        return None
+    ok = isinstance(s, SizedMasks) and not (areas and s.area is None) and not (boxes and s.box is None)
+    if ok and not (empty and len(s.sizes) == 0):
+        ok = bool(s.bits.is_cuda) and 1 <= len(s.sizes) <= 65535
+    if not ok:
+        needs = "".join(f", with {what}" for what, on in (("areas", areas), ("boxes", boxes)) if on)
+        raise ValueError(f"{who}: {name} must be a SizedMasks of 1 .. 65535 planes on the device{needs}{', or one without a plane' if empty else ''}"
+                         f"{', or None' if optional else ''}, got {type(s).__name__}")
+    return s
+
+
+def _per_plane_ints(who: str, name: str, v, P: int, lo: int, hi: int, none: bool = False) -> np.ndarray:
+    """One int in [lo, hi] for all P planes or one per plane, no bools; none=True: or None, which is 0 everywhere -> int32 (P,)."""
+    if v is None and none:
+        return np.zeros(P, dtype=np.int32)
+    seq = [v] * P if _is_int(v) else v
+    if not _is_seq(seq) or len(seq) != P or not all(_is_int(x) for x in seq):
+        raise ValueError(f"{who}: {name} must be {'None, ' if none else ''}an int or hold one int per plane, {P} of them, got {v!r}")
+    if not all(lo <= int(x) <= hi for x in seq):
+        raise ValueError(f"{who}: {name} must lie in [{lo}, {hi}], got {v!r}")
+    return np.asarray([int(x) for x in seq], dtype=np.int32).reshape(P)
+
+
+def _plane_by_plane(who: str, Pa: int, Pb: int, instead: str = "pairs=") -> np.ndarray:
+    """The pairs of a call that names none: plane p of a against plane p of b -> int64 (P, 2)."""
+    if Pa != Pb:
+        raise ValueError(f"{who}: without {instead} both sides need as many planes, got {Pa} and {Pb}")
+    return np.stack([np.arange(Pa)] * 2, axis=1)
+
+
+def _capped(total: int, one: int, cap: int) -> int:
+    """The bytes of a grow-only workspace: what all planes want in flight, up to `cap`, and never below one plane's."""
+    return min(total, max(cap, one))
+
+
+def _upload(a, dev) -> torch.Tensor:
+    """One host-to-device copy of a numpy array."""
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _empty(dev, *shape, dtype=torch.int32) -> torch.Tensor:
+    """The allocation of a call's results: an unwritten tensor on dev, int32 unless told; `partial(_empty, dev)` where a call makes many."""
+    return torch.empty(*shape, dtype=dtype, device=dev)
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """Detached, contiguous and, where the view starts off a 4-byte boundary, copied: the kernels read packed planes as 32-bit words."""
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 4 != 0 else t
+
+
+def _integer_map(who: str, name: str, m, int32: bool = True) -> torch.Tensor:
+    """A non-empty integer tensor or array as a tensor (ValueError otherwise); int32=True: a host map of a wider type is also held to
+    the int32 range, which the kernels read -- a device tensor is the caller's contract, a check would synchronise."""
+    t = torch.as_tensor(m) if isinstance(m, (torch.Tensor, np.ndarray)) else None
+    if t is None or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.numel() < 1:
+        raise ValueError(f"{who}: {name} must be a non-empty integer tensor or array, got {type(m).__name__}")
+    if int32 and not t.is_cuda and t.dtype not in (torch.int32, torch.uint8, torch.int16, torch.int8) and \
+            (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+        raise ValueError(f"{who}: {name} holds a value outside the int32 range")
+    return t
 
 
 MASK_MODES = ("logits", "bits", "both")
@@ -44,19 +174,14 @@ def components_request(*, components=None, min_area=0, connectivity=8, masks="bi
     """Every check of the components= / min_area= / connectivity= arguments of Cascade.infer_classes / decode / mask_components
     (DESIGN.md §14), on the host, before anything is launched (ValueError) -> (asked for, M, min_area, connectivity).  components=None
     with min_area=0 asks for nothing; components=0 asks for the counts without a table.  side: the width of the model's masks."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if components is not None and not (is_int(components) and 0 <= int(components) <= COMPONENTS_MAXM):
-        raise ValueError(f"{who}: components must be None or an int in [0, {COMPONENTS_MAXM}], got {components!r}")
-    if not (is_int(min_area) and int(min_area) >= 0):
-        raise ValueError(f"{who}: min_area must be a non-negative int, got {min_area!r}")
-    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
-        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
-    asked = components is not None or int(min_area) > 0
+    M = 0 if components is None else _int_in(who, "components", components, 0, COMPONENTS_MAXM, none=True)
+    min_area, connectivity = _int_in(who, "min_area", min_area, 0), _connectivity(who, connectivity)
+    asked = components is not None or min_area > 0
     if asked and masks == "logits":
         raise ValueError(f"{who}: components= / min_area= label packed masks: ask for masks='bits' or 'both'")
     if asked and side is not None and side % 32 != 0:
         raise ValueError(f"{who}: components= / min_area= need rows of whole 32-pixel words, the masks are {side} wide")
-    return asked, int(components or 0), int(min_area), int(connectivity)
+    return asked, M, min_area, connectivity
 
 
 @dataclass
@@ -79,19 +204,14 @@ def holes_request(*, holes=None, fill_holes=0, connectivity=8, masks="bits", sid
     before anything is launched (ValueError) -> (asked for, M, fill_below, connectivity).  holes=None with fill_holes=0 asks for nothing;
     holes=0 asks for the counts without a table.  connectivity is the foreground's, shared with components=.  side: the width of the
     model's masks."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if holes is not None and not (is_int(holes) and 0 <= int(holes) <= HOLES_MAXM):
-        raise ValueError(f"{who}: holes must be None or an int in [0, {HOLES_MAXM}], got {holes!r}")
-    if not (is_int(fill_holes) and 0 <= int(fill_holes) < 2 ** 31):
-        raise ValueError(f"{who}: fill_holes must be a non-negative int, got {fill_holes!r}")
-    if not (is_int(connectivity) and int(connectivity) in (4, 8)):
-        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
-    asked = holes is not None or int(fill_holes) > 0
+    M = 0 if holes is None else _int_in(who, "holes", holes, 0, HOLES_MAXM, none=True)
+    fill_holes, connectivity = _int_in(who, "fill_holes", fill_holes, 0, 2 ** 31 - 1), _connectivity(who, connectivity)
+    asked = holes is not None or fill_holes > 0
     if asked and masks == "logits":
         raise ValueError(f"{who}: holes= / fill_holes= label packed masks: ask for masks='bits' or 'both'")
     if asked and side is not None and side % 32 != 0:
         raise ValueError(f"{who}: holes= / fill_holes= need rows of whole 32-pixel words, the masks are {side} wide")
-    return asked, int(holes or 0), int(fill_holes), int(connectivity)
+    return asked, M, fill_holes, connectivity
 
 
 @dataclass
@@ -114,13 +234,12 @@ def morph_request(*, band=None, masks="bits", overlaps=False, side: Optional[int
     (2 r + 1)^2 square, and with overlaps=True for the bands' pairwise intersections as well.  side: the width of the model's masks."""
     if band is None:
         return False, 0, False
-    if isinstance(band, (bool, np.bool_)) or not isinstance(band, (int, np.integer)) or not 1 <= int(band) <= MORPH_MAXR:
-        raise ValueError(f"{who}: band must be None or an int in [1, {MORPH_MAXR}], got {band!r}")
+    band = _int_in(who, "band", band, 1, MORPH_MAXR, none=True)
     if masks == "logits":
         raise ValueError(f"{who}: band= is derived from packed masks: ask for masks='bits' or 'both'")
     if side is not None and side % 32 != 0:
         raise ValueError(f"{who}: band= needs rows of whole 32-pixel words, the masks are {side} wide")
-    return True, int(band), bool(overlaps)
+    return True, band, bool(overlaps)
 
 
 @dataclass
@@ -141,7 +260,7 @@ EDGE_FIELDS = ("edge_bits", "edge_area", "edge_band", "edge_inter")
 def _edge_threshold(edge_threshold, who: str) -> float:
     """The threshold as the float32 the kernel compares against, or ValueError: a real number (no bool, no NaN) strictly between 0
     and 1 whose float32 rounding is strictly between 0 and 1 as well."""
-    if isinstance(edge_threshold, (bool, np.bool_)) or not isinstance(edge_threshold, (int, float, np.integer, np.floating)):
+    if not _is_real(edge_threshold):
         raise ValueError(f"{who}: edge_threshold must be a real number strictly between 0 and 1, got {edge_threshold!r}")
     t = float(edge_threshold)
     with np.errstate(over="ignore", under="ignore"):
@@ -195,10 +314,9 @@ def rle_request(*, rle=None, masks="bits", min_area=0, fill_holes=0, side: Optio
         raise ValueError(f"{who}: rle must be None or one of {tuple(RLE_SOURCES) + (RLE_SIZED,)}, got {rle!r}")
     if masks == "logits":
         raise ValueError(f"{who}: rle= encodes packed masks: ask for masks='bits' or 'both'")
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if rle == "kept" and not (is_int(min_area) and int(min_area) >= 1):
+    if rle == "kept" and not (_is_int(min_area) and int(min_area) >= 1):
         raise ValueError(f"{who}: rle='kept' encodes kept_bits: ask for min_area >= 1")
-    if rle == "filled" and not (is_int(fill_holes) and int(fill_holes) >= 1):
+    if rle == "filled" and not (_is_int(fill_holes) and int(fill_holes) >= 1):
         raise ValueError(f"{who}: rle='filled' encodes filled_bits: ask for fill_holes >= 1")
     if side is not None and side % 32 != 0:
         raise ValueError(f"{who}: rle= needs rows of whole 32-pixel words, the masks are {side} wide")
@@ -266,28 +384,14 @@ def sized_request(*, sizes=None, sized_level=128, n: int, masks="bits", rle=None
     ints, the level).  sizes: one (h, w) per image of the call, 1 <= h, w <= 16384; sized_level: an int in 1 .. 255, the level the
     reference's uint8 mask is compared with (128: the half; 1: demo.py's `> 0` overlay).  They need packed masks (masks="bits" or
     "both"), and rle="sized" needs sizes=."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not is_int(sized_level) or not 1 <= int(sized_level) <= 255:
-        raise ValueError(f"{who}: sized_level must be an int in [1, 255], got {sized_level!r}")
+    sized_level = _int_in(who, "sized_level", sized_level, 1, 255)
     if sizes is None:
         if isinstance(rle, str) and rle == RLE_SIZED:
             raise ValueError(f"{who}: rle='sized' encodes the sized planes: give sizes=")
         return None
     if masks == "logits":
         raise ValueError(f"{who}: sizes= packs masks at the images' sizes: ask for masks='bits' or 'both'")
-    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
-        raise ValueError(f"{who}: sizes must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
-    if len(sizes) != n:
-        raise ValueError(f"{who}: sizes holds {len(sizes)} pairs for {n} images")
-    out = []
-    for pair in sizes:
-        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
-            raise ValueError(f"{who}: sizes must hold (h, w) pairs, got {pair!r}")
-        h, w = pair
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: a size of sizes= must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
-        out.append((int(h), int(w)))
-    return out, int(sized_level)
+    return _plane_sizes(sizes, who, n=n), sized_level
 
 
 @dataclass
@@ -307,9 +411,24 @@ class SizedMasks:
     level: int = 128                # 0: not a threshold -- the planes were decoded from run counts (Cascade.rle_decode)
     #                                 or rasterised from polygons (Cascade.polygons_decode, §21)
 
+    @classmethod
+    def empty(cls, sizes, dev, *, level: int, stats: bool = True, n_status: int = 1):
+        """Unwritten planes of these sizes on `dev`, back to back under offsets of their own (one upload): the bits, area and box (None
+        without stats) and n_status status words -> (the SizedMasks, the planes' dims on the host for the caller to upload, the largest
+        plane's word count)."""
+        dims, offsets, max_words = sized_tables(sizes)
+        P, i32 = len(sizes), partial(_empty, dev)
+        out = cls(bits=_empty(dev, int(offsets[P]), dtype=torch.uint8), offsets=_upload(offsets, dev), area=i32(P) if stats else None,
+                  box=i32(P, 4) if stats else None, status=i32(n_status), sizes=[(int(h), int(w)) for h, w in sizes], level=level)
+        return out, dims, max_words
+
+    def tables(self):
+        """`sized_tables` of these planes, from `sizes` as they are now: (dims, byte offsets, largest word count) on the host."""
+        return sized_tables(self.sizes)
+
     def byte_range(self, p: int) -> Tuple[int, int]:
         """Where plane p lies in `bits`, from the sizes alone (the planes lie back to back): no read of the device."""
-        _, offsets, _ = sized_tables(self.sizes)
+        _, offsets, _ = self.tables()
         return int(offsets[p]), int(offsets[p + 1])
 
     def plane(self, p: int) -> torch.Tensor:
@@ -339,7 +458,7 @@ class SizedMasks:
         ORed into one.  What it is for: `polygons_decode` of an image set's iscrowd = 0 annotations and `rle_decode` of its crowd regions
         as ONE ground_truth= -- the image ids given with it carry the association, so the order is free.  Parts with
         and without area / box do not mix (ValueError); the level is kept where all parts share it and is 0 otherwise."""
-        if isinstance(parts, SizedMasks) or not hasattr(parts, "__len__") or len(parts) < 1 or not all(isinstance(s, SizedMasks) for s in parts):
+        if isinstance(parts, SizedMasks) or not _is_seq(parts) or len(parts) < 1 or not all(isinstance(s, SizedMasks) for s in parts):
             raise ValueError("SizedMasks.concat: a non-empty sequence of SizedMasks")
         parts = list(parts)
         if len({s.area is None for s in parts}) != 1 or any((s.area is None) != (s.box is None) for s in parts):
@@ -347,7 +466,7 @@ class SizedMasks:
         if len({s.bits.device for s in parts}) != 1:
             raise ValueError("SizedMasks.concat: the parts live on different devices")
         sizes = [tuple(z) for s in parts for z in s.sizes]
-        starts = np.cumsum([0] + [sized_tables(s.sizes)[1][-1] for s in parts[:-1]])      # from the sizes alone: no read of the device
+        starts = np.cumsum([0] + [s.tables()[1][-1] for s in parts[:-1]])                 # from the sizes alone: no read of the device
         offsets = torch.cat([parts[0].offsets] + [s.offsets[1:] + int(b) for s, b in zip(parts[1:], starts[1:])])
         stats = parts[0].area is not None
         status = parts[0].status.reshape(-1).ne(0).any().to(torch.int32).reshape(1)
@@ -394,11 +513,8 @@ def labels_request(*, label_maps=False, sizes=None, weights=None, level=128, ove
         raise ValueError(f"{who}: label_maps=True goes with the packed masks: ask for masks='bits' or 'both'")
     if not 1 <= K <= LABELS_MAX_K:
         raise ValueError(f"{who}: a label map holds 1 .. {LABELS_MAX_K} hypotheses per image, got K = {K}")
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not is_int(level) or not 1 <= int(level) <= 255:
-        raise ValueError(f"{who}: the level of a label map must be an int in [1, 255], got {level!r}")
-    is_real = isinstance(overlap_threshold, (int, float, np.integer, np.floating)) and not isinstance(overlap_threshold, (bool, np.bool_))
-    if not is_real or not 0.0 < float(overlap_threshold) <= 1.0:      # a NaN fails the comparison too
+    level = _int_in(who, "the level of a label map", level, 1, 255)
+    if not _is_real(overlap_threshold) or not 0.0 < float(overlap_threshold) <= 1.0:      # a NaN fails the comparison too
         raise ValueError(f"{who}: overlap_threshold must be a real in (0, 1], got {overlap_threshold!r}")
     if isinstance(weights, torch.Tensor) and weights.is_cuda:
         if weights.dtype != torch.float32 or tuple(weights.shape) not in ((n, K), (n * K,)):
@@ -414,7 +530,7 @@ def labels_request(*, label_maps=False, sizes=None, weights=None, level=128, ove
         if np.isnan(host).any():
             raise ValueError(f"{who}: a label weight is NaN: leave the hypothesis out with class -1 instead")
         weights = np.ascontiguousarray(host.reshape(-1), dtype=np.float32)
-    return weights, int(level), float(overlap_threshold)
+    return weights, level, float(overlap_threshold)
 
 
 @dataclass
@@ -469,12 +585,10 @@ class LabelMaps:
     def _lookup(self, table: torch.Tensor, which: str, void: int) -> torch.Tensor:
         if which not in ("winner", "segment"):
             raise ValueError(f"LabelMaps: which must be 'winner' or 'segment', got {which!r}")
-        is_int = isinstance(void, (int, np.integer)) and not isinstance(void, (bool, np.bool_))
-        if not is_int or not -2 ** 31 <= int(void) < 2 ** 31:
-            raise ValueError(f"LabelMaps: void must be an int32 value, got {void!r}")
+        void = _int_in("LabelMaps", "void", void, -2 ** 31, 2 ** 31 - 1)
         out = torch.empty(self.winner.numel(), dtype=torch.int32, device=self.winner.device)
         _, _, max_pixels = label_tables(self.sizes)
-        hip.label_lookup(getattr(self, which), self.B, self.K, self.dims, self.pix_offsets, max_pixels, table, int(void), out, self.status)
+        hip.label_lookup(getattr(self, which), self.B, self.K, self.dims, self.pix_offsets, max_pixels, table, void, out, self.status)
         return out
 
     def categories(self, labels, which: str = "winner", void: int = 255) -> torch.Tensor:
@@ -541,6 +655,13 @@ def _pq_table(who: str, name: str, table, B: int, dtype):
     return host
 
 
+def _image_sizes(sizes, who: str) -> list:
+    """The 1 .. 65535 (h, w) at which the maps of a panoptic call lie image by image -> the pairs as ints (ValueError otherwise)."""
+    if sizes is None:
+        raise ValueError(f"{who}: the maps lie image by image at the images' own sizes: give sizes")
+    return _plane_sizes(sizes, who, of="images")
+
+
 def pq_request(pred_cat, gt_cat, gt_crowd, sizes, *, num_classes, n_pred: int, n_gt: int, who: str = "panoptic_quality"):
     """Every check of the arguments of Cascade.panoptic_quality, on the host, before anything is launched (ValueError)
     -> (the B (h, w) pairs, pred_cat, gt_cat, gt_crowd, G, S): a table is an int32 / uint8 numpy array to upload, or the caller's device
@@ -548,15 +669,9 @@ def pq_request(pred_cat, gt_cat, gt_crowd, sizes, *, num_classes, n_pred: int, n
     and gt_cat (B, G) integers in [-1, num_classes) with -1 in slot 0, which is void; gt_crowd (B, G) of 0 / 1; G * S <= 2^24.  A host
     table is checked value by value; of a device tensor only shape and dtype are (the kernels read a category outside [0,
     num_classes) as "slot unused")."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not is_int(num_classes) or not 1 <= int(num_classes) <= LABELS_MAX_CLASSES:
-        raise ValueError(f"{who}: num_classes must be an int in [1, {LABELS_MAX_CLASSES}], got {num_classes!r}")
-    if sizes is None:
-        raise ValueError(f"{who}: the maps lie image by image at the images' own sizes: give sizes")
-    sizes, _ = sized_request(sizes=sizes, n=len(sizes) if hasattr(sizes, "__len__") else 0, who=who)
+    num_classes = _int_in(who, "num_classes", num_classes, 1, LABELS_MAX_CLASSES)
+    sizes = _image_sizes(sizes, who)
     B = len(sizes)
-    if not 1 <= B <= 65535:
-        raise ValueError(f"{who}: a call scores 1 .. 65535 images, got {B}")
     pixels = sum(h * w for h, w in sizes)
     if n_pred != n_gt:
         raise ValueError(f"{who}: pred holds {n_pred} pixels, gt {n_gt}")
@@ -573,8 +688,8 @@ def pq_request(pred_cat, gt_cat, gt_crowd, sizes, *, num_classes, n_pred: int, n
     for name, t in (("pred_cat", pred_cat), ("gt_cat", gt_cat)):
         if isinstance(t, torch.Tensor):
             continue
-        if int(t.min()) < -1 or int(t.max()) >= int(num_classes):
-            raise ValueError(f"{who}: {name} holds a category outside [-1, {int(num_classes)})")
+        if int(t.min()) < -1 or int(t.max()) >= num_classes:
+            raise ValueError(f"{who}: {name} holds a category outside [-1, {num_classes})")
         if (t[:, 0] != -1).any():
             raise ValueError(f"{who}: slot 0 of {name} is void and must be -1")
     if not isinstance(gt_crowd, torch.Tensor) and gt_crowd.dtype != np.bool_ and (int(gt_crowd.min()) < 0 or int(gt_crowd.max()) > 1):
@@ -588,8 +703,7 @@ def pq_segments_request(segments, B: int, *, num_classes=None, who: str = "panop
     kernels' tables (ValueError otherwise) -> (keys int32, vals int32, table_offsets int64 (B + 1,), gt_cat int32 (B, G), gt_crowd uint8
     (B, G)): keys ascending per image, vals the 1-based position in the annotation, G = the largest count + 1.  An id is an int in [1,
     2^24) (0 is void), unique within its image; a category an int >= 0 (below num_classes where that is given)."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if isinstance(segments, (str, bytes)) or not hasattr(segments, "__len__") or len(segments) != B:
+    if not _is_seq(segments) or len(segments) != B or not all(hasattr(s, "__len__") for s in segments):
         raise ValueError(f"{who}: segments must hold one list of (id, category, iscrowd) per image, {B} in all")
     G = max([len(s) for s in segments] + [0]) + 1
     keys, vals, offsets = [], [], [0]
@@ -597,12 +711,12 @@ def pq_segments_request(segments, B: int, *, num_classes=None, who: str = "panop
     for b, segs in enumerate(segments):
         ids = []
         for i, seg in enumerate(segs):
-            if isinstance(seg, (str, bytes)) or not hasattr(seg, "__len__") or len(seg) != 3:
+            if not _is_seq(seg) or len(seg) != 3:
                 raise ValueError(f"{who}: a segment is (id, category, iscrowd), got {seg!r}")
             sid, cat, crowd = seg
-            if not is_int(sid) or not 1 <= int(sid) < 2 ** 24:
+            if not _is_int(sid) or not 1 <= int(sid) < 2 ** 24:
                 raise ValueError(f"{who}: a segment id must be an int in [1, 2^24), got {sid!r}")
-            if not is_int(cat) or int(cat) < 0 or (num_classes is not None and int(cat) >= int(num_classes)):
+            if not _is_int(cat) or int(cat) < 0 or (num_classes is not None and int(cat) >= int(num_classes)):
                 raise ValueError(f"{who}: a segment's category must be an int >= 0 and below num_classes, got {cat!r}")
             if crowd not in (0, 1, False, True):
                 raise ValueError(f"{who}: iscrowd must be 0 or 1, got {crowd!r}")
@@ -669,8 +783,7 @@ def rle_decode_request(rles, who: str = "rle_decode"):
     A string is COCO's compressed form (rle.string_to_counts).  h and w are ints in [1, 16384]; the counts are non-negative -- zeros are
     legal anywhere, pycocotools emits them -- and sum to h * w."""
     from . import rle as _rle
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if isinstance(rles, (str, bytes, dict)) or not hasattr(rles, "__len__") or not hasattr(rles, "__iter__"):
+    if isinstance(rles, dict) or not _is_seq(rles) or not hasattr(rles, "__iter__"):
         raise ValueError(f"{who}: rles must be a sequence of COCO dicts, got {type(rles).__name__}")
     if not 1 <= len(rles) <= 65535:
         raise ValueError(f"{who}: 1 .. 65535 planes, got {len(rles)}")
@@ -678,27 +791,22 @@ def rle_decode_request(rles, who: str = "rle_decode"):
     for i, d in enumerate(rles):
         if not isinstance(d, dict) or "size" not in d or "counts" not in d:
             raise ValueError(f"{who}: entry {i} must be a dict with 'size' and 'counts'")
-        size = d["size"]
-        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
-            raise ValueError(f"{who}: entry {i}: size must be [h, w], got {size!r}")
-        h, w = size
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: entry {i}: size must be two ints in [1, {SIZED_MAX_SIDE}], got {size!r}")
+        h, w = _size_pair(who, f"entry {i}: size", d["size"])
         c = d["counts"]
         if isinstance(c, (bytes, str)):
             c = _rle.string_to_counts(c)
         else:
             if isinstance(c, dict) or not hasattr(c, "__len__"):
                 raise ValueError(f"{who}: entry {i}: counts must be a list of ints, bytes or str, got {type(c).__name__}")
-            if not isinstance(c, np.ndarray) and not all(is_int(v) for v in c):
+            if not isinstance(c, np.ndarray) and not all(_is_int(v) for v in c):
                 raise ValueError(f"{who}: entry {i}: counts must hold ints")
             c = np.asarray(c)
             if c.ndim != 1 or (c.size and c.dtype.kind not in "iu"):
                 raise ValueError(f"{who}: entry {i}: counts must be a flat sequence of ints")
             c = c.astype(np.int64)
-        if c.size == 0 or bool((c < 0).any()) or int(c.sum()) != int(h) * int(w):
+        if c.size == 0 or bool((c < 0).any()) or int(c.sum()) != h * w:
             raise ValueError(f"{who}: entry {i}: {c.size} counts summing to {int(c.sum())} do not describe a plane of {h} x {w}")
-        sizes.append((int(h), int(w)))
+        sizes.append((h, w))
         parts.append(c.astype(np.int32))
     offsets = np.zeros(len(parts) + 1, dtype=np.int64)
     np.cumsum([p.size for p in parts], out=offsets[1:])
@@ -718,8 +826,7 @@ def polygons_request(anns, who: str = "polygons_decode"):
     65535 planes; h and w ints in [1, 16384]; 1 .. 4096 polygons per plane; a polygon is a flat sequence of an even number of real
     numbers, 3 .. 65535 vertices, finite, |c| <= 65536, and walks at most 2^24 points -- counted here as the kernel counts them, in
     numpy over the polygon's vertices."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if isinstance(anns, (str, bytes, dict)) or not hasattr(anns, "__len__") or not hasattr(anns, "__iter__"):
+    if isinstance(anns, dict) or not _is_seq(anns) or not hasattr(anns, "__iter__"):
         raise ValueError(f"{who}: anns must be a sequence of dicts with 'size' and 'polygons', got {type(anns).__name__}")
     if not 1 <= len(anns) <= 65535:
         raise ValueError(f"{who}: 1 .. 65535 planes, got {len(anns)}")
@@ -727,17 +834,12 @@ def polygons_request(anns, who: str = "polygons_decode"):
     for i, d in enumerate(anns):
         if not isinstance(d, dict) or "size" not in d or "polygons" not in d:
             raise ValueError(f"{who}: entry {i} must be a dict with 'size' and 'polygons'")
-        size = d["size"]
-        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != 2:
-            raise ValueError(f"{who}: entry {i}: size must be [h, w], got {size!r}")
-        h, w = size
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: entry {i}: size must be two ints in [1, {SIZED_MAX_SIDE}], got {size!r}")
+        size = _size_pair(who, f"entry {i}: size", d["size"])
         polys = d["polygons"]
-        if isinstance(polys, (str, bytes, dict)) or not hasattr(polys, "__len__") or not 1 <= len(polys) <= POLY_MAX_POLYS:
+        if isinstance(polys, dict) or not _is_seq(polys) or not 1 <= len(polys) <= POLY_MAX_POLYS:
             raise ValueError(f"{who}: entry {i}: polygons must be a list of 1 .. {POLY_MAX_POLYS} polygons")
         for j, poly in enumerate(polys):
-            if isinstance(poly, (str, bytes, dict)) or not hasattr(poly, "__len__"):
+            if isinstance(poly, dict) or not _is_seq(poly):
                 raise ValueError(f"{who}: entry {i}, polygon {j}: a flat sequence of numbers, got {type(poly).__name__}")
             try:
                 a = np.asarray(poly)
@@ -755,7 +857,7 @@ def polygons_request(anns, who: str = "polygons_decode"):
             if int(step.sum()) > POLY_MAX_POINTS:
                 raise ValueError(f"{who}: entry {i}, polygon {j}: {int(step.sum())} walk points, at most {POLY_MAX_POINTS} are taken")
             parts.append(a)
-        sizes.append((int(h), int(w)))
+        sizes.append(size)
         per_plane.append(len(polys))
     offsets = np.zeros(len(parts) + 1, dtype=np.int64)
     np.cumsum([p.size for p in parts], out=offsets[1:])
@@ -769,7 +871,6 @@ def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, w
     (ValueError) -> int32 (N, 2) on the host, or the caller's device tensor as it is.  Either pairs= -- (N, 2) ints (plane of a, plane of
     b), in range; a tensor on the device is only checked by shape and left to the kernel --, or a_image= and b_image=, one image id per
     plane of each: all (p, q) with a_image[p] == b_image[q], ordered by p, then q.  1 <= N <= 2^20."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     Pa, Pb = len(a_sizes), len(b_sizes)
     if (pairs is None) == (a_image is None and b_image is None) or (a_image is None) != (b_image is None):
         raise ValueError(f"{who}: give either pairs= or both a_image= and b_image=")
@@ -787,11 +888,7 @@ def pairs_request(a_sizes, b_sizes, *, pairs=None, a_image=None, b_image=None, w
         if bool((arr < 0).any()) or bool((arr[:, 0] >= Pa).any()) or bool((arr[:, 1] >= Pb).any()):
             raise ValueError(f"{who}: a pair names a plane outside [0, {Pa}) x [0, {Pb})")
         return np.ascontiguousarray(arr.astype(np.int32))
-    ids = []
-    for name, seq, P in (("a_image", a_image, Pa), ("b_image", b_image, Pb)):
-        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
-            raise ValueError(f"{who}: {name} must hold one int per plane, {P} of them")
-        ids.append(np.asarray([int(v) for v in seq], dtype=np.int64))
+    ids = [np.asarray(_int_list(who, name, seq, P), dtype=np.int64) for name, seq, P in (("a_image", a_image, Pa), ("b_image", b_image, Pb))]
     p, q = np.nonzero(ids[0][:, None] == ids[1][None, :])             # row-major: ordered by p, then q
     if not 1 <= p.size <= 1 << 20:
         raise ValueError(f"{who}: the image ids give {p.size} pairs, 1 .. 2^20 are taken")
@@ -820,9 +917,7 @@ def boundary_request(sizes, *, dilation_ratio=BOUNDARY_RATIO, radius=None, who: 
     dilation_ratio: a finite real > 0 (no bool), the share of each plane's own diagonal (`boundary_radius`); a plane whose radius would
     exceed 16384 is refused.  radius: instead of it, one int in [1, 16384] for all planes or one per plane (no bools); together with a
     dilation_ratio other than the default it is a contradiction."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    is_real = isinstance(dilation_ratio, (int, float, np.integer, np.floating)) and not isinstance(dilation_ratio, (bool, np.bool_))
-    if not is_real or not np.isfinite(float(dilation_ratio)) or not float(dilation_ratio) > 0.0:
+    if not _is_real(dilation_ratio) or not np.isfinite(float(dilation_ratio)) or not float(dilation_ratio) > 0.0:
         raise ValueError(f"{who}: the dilation ratio must be a finite real > 0, got {dilation_ratio!r}")
     P = len(sizes)
     if radius is None:
@@ -832,13 +927,7 @@ def boundary_request(sizes, *, dilation_ratio=BOUNDARY_RATIO, radius=None, who: 
         return np.asarray(out, dtype=np.int32).reshape(P)
     if float(dilation_ratio) != BOUNDARY_RATIO:
         raise ValueError(f"{who}: give either radius= or a dilation ratio, not both")
-    if is_int(radius):
-        radius = [radius] * P
-    if isinstance(radius, (str, bytes)) or not hasattr(radius, "__len__") or len(radius) != P or not all(is_int(v) for v in radius):
-        raise ValueError(f"{who}: radius must be an int or hold one int per plane, {P} of them")
-    if not all(1 <= int(v) <= BOUNDARY_MAX_RADIUS for v in radius):
-        raise ValueError(f"{who}: a radius must lie in [1, {BOUNDARY_MAX_RADIUS}]")
-    return np.asarray([int(v) for v in radius], dtype=np.int32).reshape(P)
+    return _per_plane_ints(who, "radius", radius, P, 1, BOUNDARY_MAX_RADIUS)
 
 
 CONTOUR_MAX_VERTS = 1 << 22       # vertices of one plane's contour (csrc/contour_logic.h: CT_MAX_VERTS)
@@ -848,22 +937,8 @@ def contour_request(sizes, *, connectivity=8, who: str = "mask_contours_sized"):
     """Every check of the arguments of Cascade.mask_contours_sized, on the host, before anything is launched
     (ValueError) -> (the (h, w) pairs as ints, the connectivity).  sizes: 1 .. 65535 pairs of ints in [1, 16384], no bools;
     connectivity: the int 4 or 8, no bool -- how the foreground hangs together where two pixels touch at a corner."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not is_int(connectivity) or int(connectivity) not in (4, 8):
-        raise ValueError(f"{who}: connectivity must be the int 4 or 8, got {connectivity!r}")
-    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
-        raise ValueError(f"{who}: sizes must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
-    if not 1 <= len(sizes) <= 65535:
-        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(sizes)}")
-    out = []
-    for pair in sizes:
-        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
-            raise ValueError(f"{who}: sizes must hold (h, w) pairs, got {pair!r}")
-        h, w = pair
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: a size must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
-        out.append((int(h), int(w)))
-    return out, int(connectivity)
+    connectivity = _connectivity(who, connectivity)
+    return _plane_sizes(sizes, who), connectivity
 
 
 def contour_rounds(n_vertices, max_words: int, cap: int, need) -> list:
@@ -952,45 +1027,13 @@ def surface_tolerance(h: int, w: int, ratio: float = SURFACE_RATIO) -> int:
     return int(np.ceil(ratio * np.sqrt(h ** 2 + w ** 2))) if ratio < 1 else int(np.ceil(ratio))
 
 
-def _plane_sizes(sizes, who: str, name: str = "sizes") -> list:
-    """1 .. 65535 (h, w) pairs of ints in [1, 16384], no bools -> the pairs as ints (ValueError otherwise)."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__len__") or not hasattr(sizes, "__iter__"):
-        raise ValueError(f"{who}: {name} must be a sequence of (h, w) pairs, got {type(sizes).__name__}")
-    if not 1 <= len(sizes) <= 65535:
-        raise ValueError(f"{who}: 1 .. 65535 planes, got {len(sizes)}")
-    out = []
-    for pair in sizes:
-        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
-            raise ValueError(f"{who}: {name} must hold (h, w) pairs, got {pair!r}")
-        h, w = pair
-        if not is_int(h) or not is_int(w) or not 1 <= int(h) <= SIZED_MAX_SIDE or not 1 <= int(w) <= SIZED_MAX_SIDE:
-            raise ValueError(f"{who}: a size must be two ints in [1, {SIZED_MAX_SIDE}], got {pair!r}")
-        out.append((int(h), int(w)))
-    return out
-
-
-def _reaches(reach, P: int, who: str) -> np.ndarray:
-    """reach= as one int in [0, 23170] for all planes or one per plane, None for 0 (unlimited), no bools -> int32 (P,)."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if reach is None:
-        reach = 0
-    if is_int(reach):
-        reach = [reach] * P
-    if isinstance(reach, (str, bytes)) or not hasattr(reach, "__len__") or len(reach) != P or not all(is_int(v) for v in reach):
-        raise ValueError(f"{who}: reach must be None, an int or hold one int per plane, {P} of them")
-    if not all(0 <= int(v) <= DISTANCE_MAX_REACH for v in reach):
-        raise ValueError(f"{who}: a reach must lie in [0, {DISTANCE_MAX_REACH}]")
-    return np.asarray([int(v) for v in reach], dtype=np.int32).reshape(P)
-
-
 def distance_request(sizes, *, reach=None, who: str = "mask_distance_sized"):
     """Every check of the arguments of Cascade.mask_distance_sized, on the host, before anything is launched
     (ValueError) -> (the (h, w) pairs as ints, the reach of each plane as int32 (P,)).  sizes: 1 .. 65535 pairs of ints in [1, 16384];
     reach: None or 0 for an unlimited search, or an int in [1, 23170] -- for all planes or one per plane -- beyond which a pixel is
     far; no bools."""
     sizes = _plane_sizes(sizes, who)
-    return sizes, _reaches(reach, len(sizes), who)
+    return sizes, _per_plane_ints(who, "reach", reach, len(sizes), 0, DISTANCE_MAX_REACH, none=True)
 
 
 @dataclass
@@ -1011,14 +1054,11 @@ def surface_request(a_sizes, b_sizes, *, pairs=None, tolerance=SURFACE_RATIO, re
     each an int in [0, 23170] -- pixels -- or a real in (0, 1) -- a share of the pair's diagonal, `surface_tolerance` --; no bools.
     reach: None -- unlimited --, an int in [0, 23170] for every plane, or "tolerance": each plane's reach is the largest radius of the
     pairs that name it (1 at least), the cheap path when only NSD and F are wanted."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    is_real = lambda v: isinstance(v, (float, np.floating))
+    is_ratio = lambda v: isinstance(v, (float, np.floating))          # an int is a pixel count, whatever its value
     a_sizes, b_sizes = _plane_sizes(a_sizes, who, "a's sizes"), _plane_sizes(b_sizes, who, "b's sizes")
     Pa, Pb = len(a_sizes), len(b_sizes)
     if pairs is None:
-        if Pa != Pb:
-            raise ValueError(f"{who}: without pairs= both sides need as many planes, got {Pa} and {Pb}")
-        arr = np.stack([np.arange(Pa), np.arange(Pa)], axis=1)
+        arr = _plane_by_plane(who, Pa, Pb)
     else:
         if isinstance(pairs, (str, bytes)) or isinstance(pairs, torch.Tensor) and pairs.is_cuda:
             raise ValueError(f"{who}: pairs must be (N, 2) ints on the host")
@@ -1035,14 +1075,14 @@ def surface_request(a_sizes, b_sizes, *, pairs=None, tolerance=SURFACE_RATIO, re
     if bool((dims_a != dims_b).any()):
         i = int(np.nonzero((dims_a != dims_b).any(axis=1))[0][0])
         raise ValueError(f"{who}: pair {i} holds planes of different sizes, {tuple(dims_a[i])} and {tuple(dims_b[i])}")
-    tols = [tolerance] if is_int(tolerance) or is_real(tolerance) else tolerance
-    if isinstance(tols, (str, bytes, bool, np.bool_)) or not hasattr(tols, "__len__") or not 1 <= len(tols) <= SURFACE_MAX_T:
+    tols = [tolerance] if _is_int(tolerance) or is_ratio(tolerance) else tolerance
+    if not _is_seq(tols) or not 1 <= len(tols) <= SURFACE_MAX_T:
         raise ValueError(f"{who}: tolerance must be one tolerance or 1 .. {SURFACE_MAX_T} of them, got {tolerance!r}")
     radii = np.empty((arr.shape[0], len(tols)), dtype=np.int32)
     for k, t in enumerate(tols):
-        if is_int(t) and 0 <= int(t) <= DISTANCE_MAX_REACH:
+        if _is_int(t) and 0 <= int(t) <= DISTANCE_MAX_REACH:
             radii[:, k] = int(t)
-        elif is_real(t) and 0.0 < float(t) < 1.0:
+        elif is_ratio(t) and 0.0 < float(t) < 1.0:
             radii[:, k] = [surface_tolerance(int(h), int(w), float(t)) for h, w in dims_a]
         else:
             raise ValueError(f"{who}: a tolerance must be an int in [0, {DISTANCE_MAX_REACH}] or a ratio in (0, 1), got {t!r}")
@@ -1051,8 +1091,8 @@ def surface_request(a_sizes, b_sizes, *, pairs=None, tolerance=SURFACE_RATIO, re
         reach_a, reach_b = np.ones(Pa, dtype=np.int32), np.ones(Pb, dtype=np.int32)
         np.maximum.at(reach_a, arr[:, 0], top)
         np.maximum.at(reach_b, arr[:, 1], top)
-    elif reach is None or is_int(reach):
-        reach_a, reach_b = _reaches(reach, Pa, who), _reaches(reach, Pb, who)
+    elif reach is None or _is_int(reach):
+        reach_a, reach_b = (_per_plane_ints(who, "reach", reach, P, 0, DISTANCE_MAX_REACH, none=True) for P in (Pa, Pb))
     else:
         raise ValueError(f"{who}: reach must be None, an int in [0, {DISTANCE_MAX_REACH}] or 'tolerance', got {reach!r}")
     return SurfaceRequest(a_sizes=a_sizes, b_sizes=b_sizes, pairs=arr, radii=radii, reach_a=reach_a, reach_b=reach_b)
@@ -1147,23 +1187,11 @@ def thin_request(sizes, *, max_iter=None, path="auto", steps=64, who: str = "mas
     pairs of ints in [1, 16384]; max_iter: None -- thin to the fixed point --, an int in [1, 2^30] for all planes or one such per
     plane; path: "auto" -- a plane that fits the resident kernel's LDS is thinned there, the others in rounds of `steps` stepped
     iterations -- or "steps": every plane is stepped; steps: an int in [1, 1024]; no bools."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     sizes = _plane_sizes(sizes, who)
-    P = len(sizes)
-    if max_iter is None:
-        limits = np.zeros(P, dtype=np.int32)
-    else:
-        seq = [max_iter] * P if is_int(max_iter) else max_iter
-        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
-            raise ValueError(f"{who}: max_iter must be None, an int or hold one int per plane, {P} of them")
-        if not all(1 <= int(v) <= THIN_MAX_ITER for v in seq):
-            raise ValueError(f"{who}: a max_iter must lie in [1, 2^30]")
-        limits = np.asarray([int(v) for v in seq], dtype=np.int32).reshape(P)
+    limits = _per_plane_ints(who, "max_iter", max_iter, len(sizes), 1, THIN_MAX_ITER, none=True)
     if not isinstance(path, str) or path not in THIN_PATHS:
         raise ValueError(f"{who}: path must be 'auto' or 'steps', got {path!r}")
-    if not is_int(steps) or not 1 <= int(steps) <= THIN_MAX_STEPS:
-        raise ValueError(f"{who}: steps must be an int in [1, {THIN_MAX_STEPS}], got {steps!r}")
-    return sizes, limits, THIN_PATHS.index(path), int(steps)
+    return sizes, limits, THIN_PATHS.index(path), _int_in(who, "steps", steps, 1, THIN_MAX_STEPS)
 
 
 @dataclass
@@ -1215,15 +1243,9 @@ def regions_request(sizes, *, regions=8, min_area=0, connectivity=8, who: str = 
     -> (the (h, w) pairs as ints, M, min_area, connectivity).  sizes: 1 .. 65535 pairs of ints in [1, 16384]; regions: an int in
     [1, 64], the slots each plane is split into; min_area: an int in [0, 2^31), regions below it are neither counted nor kept (0 and 1
     keep every region); connectivity: 4 or 8; no bools."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     sizes = _plane_sizes(sizes, who)
-    if not is_int(regions) or not 1 <= int(regions) <= REGIONS_MAXM:
-        raise ValueError(f"{who}: regions must be an int in [1, {REGIONS_MAXM}], got {regions!r}")
-    if not is_int(min_area) or not 0 <= int(min_area) < 2 ** 31:
-        raise ValueError(f"{who}: min_area must be an int in [0, 2^31), got {min_area!r}")
-    if not is_int(connectivity) or int(connectivity) not in (4, 8):
-        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
-    return sizes, int(regions), int(min_area), int(connectivity)
+    return (sizes, _int_in(who, "regions", regions, 1, REGIONS_MAXM), _int_in(who, "min_area", min_area, 0, 2 ** 31 - 1),
+            _connectivity(who, connectivity))
 
 
 @dataclass
@@ -1254,7 +1276,7 @@ class MaskRegions:
         real = np.minimum(host[:P].astype(np.int64), M)
         plane_of = np.repeat(np.arange(P, dtype=np.int64), real)
         rank = np.concatenate([np.arange(r, dtype=np.int64) for r in real]) if P else np.zeros(0, np.int64)
-        _, off, _ = sized_tables(src.sizes)                           # of the P * M slots, from the sizes alone
+        _, off, _ = src.tables()                                      # of the P * M slots, from the sizes alone
         keep = [p for p in range(P) if real[p] > 0]
         cat = lambda parts, empty: torch.cat(parts) if parts else empty
         bits = cat([src.bits[int(off[p * M]):int(off[p * M + real[p]])] for p in keep], src.bits[:0])
@@ -1262,8 +1284,7 @@ class MaskRegions:
         box = cat([src.box[p * M:p * M + int(real[p])] for p in keep], src.box[:0])
         sizes = [src.sizes[p * M] for p in plane_of]
         offsets = np.zeros(1, np.int64) if not sizes else sized_tables(sizes)[1]
-        out = SizedMasks(bits=bits, offsets=torch.from_numpy(offsets).to(src.bits.device), area=area, box=box, status=src.status, sizes=sizes,
-                         level=src.level)
+        out = SizedMasks(bits=bits, offsets=_upload(offsets, src.bits.device), area=area, box=box, status=src.status, sizes=sizes, level=src.level)
         return out, plane_of, rank
 
 
@@ -1334,13 +1355,10 @@ def match_request(det_sizes, gt_sizes, *, det_image, gt_image, det_category=None
     annotation; scores: None (they are on the device) or one number per detection, no NaN.  iou_thrs: 1 .. 16 numbers in (0, 1], default
     COCO's ten; area_rngs: 1 .. 8 pairs lo <= hi, default all / small / medium / large; max_det: an int >= 1.  All planes of a group have
     one size; a group has at most 1024 detections and 1024 annotations; all groups together at most 2^20 pairs."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not hasattr(det_sizes, "__len__") or not hasattr(gt_sizes, "__len__"):
+        raise ValueError(f"{who}: det_sizes and gt_sizes must be sequences of (h, w) pairs")
     Pd, Pg = len(det_sizes), len(gt_sizes)
-
-    def ints(name, seq, P):
-        if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != P or not all(is_int(v) for v in seq):
-            raise ValueError(f"{who}: {name} must hold one int per plane, {P} of them")
-        return np.asarray([int(v) for v in seq], dtype=np.int64)
+    ints = lambda name, seq, P: np.asarray(_int_list(who, name, seq, P), dtype=np.int64)
 
     def reals(name, seq, P, what):
         try:
@@ -1377,9 +1395,8 @@ def match_request(det_sizes, gt_sizes, *, det_image, gt_image, det_category=None
         raise ValueError(f"{who}: iou_thrs must be 1 .. {MATCH_MAX_T} numbers in (0, 1]")
     if rngs.ndim != 2 or rngs.shape[1] != 2 or not 1 <= rngs.shape[0] <= MATCH_MAX_A or not bool((rngs[:, 0] <= rngs[:, 1]).all()):
         raise ValueError(f"{who}: area_rngs must be 1 .. {MATCH_MAX_A} pairs (lo, hi) with lo <= hi")
-    if not is_int(max_det) or not 1 <= int(max_det) < 2 ** 31:
-        raise ValueError(f"{who}: max_det must be an int >= 1, got {max_det!r}")
-    rows = {}                                                         # (category, image) -> ([detection planes], [annotation planes])
+    max_det = _int_in(who, "max_det", max_det, 1, 2 ** 31 - 1)
+    rows = {}                                                       # (category, image) -> ([detection planes], [annotation planes])
     for side, (cat, img) in enumerate(((d_cat, d_img), (g_cat, g_img))):
         for p, key in enumerate(zip(cat.tolist(), img.tolist())):
             rows.setdefault(key, ([], []))[side].append(p)
@@ -1405,7 +1422,7 @@ def match_request(det_sizes, gt_sizes, *, det_image, gt_image, det_category=None
     return MatchRequest(keys=[(k[0] if cats else None, k[1]) for k in keys], det_perm=det_perm, gt_perm=gt_perm, det_offsets=offs(D, np.int32),
                         gt_offsets=offs(G, np.int32), pair_offsets=offs([d * g for d, g in zip(D, G)], np.int64),
                         pairs=np.ascontiguousarray(pairs), crowd=crowd[gt_perm], range_area=None if ra is None else ra[gt_perm],
-                        scores=None if sc is None else sc[det_perm], iou_thrs=thrs, area_rngs=np.ascontiguousarray(rngs), max_det=int(max_det))
+                        scores=None if sc is None else sc[det_perm], iou_thrs=thrs, area_rngs=np.ascontiguousarray(rngs), max_det=max_det)
 
 
 NMS_MAX_PAIRS = 1 << 22           # pairs of one call (csrc/nms_logic.h: NM_MAX_PAIRS)
@@ -1436,23 +1453,19 @@ def nms_request(sizes, *, image, iou=0.5, measure="iou", method="greedy", sigma=
     above it); measure: "iou" or "min" (intersection over the smaller area); method: "greedy", "linear" or "gaussian" (Matrix NMS);
     sigma: a finite number > 0, the gaussian's.  All planes of a group have one size; a group has at most 1024 instances; all groups
     together at most 2^22 pairs.  No bools."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    is_real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
     sizes = _plane_sizes(sizes, who)
-    Q = len(sizes)
-    if isinstance(image, (str, bytes)) or not hasattr(image, "__len__") or len(image) != Q or not all(is_int(v) for v in image):
-        raise ValueError(f"{who}: image must hold one int per instance, {Q} of them")
-    if not is_real(iou) or not 0.0 <= float(iou) <= 1.0:
+    image = _int_list(who, "image", image, len(sizes), "instance")
+    if not _is_real(iou) or not 0.0 <= float(iou) <= 1.0:
         raise ValueError(f"{who}: iou must be a number in [0, 1], got {iou!r}")
     if not isinstance(measure, str) or measure not in hip.NMS_MEASURES:
         raise ValueError(f"{who}: measure must be one of {sorted(hip.NMS_MEASURES)}, got {measure!r}")
     if not isinstance(method, str) or method not in hip.NMS_METHODS:
         raise ValueError(f"{who}: method must be one of {sorted(hip.NMS_METHODS)}, got {method!r}")
-    if not is_real(sigma) or not np.isfinite(float(sigma)) or not float(sigma) > 0.0:
+    if not _is_real(sigma) or not np.isfinite(float(sigma)) or not float(sigma) > 0.0:
         raise ValueError(f"{who}: sigma must be a finite number > 0, got {sigma!r}")
     rows = {}
     for q, img in enumerate(image):
-        rows.setdefault(int(img), []).append(q)
+        rows.setdefault(img, []).append(q)
     keys = sorted(rows)
     for k in keys:
         if len(rows[k]) > MATCH_CAP:
@@ -1504,7 +1517,7 @@ class MaskNms:
         so the result is one slice of bits per run of kept rows, by byte ranges from the sizes alone -- the style of
         MaskRegions.compact."""
         Q = int(self.keep.numel())
-        if not isinstance(instances, SizedMasks) or len(instances.sizes) != Q or instances.area is None:
+        if not isinstance(instances, SizedMasks) or len(instances.sizes) != Q or instances.area is None:      # as the call took them: Q may be 0
             raise ValueError(f"MaskNms.select: instances must be the SizedMasks of the call, {Q} planes with areas")
         host = torch.cat([self.status.reshape(-1).view(torch.uint8), self.keep.reshape(-1)]).cpu().numpy()
         n_status = 4 * int(self.status.numel())
@@ -1512,7 +1525,7 @@ class MaskNms:
             raise RuntimeError("mask_nms_sized: cvlm_mask_nms_inter or cvlm_mask_nms refused a pair or a group: a slice that does not fit "
                                "its size, or a box outside its plane")
         idx = np.flatnonzero(host[n_status:]).astype(np.int64)
-        _, off, _ = sized_tables(instances.sizes) if Q else (None, np.zeros(1, np.int64), 0)
+        _, off, _ = instances.tables() if Q else (None, np.zeros(1, np.int64), 0)
         starts = [int(q) for k, q in enumerate(idx) if k == 0 or idx[k - 1] != q - 1]
         ends = [int(q) + 1 for k, q in enumerate(idx) if k + 1 == idx.size or idx[k + 1] != q + 1]
         cat = lambda parts, empty: torch.cat(parts) if parts else empty
@@ -1521,8 +1534,8 @@ class MaskNms:
         box = cat([instances.box[a:b] for a, b in zip(starts, ends)], instances.box[:0])
         sizes = [instances.sizes[int(q)] for q in idx]
         offsets = np.zeros(1, np.int64) if not sizes else sized_tables(sizes)[1]
-        out = SizedMasks(bits=bits, offsets=torch.from_numpy(offsets).to(instances.bits.device), area=area, box=box,
-                         status=instances.status, sizes=sizes, level=instances.level)
+        out = SizedMasks(bits=bits, offsets=_upload(offsets, instances.bits.device), area=area, box=box, status=instances.status, sizes=sizes,
+                         level=instances.level)
         return out, idx
 
 
@@ -1586,21 +1599,20 @@ def sized_images(images, device) -> SizedImages:
             host = im.detach().numpy() if isinstance(im, torch.Tensor) else im
             flat[int(offsets[b]):int(offsets[b]) + host.size] = np.ascontiguousarray(host).reshape(-1)
     dev = torch.device(device)
-    data = torch.from_numpy(flat).to(dev)
+    data = _upload(flat, dev)
     for b, im in enumerate(images):
         if isinstance(im, torch.Tensor) and im.is_cuda:
             data[int(offsets[b]):int(offsets[b]) + im.numel()] = im.detach().to(dev).reshape(-1)
-    return SizedImages(data=data, offsets=torch.from_numpy(offsets).to(dev), dims=torch.from_numpy(dims).to(dev), sizes=sizes)
+    return SizedImages(data=data, offsets=_upload(offsets, dev), dims=_upload(dims, dev), sizes=sizes)
 
 
 def palette(n: int) -> np.ndarray:
     """A deterministic colour table, uint8 (n, 3), by the well-known bit-interleave rule: bits 0, 1 and 2 of the id feed r, g and b from
     the top bit down, three bits of the id per round -- 0 black, 1 (128, 0, 0), 2 (0, 128, 0), 3 (128, 128, 0), 4 (0, 0, 128), ..., 15
     (192, 128, 128), ..., 255 (224, 224, 192); ids from 256 on repeat the table."""
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= RENDER_MAX_ROWS:
-        raise ValueError(f"palette: n must be an int in [1, {RENDER_MAX_ROWS}], got {n!r}")
-    ids = np.arange(int(n), dtype=np.int64) & 255
-    out = np.zeros((int(n), 3), dtype=np.uint8)
+    n = _int_in("palette", "n", n, 1, RENDER_MAX_ROWS)
+    ids = np.arange(n, dtype=np.int64) & 255
+    out = np.zeros((n, 3), dtype=np.uint8)
     for j in range(8):
         for ch in range(3):
             out[:, ch] |= (((ids >> (3 * j + ch)) & 1) << (7 - j)).astype(np.uint8)
@@ -1647,7 +1659,7 @@ def _render_alphas(who: str, v, n: int) -> np.ndarray:
 
 
 def _render_index(who: str, name: str, v, n: int) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < n:
+    if not _is_int(v) or not 0 <= int(v) < n:
         raise ValueError(f"{who}: {name} must be an int in [0, {n}), got {v!r}")
     return int(v)
 
@@ -1711,11 +1723,9 @@ def render_request(sizes, layers, *, device=None, who: str = "render") -> Render
     sizes: the (h, w) of each image; layers: one sequence of RenderLayers per image, in painter's order (an empty one: the image is
     copied).  A layer's plane or map has the size of the image it is painted on and lies inside its source; colours are ints in 0 ..
     255; alphas are finite and in [0, 1]; a LUT has 256 rows; sources live on `device`; at most 2^20 layers and 2^24 table rows."""
-    sizes = _plane_sizes(sizes, who)
+    sizes = _plane_sizes(sizes, who)                                  # 65535 at most: RENDER_MAX_IMAGES
     B = len(sizes)
-    if B > RENDER_MAX_IMAGES:
-        raise ValueError(f"{who}: at most {RENDER_MAX_IMAGES} images are taken, got {B}")
-    if isinstance(layers, (str, bytes, RenderLayer)) or not hasattr(layers, "__len__") or len(layers) != B or \
+    if isinstance(layers, RenderLayer) or not _is_seq(layers) or len(layers) != B or \
             any(isinstance(ls, (str, bytes, RenderLayer)) or not hasattr(ls, "__iter__") for ls in layers):
         raise ValueError(f"{who}: layers must hold one sequence of layers per image, {B} of them")
     rows, rgb, alpha, counts = [], [], [], []
@@ -1824,19 +1834,13 @@ def ground_truth_request(ground_truth, sreq, n: int, who: str = "decode"):
     the annotation belongs to; it needs sizes=, and every gt.sizes[q] must be the size of image gt_image[q]."""
     if ground_truth is None:
         return None
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     if not isinstance(ground_truth, (tuple, list)) or len(ground_truth) != 2 or not isinstance(ground_truth[0], SizedMasks):
         raise ValueError(f"{who}: ground_truth must be (SizedMasks, image id of each of its planes)")
     gt, ids = ground_truth
     if sreq is None:
         raise ValueError(f"{who}: ground_truth= is held against the sized planes: give sizes=")
-    if gt.area is None or not gt.bits.is_cuda:
-        raise ValueError(f"{who}: ground_truth= needs planes on the device with their areas (rle_decode(stats=True))")
-    if isinstance(ids, (str, bytes)) or not hasattr(ids, "__len__") or len(ids) != len(gt.sizes) or not all(is_int(v) for v in ids):
-        raise ValueError(f"{who}: ground_truth= needs one int image id per annotation, {len(gt.sizes)} of them")
-    ids = [int(v) for v in ids]
-    if not 1 <= len(ids) <= 65535:
-        raise ValueError(f"{who}: ground_truth= takes 1 .. 65535 annotations")
+    _sized_arg(who, "the annotations of ground_truth=", gt, areas=True)
+    ids = _int_list(who, "the image ids of ground_truth=", ids, len(gt.sizes), "annotation")
     sizes, _ = sreq
     for q, b in enumerate(ids):
         if not 0 <= b < n:
@@ -1896,8 +1900,7 @@ class MaskUtilities:
         """The (bits, H, W) arguments of a utility on packed planes, checked (ValueError) -> (bits, N, H, W): uint8 (N, H * W / 8) on
         the device, W a multiple of 32; detached, contiguous and, where a view starts off a 4-byte boundary, copied (the kernels read
         32-bit words)."""
-        if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, (int, np.integer)) or not isinstance(W, (int, np.integer)) \
-                or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
+        if not _is_int(H) or not _is_int(W) or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
             raise ValueError(f"{who}: planes of {H} x {W}: W must be a multiple of 32 and H * W below 2^31")
         H, W = int(H), int(W)
         if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or int(bits.shape[1]) != H * W // 8 \
@@ -1905,10 +1908,7 @@ class MaskUtilities:
             raise ValueError(f"{who}: bits must be a uint8 tensor (N, {H * W // 8}) with 1 <= N <= 65535")
         if not bits.is_cuda:
             raise ValueError(f"{who}: bits must be on the device")
-        bits = bits.detach().contiguous()
-        if bits.data_ptr() % 4 != 0:
-            bits = bits.clone()
-        return bits, int(bits.shape[0]), H, W
+        return _aligned(bits), int(bits.shape[0]), H, W
 
     @staticmethod
     def _f32_planes(who: str, name: str, t, hw: str):
@@ -1929,9 +1929,8 @@ class MaskUtilities:
         if not logits.is_cuda:
             raise ValueError("pack_masks: logits must be on the device")
         planes = logits.detach().contiguous().view(N, H, W)
-        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=logits.device)
-        area = torch.empty(N, dtype=torch.int32, device=logits.device)
-        box = torch.empty(N, 4, dtype=torch.int32, device=logits.device)
+        dev = logits.device
+        bits, area, box = _empty(dev, N, H * W // 8, dtype=torch.uint8), _empty(dev, N), _empty(dev, N, 4)
         hip.mask_pack(planes, bits, area, box)
         return bits, area, box
 
@@ -1939,15 +1938,15 @@ class MaskUtilities:
     def _component_outputs(self, lead: tuple, nbytes: int, M: int, min_area: int):
         """The result's own (n_comp, comps, n_kept, kept_bits, kept_area, kept_box) for planes of shape `lead`: no table with M = 0, the
         last four only with min_area >= 1."""
-        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
+        i32 = partial(_empty, self.device, *lead)
         if min_area < 1:
             return i32(), i32(M, 6) if M else None, None, None, None, None
-        return (i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32(), i32(4))
+        return i32(), i32(M, 6) if M else None, i32(), i32(nbytes, dtype=torch.uint8), i32(), i32(4)
 
     def _components(self, bits: torch.Tensor, H: int, W: int, connectivity: int, min_area: int, rows) -> None:
         """cvlm_mask_components of the planes bits (N, H * W / 8) into `rows`, their N rows of the six result tensors.  The workspace
         "cls_comp" grows to what these planes want in flight, up to COMPONENTS_WS_CAP (and never below one plane's)."""
-        want = min(hip.mask_components_workspace_bytes(int(bits.shape[0]), H, W), max(COMPONENTS_WS_CAP, hip.mask_components_workspace_bytes(1, H, W)))
+        want = _capped(hip.mask_components_workspace_bytes(int(bits.shape[0]), H, W), hip.mask_components_workspace_bytes(1, H, W), COMPONENTS_WS_CAP)
         hip.mask_components(bits, H, W, connectivity, min_area, self.ws.scratch("cls_comp", want), *rows)
 
     def mask_components(self, bits: torch.Tensor, H: int, W: int, *, components: Optional[int] = 1, min_area: int = 0,
@@ -1967,15 +1966,15 @@ class MaskUtilities:
     def _hole_outputs(self, lead: tuple, nbytes: int, M: int, fill_below: int):
         """The result's own (n_holes, holes, n_filled, filled_bits, filled_area) for planes of shape `lead`: no table with M = 0, the
         last three only with fill_below >= 1."""
-        i32 = lambda *shape: torch.empty(*lead, *shape, dtype=torch.int32, device=self.device)
+        i32 = partial(_empty, self.device, *lead)
         if fill_below < 1:
             return i32(), i32(M, 6) if M else None, None, None, None
-        return i32(), i32(M, 6) if M else None, i32(), torch.empty(*lead, nbytes, dtype=torch.uint8, device=self.device), i32()
+        return i32(), i32(M, 6) if M else None, i32(), i32(nbytes, dtype=torch.uint8), i32()
 
     def _holes(self, bits: torch.Tensor, H: int, W: int, connectivity: int, fill_below: int, rows) -> None:
         """cvlm_mask_holes of the planes bits (N, H * W / 8) into `rows`, their N rows of the five result tensors.  The workspace is
         `_components`' "cls_comp", grow-only under the same COMPONENTS_WS_CAP: the two entries are ordered on one stream."""
-        want = min(hip.mask_holes_workspace_bytes(int(bits.shape[0]), H, W), max(COMPONENTS_WS_CAP, hip.mask_holes_workspace_bytes(1, H, W)))
+        want = _capped(hip.mask_holes_workspace_bytes(int(bits.shape[0]), H, W), hip.mask_holes_workspace_bytes(1, H, W), COMPONENTS_WS_CAP)
         hip.mask_holes(bits, H, W, connectivity, fill_below, self.ws.scratch("cls_comp", want), *rows)
 
     def mask_holes(self, bits: torch.Tensor, H: int, W: int, *, holes: Optional[int] = 1, fill_holes: int = 0,
@@ -2004,8 +2003,7 @@ class MaskUtilities:
         N, h, w = self._f32_planes("pack_edges", "prob", prob, "h, w")
         if size is None:
             size = (h, w)
-        if not isinstance(size, (tuple, list)) or len(size) != 2 or \
-                any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in size):
+        if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(_is_int(v) for v in size):
             raise ValueError(f"pack_edges: size must be None or a pair of ints (H, W), got {size!r}")
         H, W = (int(v) for v in size)
         if not 1 <= N <= 65535 or h < 1 or w < 1 or h * w >= 2 ** 31 or H < 1 or W < 1 or W % 32 != 0 or H * W >= 2 ** 31:
@@ -2018,13 +2016,11 @@ class MaskUtilities:
                 raise ValueError(f"pack_edges: with_bits must be a uint8 tensor ({N}, {H * W // 8})")
             if with_bits.device != prob.device:
                 raise ValueError("pack_edges: with_bits must be on prob's device")
-            with_bits = with_bits.detach().contiguous()
-            if with_bits.data_ptr() % 4 != 0:
-                with_bits = with_bits.clone()
+            with_bits = _aligned(with_bits)
         planes = prob.detach().contiguous().view(N, h, w)
-        bits = torch.empty(N, H * W // 8, dtype=torch.uint8, device=prob.device)
-        area = torch.empty(N, dtype=torch.int32, device=prob.device)
-        inter = torch.empty(N, dtype=torch.int32, device=prob.device) if with_bits is not None else None
+        dev = prob.device
+        bits, area = _empty(dev, N, H * W // 8, dtype=torch.uint8), _empty(dev, N)
+        inter = _empty(dev, N) if with_bits is not None else None
         hip.edge_pack(planes, H, W, t, bits, area, with_bits, inter)
         return EdgeBits(bits, area, inter)
 
@@ -2039,8 +2035,7 @@ class MaskUtilities:
         dilate=True, band=False).dil_bits, closing the reverse; a SAM-style chain is
         mask_components(mask_holes(mask_morph(bits, H, W, dilate=True, band=False).dil_bits, H, W, fill_holes=t).filled_bits, H, W,
         min_area=t).  Launches on the caller's stream; ValueError before them for anything else."""
-        if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MORPH_MAXR:
-            raise ValueError(f"mask_morph: radius must be an int in [1, {MORPH_MAXR}], got {radius!r}")
+        radius = _int_in("mask_morph", "radius", radius, 1, MORPH_MAXR)
         for name, v in (("dilate", dilate), ("erode", erode), ("band", band)):
             if not isinstance(v, (bool, np.bool_)):
                 raise ValueError(f"mask_morph: {name} must be a bool, got {type(v).__name__}")
@@ -2049,8 +2044,8 @@ class MaskUtilities:
         bits, N, H, W = self._packed_planes("mask_morph", bits, H, W)
         out = []
         for asked in (dilate, erode, band):
-            out += [torch.empty_like(bits), torch.empty(N, dtype=torch.int32, device=bits.device)] if asked else [None, None]
-        hip.mask_morph(bits, H, W, int(radius), *out)
+            out += [torch.empty_like(bits), _empty(bits.device, N)] if asked else [None, None]
+        hip.mask_morph(bits, H, W, radius, *out)
         return MaskMorph(*out)
 
     # ---- run-length encoding of packed masks ------------------------------------------------------------------------
@@ -2062,15 +2057,14 @@ class MaskUtilities:
         walks the planes in rounds).  The emit's status word stays on the device: `MaskRle.check()` / `to_coco()` read it.  Launches on
         the caller's stream; ValueError before them for anything else."""
         bits, N, H, W = self._packed_planes("mask_rle", bits, H, W)
-        dev = bits.device
-        n_runs = torch.empty(N, dtype=torch.int32, device=dev)
+        dev, i32 = bits.device, partial(_empty, bits.device)
+        n_runs = i32(N)
         hip.mask_rle_count(bits, H, W, n_runs)
         offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
         torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
         total = int(offsets[N].item())                               # the one synchronisation
-        counts = torch.empty(total, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
-        want = min(hip.mask_rle_workspace_bytes(N, H, W), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, H, W)))
+        counts, status = i32(total), i32(1)
+        want = _capped(hip.mask_rle_workspace_bytes(N, H, W), hip.mask_rle_workspace_bytes(1, H, W), RLE_WS_CAP)
         hip.mask_rle_emit(bits, H, W, offsets, counts, status, self.ws.scratch("cls_rle", want))
         return MaskRle(counts=counts, offsets=offsets, n_runs=n_runs, size=(H, W), status=status)
 
@@ -2078,13 +2072,8 @@ class MaskUtilities:
     def _sized_outputs(self, sizes, level: int, K: int, n_calls: int):
         """The SizedMasks of K planes per (h, w) of `sizes`, one status word per cvlm_mask_pack_sized call, and the device table of the
         planes' (h, w) -- built on the host and uploaded once -> (SizedMasks, dims, largest word count)."""
-        per_plane = [s for s in sizes for _ in range(K)]
-        dims, offsets, max_words = sized_tables(per_plane)
-        dev, P = self.device, len(per_plane)
-        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
-                         area=torch.empty(P, dtype=torch.int32, device=dev), box=torch.empty(P, 4, dtype=torch.int32, device=dev),
-                         status=torch.empty(n_calls, dtype=torch.int32, device=dev), sizes=per_plane, level=level)
-        return out, torch.from_numpy(dims).to(dev), max_words
+        out, dims, max_words = SizedMasks.empty([s for s in sizes for _ in range(K)], self.device, level=level, n_status=n_calls)
+        return out, _upload(dims, self.device), max_words
 
     @staticmethod
     def _pack_sized(planes: torch.Tensor, out: "SizedMasks", dims: torch.Tensor, max_words: int, p0: int, p1: int, call: int) -> None:
@@ -2119,14 +2108,12 @@ class MaskUtilities:
         the largest image's pixel count; cvlm_label_init has written the fill."""
         dims, offsets, max_pixels = label_tables(sizes)
         dev, B, n_pix = self.device, len(sizes), int(offsets[-1])
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-        i16 = lambda: torch.empty(n_pix, dtype=torch.int16, device=dev)
-        out = LabelMaps(score=torch.empty(n_pix, dtype=torch.float32, device=dev), winner=i16(), segment=i16(), areas=i32(3, B * K),
-                        segment_id=i32(B * K), n_segments=i32(B), status=i32(1), dims=torch.from_numpy(dims).to(dev),
-                        pix_offsets=torch.from_numpy(offsets).to(dev), sizes=[tuple(s) for s in sizes], K=K, level=level,
-                        overlap_threshold=overlap_threshold)
+        i32 = partial(_empty, dev)
+        out = LabelMaps(score=i32(n_pix, dtype=torch.float32), winner=i32(n_pix, dtype=torch.int16), segment=i32(n_pix, dtype=torch.int16), areas=i32(3, B * K),
+                        segment_id=i32(B * K), n_segments=i32(B), status=i32(1), dims=_upload(dims, dev), pix_offsets=_upload(offsets, dev),
+                        sizes=[tuple(s) for s in sizes], K=K, level=level, overlap_threshold=overlap_threshold)
         if isinstance(weights, np.ndarray):
-            weights = torch.from_numpy(weights).to(dev)
+            weights = _upload(weights, dev)
         elif weights is not None:
             weights = weights.detach().contiguous().view(-1)
         hip.label_init(out.score, out.winner, out.segment, out.areas, out.segment_id, out.n_segments, out.status, B, K)
@@ -2152,8 +2139,7 @@ class MaskUtilities:
         logits at the hypothesis's class, a predicted quality --, None for 1.  Five launches on the caller's stream, the tables
         uploaded before them; no workspace, no synchronisation.  ValueError before anything is launched for anything else."""
         N, Hs, Ws = self._f32_planes("label_maps", "logits", logits, "H, W")
-        is_int = isinstance(K, (int, np.integer)) and not isinstance(K, (bool, np.bool_))
-        if not is_int or K < 1 or N % K != 0:
+        if not _is_int(K) or K < 1 or N % K != 0:
             raise ValueError(f"label_maps: {N} planes are no whole number of images of K = {K!r} hypotheses")
         B = N // int(K)
         if not 1 <= B <= 65535 or Hs < 1 or Ws < 1 or Hs * Ws >= 2 ** 31:
@@ -2179,33 +2165,24 @@ class MaskUtilities:
         of an earlier call, accumulated into -- a dataset's batches sum on the device; None starts from zero.  A value outside
         [0, num_classes - 1] is counted nowhere (np.histogram would count the value num_classes in the last class); `label_map` is the
         caller's: remap before upload.  No synchronisation.  ValueError before anything is launched for anything else."""
-        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-        if not is_int(num_classes) or not 1 <= int(num_classes) <= LABELS_MAX_CLASSES:
-            raise ValueError(f"label_iou: num_classes must be an int in [1, {LABELS_MAX_CLASSES}], got {num_classes!r}")
-        if not is_int(ignore_index) or not -2 ** 31 <= int(ignore_index) < 2 ** 31:
-            raise ValueError(f"label_iou: ignore_index must be an int32 value, got {ignore_index!r}")
+        C_ = _int_in("label_iou", "num_classes", num_classes, 1, LABELS_MAX_CLASSES)
+        ignore_index = _int_in("label_iou", "ignore_index", ignore_index, -2 ** 31, 2 ** 31 - 1)
         if not isinstance(reduce_zero_label, (bool, np.bool_)):
             raise ValueError(f"label_iou: reduce_zero_label must be a bool, got {reduce_zero_label!r}")
         maps = []
         for name, m in (("pred", pred), ("gt", gt)):
-            t = torch.as_tensor(m) if isinstance(m, (torch.Tensor, np.ndarray)) else None
-            if t is None or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.numel() < 1:
-                raise ValueError(f"label_iou: {name} must be a non-empty integer tensor or array, got {type(m).__name__}")
+            t = _integer_map("label_iou", name, m)
             keep = name == "gt" and t.dtype == torch.uint8
-            if not t.is_cuda and t.dtype not in (torch.int32, torch.uint8, torch.int16, torch.int8) and \
-                    (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
-                raise ValueError(f"label_iou: {name} holds a value outside the int32 range")
             maps.append(t.detach().to(device=self.device, dtype=torch.uint8 if keep else torch.int32).contiguous().view(-1))
         if maps[0].numel() != maps[1].numel():
             raise ValueError(f"label_iou: pred holds {maps[0].numel()} pixels, gt {maps[1].numel()}")
-        C_ = int(num_classes)
         fresh = totals is None
         if fresh:
             totals = torch.empty(3, C_, dtype=torch.int64, device=self.device)
         elif not isinstance(totals, torch.Tensor) or totals.dtype != torch.int64 or tuple(totals.shape) != (3, C_) or \
                 totals.device != maps[0].device or not totals.is_contiguous():
             raise ValueError(f"label_iou: totals must be what an earlier call with num_classes = {C_} returned")
-        hip.label_iou_hist(maps[0], maps[1], C_, int(ignore_index), bool(reduce_zero_label), fresh, totals)
+        hip.label_iou_hist(maps[0], maps[1], C_, ignore_index, bool(reduce_zero_label), fresh, totals)
         return totals
 
     # ---- panoptic quality (DESIGN.md §24) ----------------------------------------------------------------------------------------------
@@ -2215,16 +2192,11 @@ class MaskUtilities:
         if isinstance(m, (list, tuple)) and m and all(isinstance(a, (torch.Tensor, np.ndarray)) for a in m):
             parts = [torch.as_tensor(a) for a in m]
             m = torch.cat([a.reshape(-1, 3) if rgb else a.reshape(-1) for a in parts])
-        t = torch.as_tensor(m) if isinstance(m, (torch.Tensor, np.ndarray)) else None
-        if t is None or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.numel() < 1:
-            raise ValueError(f"{who}: {name} must be a non-empty integer tensor or array, got {type(m).__name__}")
+        t = _integer_map(who, name, m, int32=not rgb)
         if rgb:
             if t.dtype != torch.uint8 or t.shape[-1] != 3:
                 raise ValueError(f"{who}: with rgb=True {name} must be uint8 with a last axis of 3, got {t.dtype} {tuple(t.shape)}")
             return t.detach().to(device=self.device).contiguous().view(-1, 3)
-        if not t.is_cuda and t.dtype not in (torch.int32, torch.uint8, torch.int16, torch.int8) and \
-                (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
-            raise ValueError(f"{who}: {name} holds a value outside the int32 range")
         return t.detach().to(device=self.device, dtype=torch.int32).contiguous().view(-1)
 
     def panoptic_remap(self, raw, sizes, segments, *, rgb: bool = False) -> "PanopticGroundTruth":
@@ -2236,20 +2208,15 @@ class MaskUtilities:
         list becomes void and is counted in `unknown`.  No synchronisation.  ValueError before anything is launched."""
         if not isinstance(rgb, (bool, np.bool_)):
             raise ValueError(f"panoptic_remap: rgb must be a bool, got {rgb!r}")
-        if sizes is None:
-            raise ValueError("panoptic_remap: the maps lie image by image at the images' own sizes: give sizes")
-        sizes, _ = sized_request(sizes=sizes, n=len(sizes) if hasattr(sizes, "__len__") else 0, who="panoptic_remap")
+        sizes = _image_sizes(sizes, "panoptic_remap")
         B = len(sizes)
-        if not 1 <= B <= 65535:
-            raise ValueError(f"panoptic_remap: a call takes 1 .. 65535 images, got {B}")
         keys, vals, offsets, gt_cat, gt_crowd = pq_segments_request(segments, B)
         t = self._pq_map("panoptic_remap", "raw", raw, bool(rgb))
         dims, pix_offsets, max_pixels = label_tables(sizes)
         if t.shape[0] != int(pix_offsets[-1]):
             raise ValueError(f"panoptic_remap: raw holds {t.shape[0]} pixels, sizes {int(pix_offsets[-1])}")
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        out = PanopticGroundTruth(gt=torch.empty(t.shape[0], dtype=torch.int32, device=self.device),
-                                  unknown=torch.empty(B, dtype=torch.int32, device=self.device), gt_cat=gt_cat, gt_crowd=gt_crowd,
+        up, i32 = partial(_upload, dev=self.device), partial(_empty, self.device)
+        out = PanopticGroundTruth(gt=i32(t.shape[0]), unknown=i32(B), gt_cat=gt_cat, gt_crowd=gt_crowd,
                                   status=torch.zeros(1, dtype=torch.int32, device=self.device), sizes=sizes)
         hip.pan_remap(t, B, up(dims), up(pix_offsets), max_pixels, up(keys), up(vals), up(offsets), out.gt, out.unknown, out.status)
         return out
@@ -2270,15 +2237,14 @@ class MaskUtilities:
             raise ValueError(f"panoptic_quality: totals must be what an earlier call with num_classes = {C_} returned")
         B = len(sizes)
         dev = self.device
-        up = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        up = lambda a: a if isinstance(a, torch.Tensor) else _upload(a, dev)
         pred_cat, gt_cat, gt_crowd = up(pred_cat).contiguous(), up(gt_cat).contiguous(), up(gt_crowd).contiguous()
         dims, pix_offsets, max_pixels = label_tables(sizes)
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        i32, f64 = partial(_empty, dev), partial(_empty, dev, dtype=torch.float64)
         fresh = totals is None
-        out = PanopticTotals(counts=torch.empty(3, C_, dtype=torch.int64, device=dev) if fresh else totals.counts,
-                             iou_sum=torch.empty(C_, dtype=torch.float64, device=dev) if fresh else totals.iou_sum,
+        out = PanopticTotals(counts=i32(3, C_, dtype=torch.int64) if fresh else totals.counts, iou_sum=f64(C_) if fresh else totals.iou_sum,
                              status=torch.zeros(1, dtype=torch.int32, device=dev) if fresh else totals.status,
-                             inter=i32(B, G, S), pred_match=i32(B, S), pred_iou=torch.empty(B, S, dtype=torch.float64, device=dev),
+                             inter=i32(B, G, S), pred_match=i32(B, S), pred_iou=f64(B, S),
                              gt_match=i32(B, G), pred_area=i32(B, S), gt_area=i32(B, G), num_classes=C_)
         hip.pan_pair_hist(maps[0], maps[1], B, G, S, up(dims), up(pix_offsets), max_pixels, True, out.inter, out.status)
         hip.pan_match(out.inter, pred_cat, gt_cat, gt_crowd, C_, out.pred_match, out.pred_iou, out.gt_match, out.pred_area, out.gt_area)
@@ -2291,19 +2257,16 @@ class MaskUtilities:
         planes of one size -- per image where the planes come from the engine --, one torch.cumsum, ONE read of the total (the call's
         only synchronisation), then one cvlm_mask_rle_emit_w call per run through the workspace "cls_rle", all on absolute offsets
         into one `counts`.  The status words of the runs are folded into one on the device."""
-        if not isinstance(sized, SizedMasks):
-            raise ValueError(f"mask_rle_sized: sized must be a SizedMasks, got {type(sized).__name__}")
-        sizes = sized.sizes
+        sizes = _sized_arg("mask_rle_sized", "sized", sized).sizes
         P, dev = len(sizes), sized.bits.device
-        if not 1 <= P <= 65535 or not sized.bits.is_cuda:
-            raise ValueError("mask_rle_sized: 1 .. 65535 planes on the device")
-        _, host_off, _ = sized_tables(sizes)
+        i32 = partial(_empty, dev)
+        _, host_off, _ = sized.tables()
         runs, a = [], 0                                               # (first plane, one past the last) of each run of equal sizes
         for p in range(1, P + 1):
             if p == P or sizes[p] != sizes[a]:
                 runs.append((a, p))
                 a = p
-        n_runs = torch.empty(P, dtype=torch.int32, device=dev)
+        n_runs = i32(P)
         rows = lambda a, b: sized.bits[int(host_off[a]):int(host_off[b])].view(b - a, -1)
         for a, b in runs:
             h, w = sizes[a]
@@ -2311,13 +2274,12 @@ class MaskUtilities:
         offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
         torch.cumsum(n_runs, 0, dtype=torch.int64, out=offsets[1:])
         total = int(offsets[P].item())                               # the one synchronisation
-        counts = torch.empty(total, dtype=torch.int32, device=dev)
-        status = torch.empty(len(runs), dtype=torch.int32, device=dev)
+        counts, status = i32(total), i32(len(runs))
         want = 0
         for a, b in runs:
             h, w = sizes[a]
             pitch = 32 * ((w + 31) // 32)
-            want = max(want, min(hip.mask_rle_workspace_bytes(b - a, h, pitch), max(RLE_WS_CAP, hip.mask_rle_workspace_bytes(1, h, pitch))))
+            want = max(want, _capped(hip.mask_rle_workspace_bytes(b - a, h, pitch), hip.mask_rle_workspace_bytes(1, h, pitch), RLE_WS_CAP))
         ws = self.ws.scratch("cls_rle", want)
         for i, (a, b) in enumerate(runs):
             h, w = sizes[a]
@@ -2346,19 +2308,18 @@ class MaskUtilities:
             counts, run_offsets = rles.counts.contiguous(), rles.offsets.contiguous()
         else:
             c, o, sizes = rle_decode_request(rles)
-            P = len(sizes)
-            counts, run_offsets = torch.from_numpy(c).to(dev), torch.from_numpy(o).to(dev)
-        dims, offsets, _ = sized_tables(sizes)
-        max_pixels = max(h * w for h, w in sizes)
-        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
-                         area=torch.empty(P, dtype=torch.int32, device=dev) if stats else None,
-                         box=torch.empty(P, 4, dtype=torch.int32, device=dev) if stats else None,
-                         status=torch.empty(1, dtype=torch.int32, device=dev), sizes=[(int(h), int(w)) for h, w in sizes], level=0)
-        one = hip.mask_rle_decode_workspace_bytes(1, max_pixels)
-        ws = self.ws.scratch("cls_rle", min(P * one, max(RLE_WS_CAP, one)))
-        hip.mask_rle_decode(counts, run_offsets, torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box,
-                            out.status, ws)
+            counts, run_offsets = _upload(c, dev), _upload(o, dev)
+        out, dims, max_pixels, ws = self._decoded(sizes, stats, hip.mask_rle_decode_workspace_bytes)
+        hip.mask_rle_decode(counts, run_offsets, dims, out.offsets, max_pixels, out.bits, out.area, out.box, out.status, ws)
         return out
+
+    def _decoded(self, sizes, stats: bool, workspace_bytes):
+        """What the two decoders share behind their entries: the result's planes with their offsets uploaded, the planes' dims uploaded,
+        the largest plane's pixel count and the workspace "cls_rle" by the entry's own size query, capped at RLE_WS_CAP."""
+        out, dims, _ = SizedMasks.empty(sizes, self.device, level=0, stats=stats)
+        max_pixels = max(h * w for h, w in sizes)
+        one = workspace_bytes(1, max_pixels)
+        return out, _upload(dims, self.device), max_pixels, self.ws.scratch("cls_rle", _capped(len(sizes) * one, one, RLE_WS_CAP))
 
     # ---- COCO polygon annotations on the device (DESIGN.md §21) -------------------------------------------------------------------------
     def polygons_decode(self, anns, *, stats: bool = True) -> "SizedMasks":
@@ -2372,17 +2333,9 @@ class MaskUtilities:
         planes in rounds).  Launches on the caller's stream, without a synchronisation."""
         dev = self.device
         xy, po, pp, sizes = polygons_request(anns)
-        P = len(sizes)
-        dims, offsets, _ = sized_tables(sizes)
-        max_pixels = max(h * w for h, w in sizes)
-        out = SizedMasks(bits=torch.empty(int(offsets[P]), dtype=torch.uint8, device=dev), offsets=torch.from_numpy(offsets).to(dev),
-                         area=torch.empty(P, dtype=torch.int32, device=dev) if stats else None,
-                         box=torch.empty(P, 4, dtype=torch.int32, device=dev) if stats else None,
-                         status=torch.empty(1, dtype=torch.int32, device=dev), sizes=sizes, level=0)
-        one = hip.mask_poly_decode_workspace_bytes(1, max_pixels)
-        ws = self.ws.scratch("cls_rle", min(P * one, max(RLE_WS_CAP, one)))
-        hip.mask_poly_decode(torch.from_numpy(xy).to(dev), torch.from_numpy(po).to(dev), torch.from_numpy(pp).to(dev),
-                             torch.from_numpy(dims).to(dev), out.offsets, max_pixels, out.bits, out.area, out.box, out.status, ws)
+        out, dims, max_pixels, ws = self._decoded(sizes, stats, hip.mask_poly_decode_workspace_bytes)
+        hip.mask_poly_decode(_upload(xy, dev), _upload(po, dev), _upload(pp, dev), dims, out.offsets, max_pixels, out.bits, out.area, out.box,
+                             out.status, ws)
         return out
 
     def mask_inter_sized(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, a_image=None, b_image=None) -> "SizedOverlaps":
@@ -2393,18 +2346,16 @@ class MaskUtilities:
         One upload of the pair table and of the two small size tables, one launch pair, two gathers of the areas; no workspace, no
         synchronisation: `SizedOverlaps.iou()` does the one read."""
         for name, s in (("a", a), ("b", b)):
-            if not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535:
-                raise ValueError(f"mask_inter_sized: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas")
+            _sized_arg("mask_inter_sized", name, s, areas=True)
         table = pairs_request(a.sizes, b.sizes, pairs=pairs, a_image=a_image, b_image=b_image)
         dev = a.bits.device
-        tab = table.to(torch.int32).contiguous() if isinstance(table, torch.Tensor) else torch.from_numpy(table).to(dev)
+        tab = table.to(torch.int32).contiguous() if isinstance(table, torch.Tensor) else _upload(table, dev)
         N = int(tab.shape[0])
-        a_dims, _, a_words = sized_tables(a.sizes)
-        b_dims, _, b_words = (a_dims, None, a_words) if b is a else sized_tables(b.sizes)
-        a_dims = torch.from_numpy(a_dims).to(dev)
-        b_dims = a_dims if b is a else torch.from_numpy(b_dims).to(dev)
-        inter = torch.empty(N, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
+        a_dims, _, a_words = a.tables()
+        b_dims, _, b_words = (a_dims, None, a_words) if b is a else b.tables()
+        a_dims = _upload(a_dims, dev)
+        b_dims = a_dims if b is a else _upload(b_dims, dev)
+        inter, status = _empty(dev, N), _empty(dev, 1)
         hip.mask_inter_sized(a.bits, a.offsets, a_dims, b.bits, b.offsets, b_dims, tab, max(a_words, b_words), inter, status)
         pick = lambda s, col: s.area.index_select(0, tab[:, col].long().clamp_(0, len(s.sizes) - 1))
         return SizedOverlaps(pairs=tab, inter=inter, area_a=pick(a, 0), area_b=pick(b, 1), status=status)
@@ -2420,18 +2371,15 @@ class MaskUtilities:
         `status` is the kernel's.  The result feeds `mask_inter_sized`, `mask_rle_sized` and `SizedMasks.concat` as it is: the Boundary
         IoU of pairs is `mask_inter_sized(boundary(a), boundary(b), ...).iou()`.  One upload of the radius table and of the size
         table, a workspace as large as the planes from torch.empty, no synchronisation."""
-        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda or not 1 <= len(sized.sizes) <= 65535:
-            raise ValueError("mask_boundary_sized: sized must be a SizedMasks of 1 .. 65535 planes on the device")
+        _sized_arg("mask_boundary_sized", "sized", sized)
         radii = boundary_request(sized.sizes, dilation_ratio=dilation_ratio, radius=radius)
-        dev = sized.bits.device
-        dims, _, max_words = sized_tables(sized.sizes)
+        dev, i32 = sized.bits.device, partial(_empty, sized.bits.device)
+        dims, _, max_words = sized.tables()
         stats = sized.area is not None
-        out = SizedMasks(bits=torch.empty_like(sized.bits), offsets=sized.offsets,
-                         area=torch.empty(len(sized.sizes), dtype=torch.int32, device=dev) if stats else None,
-                         box=sized.box.clone() if stats else None, status=torch.empty(1, dtype=torch.int32, device=dev),
-                         sizes=[tuple(z) for z in sized.sizes], level=sized.level)
-        hip.mask_boundary_sized(sized.bits, sized.offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(radii).to(dev), max_words,
-                                torch.empty_like(sized.bits), out.bits, out.area, out.status)
+        out = SizedMasks(bits=torch.empty_like(sized.bits), offsets=sized.offsets, area=i32(len(sized.sizes)) if stats else None,
+                         box=sized.box.clone() if stats else None, status=i32(1), sizes=[tuple(z) for z in sized.sizes], level=sized.level)
+        hip.mask_boundary_sized(sized.bits, sized.offsets, _upload(dims, dev), _upload(radii, dev), max_words, torch.empty_like(sized.bits),
+                                out.bits, out.area, out.status)
         return out
 
     # ---- Contours: COCO polygons out (DESIGN.md §26) ---------------------------------------------------------------------------------------
@@ -2442,24 +2390,21 @@ class MaskUtilities:
         call's only synchronisation), then the host cuts the planes into rounds whose workspace stays within RLE_WS_CAP -- a plane
         that needs more on its own is a round of its own -- and one emit call per round goes through the grow-only workspace
         "cls_rle".  The status words are folded into one on the device.  Launches on the caller's stream."""
-        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
-            raise ValueError("mask_contours_sized: sized must be a SizedMasks on the device")
+        _sized_arg("mask_contours_sized", "sized", sized)
         sizes, connectivity = contour_request(sized.sizes, connectivity=connectivity)
         P, dev = len(sizes), sized.bits.device
+        i32 = partial(_empty, dev)
         dims, _, max_words = sized_tables(sizes)
-        dims = torch.from_numpy(dims).to(dev)
-        n_vertices = torch.empty(P, dtype=torch.int32, device=dev)
-        count_status = torch.empty(1, dtype=torch.int32, device=dev)
+        dims = _upload(dims, dev)
+        n_vertices, count_status = i32(P), i32(1)
         hip.mask_contour_count(sized.bits, sized.offsets, dims, connectivity, max_words, n_vertices, count_status)
         offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
         torch.cumsum(n_vertices, 0, dtype=torch.int64, out=offsets[1:])
         counted = n_vertices.cpu().numpy()                           # the one synchronisation
         total = int(counted.astype(np.int64).sum())
         rounds = contour_rounds(counted, max_words, RLE_WS_CAP, hip.mask_contour_workspace_bytes)
-        xy = torch.empty(total, 2, dtype=torch.int16, device=dev)
-        ring_start = torch.empty(total, dtype=torch.uint8, device=dev)
-        n_rings = torch.empty(P, 2, dtype=torch.int32, device=dev)
-        status = torch.empty(len(rounds), dtype=torch.int32, device=dev)
+        xy, ring_start = i32(total, 2, dtype=torch.int16), i32(total, dtype=torch.uint8)
+        n_rings, status = i32(P, 2), i32(len(rounds))
         ws = self.ws.scratch("cls_rle", max(r[3] for r in rounds))
         for i, (a, b, rv, need) in enumerate(rounds):
             hip.mask_contour_emit(sized.bits, sized.offsets[a:b + 1], dims[a:b], connectivity, max_words, offsets[a:b + 1], rv, xy, ring_start,
@@ -2474,8 +2419,7 @@ class MaskUtilities:
         dev = bits.device
         dims, _, max_words = sized_tables(sizes)
         _, pix, _ = label_tables(sizes)
-        hip.mask_distance_sized(bits, offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(np.ascontiguousarray(reach)).to(dev), max_words,
-                                torch.from_numpy(pix).to(dev), ws, out_d2, status)
+        hip.mask_distance_sized(bits, offsets, _upload(dims, dev), _upload(reach, dev), max_words, _upload(pix, dev), ws, out_d2, status)
 
     def mask_distance_sized(self, sized: "SizedMasks", *, reach=None) -> "MaskDistances":
         """The squared Euclidean distance map of each sized plane -> MaskDistances (cvlm_mask_distance_sized): for every
@@ -2484,14 +2428,12 @@ class MaskUtilities:
         pixel's work by O(reach).  `distance_request` checks the arguments on the host before anything is launched (ValueError).
         Memory: 4 bytes per pixel of result and 2 bytes per pixel of the grow-only workspace "cls_rle".  One upload of the three small
         tables, three launches on the caller's stream, no synchronisation."""
-        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
-            raise ValueError("mask_distance_sized: sized must be a SizedMasks on the device")
+        _sized_arg("mask_distance_sized", "sized", sized)
         sizes, reaches = distance_request(sized.sizes, reach=reach)
-        dev = sized.bits.device
+        dev, i32 = sized.bits.device, partial(_empty, sized.bits.device)
         _, pix, _ = label_tables(sizes)
         n_pix = int(pix[-1])
-        out = MaskDistances(d2=torch.empty(n_pix, dtype=torch.int32, device=dev), pix_offsets=torch.from_numpy(pix).to(dev), sizes=sizes,
-                            reach=reaches, status=torch.empty(1, dtype=torch.int32, device=dev))
+        out = MaskDistances(d2=i32(n_pix), pix_offsets=_upload(pix, dev), sizes=sizes, reach=reaches, status=i32(1))
         ws = self.ws.scratch("cls_rle", (2 * n_pix + 15) // 16 * 16)
         self._distance(sized.bits, sized.offsets, sizes, reaches, out.d2, ws, out.status)
         return out
@@ -2502,10 +2444,10 @@ class MaskUtilities:
         gather of their byte ranges otherwise (the ranges come from the sizes: no read of the device)."""
         if planes == list(range(len(sized.sizes))):
             return sized.bits, sized.offsets, list(sized.sizes)
-        _, off, _ = sized_tables(sized.sizes)
+        _, off, _ = sized.tables()
         sizes = [sized.sizes[p] for p in planes]
         bits = torch.cat([sized.bits[int(off[p]):int(off[p + 1])] for p in planes])
-        return bits, torch.from_numpy(sized_tables(sizes)[1]).to(bits.device), sizes
+        return bits, _upload(sized_tables(sizes)[1], bits.device), sizes
 
     def mask_surface_distances(self, a: "SizedMasks", b: "SizedMasks", *, pairs=None, tolerance=SURFACE_RATIO, surface="boundary",
                                reach=None) -> "SurfaceTotals":
@@ -2524,8 +2466,7 @@ class MaskUtilities:
         then the totals entry, through the grow-only workspace "cls_rle", on the caller's stream.  A plane named by many pairs is
         transformed once per round it appears in.  No synchronisation: `SurfaceTotals.to_host()` does the one read."""
         for name, s in (("a", a), ("b", b)):
-            if not isinstance(s, SizedMasks) or not s.bits.is_cuda:
-                raise ValueError(f"mask_surface_distances: {name} must be a SizedMasks on the device")
+            _sized_arg("mask_surface_distances", name, s)
         if surface is not None and not (isinstance(surface, str) and surface == "boundary"):
             raise ValueError(f"mask_surface_distances: surface must be 'boundary' or None, got {surface!r}")
         req = surface_request(a.sizes, b.sizes, pairs=pairs, tolerance=tolerance, reach=reach)
@@ -2537,18 +2478,17 @@ class MaskUtilities:
             sb = sa if b is a else self.mask_boundary_sized(b, radius=1)
         else:
             sa, sb = a, b
-        table = lambda: dict(n=torch.empty(N, dtype=torch.int32, device=dev), far=torch.empty(N, dtype=torch.int32, device=dev),
-                             within=torch.empty(N, T, dtype=torch.int32, device=dev), max_d2=torch.empty(N, dtype=torch.int32, device=dev),
-                             sum_d2=torch.empty(N, dtype=torch.int64, device=dev), sum_d=torch.empty(N, dtype=torch.float64, device=dev))
-        out = SurfaceTotals(pairs=torch.from_numpy(req.pairs).to(dev), radii=torch.from_numpy(req.radii).to(dev), ab=table(), ba=table(),
-                            status=None)
-        status = torch.empty(len(rounds), 4, dtype=torch.int32, device=dev)
+        i32 = partial(_empty, dev)
+        table = lambda: dict(n=i32(N), far=i32(N), within=i32(N, T), max_d2=i32(N), sum_d2=i32(N, dtype=torch.int64),
+                             sum_d=i32(N, dtype=torch.float64))
+        out = SurfaceTotals(pairs=_upload(req.pairs, dev), radii=_upload(req.radii, dev), ab=table(), ba=table(), status=None)
+        status = i32(len(rounds), 4)
         r16 = lambda v: (v + 15) // 16 * 16
         need = lambda px, n: r16(4 * px) + r16(2 * px) + hip.mask_surface_workspace_bytes(n)
         pixels = lambda sizes, planes: sum(sizes[p][0] * sizes[p][1] for p in planes)
         ws = self.ws.scratch("cls_rle", max(need(max(pixels(req.a_sizes, ua), pixels(req.b_sizes, ub)), i1 - i0) for i0, i1, ua, ub, _ in rounds))
-        dims_of = {id(s): torch.from_numpy(sized_tables(s.sizes)[0]).to(dev) for s in (sa, sb)}
-        words_of = {id(s): sized_tables(s.sizes)[2] for s in (sa, sb)}
+        dims_of = {id(s): _upload(s.tables()[0], dev) for s in (sa, sb)}
+        words_of = {id(s): s.tables()[2] for s in (sa, sb)}
         for r, (i0, i1, ua, ub, _) in enumerate(rounds):
             # direction 0, "ab": the pixels of a's surfaces against the maps of the b planes of the round; direction 1 the reverse
             for way, (pix_src, map_src, named, reaches, col, tab) in enumerate(((sa, sb, ub, req.reach_b, 1, out.ab),
@@ -2562,8 +2502,8 @@ class MaskUtilities:
                 self._distance(bits, offsets, sizes, reaches[named], d2, f, status[r, 2 * way:2 * way + 1])
                 local = np.searchsorted(named, req.pairs[i0:i1, col]).astype(np.int32)
                 pr = np.ascontiguousarray(np.stack([req.pairs[i0:i1, 1 - col], local], axis=1))
-                hip.mask_surface_totals(pix_src.bits, pix_src.offsets, dims_of[id(pix_src)], d2, torch.from_numpy(pix).to(dev),
-                                        torch.from_numpy(sized_tables(sizes)[0]).to(dev), torch.from_numpy(pr).to(dev), out.radii[i0:i1],
+                hip.mask_surface_totals(pix_src.bits, pix_src.offsets, dims_of[id(pix_src)], d2, _upload(pix, dev),
+                                        _upload(sized_tables(sizes)[0], dev), _upload(pr, dev), out.radii[i0:i1],
                                         words_of[id(pix_src)], part, tab["n"][i0:i1], tab["far"][i0:i1], tab["within"][i0:i1],
                                         tab["max_d2"][i0:i1], tab["sum_d2"][i0:i1], tab["sum_d"][i0:i1], status[r, 2 * way + 1:2 * way + 2])
         out.status = torch.amax(status.reshape(-1), 0, keepdim=True)
@@ -2578,8 +2518,8 @@ class MaskUtilities:
         dev = bits.device
         dims, _, max_words = sized_tables(sizes)
         ws = self.ws.scratch("cls_rle", hip.mask_thin_workspace_bytes(int(bits.numel()), len(sizes), steps))
-        hip.mask_thin_sized(bits, offsets, torch.from_numpy(dims).to(dev), torch.from_numpy(np.ascontiguousarray(limits)).to(dev), max_words,
-                            mode, steps, ws, out_bits, area, box, iters, done, status)
+        hip.mask_thin_sized(bits, offsets, _upload(dims, dev), _upload(limits, dev), max_words, mode, steps, ws, out_bits, area, box, iters, done,
+                            status)
 
     def mask_thin_sized(self, sized: "SizedMasks", *, max_iter=None, path="auto", steps=64) -> "MaskThin":
         """Each sized plane reduced to its centre lines -> MaskThin (cvlm_mask_thin_sized): Guo & Hall's thinning -- MATLAB's
@@ -2593,11 +2533,10 @@ class MaskUtilities:
         followed by ONE read of done (and status), then the next round runs on the planes that are not yet done, gathered back to back,
         their output as the input and their max_iter less the iterations spent -- exact, because the state of the rule is the bits alone.
         Workspace: the grow-only "cls_rle", as many bytes as the planes of a round plus 4 * steps per plane."""
-        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
-            raise ValueError("mask_thin_sized: sized must be a SizedMasks on the device")
+        _sized_arg("mask_thin_sized", "sized", sized)
         sizes, limits, mode, steps = thin_request(sized.sizes, max_iter=max_iter, path=path, steps=steps)
         P, dev = len(sizes), sized.bits.device
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        i32 = partial(_empty, dev)
         out = MaskThin(masks=SizedMasks(bits=torch.empty_like(sized.bits), offsets=sized.offsets, area=i32(P), box=i32(P, 4), status=i32(1),
                                         sizes=sizes, level=sized.level), iters=i32(P), done=i32(P), status=None)
         out.status = out.masks.status
@@ -2619,8 +2558,7 @@ class MaskUtilities:
             rest = np.where(limits[left] == 0, 0, limits[left] - spent).astype(np.int32)      # > 0 where limited: the plane is not done
             r_bits, r_area, r_box, r_iters, r_done, r_status = torch.empty_like(bits), i32(len(left)), i32(len(left), 4), i32(len(left)), \
                 i32(len(left)), i32(1)
-            self._thin(bits, torch.from_numpy(sized_tables(part)[1]).to(dev), part, rest, mode, steps, r_bits, r_area, r_box, r_iters, r_done,
-                       r_status)
+            self._thin(bits, _upload(sized_tables(part)[1], dev), part, rest, mode, steps, r_bits, r_area, r_box, r_iters, r_done, r_status)
             at = 0
             for p in left:
                 n = int(off[p + 1] - off[p])
@@ -2642,14 +2580,11 @@ class MaskUtilities:
         calls count the skeletons inside the other side's masks, the second with the pair columns swapped.  No synchronisation beyond
         `mask_thin_sized`'s: none where every plane is resident."""
         for name, s in (("a", a), ("b", b)):
-            if not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535:
-                raise ValueError(f"mask_cldice: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas")
-        if isinstance(pairs, torch.Tensor) and pairs.is_cuda:
+            _sized_arg("mask_cldice", name, s, areas=True)
+        if isinstance(pairs, torch.Tensor) and pairs.is_cuda:         # the second count swaps the columns on the host
             raise ValueError("mask_cldice: pairs must be (N, 2) ints on the host")
-        if pairs is None and a_image is None and b_image is None:     # plane p against plane p
-            if len(a.sizes) != len(b.sizes):
-                raise ValueError(f"mask_cldice: without pairs= or image ids both sides need as many planes, got {len(a.sizes)} and {len(b.sizes)}")
-            pairs = np.stack([np.arange(len(a.sizes))] * 2, axis=1)
+        if pairs is None and a_image is None and b_image is None:
+            pairs = _plane_by_plane("mask_cldice", len(a.sizes), len(b.sizes), "pairs= or image ids")
         table = pairs_request(a.sizes, b.sizes, pairs=pairs, a_image=a_image, b_image=b_image, who="mask_cldice")
         ta = self.mask_thin_sized(a)
         tb = ta if b is a else self.mask_thin_sized(b)
@@ -2667,21 +2602,20 @@ class MaskUtilities:
         before anything is launched (ValueError).  One upload of the two small tables and one entry call on the caller's stream,
         without a synchronisation; the grow-only workspace "cls_comp" holds every plane in flight up to COMPONENTS_WS_CAP (and never
         less than the largest plane), beyond it the entry walks the planes in rounds."""
-        if not isinstance(sized, SizedMasks) or not sized.bits.is_cuda:
-            raise ValueError("mask_regions_sized: sized must be a SizedMasks on the device")
+        _sized_arg("mask_regions_sized", "sized", sized)
         sizes, M, min_area, connectivity = regions_request(sized.sizes, regions=regions, min_area=min_area, connectivity=connectivity)
         P, dev = len(sizes), sized.bits.device
         dims, _, max_words = sized_tables(sizes)
         slots = [z for z in sizes for _ in range(M)]
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        i32 = partial(_empty, dev)
         n_regions, table, status = i32(P), i32(P, M, 6), i32(1)
-        out_bits = torch.empty(M * int(sized.bits.numel()), dtype=torch.uint8, device=dev)
         n_bytes = int(sized.bits.numel())
-        least = hip.mask_regions_workspace_bytes(4 * max_words, 1, max_words)
-        want = min(hip.mask_regions_workspace_bytes(n_bytes, P, max_words), max(COMPONENTS_WS_CAP, least))
-        hip.mask_regions_sized(sized.bits, sized.offsets, torch.from_numpy(dims).to(dev), max_words, connectivity, min_area,
+        out_bits = i32(M * n_bytes, dtype=torch.uint8)
+        want = _capped(hip.mask_regions_workspace_bytes(n_bytes, P, max_words), hip.mask_regions_workspace_bytes(4 * max_words, 1, max_words),
+                       COMPONENTS_WS_CAP)
+        hip.mask_regions_sized(sized.bits, sized.offsets, _upload(dims, dev), max_words, connectivity, min_area,
                                self.ws.scratch("cls_comp", want), n_regions, table, out_bits, status)
-        masks = SizedMasks(bits=out_bits, offsets=torch.from_numpy(sized_tables(slots)[1]).to(dev), area=table[..., 0].reshape(P * M),
+        masks = SizedMasks(bits=out_bits, offsets=_upload(sized_tables(slots)[1], dev), area=table[..., 0].reshape(P * M),
                            box=table[..., 1:5].reshape(P * M, 4), status=status, sizes=slots, level=sized.level)
         return MaskRegions(n_regions=n_regions, table=table, masks=masks, M=M)
 
@@ -2695,17 +2629,14 @@ class MaskUtilities:
         category suppress each other.  image and the other arguments are `nms_request`'s, which checks them on the host before anything
         is launched (ValueError).  One upload of the three tables and the sizes, the two entry calls on the caller's stream, no workspace, no
         synchronisation: `MaskNms.select(instances)` does the one read.  No instance: empty tensors, nothing launched."""
-        if not isinstance(instances, SizedMasks) or instances.area is None or instances.box is None:
-            raise ValueError("mask_nms_sized: instances must be a SizedMasks with areas and boxes")
+        _sized_arg("mask_nms_sized", "instances", instances, areas=True, boxes=True, empty=True)
         dev, Q = instances.bits.device, len(instances.sizes)
-        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+        i32 = partial(_empty, dev)
         if Q == 0:
             if len(image) != 0 or len(scores) != 0 or (category is not None and len(category) != 0):
                 raise ValueError("mask_nms_sized: scores, image and category must hold one value per instance, 0 of them")
-            return MaskNms(keep=e(0, torch.uint8), by=e(0, torch.int32), decay=e(0, torch.float32), order=e(0, torch.int32),
-                           n_keep=e(0, torch.int32), inter=e(0, torch.int32), status=torch.zeros(2, dtype=torch.int32, device=dev))
-        if not instances.bits.is_cuda:
-            raise ValueError("mask_nms_sized: instances must be on the device")
+            return MaskNms(keep=i32(0, dtype=torch.uint8), by=i32(0), decay=i32(0, dtype=torch.float32), order=i32(0), n_keep=i32(0), inter=i32(0),
+                           status=torch.zeros(2, dtype=torch.int32, device=dev))
         req = nms_request(instances.sizes, image=image, iou=iou, measure=measure, method=method, sigma=sigma)
 
         def column(name, v, dtype, kinds):
@@ -2720,22 +2651,22 @@ class MaskUtilities:
                 raise ValueError(f"mask_nms_sized: {name} must hold one number per instance") from err
             if arr.shape != (Q,) or arr.dtype.kind not in kinds:
                 raise ValueError(f"mask_nms_sized: {name} must hold one number per instance, {Q} of them")
-            return torch.from_numpy(np.ascontiguousarray(arr.astype(np.float32 if dtype == torch.float32 else np.int32))).to(dev)
+            return _upload(arr.astype(np.float32 if dtype == torch.float32 else np.int32), dev)
 
         score = column("scores", scores, torch.float32, "iuf")
         cat = None if category is None else column("category", category, torch.int32, "iu")
         G = len(req.keys)
-        dims = np.ascontiguousarray(sized_tables(instances.sizes)[0])
+        dims = np.ascontiguousarray(instances.tables()[0])
         tables = np.concatenate([req.pair_offsets.view(np.uint8), req.group_offsets.view(np.uint8), req.member.view(np.uint8),
                                  dims.reshape(-1).view(np.uint8)])
-        tables = torch.from_numpy(tables).to(dev)                     # the one upload: the int64 table first, so every view is aligned
+        tables = _upload(tables, dev)                                 # the one upload: the int64 table first, so every view is aligned
         pair_offsets = tables[:8 * (G + 1)].view(torch.int64)
         group_offsets = tables[8 * (G + 1):12 * (G + 1)].view(torch.int32)
         member = tables[12 * (G + 1):12 * (G + 1) + 4 * Q].view(torch.int32)
         dims = tables[12 * (G + 1) + 4 * Q:].view(torch.int32).view(Q, 2)
-        status = e(2, torch.int32)
-        out = MaskNms(keep=e(Q, torch.uint8), by=e(Q, torch.int32), decay=e(Q, torch.float32), order=e(Q, torch.int32),
-                      n_keep=e(G, torch.int32), inter=e(req.n_pairs, torch.int32), status=status, request=req)
+        status = i32(2)
+        out = MaskNms(keep=i32(Q, dtype=torch.uint8), by=i32(Q), decay=i32(Q, dtype=torch.float32), order=i32(Q), n_keep=i32(G),
+                      inter=i32(req.n_pairs), status=status, request=req)
         hip.mask_nms_inter(instances.bits, instances.offsets, dims, instances.area.contiguous(), instances.box.contiguous(), group_offsets,
                            member, pair_offsets, out.inter, status[0:1])
         hip.mask_nms(group_offsets, member, pair_offsets, out.inter, instances.area.contiguous(), score, cat, req.measure, req.method,
@@ -2762,7 +2693,7 @@ class MaskUtilities:
         B, L, T = len(sizes), req.L, int(req.alpha.shape[0])
         tables = np.concatenate([req.layers.reshape(-1).view(np.uint8), req.layer_offsets.view(np.uint8), req.alpha.view(np.uint8),
                                  req.rgb.reshape(-1)])
-        tables = torch.from_numpy(tables).to(dev)                     # the one upload: the int64 table first, so every view is aligned
+        tables = _upload(tables, dev)                                 # the one upload: the int64 table first, so every view is aligned
         at = np.cumsum([0, 32 * L, 4 * (B + 1), 4 * T, 3 * T])
         rows = tables[at[0]:at[1]].view(torch.int64).view(L, 4)
         layer_offsets = tables[at[1]:at[2]].view(torch.int32)
@@ -2793,7 +2724,7 @@ class MaskUtilities:
         if not isinstance(images, SizedImages) or not isinstance(sized, SizedMasks):
             raise ValueError("render_overlay: images must be a SizedImages and sized a SizedMasks")
         B, P = len(images.sizes), len(sized.sizes)
-        if isinstance(image_of, (str, bytes)) or not hasattr(image_of, "__len__") or len(image_of) != P:
+        if not _is_seq(image_of) or len(image_of) != P:
             raise ValueError(f"render_overlay: image_of must hold one image index per plane, {P} of them")
         image_of = [_render_index("render_overlay", "an image index", b, B) for b in image_of]
         cols = np.asarray(colors)
@@ -2833,8 +2764,7 @@ class MaskUtilities:
         `boundary_overlaps`), the gathers of the boundaries' areas, and cvlm_coco_match_boundary in place of cvlm_coco_match.  The area
         ranges keep using the masks' areas and gt_area."""
         for name, s in (("dets", dets), ("gts", gts)):
-            if s is not None and (not isinstance(s, SizedMasks) or not s.bits.is_cuda or s.area is None or not 1 <= len(s.sizes) <= 65535):
-                raise ValueError(f"coco_match: {name} must be a SizedMasks of 1 .. 65535 planes on the device, with areas, or None")
+            _sized_arg("coco_match", name, s, areas=True, optional=True)
         d_sizes, g_sizes = ([] if s is None else s.sizes for s in (dets, gts))
         on_device = isinstance(scores, torch.Tensor) and scores.is_cuda
         if on_device and (scores.dtype != torch.float32 or tuple(scores.shape) != (len(d_sizes),)):
@@ -2849,33 +2779,31 @@ class MaskUtilities:
                 if s is not None:
                     boundary_request(s.sizes, dilation_ratio=boundary, who="coco_match")
         dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        up, i32 = partial(_upload, dev=dev), partial(_empty, dev)
         ND, NG = int(req.det_perm.size), int(req.gt_perm.size)
         A, T = int(req.area_rngs.shape[0]), int(req.iou_thrs.size)
         overlaps = self.mask_inter_sized(dets, gts, pairs=req.pairs) if req.pairs.shape[0] else None
-        inter = overlaps.inter if overlaps is not None else torch.empty(0, dtype=torch.int32, device=dev)
+        inter = overlaps.inter if overlaps is not None else i32(0)
         if ND:
             det_perm = up(req.det_perm)
             det_area = dets.area.index_select(0, det_perm)
             score = scores.detach().index_select(0, det_perm) if on_device else up(req.scores)
         else:
-            det_area, score = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+            det_area, score = i32(0), torch.empty(0, dtype=torch.float32, device=dev)
         if NG:
             g_area = gts.area.index_select(0, up(req.gt_perm))
             range_area = g_area.to(torch.float64) if req.range_area is None else up(req.range_area)
         else:
-            g_area, range_area = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev)
-        out = CocoMatches(dt_order=torch.empty(ND, dtype=torch.int32, device=dev), dt_match=torch.empty(A, T, ND, dtype=torch.int32, device=dev),
-                          dt_ignore=torch.empty(A, T, ND, dtype=torch.uint8, device=dev),
-                          gt_match=torch.empty(A, T, NG, dtype=torch.int32, device=dev),
-                          gt_ignore=torch.empty(A, NG, dtype=torch.uint8, device=dev), score=score,
-                          status=torch.empty(1, dtype=torch.int32, device=dev), overlaps=overlaps, request=req)
+            g_area, range_area = i32(0), torch.empty(0, dtype=torch.float64, device=dev)
+        u8 = partial(_empty, dev, dtype=torch.uint8)
+        out = CocoMatches(dt_order=i32(ND), dt_match=i32(A, T, ND), dt_ignore=u8(A, T, ND), gt_match=i32(A, T, NG), gt_ignore=u8(A, NG), score=score,
+                          status=i32(1), overlaps=overlaps, request=req)
         if boundary is None:
             hip.coco_match(up(req.det_offsets), up(req.gt_offsets), up(req.pair_offsets), inter, det_area.contiguous(), score.contiguous(),
                            g_area.contiguous(), range_area.contiguous(), up(req.crowd), up(req.iou_thrs), up(req.area_rngs), req.max_det,
                            out.dt_order, out.dt_match, out.dt_ignore, out.gt_match, out.gt_ignore, out.status)
             return out
-        none = torch.empty(0, dtype=torch.int32, device=dev)
+        none = i32(0)
         det_b = None if dets is None else self.mask_boundary_sized(dets, dilation_ratio=boundary)
         gt_b = None if gts is None else det_b if gts is dets else self.mask_boundary_sized(gts, dilation_ratio=boundary)
         out.boundary_overlaps = self.mask_inter_sized(det_b, gt_b, pairs=req.pairs) if req.pairs.shape[0] else None
