@@ -262,6 +262,12 @@ class SAM(nn.Module):
         host -> engine.MaskContours, whose `to_coco()` gives the polygon lists (engine.Cascade.mask_contours_sized)."""
         return self.cascade().mask_contours_sized(sized, connectivity=connectivity)
 
+    def simplify_contours(self, contours, *, tolerance=1.0):
+        """EXTENSION, not a reference method: the rings of an engine.MaskContours simplified on the device by Ramer-Douglas-Peucker at
+        `tolerance` pixels -- what a consumer of the reference's GenericMask.polygons does ring by ring on the host -> engine.MaskPolygons,
+        whose `to_coco()` gives the short polygon lists (engine.Cascade.simplify_contours)."""
+        return self.cascade().simplify_contours(contours, tolerance=tolerance)
+
     def mask_distance_sized(self, sized, *, reach=None):
         """EXTENSION, not a reference method: the exact squared Euclidean distance map of each plane of an engine.SizedMasks
         -> engine.MaskDistances (engine.Cascade.mask_distance_sized)."""

@@ -29,6 +29,7 @@ from .maskpost import (BAND_FIELDS, COMPONENTS_MAXM, COMPONENTS_WS_CAP, EDGE_FIE
                        _edge_threshold, compact_request, components_request, edge_request, ground_truth_request, holes_request, match_request,
                        BOUNDARY_MAX_RADIUS, BOUNDARY_RATIO, boundary_radius, boundary_request,
                        CONTOUR_MAX_VERTS, MaskContours, contour_request, contour_rounds,
+                       SIMPLIFY_MAX_T, MaskPolygons, simplify_request,
                        DISTANCE_FAR, DISTANCE_MAX_REACH, SURFACE_MAX_T, SURFACE_RATIO, MaskDistances, SurfaceRequest, SurfaceTotals, distance_request,
                        surface_request, surface_rounds, surface_tolerance,
                        THIN_MAX_ITER, THIN_MAX_STEPS, ClDiceTotals, MaskThin, thin_request,

@@ -97,6 +97,10 @@ _SIGNATURES = {
     "cvlm_mask_contour_count": "i:plppiilpps",
     "cvlm_mask_contour_emit": "i:plppiilplppplppls",
     "cvlm_debug_mask_contour_host": "i:plppiippppplp",
+    "cvlm_contour_simplify_workspace_bytes": "l:il",
+    "cvlm_contour_simplify_mark": "i:ppplpilpppppls",
+    "cvlm_contour_simplify_emit": "i:ppplpippplps",
+    "cvlm_debug_contour_simplify_host": "i:ppplpipppppplp",
     "cvlm_mask_distance_workspace_bytes": "l:il",
     "cvlm_mask_distance_sized": "i:plpppilplplpps",
     "cvlm_debug_mask_distance_sized_host": "i:plpppilplplpp",
@@ -1343,6 +1347,74 @@ def mask_contour_host(bits: torch.Tensor, offsets: torch.Tensor, dims: torch.Ten
     assert not bits.is_cuda
     _call("cvlm_debug_mask_contour_host", bits.data_ptr(), bits.numel(), offsets.data_ptr(), dims.data_ptr(), P, int(connectivity),
           n_vertices.data_ptr(), _p(vertex_offsets), _pn(xy), _pn(ring_start), _p(n_rings), total, status.data_ptr())
+
+
+# ---- Simplified contour rings: Douglas-Peucker polygons out ----------------------------------------------------------------
+def _simplify_rings(xy, ring_start, vertex_offsets) -> Tuple[int, int]:
+    """The check of the rings a simplify entry reads -- xy int16 [total][2], ring_start uint8 [total], vertex_offsets int64 [P + 1], a
+    view of a longer table allowed -> (P, total)."""
+    P, total = int(vertex_offsets.shape[0]) - 1, int(xy.shape[0])
+    assert P >= 1, f"vertex_offsets: one entry more than planes, got {tuple(vertex_offsets.shape)}"
+    _check_tensors(xy, ("xy", xy, _I16, (total, 2)), ("ring_start", ring_start, _U8, (total,)), ("vertex_offsets", vertex_offsets, _I64, (P + 1,)))
+    return P, total
+
+
+def _simplify_marks(P: int, total: int, like, T, keep, n_kept, n_rings_out, status) -> None:
+    _check_tensors(like, ("T", T, _I32, (P,)), ("keep", keep, _U8, (total,)), ("n_kept", n_kept, _I32, (P,)),
+                   ("n_rings_out", n_rings_out, _I32, (P, 2)), ("status", status, _I32, (1,)))
+
+
+def _simplify_outputs(P: int, like, out_offsets, xy_out, ring_start_out, all_or_none: bool = False) -> int:
+    """The check of the outputs of the simplify emit (all_or_none: the host entry, which only marks without them) -> total_out."""
+    total_out = 0 if xy_out is None else int(xy_out.shape[0])
+    _check_tensors(like, ("out_offsets", out_offsets, _I64, (P + 1,)), ("xy_out", xy_out, _I16, (total_out, 2)),
+                   ("ring_start_out", ring_start_out, _U8, (total_out,)),
+                   together=(("out_offsets", "xy_out", "ring_start_out"),) if all_or_none else ())
+    return total_out
+
+
+def contour_simplify_workspace_bytes(P: int, round_vertices: int) -> int:
+    """Bytes of workspace of one `contour_simplify_mark` call on P planes that hold round_vertices vertices together (host arithmetic)."""
+    return _workspace_bytes("cvlm_contour_simplify_workspace_bytes", P, round_vertices)
+
+
+def contour_simplify_mark(xy: torch.Tensor, ring_start: torch.Tensor, vertex_offsets: torch.Tensor, T: torch.Tensor, round_vertices: int,
+                          keep: torch.Tensor, n_kept: torch.Tensor, n_rings_out: torch.Tensor, status: torch.Tensor,
+                          workspace: torch.Tensor) -> None:
+    """Which vertices of each plane's rings Ramer-Douglas-Peucker keeps (include/cvlm.h: cvlm_contour_simplify_mark): xy
+    int16 [total][2], ring_start uint8 [total], vertex_offsets int64 [P + 1], T int32 [P] in quarter pixels -> keep uint8 [total], n_kept
+    int32 [P], n_rings_out int32 [P][2], status int32 [1] = 1 if a plane was refused.  vertex_offsets / T / n_kept / n_rings_out may be
+    views of longer tables -- one round of planes of a larger call --; xy, ring_start and keep are whole and vertex_offsets absolute.
+    round_vertices: at least the vertices of these planes."""
+    P, total = _simplify_rings(xy, ring_start, vertex_offsets)
+    _simplify_marks(P, total, xy, T, keep, n_kept, n_rings_out, status)
+    _check_tensors(xy, ("workspace", workspace, _U8, (None,)))
+    _call(_entry("cvlm_contour_simplify_mark", False, xy), _pn(xy), _pn(ring_start), vertex_offsets.data_ptr(), total, T.data_ptr(), P,
+          int(round_vertices), _pn(keep), n_kept.data_ptr(), n_rings_out.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel())
+
+
+def contour_simplify_emit(xy: torch.Tensor, ring_start: torch.Tensor, vertex_offsets: torch.Tensor, keep: torch.Tensor,
+                          out_offsets: torch.Tensor, xy_out: torch.Tensor, ring_start_out: torch.Tensor, status: torch.Tensor) -> None:
+    """The kept vertices of each plane, in order (include/cvlm.h: cvlm_contour_simplify_emit): plane p's go to the entries
+    [out_offsets[p], out_offsets[p + 1]) of xy_out int16 [total_out][2] and ring_start_out uint8 [total_out] (1 outer ring, 2 hole)."""
+    P, total = _simplify_rings(xy, ring_start, vertex_offsets)
+    total_out = _simplify_outputs(P, xy, out_offsets, xy_out, ring_start_out)
+    _check_tensors(xy, ("keep", keep, _U8, (total,)), ("status", status, _I32, (1,)))
+    _call(_entry("cvlm_contour_simplify_emit", False, xy), _pn(xy), _pn(ring_start), vertex_offsets.data_ptr(), total, _pn(keep), P,
+          out_offsets.data_ptr(), _pn(xy_out), _pn(ring_start_out), total_out, status.data_ptr())
+
+
+def contour_simplify_sequential(xy: torch.Tensor, ring_start: torch.Tensor, vertex_offsets: torch.Tensor, T: torch.Tensor, keep: torch.Tensor,
+                                n_kept: torch.Tensor, n_rings_out: torch.Tensor, status: torch.Tensor,
+                                out_offsets: Optional[torch.Tensor] = None, xy_out: Optional[torch.Tensor] = None,
+                                ring_start_out: Optional[torch.Tensor] = None) -> None:
+    """`contour_simplify_mark` (out_offsets, xy_out and ring_start_out None) or mark and emit (all three) on HOST tensors without a device
+    (cvlm_debug_contour_simplify_host: a sequential recursion with an explicit stack over the kernels' key, keep test and anchor rule)."""
+    P, total = _simplify_rings(xy, ring_start, vertex_offsets)
+    _simplify_marks(P, total, xy, T, keep, n_kept, n_rings_out, status)
+    total_out = _simplify_outputs(P, xy, out_offsets, xy_out, ring_start_out, all_or_none=True)
+    _call(_entry("cvlm_contour_simplify", True, xy), _pn(xy), _pn(ring_start), vertex_offsets.data_ptr(), total, T.data_ptr(), P, _pn(keep),
+          n_kept.data_ptr(), n_rings_out.data_ptr(), _p(out_offsets), _pn(xy_out), _pn(ring_start_out), total_out, status.data_ptr())
 
 
 # ---- Distance maps and surface totals (DESIGN.md §27) --------------------------------------------------------------------------------------

@@ -1,9 +1,9 @@
-"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §31): packed masks with areas, boxes and overlaps, connected
+"""Post-processing of mask hypotheses on the device (DESIGN.md §13 - §31, §34): packed masks with areas, boxes and overlaps, connected
 components, holes, the edge band, packed edge maps, COCO run-length encoding, masks at each image's own size, their intersections
-with ground truth and COCO's matching of detections to annotations, label maps, panoptic quality, boundaries, contours, distance
-maps, thinning, regions, mask NMS and rendering.  Three layers: the pure host checks of every argument (`*_request`) with the result
-types; `MaskUtilities`, the stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan of these outputs for one
-Cascade.infer_classes / decode call.  All three are written in the few private helpers at the top of the file: what an
+with ground truth and COCO's matching of detections to annotations, label maps, panoptic quality, boundaries, contours and their
+simplification, distance maps, thinning, regions, mask NMS and rendering.  Three layers: the pure host checks of every argument
+(`*_request`) with the result types; `MaskUtilities`, the stand-alone utilities, which Cascade inherits; and `MaskPost`, the plan
+of these outputs for one Cascade.infer_classes / decode call.  All three are written in the few private helpers at the top of the file: what an
 int, a real and a sequence are, the one check of an (h, w) list, of "one int or one per plane", of the connectivity and of a
 SizedMasks argument, the one upload, allocator and workspace rule.  `engine` imports every public name back: callers keep importing
 them from there.  Kernels are called as `hip.<name>(...)`, looked up at call time, so that a test can stand in for a launch."""
@@ -1011,6 +1011,85 @@ class MaskContours:
         """On the host: per plane the float64 array of its rings' signed areas 1/2 sum(x_k y_k+1 - x_k+1 y_k).  Synchronises."""
         area = lambda r: 0.5 * float((r[:, 0] * np.roll(r[:, 1], -1) - np.roll(r[:, 0], -1) * r[:, 1]).sum())
         return [np.asarray([area(r) for r in rings], dtype=np.float64) for rings in self._host_rings()]
+
+
+SIMPLIFY_MAX_T = 65535            # the tolerance of a plane in quarter pixels (DESIGN.md §34; csrc/simplify_logic.h: SP_MAX_T): 16383.75 px
+
+
+def simplify_request(contours_or_sizes, *, tolerance=1.0, who: str = "simplify_contours") -> np.ndarray:
+    """Every check of the arguments of Cascade.simplify_contours, on the host, before anything is launched (ValueError)
+    -> the tolerance of each plane in quarter pixels, int32 (P,).  contours_or_sizes: a MaskContours or its (h, w) pairs, 1 .. 65535
+    of them.  tolerance: in pixels, an int or a float >= 0 that is a multiple of 0.25 and at most 16383.75 -- one for all planes or one
+    per plane; nothing is rounded, no bools."""
+    sizes = contours_or_sizes.sizes if isinstance(contours_or_sizes, MaskContours) else contours_or_sizes
+    P = len(_plane_sizes(sizes, who))
+
+    def quarters(v) -> int:
+        if not _is_real(v) or not np.isfinite(float(v)) or float(v) * 4.0 != np.floor(float(v) * 4.0):
+            raise ValueError(f"{who}: a tolerance must be an int or a float that is a multiple of 0.25 pixels (nothing is rounded), got {v!r}")
+        return int(float(v) * 4.0)
+
+    if _is_real(tolerance):
+        T = quarters(tolerance)
+    elif _is_seq(tolerance) and not isinstance(tolerance, torch.Tensor):
+        T = [quarters(v) for v in tolerance]
+    else:
+        raise ValueError(f"{who}: tolerance must be an int or a float in pixels, or hold one per plane, got {tolerance!r}")
+    return _per_plane_ints(who, "tolerance, in quarter pixels,", T, P, 0, SIMPLIFY_MAX_T)
+
+
+@dataclass
+class MaskPolygons:
+    """Simplified rings of P sized planes (Cascade.simplify_contours), on the device: of every ring of a MaskContours the
+    vertices that Ramer-Douglas-Peucker keeps at the plane's tolerance, in the ring's order and from its start; every vertex of the
+    ring lies within the tolerance of the segment between the kept vertices around it.  Plane p's vertices are
+    xy[vertex_offsets[p] : vertex_offsets[p + 1]], ring after ring, the rings in the order they had.  A ring left with fewer than three
+    vertices is dropped and counted in n_dropped.  Simplification does not keep a ring's first edge, so ring_start says what the ring
+    was: 1 on the first vertex of an outer ring, 2 on a hole's."""
+    xy: torch.Tensor                # (total, 2) int16 (x, y)
+    ring_start: torch.Tensor        # (total,) uint8: 1 on the first vertex of an outer ring, 2 on a hole's, 0 elsewhere
+    vertex_offsets: torch.Tensor    # (P + 1,) int64
+    n_vertices: torch.Tensor        # (P,) int32
+    n_rings: torch.Tensor           # (P, 2) int32 (outer rings, holes) that are left
+    n_dropped: torch.Tensor         # (P,) int32 rings that were dropped
+    sizes: list                     # P (h, w) pairs, on the host
+    tolerance: np.ndarray           # (P,) float64, pixels, on the host
+    status: torch.Tensor            # int32 on the device, non-zero if a plane was refused
+
+    def check(self) -> None:
+        """RuntimeError if a plane was refused (synchronises): a plane that the contour call had refused, or tables that were written
+        while the call ran."""
+        if bool(self.status.ne(0).any().item()):
+            raise RuntimeError("simplify_contours: a plane was refused: did the contour call refuse it, or were the rings written while the "
+                               "call ran?")
+
+    def rings(self) -> torch.Tensor:
+        """Ring r of the call is xy[rings[r] : rings[r + 1]] -> (R + 1,) int64 on the device (synchronises: R is data)."""
+        first = torch.nonzero(self.ring_start, as_tuple=False).reshape(-1)
+        return torch.cat([first, torch.full((1,), int(self.xy.shape[0]), dtype=torch.int64, device=first.device)])
+
+    def _host_rings(self):
+        """-> per plane the list of its rings as (int64 array (n, 2), whether it is a hole); one copy of each of the three tensors."""
+        self.check()
+        xy, start = self.xy.cpu().numpy().astype(np.int64), self.ring_start.cpu().numpy()
+        vo = self.vertex_offsets.cpu().numpy()
+        out = []
+        for p in range(vo.size - 1):
+            a, b = int(vo[p]), int(vo[p + 1])
+            cuts = a + np.flatnonzero(start[a:b])
+            out.append([(xy[c:d], int(start[c]) == 2) for c, d in zip(cuts, list(cuts[1:]) + [b])])
+        return out
+
+    def to_coco(self, holes: bool = True) -> list:
+        """On the host: one {"size": [h, w], "polygons": [[x0, y0, x1, y1, ...], ...]} per plane, a ring per polygon -- the list
+        `polygons_request` takes.  holes=False drops the rings that ring_start marks 2.  Synchronises."""
+        return [{"size": [int(h), int(w)], "polygons": [r.reshape(-1).tolist() for r, hole in rings if holes or not hole]}
+                for (h, w), rings in zip(self.sizes, self._host_rings())]
+
+    def signed_areas(self) -> list:
+        """On the host: per plane the float64 array of its rings' signed areas 1/2 sum(x_k y_k+1 - x_k+1 y_k).  Synchronises."""
+        area = lambda r: 0.5 * float((r[:, 0] * np.roll(r[:, 1], -1) - np.roll(r[:, 0], -1) * r[:, 1]).sum())
+        return [np.asarray([area(r) for r, _ in rings], dtype=np.float64) for rings in self._host_rings()]
 
 
 DISTANCE_FAR = hip.DT_FAR        # D2 of a pixel with no set pixel within reach (DESIGN.md §27)
@@ -2411,6 +2490,42 @@ class MaskUtilities:
                                   n_rings[a:b], status[i:i + 1], ws[:need])
         return MaskContours(xy=xy, ring_start=ring_start, vertex_offsets=offsets, n_vertices=n_vertices, n_rings=n_rings, sizes=sizes,
                             connectivity=connectivity, status=torch.maximum(torch.amax(status, 0, keepdim=True), count_status))
+
+    # ---- Simplified contour rings: Douglas-Peucker polygons out ---------------------------------------------------------------
+    def simplify_contours(self, contours: "MaskContours", *, tolerance=1.0) -> "MaskPolygons":
+        """The rings of a MaskContours simplified on the device -> MaskPolygons (cvlm_contour_simplify_mark / cvlm_contour_simplify_emit,
+        DESIGN.md §34): Ramer-Douglas-Peucker on every closed ring, in exact integers, at `tolerance` pixels (a multiple of 0.25, one for
+        all planes or one per plane; 0 returns the rings as they are).  `simplify_request` checks the arguments on the host before
+        anything is launched (ValueError).  The mark runs in rounds whose workspace stays within RLE_WS_CAP through the grow-only
+        workspace "cls_rle" -- the whole input as one round when it fits, which needs no look at the counts; otherwise the host reads
+        the input's vertex counts and cuts the planes as `contour_rounds` does --, then one torch.cumsum of the kept counts, ONE read
+        of their total (the only synchronisation of a call that fits one round), the outputs, the emit.  The status words are folded
+        into one on the device together with the input's: a plane the contour call refused comes out empty and sets it.  Launches
+        on the caller's stream."""
+        if not isinstance(contours, MaskContours) or not contours.xy.is_cuda:
+            raise ValueError(f"simplify_contours: contours must be a MaskContours on the device, got {type(contours).__name__}")
+        T = simplify_request(contours, tolerance=tolerance)
+        P, dev, total = len(contours.sizes), contours.xy.device, int(contours.xy.shape[0])
+        i32 = partial(_empty, dev)
+        need = lambda planes, vertices, _=0: hip.contour_simplify_workspace_bytes(planes, vertices)
+        rounds = [(0, P, total, need(P, total))]
+        if rounds[0][3] > RLE_WS_CAP and P > 1:
+            rounds = contour_rounds(contours.n_vertices.cpu().numpy(), 0, RLE_WS_CAP, need)
+        T_dev = _upload(T, dev)
+        keep, n_kept, n_rings, status = i32(total, dtype=torch.uint8), i32(P), i32(P, 2), i32(len(rounds) + 1)
+        ws = self.ws.scratch("cls_rle", max(r[3] for r in rounds))
+        for i, (a, b, rv, nbytes) in enumerate(rounds):
+            hip.contour_simplify_mark(contours.xy, contours.ring_start, contours.vertex_offsets[a:b + 1], T_dev[a:b], rv, keep, n_kept[a:b],
+                                      n_rings[a:b], status[i:i + 1], ws[:nbytes])
+        offsets = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_kept, 0, dtype=torch.int64, out=offsets[1:])
+        total_out = int(offsets[P].item())                           # the one read of the counts
+        xy, ring_start = i32(total_out, 2, dtype=torch.int16), i32(total_out, dtype=torch.uint8)
+        hip.contour_simplify_emit(contours.xy, contours.ring_start, contours.vertex_offsets, keep, offsets, xy, ring_start, status[-1:])
+        n_dropped = (contours.n_rings.sum(1) - n_rings.sum(1)).clamp_(min=0).to(torch.int32)
+        return MaskPolygons(xy=xy, ring_start=ring_start, vertex_offsets=offsets, n_vertices=n_kept, n_rings=n_rings, n_dropped=n_dropped,
+                            sizes=[tuple(z) for z in contours.sizes], tolerance=T.astype(np.float64) / 4.0,
+                            status=torch.maximum(torch.amax(status, 0, keepdim=True), contours.status.reshape(-1)[:1].to(torch.int32)))
 
     # ---- Distance maps and surface distances (DESIGN.md §27) ----------------------------------------------------------------------------------
     @staticmethod

@@ -980,6 +980,64 @@ int cvlm_debug_mask_contour_host(const uint8_t* bits, int64_t n_bytes, const int
                                  int32_t connectivity, int32_t* n_vertices, const int64_t* vertex_offsets, int16_t* xy, uint8_t* ring_start,
                                  int32_t* n_rings, int64_t total, int32_t* status);
 
+/* Simplified contour rings: Douglas-Peucker polygons out.  Ramer-Douglas-Peucker on the closed rings that
+ * cvlm_mask_contour_emit writes, in exact integers, on the device.  A ring is v_0 .. v_(n-1), v_0 its canonical start; the tolerance
+ * of a plane is an integer T in quarter pixels, 0 <= T <= 65535 (eps = T / 4).
+ *   Anchors: A = v_0; B = the vertex with the largest |v - v_0|^2, the smallest index on a tie.  The ring is opened into the polyline
+ *   v_0 .. v_(n-1), v_0 -- the closing point is a second appearance of v_0 -- and the kept set starts as {A, B, the closing A}.
+ *   Distance of v to the chord (i, j), i < v < j: to the SEGMENT P_i P_j, as a numerator num over the chord's denominator L.
+ *   P_i == P_j (at connectivity 8 a ring passes through a diagonal point twice): L = 1, num = |v - i|^2.  Otherwise L = |j - i|^2,
+ *   t = (v - i).(j - i); t <= 0: num = |v - i|^2 L; t >= L: num = |v - j|^2 L; else num = ((j - i) x (v - i))^2.  With sides <= 16384
+ *   |.|^2 <= 2^29, num <= 2^58, 16 num <= 2^62, T^2 L <= 2^61: all uint64.
+ *   Split: of the vertices inside a chord the one with the largest num, the smallest index on a tie, is kept iff 16 num > T^2 L; both
+ *   halves are split in turn until no chord splits.  The sub-problems are independent: the result does not depend on the order.
+ *   A ring left with fewer than 3 kept vertices (A and B alone) lies within eps of one segment and is DROPPED whole.
+ * So T = 0 returns a crack contour as it is; the kept vertices of a ring are a subsequence of it that starts at v_0, the rings of a
+ * plane keep their order; every vertex of a kept ring lies within T / 4 of the segment between the kept vertices around it.  Not
+ * promised: freedom from self-intersection, OpenCV's choice of start points, the area.
+ * Rings: xy int16 [total][2], ring_start uint8 [total] (non-zero on a ring's first vertex), vertex_offsets int64 [P + 1] as
+ * cvlm_mask_contour_emit's; T int32 [P]; all device memory.  A caller may pass a sub-range of longer tables as vertex_offsets + p0,
+ * T + p0, n_kept + p0, n_rings_out + 2 p0 with the absolute xy, ring_start, keep and total: rounds under a workspace cap are calls.
+ * cvlm_contour_simplify_mark: keep uint8 [total], 1 on every kept vertex of the call's planes, 0 on the others -- on every vertex of a
+ * dropped ring and of a refused plane; n_kept int32 [P]; n_rings_out int32 [P][2] = the (outer rings, holes) that are left, told apart
+ * by the second vertex of the INPUT ring (the start's y: east, outer).  round_vertices >= vertex_offsets[P] - vertex_offsets[0].  Two
+ * launches: init, then one workgroup of 1024 per plane that loops the rounds of the split inside itself (ring starts by a segmented
+ * scan; per round an integer atomicMax of the keys and an atomicMin of the indices at each chord's left anchor, the keep test, the
+ * hand-over of the vertices behind a new anchor; a workgroup-uniform flag ends the loop, and a round that goes on keeps a vertex).
+ * cvlm_contour_simplify_emit: plane p's kept vertices, in order, to the entries [out_offsets[p], out_offsets[p + 1]) of xy_out int16
+ * [total_out][2] and ring_start_out uint8 [total_out]: 1 on an outer ring's first vertex, 2 on a hole's, 0 elsewhere.  Two launches:
+ * init, then one workgroup per plane (count, a streaming scan of keep, one 32-bit store per kept vertex, every slot checked against
+ * the slice first).  The host sizes the output between the two entries: out_offsets is the prefix sum of n_kept.
+ * A plane is REFUSED -- status[0] |= 1 (each call zeroes it first), nothing of it read -- in the mark if its slice is not 0 <= v0 <=
+ * v1 <= total or longer than 2^22, lies before vertex_offsets[0] or ends beyond round_vertices behind it, if T[p] is outside
+ * [0, 65535], or if its first vertex starts no ring (the zeroed slice of a plane that cvlm_mask_contour_emit refused): keep 0 on its
+ * slice where that is inside [0, total], n_kept 0, n_rings_out (0, 0); in the emit if either of its slices is not inside its table or
+ * if it does not have exactly out_offsets[p + 1] - out_offsets[p] kept vertices: its output slice, where inside [0, total_out],
+ * zeroed.  Coordinates outside [0, 16384] wrap in uint64 and give marks of no meaning; no table content makes a kernel read or store
+ * outside the tables or the workspace.
+ * workspace (mark): caller-owned, 16-byte aligned, cvlm_contour_simplify_workspace_bytes(P, round_vertices) bytes = 24 round_vertices
+ * (rounded to 16) + 16; contents need no initialisation.  No allocation, no synchronisation, no pointer kept; every output is
+ * initialised by the call, so a launch sequence replays.
+ * CVLM_E_BADARG, before anything touches the device: a NULL pointer (xy, ring_start and keep may be NULL when total is 0, xy_out and
+ * ring_start_out when total_out is 0); xy / T / n_kept / n_rings_out / xy_out / status not 4-byte aligned, vertex_offsets /
+ * out_offsets not 8-byte aligned, the workspace not 16-byte aligned; P outside [1, 65535]; total or total_out < 0; round_vertices
+ * outside [0, 2^22 P]; a workspace below cvlm_contour_simplify_workspace_bytes; an output or the workspace sharing a byte with an
+ * input or with another output. */
+int64_t cvlm_contour_simplify_workspace_bytes(int32_t P, int64_t round_vertices);
+int cvlm_contour_simplify_mark(const int16_t* xy, const uint8_t* ring_start, const int64_t* vertex_offsets, int64_t total, const int32_t* T,
+                               int32_t P, int64_t round_vertices, uint8_t* keep, int32_t* n_kept, int32_t* n_rings_out, int32_t* status,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int cvlm_contour_simplify_emit(const int16_t* xy, const uint8_t* ring_start, const int64_t* vertex_offsets, int64_t total, const uint8_t* keep,
+                               int32_t P, const int64_t* out_offsets, int16_t* xy_out, uint8_t* ring_start_out, int64_t total_out,
+                               int32_t* status, void* stream);
+/* Outside the ABI contract: mark and emit on HOST memory, no stream, no workspace -- a sequential recursion with an explicit stack of
+ * chords over csrc/simplify_logic.h.  out_offsets == NULL (then xy_out and ring_start_out too): only keep, the counts and status.
+ * Same outputs, same refusals (the two that concern the workspace aside); keep is an output here. */
+int cvlm_debug_contour_simplify_host(const int16_t* xy, const uint8_t* ring_start, const int64_t* vertex_offsets, int64_t total,
+                                     const int32_t* T, int32_t P, uint8_t* keep, int32_t* n_kept, int32_t* n_rings_out,
+                                     const int64_t* out_offsets, int16_t* xy_out, uint8_t* ring_start_out, int64_t total_out,
+                                     int32_t* status);
+
 /* Distance maps of sized planes and directed surface totals: the Hausdorff distance, the average symmetric surface
  * distance, the normalised surface Dice and the boundary F-measure of two planes are functions of one thing -- for every set pixel of
  * plane A the distance to the nearest set pixel of plane B.  Everything is exact in integers.
