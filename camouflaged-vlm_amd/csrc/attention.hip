@@ -46,7 +46,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const half_t* p) {
     return __builtin_bit_cast(half4, r);
 }
 
-template <int HD, int NW, int MODE, int SQK, int SPV, bool CAUSAL>
+template <int HD, int NW, int MODE, int SQK, int SPV, bool CAUSAL, bool SMALL_L>
 __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
     constexpr int CPR = HD / 8;                   // 16-byte chunks per K/V row
     constexpr int KP = HD + 8;                    // LDS row pitch in halves (odd number of 16-B chunks)
@@ -263,6 +263,9 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
                     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
                     mx *= scale;                                          // scale > 0
                 }
+                // (kh, kw) of slot b0 + c, c <= 27: three conditional wraps of kw reach it when 3 L + (L - 1) >= (L - 1) + 27, i.e. L >= 8 --
+                // every shape the encoders run.  Below that (5 x 5 to 7 x 7 maps and windows need up to six wraps) the kernel is built
+                // as SMALL_L and divides: slots stay below 64 there (one key tile), so kh = slot * (2^16 / L + 1) >> 16 is exact.
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     if (MODE == 0) break;
@@ -270,10 +273,15 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
                     const int slot = b0 + c;
                     float v = s[r] * scale;
                     if (MODE != 0) {
-                        int kw = kw0 + c, kh = kh0;
-                        if (kw >= L) { kw -= L; ++kh; }
-                        if (kw >= L) { kw -= L; ++kh; }
-                        if (kw >= L) { kw -= L; ++kh; }
+                        int kw, kh;
+                        if (SMALL_L) {
+                            kh = (int)(__umul24((unsigned)slot, 65536u / (unsigned)L + 1u) >> 16); kw = slot - kh * L;
+                        } else {
+                            kw = kw0 + c; kh = kh0;
+                            if (kw >= L) { kw -= L; ++kh; }
+                            if (kw >= L) { kw -= L; ++kh; }
+                            if (kw >= L) { kw -= L; ++kh; }
+                        }
                         kh = kh < L ? kh : L - 1;
                         v += Thq[kh] + Twq[kw];
                     }
@@ -364,13 +372,15 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnParams p) {
     }
 }
 
-template <int HD, int NW, int MODE, int SQK, int SPV, bool CAUSAL>
+template <int HD, int NW, int MODE, int SQK, int SPV, bool CAUSAL, bool SMALL_L = false>
 int launch(const AttnParams& p, hipStream_t s) {
+    // rel-pos side lengths below 8 have a kernel of their own (the bias' slot -> (row, column) map); NW = 7 means 129 .. 224 slots: L >= 12
+    if (MODE != 0 && NW == 4 && !SMALL_L && p.L < 8) return launch<HD, NW, MODE, SQK, SPV, CAUSAL, MODE != 0 && NW == 4>(p, s);
     constexpr int KP = HD + 8;
     constexpr int NPL = (SQK == 3 || SPV == 3) ? 2 : 1;
     size_t smem = (size_t)2 * NPL * 64 * KP * 2 + 128 + 64 * 4;
     if (MODE != 0) smem += (size_t)2 * NW * 32 * p.LTP * 4;
-    auto kern = attn_kernel<HD, NW, MODE, SQK, SPV, CAUSAL>;
+    auto kern = attn_kernel<HD, NW, MODE, SQK, SPV, CAUSAL, SMALL_L>;
     if (smem > 160 * 1024) return CVLM_E_UNSUPPORTED;
     if (smem > 48 * 1024)
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

@@ -241,6 +241,11 @@ int cvlm_reinterpret_transpose(const float* x, int32_t B, int32_t T, int32_t D, 
  * mode 2: windows of `window` x `window` tokens on a grid x grid map, zero padded: pad tokens carry
  *         q = k = v = qkv bias (pad_hi/pad_lo = h2 of the 3*heads*hd bias vector).
  * rel_h/rel_w: h2 [(2*L-1)][hd] tables (L = grid or window).  scale = hd^-0.5 applied to q.k only.
+ * grid / window: any value >= 1 (grid = 0 or, in mode 2, window = 0: CVLM_E_BADARG), as long as the two bias tables of a workgroup fit
+ *   its LDS (CVLM_E_UNSUPPORTED beyond: L of about 100 and more); a window may be larger than the map (one mostly-pad window) and need
+ *   not divide it.  (Until the edge-shape suite, tests/test_attention_edges_gpu.py, L = 5, 6 and 7 took the bias of some key slots from
+ *   the wrong table entries: the slot -> (row, column) map of the generic kernel wrapped three times at most.  L <= 4 and L >= 8 were
+ *   right.)
  * out: h2 [B*S_img][heads*hd].
  * split_qk / split_pv: fp16 MFMA products per multiply of q.k^T / P.v.  3: hi/lo operands on both sides (hi.hi + lo.hi + hi.lo, fp32-grade);
  *   1: hi planes only (lo pointers may be NULL); (3, 1) mixes them.  ABI 11 -- (2, 2): K and V keep their lo planes, Q and the

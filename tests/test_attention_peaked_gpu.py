@@ -8,6 +8,7 @@ families of operands, all built from the packed planes the kernels read:
   peak   one key Delta above the rest for every query, in the first key tile, in the last one, or (windows) on the pad keys;
   ramp   a key-index term: +1 per 64-key tile (P grows towards e^TAU before one rescale), +6 per tile (a rescale every tile), +6 per tile
          for half of the queries of every 32-query group only (lanes rescale whose own max did not move), and a descending ramp.
+Operands, the fp64 side and the bound live in tests/attn_cases.py, shared with tests/test_attention_edges_gpu.py.
 Bound per case: err_kernel <= K_EMU * err_emulated + FLOOR (relative to max |reference|), with the emulation of THAT split on the same
 operands; and, for the lossy ViT-H kernels, err_kernel > LOSSY_MIN * err_emulated (a silent fall-back to (3, 3) fails).  Every output row
 is written (the output starts as NaN).  SPLIT_TOL of tests/test_ops_gpu.py is the flat regime's bar and is not used here.
@@ -18,15 +19,8 @@ import pytest
 import torch
 
 import attn_emulate as E
-
-K_EMU = 2.5         # kernel error / emulated error: the emulation takes the rounding points, not the fp32 summation order
-FLOOR = 2e-6        # relative: fp32 scores and exponentials of |s| up to ~400 (the +6-per-tile ramp on 4096 keys)
-LOSSY_MIN = 0.2     # a lossy kernel's error is at least this fraction of its emulation's
-# fp32 online softmax: the output accumulators, rescale factors and fp32 products of the kernels carry errors of |s| * 2^-24 grade that the
-# emulation does not take; this many units of max|s| * 2^-24 are allowed on top (measured: at most 4.1, the 96 x 96 map with a peak of 12).
-# Measured kernel / emulation on the lossy ViT-H kernels: 0.79-1.08; on the generic (3, 1) / (1, 1): up to 1.48.
-C_F32 = 8.0
-SPLITS = [(3, 3), (2, 2), (1, 2), (3, 1), (1, 1)]
+from attn_cases import (G64PAIR, G96PP, GENERIC64, SPLITS, WIN2, _fid, _gen, check, cpu_side, emulations, form_of, make_qkv, planes_bhsd,
+                        relpos_rows, sampled_rows, sigma_of, to_head_major, unwindow, windows)
 
 
 @pytest.fixture(scope="module")
@@ -38,179 +32,11 @@ def hip():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# operands
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def family_terms(fam, nq, nk, window_local=None):
-    """(q coordinate per query, k coordinate per key) of the planted / ramp families; window_local maps token -> key index in its window."""
-    kind = fam[0]
-    jq = torch.arange(nq) if window_local is None else window_local
-    jk = torch.arange(nk) if window_local is None else window_local
-    tile = (jk // 64).double()
-    if kind == "ramp":
-        how = fam[1]
-        if how == "slow":
-            r, cq = tile * 1.0, torch.ones(nq)
-        elif how == "fast":
-            r, cq = tile * 6.0, torch.ones(nq)
-        elif how == "half":
-            r, cq = tile * 6.0, ((jq % 32) < 16).double()
-        else:                                                            # "desc"
-            r, cq = (tile.max() - tile) * 1.0, torch.ones(nq)
-        return cq.double(), r
-    if kind == "peak":
-        d, where = fam[1], fam[2]
-        r = torch.zeros(nk, dtype=torch.float64)
-        if where == "first":
-            r[jk == 5] = d
-        elif where == "last":
-            r[jk == int(jk.max()) - 2] = d
-        return torch.ones(nq, dtype=torch.float64), r
-    return None
-
-
-def sigma_of(fam):
-    return fam[1] if fam[0] == "gauss" else 1.0
-
-
-def make_qkv(fam, B, S, Hh, hd, seed, window=0, G=0):
-    """Token-major fp32 qkv [B*S][3*Hh*hd] with the family's score structure (scale = 1: q carries it, as in the engine) and the
-    rel-pos table std that makes the bias ~0.3 sigma.  Coordinate 0 of every head carries the planted / ramp term."""
-    g = _gen(seed)
-    sig = sigma_of(fam)
-    a = math.sqrt(sig) / hd ** 0.25
-    x = torch.randn(B * S, 3, Hh, hd, generator=g, dtype=torch.float64)
-    x[:, 0] *= a
-    x[:, 1] *= a
-    wl = None
-    if window:
-        ty, tx = torch.arange(S) // G, torch.arange(S) % G
-        wl = (ty % window) * window + (tx % window)
-    terms = family_terms(fam, S, S, wl)
-    if terms is not None:
-        cq, r = terms
-        x[:, 0, :, 0] = cq.repeat(B)[:, None]
-        x[:, 1, :, 0] = r.repeat(B)[:, None]
-    rstd = 0.3 * sig / (math.sqrt(2.0) * a * math.sqrt(hd))
-    return x.reshape(B * S, 3 * Hh * hd).float(), rstd
-
-
-def to_head_major(t, Bn, S, Hh, hd):
-    return t.reshape(Bn, S, 3, Hh, hd).permute(2, 0, 3, 1, 4).contiguous().reshape(Bn * S, 3 * Hh * hd)
-
-
-def planes_bhsd(P, which, Bn, S, Hh, hd):
-    """(hi, lo) fp64 of q / k / v (which = 0 / 1 / 2) as (B*Hh, S, hd) from token-major planes."""
-    return tuple(P.t[i].double().cpu().reshape(Bn, S, 3, Hh, hd)[:, :, which].permute(0, 2, 1, 3).reshape(Bn * Hh, S, hd) for i in (0, 1))
-
-
-def relpos_rows(qf, RH, RW, L):
-    """Callable bias rows of image_encoder.py:589-625 for queries qf (N, L*L, hd) fp64 and tables (2L-1, hd) fp64."""
-    def rows(n, r):
-        qh, qw = r // L, r % L
-        kk = torch.arange(L)
-        Rh = RH[(qh[:, None] - kk[None, :] + L - 1)]                  # (rows, L, hd)
-        Rw = RW[(qw[:, None] - kk[None, :] + L - 1)]
-        th = torch.einsum("rc,rkc->rk", qf[n, r], Rh)
-        tw = torch.einsum("rc,rkc->rk", qf[n, r], Rw)
-        return (th[:, :, None] + tw[:, None, :]).reshape(len(r), L * L)
-    return rows
-
-
-def windows(planes, pad_planes, Bn, G, ws, Hh, hd, which):
-    """(hi, lo) of q / k / v per window, pad tokens = the pad vector: (Bn*nw*nw*Hh, ws*ws, hd)."""
-    Gp = -(-G // ws) * ws
-    nw = Gp // ws
-    out = []
-    for i in (0, 1):
-        x = planes.t[i].double().cpu().reshape(Bn, G, G, 3 * Hh * hd)
-        xp = pad_planes.t[i].double().cpu().expand(Bn, Gp, Gp, 3 * Hh * hd).clone()
-        xp[:, :G, :G] = x
-        w = xp.reshape(Bn, nw, ws, nw, ws, 3, Hh, hd)[:, :, :, :, :, which].permute(0, 1, 3, 5, 2, 4, 6)
-        out.append(w.reshape(Bn * nw * nw * Hh, ws * ws, hd))
-    return tuple(out)
-
-
-def unwindow(o, Bn, G, ws, Hh, hd):
-    Gp = -(-G // ws) * ws
-    nw = Gp // ws
-    o = o.reshape(Bn, nw, nw, Hh, ws, ws, hd).permute(0, 1, 4, 2, 5, 3, 6).reshape(Bn, Gp, Gp, Hh * hd)
-    return o[:, :G, :G].reshape(Bn * G * G, Hh * hd)
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# the fp64 side of a case, computed once per (dispatch geometry, family) and shared by every split
-_CPU = {}
-
-
-def cpu_side(key, build):
-    if key not in _CPU:
-        _CPU[key] = build()
-    return _CPU[key]
-
-
-def sampled_rows(S):
-    """Queries the fp64 side computes: all of them up to 2048; beyond, every 4th block of 256 (whole workgroups of every kernel, both
-    halves of every 32-query group) -- the CPU cost of a 96 x 96 map drops 9x, every kernel row is still checked for being written."""
-    r = torch.arange(S)
-    return r if S <= 2048 else r[(r // 256) % (4 if S <= 4096 else 9) == 0]
-
-
-def emulations(ops, kernel_of, splits, rows=None):
-    """Reference (no rounding at all) + the emulation of every split, on the same operands.  kernel_of(split) -> (family, online softmax
-    of that kernel: (key tile, tau))."""
-    q, k, v, bias, causal, scale = ops
-    st = {}
-    res = {"ref": E.emulate(q, k, v, scale, bias=bias, causal=causal, f32_scores=False, rows=rows, stats=st), "stats": st}
-    for sp in splits:
-        fam, online = kernel_of(sp)
-        form = E.rounding(fam, sp) + (online,)
-        if form not in res:
-            res[form] = E.emulate(q, k, v, scale, bias=bias, causal=causal, qk=form[0], pv=form[1], online=online, rows=rows)
-    return res
-
-
-def form_of(kernel_of, sp):
-    fam, online = kernel_of(sp)
-    return E.rounding(fam, sp) + (online,)
-
-
-# online softmax of each kernel: key tile and how far the maximum must move before the reference point does
-GENERIC64 = (E.GENERIC, (64, 5.0))                   # csrc/attention.hip: 64-key tiles, lazy (TAU = 5)
-WIN2 = (E.VITH, (32, 5.0))                           # attention_win2.hip: 32-key tiles, lazy
-G64PAIR = (E.VITH, (64, 0.0))                        # attention_g64pp.hip, 64 x 64 map: a key row (64 keys) per phase, every new maximum
-G96PP = (E.VITH, (32, 0.0))                          # attention_g64pp.hip, 96 x 96 map: 32-key tiles
-
-
-def check(tag, got, res, form, lossy_vith, rows=None):
-    ref, emu = res["ref"], res[form]
-    assert not torch.isnan(got).any(), f"{tag}: unwritten output rows"
-    if rows is not None:
-        got, ref, emu = got[:, rows], ref[:, rows], emu[:, rows]
-    ek, ee = E.relerr(got, ref), E.relerr(emu, ref)
-    st = res["stats"]
-    print(f"{tag}: score std {st['score_std']:.2f} max|s| {st['max_abs_score']:.1f} H/lnN {st['entropy_ratio']:.3f} | kernel {ek:.2e} "
-          f"emulated {ee:.2e} ratio {ek / max(ee, 1e-30):.2f}")
-    f32 = st["max_abs_score"] * 2.0 ** -24
-    print(f"    units of max|s| 2^-24 beyond K_EMU * emulated + FLOOR: {(ek - K_EMU * ee - FLOOR) / f32:.2f}")
-    assert ek <= K_EMU * ee + FLOOR + C_F32 * f32, (tag, ek, ee)
-    if lossy_vith:                                   # not better than it can be: the lossy kernel ran, not (3, 3)
-        assert ek > LOSSY_MIN * ee and (ek > 5e-6 or ee < 2.5e-5), (tag, ek, ee)
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
 GAUSS = [("gauss", s) for s in (1, 3, 6, 10)]
 PEAK = [("peak", d, w) for d in (12, 25) for w in ("first", "last")]
 RAMP = [("ramp", r) for r in ("slow", "fast", "half", "desc")]
 
-
-def _fid(f):
-    return "-".join(str(x) for x in f)
-
-
-MODE1 = ([(20, f) for f in GAUSS + PEAK + RAMP] + [(64, f) for f in GAUSS + PEAK + RAMP] +
+MODE1 =([(20, f) for f in GAUSS + PEAK + RAMP] + [(64, f) for f in GAUSS + PEAK + RAMP] +
          [(96, f) for f in [("gauss", 1), ("gauss", 6)] + PEAK])
 
 
